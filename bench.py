@@ -44,12 +44,6 @@ import sys
 import threading
 import time
 
-# Eight hardware queues for the process's HIP streams (the runtime's default is four: a decoder with four channel groups has five
-# streams, and two streams on one queue take turns) -- read by the HIP runtime when it starts, i.e. before anything below touches the
-# GPU.  With them, biglm and lattice decoders of 128 channels are asked for FOUR channel groups below (wfst_options.channel_groups;
-# the library's own default is three, it reads no environment).  An exported value wins.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -146,6 +140,9 @@ def parse():
     ap.add_argument("--detail-out", default="", help="where the FULL result (every leg, curve, count and note) is written as JSON; default "
                     "bench_detail.json beside this script (and gpurun_out/bench_detail.json when that directory exists).  The final "
                     "stdout line is the compact summary of it (summary_line(): < 4 KB, scalars only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned to "
+                    "its caller (rank 0's utterances: best paths, and in lattice mode the n-best lists and determinized lattices) as "
+                    "DIR/<name>.npy, float32 or float64, at most 64 MB in all (see dump_outputs())")
     return ap.parse_args()
 
 
@@ -645,6 +642,78 @@ def summary_line(out, detail_path=None):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_arrays(items, prefix):
+    """One dict (or None) per item -> {name: array}.  A scalar field becomes one value per item (NaN where the item has none); an
+    array field is concatenated over the items, with <name>_offsets: item i's values are [off[i], off[i + 1]).  Integers are stored
+    as float64 (exact for int32 labels and ids), float32 arrays as they are."""
+    keys = []
+    for d in items:
+        for k in (d or {}):
+            if k not in keys:
+                keys.append(k)
+    out = {}
+    for k in keys:
+        vals = [None if d is None else d.get(k) for d in items]
+        if any(isinstance(v, np.ndarray) for v in vals):
+            parts = [np.asarray(v if v is not None else []).ravel() for v in vals]
+            is_f32 = any(p.dtype == np.float32 for p in parts if p.size)
+            cat = np.concatenate([p.astype(np.float32 if is_f32 else np.float64) for p in parts]) if parts else np.zeros(0)
+            out[prefix + k] = cat
+            out[prefix + k + "_offsets"] = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.float64)
+        else:
+            out[prefix + k] = np.asarray([np.nan if v is None else float(v) for v in vals], np.float64)
+    return out
+
+
+def dump_outputs(res, out_dir, first_utt):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one .npy per field, for comparing two builds
+    output for output on the same seeded inputs.  utterance.npy holds the (global) utterance index of every row.  Best path per
+    utterance: ok, tot_score, lm_score (float64 of the float32 sums), ilabel / olabel / graph / ac (the hop list), words, tids; lattice
+    mode adds nbest_* (one row per path; nbest_utterance says whose) and det_* (the determinized lattice).  Over 64 MB in all, a
+    fixed sample of utterances (a seeded permutation, taken while it fits) is written instead of the whole batch."""
+    n = len(res)
+    nbl = getattr(res, "nbest_lazy", None)
+    best, nbest, det = [], [], []
+    for i in range(n):
+        r = res[i]
+        best.append({k: r[k] for k in ("ok", "tot_score", "lm_score", "ilabel", "olabel", "graph", "ac", "words", "tids")})
+        paths = nbl[i] if nbl is not None else r.get("nbest")
+        nbest.append(None if paths is None else [dict(p) for p in paths])
+        det.append(r.get("det"))
+    have_nbest, have_det = any(p is not None for p in nbest), any(d is not None for d in det)
+
+    def arrays(sel):
+        o = {"utterance": np.asarray([first_utt + i for i in sel], np.float64)}
+        o.update(_dump_arrays([best[i] for i in sel], ""))
+        if have_nbest:
+            rows = [(i, p) for i in sel for p in (nbest[i] or [])]
+            o["nbest_utterance"] = np.asarray([first_utt + i for i, _ in rows], np.float64)
+            o.update(_dump_arrays([p for _, p in rows], "nbest_"))
+        if have_det:
+            o["det_present"] = np.asarray([det[i] is not None for i in sel], np.float64)
+            o.update(_dump_arrays([det[i] for i in sel], "det_"))
+        return o
+
+    size = lambda o: sum(v.nbytes for v in o.values())
+    out = arrays(range(n))
+    if size(out) > DUMP_LIMIT_BYTES:
+        sel, total = [], 0
+        for i in np.random.default_rng(0).permutation(n):   # (an utterance alone costs at least its share of the sample)
+            cost = size(arrays([int(i)]))
+            if total + cost <= DUMP_LIMIT_BYTES:
+                sel.append(int(i))
+                total += cost
+        out = arrays(sorted(sel))
+        log("--dump-outputs: %d of %d utterances (64 MB limit)" % (len(sel), n))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log("--dump-outputs: %d arrays, %.1f MB, in %s" % (len(out), size(out) / 1e6, out_dir))
+
+
 def write_detail(out, path):
     """The full result -- what the line summarises -- as indented JSON (NaN / Infinity as null)."""
     def clean(o):
@@ -857,8 +926,6 @@ def main():
         log("[rank %d] LMs: old %d states / %d arcs, new %d states / %d arcs (%.1fs)" % (
             rank, lm_info[0]["n_states"], lm_info[0]["n_arcs"], lm_info[1]["n_states"], lm_info[1]["n_arcs"], time.time() - t0))
     stream = torch.cuda.current_stream(dev).cuda_stream
-    if a.groups <= 0 and (a.biglm or a.lattice_links > 0) and B >= 128 and int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 8:
-        a.groups = 4   # (chains of small launches: a fourth group finds room -- with eight hardware queues only, see the top of the file)
     opt = wfstdec.Options(use_hip_graph=0 if a.no_hip_graph else 1, debug=a.debug, **({"channel_groups": a.groups} if a.groups > 0 else {}),
                           **({"expand_workgroups": a.expand_wgs} if a.expand_wgs > 0 else {}),
                           **({"log2_partitions": a.log2_parts} if a.log2_parts >= 0 else {}),
@@ -1004,6 +1071,8 @@ def main():
         host_rows = [pinned[i].numpy() for i in range(B)]
     step = make_step(dec, ll_dev, host_rows)
     dt, res = timed(step, a.warmup, a.steps)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(res, a.dump_outputs, rank * B)
     frames_total = world * B * T * a.steps
     value = frames_total / dt
     if os.environ.get("WFST_BENCH_BREAKDOWN"):

@@ -403,7 +403,7 @@ int wfst_decoder_prefetch_determinized(wfst_decoder *d);
  * wfst_decoder_harvest_prefetched), until the harvest after that; a channel that still holds the very utterance also serves them through
  * wfst_decoder_get_determinized_lattice.  The side stream is one more HIP stream of the process: with the runtime's default of
  * four hardware queues it can end up sharing a queue with a channel group's stream, whose launches then wait behind the
- * determinizer -- export GPU_MAX_HW_QUEUES=8 before the process's first HIP call. */
+ * determinizer. */
 int wfst_decoder_prefetch_determinized_detached(wfst_decoder *d);
 /* GetLattice AND GetNbest ahead of their requests, as the service runs them one behind the other (kaldi-nnet3/kaldi-online-nnet3-
  * my-decoder.cc:97-105: NShortestPath on the lattice DeterminizeLatticeWrapper returned): like wfst_decoder_prefetch_determinized

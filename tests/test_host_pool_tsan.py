@@ -6,6 +6,8 @@ results, and one thread that misuses its decoder: every utterance's result carri
 an exception to that thread alone, the batcher batched, and the sanitizer has nothing to say (no race, no lock inversion, no
 re-entrant call).  Round 6's hang -- advance requests never marked done -- fails here in seconds (the run is under a time-out)."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -23,10 +25,17 @@ def pool_tsan(tmp_path_factory):
     return exe
 
 
+def _run(args):
+    """The driver under ThreadSanitizer, with this process's address-space randomisation off (setarch -R): where the kernel randomises
+    mmap with more bits than TSan's fixed shadow layout expects, TSan dies at start ("unexpected memory mapping") before any check."""
+    pre = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []
+    return subprocess.run(pre + args, capture_output=True, text=True, timeout=300,
+                          env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0:second_deadlock_stack=1"))
+
+
 @pytest.mark.parametrize("threads,utts", [(16, 96), (3, 20), (1, 5)])
 def test_pool_batches_without_races(pool_tsan, threads, utts):
-    p = subprocess.run([pool_tsan, str(threads), str(utts)], capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0:second_deadlock_stack=1"))
+    p = _run([pool_tsan, str(threads), str(utts)])
     assert "ThreadSanitizer" not in p.stderr, p.stderr[-3000:]
     assert p.returncode == 0, (p.returncode, p.stdout, p.stderr[-1500:])
     out = dict(zip(p.stdout.split()[0::2], p.stdout.split()[1::2]))
@@ -41,8 +50,7 @@ def test_shared_device_mode_without_races(pool_tsan):
     """GpuLatticeDecoder::ShareDevice: decoder objects constructed the reference's way -- (graph, config), one per thread -- lease
     channels of shared device decoders (16 objects over two 8-channel ones): every utterance's own rows, the misuse to its own
     thread, nothing for the sanitizer."""
-    p = subprocess.run([pool_tsan, "16", "96", "share"], capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0:second_deadlock_stack=1"))
+    p = _run([pool_tsan, "16", "96", "share"])
     assert "ThreadSanitizer" not in p.stderr, p.stderr[-3000:]
     assert p.returncode == 0, (p.returncode, p.stdout, p.stderr[-1500:])
     assert "bad 0 misuse_caught 1" in p.stdout
