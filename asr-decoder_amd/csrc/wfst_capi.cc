@@ -160,7 +160,6 @@ struct wfst_decoder {
   DevBuf<FrameCtl> fctl;
   DevBuf<unsigned long long> dbg_t;
   DevBuf<int32_t> items, item_pref, degraded;
-  int32_t det_only = -1;   // determinize_alone: the one channel wfst_decoder_get_determinized_lattice shall determinize, afresh
   DevBuf<TileDesc> tiles;
   int insert_wgs = 768;
   std::vector<int> gpar;  // step parity per group (persists across advance calls)
@@ -2462,8 +2461,6 @@ int wfst_decoder_get_raw_lattice(wfst_decoder *d, int32_t channel, int32_t use_f
 static int ensure_det_workspace(wfst_decoder *d) {
   DetDev &X = d->det;
   if (d->det_ws.p) return WFST_OK;
-    // first use: the determinizer's workspace (wfst_limits.det_raw_states / det_raw_arcs / det_workspace_bytes), for
-  // det_slots lattices at a time -- every channel of the decoder where the budget allows
   X.raw_states_cap = (int32_t)std::min<int64_t>(d->D.lat_tok_cap, d->lim.det_raw_states > 0 ? d->lim.det_raw_states : 65536);
   X.raw_arcs_cap = (int32_t)std::min<int64_t>(d->D.lat_arc_cap, d->lim.det_raw_arcs > 0 ? d->lim.det_raw_arcs : 2ll * X.raw_states_cap);
   const int32_t base = std::max(4096, X.raw_states_cap);
@@ -2492,6 +2489,23 @@ static int ensure_det_workspace(wfst_decoder *d) {
   d->det_live_nd.assign((size_t)d->n_channels, -1);
   d->det_live_final.assign((size_t)d->n_channels, 0);
   return WFST_OK;
+}
+
+// The determinizer's workspace slots hold the lattices of `list`'s current utterances (slot i = list[i]; res = the launch's result
+// words), the composition's none yet: a batched second pass / n-best right behind starts from them (postprocess_batch)
+static void hold_slots(wfst_decoder *d, const std::vector<int32_t> &list, const std::vector<int32_t> &res) {
+  d->post_dev_list = list;
+  d->post_dev_decoded.resize(list.size());
+  for (size_t i = 0; i < list.size(); ++i) d->post_dev_decoded[i] = d->h_decoded[list[i]];
+  d->post_dev_dres = res;
+  d->post_dev_cres.clear();
+  d->post_dev_o = nullptr; d->post_dev_n = nullptr;
+}
+static bool slots_hold(const wfst_decoder *d, const std::vector<int32_t> &list) {
+  if (list != d->post_dev_list) return false;
+  for (size_t i = 0; i < list.size(); ++i)
+    if (d->post_dev_decoded[i] != d->h_decoded[list[i]]) return false;
+  return true;
 }
 
 // The results of a determinize launch over `list` (workspace slot i = list[i]; res = the launch's result words, on their way or
@@ -2585,12 +2599,79 @@ static int harvest_determinized(wfst_decoder *d, const std::vector<int32_t> &lis
     all_current = all_current && d->h_state[list[i]] == 2 && res[4 * i + 2] == 0 && (detached || !d->p_ctl[list[i]].error);
   if (all_current) {
     // the workspace slots hold these lattices: a batched second pass / n-best right behind starts from them (postprocess_batch)
-    d->post_dev_list = list;
-    d->post_dev_decoded.resize(list.size());
-    for (size_t i = 0; i < list.size(); ++i) d->post_dev_decoded[i] = d->h_decoded[list[i]];
-    d->post_dev_dres = res;
-    d->post_dev_cres.clear();
-    d->post_dev_o = nullptr; d->post_dev_n = nullptr;
+    hold_slots(d, list, res);
+  }
+  return WFST_OK;
+}
+
+// ---- pieces every post-processing getter shares: the determinizer's errors, NShortestPath's workspace and its paths, the copies out
+
+// A channel's determinizer status (DetLattice::err, or the status word of a launch's result; not 0) as the error the caller sees
+static int det_error(wfst_decoder *d, int32_t channel, int32_t err) {
+  if (err & kDetErrCtl) return fail_ctl_error(channel, err & ~kDetErrCtl);
+  if (err == 2)
+    return fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": raw lattice larger than the determinizer takes (" +
+                                     std::to_string(d->det.raw_states_cap) + " states / " + std::to_string(d->det.raw_arcs_cap) + " arcs)");
+  return fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": the subset construction outgrew its workspace (lattice not determinizable within bounds)");
+}
+
+// nbest_paths_kernel's workspace for one lattice of ns states and na arcs (ints)
+static int64_t nbest_ws_ints(int64_t ns, int64_t na) { return 7ll * ns + 4ll * std::max(ns, na) + na + 16; }
+
+// The paths nbest_paths_kernel found on one lattice -- `found` paths, `total` arcs on them; off[found + 1], tot[found] and arcs[total],
+// indices into the lattice's arcs a / w -- as R's labels and costs; false where an index falls outside the lattice
+static bool map_paths(int32_t found, int32_t total, const int32_t *off, const float *tot, const int32_t *arcs, const std::vector<int4> &a,
+                      const std::vector<float2> &w, wfst_decoder::NbPaths &R) {
+  R.off.assign(1, 0);
+  if (found) R.off.assign(off, off + found + 1);
+  R.tot.assign(tot, tot + found);
+  R.olabel.resize((size_t)total); R.graph.resize((size_t)total); R.ac.resize((size_t)total);
+  for (int32_t k = 0; k < total; ++k) {
+    const size_t aidx = (size_t)arcs[k];
+    if (aidx >= a.size()) return false;
+    R.olabel[(size_t)k] = a[aidx].z;
+    R.graph[(size_t)k] = w[aidx].x;
+    R.ac[(size_t)k] = w[aidx].y;
+  }
+  return true;
+}
+
+// A lattice of ns states (final: fin[s], or without fin the states from n_proper on) into the caller's arrays, each of which may be
+// null.  The sizes are written before the capacity check: a caller short of room asks again with them.
+static int copy_lattice(int32_t ns, const int32_t *fin, int32_t n_proper, const std::vector<int4> &a, const std::vector<float2> &w,
+                        int32_t cap_states, int32_t cap_arcs, int32_t *n_states, int32_t *n_arcs, int32_t *st_final, int32_t *a_src,
+                        int32_t *a_dst, int32_t *a_ilabel, int32_t *a_olabel, float *a_graph, float *a_acoustic) {
+  *n_states = ns;
+  *n_arcs = (int32_t)a.size();
+  if (ns > cap_states || (int32_t)a.size() > cap_arcs) return fail(WFST_E_CAPACITY, "lattice larger than the given capacities");
+  for (int32_t s = 0; s < ns; ++s)
+    if (st_final) st_final[s] = fin ? fin[s] : s >= n_proper ? 1 : 0;
+  for (size_t k = 0; k < a.size(); ++k) {
+    if (a_src) a_src[k] = a[k].x;
+    if (a_dst) a_dst[k] = a[k].y;
+    if (a_ilabel) a_ilabel[k] = 0;
+    if (a_olabel) a_olabel[k] = a[k].z;
+    if (a_graph) a_graph[k] = w[k].x;
+    if (a_acoustic) a_acoustic[k] = w[k].y;
+  }
+  return WFST_OK;
+}
+
+// An n-best list into the caller's arrays (each may be null); the sizes first, as copy_lattice
+static int copy_paths(const wfst_decoder::NbPaths &R, int32_t cap_paths, int32_t cap_arcs, int32_t *n_paths, int32_t *total_arcs,
+                      int32_t *path_off, float *path_tot, int32_t *a_olabel, float *a_graph, float *a_acoustic) {
+  const int32_t found = (int32_t)R.tot.size(), total = (int32_t)R.olabel.size();
+  *n_paths = found;
+  *total_arcs = total;
+  if (found > cap_paths || total > cap_arcs) return fail(WFST_E_CAPACITY, "n-best larger than the given capacities");
+  for (int32_t q = 0; q <= found; ++q)
+    if (path_off) path_off[q] = R.off[(size_t)q];
+  for (int32_t q = 0; q < found; ++q)
+    if (path_tot) path_tot[q] = R.tot[(size_t)q];
+  for (int32_t q = 0; q < total; ++q) {
+    if (a_olabel) a_olabel[q] = R.olabel[(size_t)q];
+    if (a_graph) a_graph[q] = R.graph[(size_t)q];
+    if (a_acoustic) a_acoustic[q] = R.ac[(size_t)q];
   }
   return WFST_OK;
 }
@@ -2664,7 +2745,7 @@ static int prefetch_determinized(wfst_decoder *d, bool detached, int32_t n_paths
     P.a = d->det.out_a; P.w = d->det.out_w; P.res = d->det.result; P.fin = nullptr;
     P.in_stride = d->det.out_cap; P.fin_stride = 0;
     P.n = n_paths;
-    P.ws_ints = 7ll * kPfNpStates + 4ll * kPfNpArcs + kPfNpArcs + 16;
+    P.ws_ints = nbest_ws_ints(kPfNpStates, kPfNpArcs);
     P.list_cap = (int64_t)kPfNpStates * n_paths + 1;
     P.out_cap = n_paths * 1024;   // arcs on a lattice's n paths together (a path of a determinized lattice: a word or an epsilon per state)
     if (d->pf_np_slots < cnt || d->pf_np_n < n_paths) {
@@ -2733,20 +2814,9 @@ static int finish_prefetch(wfst_decoder *d) {
     wfst_decoder::NbPaths R;
     R.key.o = nullptr; R.key.n = nullptr; R.key.use_final = 1; R.key.n_paths = n_paths; R.key.decoded = d->h_decoded[c]; R.key.valid = true;
     const int32_t found = L.n_states > 0 ? o[0] : 0, total = L.n_states > 0 ? o[1] : 0;
-    if (total > out_cap) continue;
-    R.off.assign(1, 0);
-    if (found) R.off.assign(poff + (size_t)i * (size_t)(n_paths + 1), poff + (size_t)i * (size_t)(n_paths + 1) + found + 1);
-    R.tot.assign(ptot + (size_t)i * (size_t)n_paths, ptot + (size_t)i * (size_t)n_paths + found);
-    R.olabel.resize((size_t)total); R.graph.resize((size_t)total); R.ac.resize((size_t)total);
-    bool ok = true;
-    for (int32_t k = 0; k < total && ok; ++k) {
-      const size_t aidx = (size_t)parcs[(size_t)i * (size_t)out_cap + (size_t)k];
-      if (aidx >= L.a.size()) { ok = false; break; }
-      R.olabel[(size_t)k] = L.a[aidx].z;
-      R.graph[(size_t)k] = L.w[aidx].x;
-      R.ac[(size_t)k] = L.w[aidx].y;
-    }
-    if (!ok) continue;
+    if (total > out_cap || !map_paths(found, total, poff + (size_t)i * (size_t)(n_paths + 1), ptot + (size_t)i * (size_t)n_paths,
+                                      parcs + (size_t)i * (size_t)out_cap, L.a, L.w, R))
+      continue;
     if (detached) { d->pf_nbp[(size_t)c] = R; d->pf_nbp_have[(size_t)c] = 1; }
     // a channel that still holds the very utterance: wfst_decoder_get_nbest_paths(channel, n, 1, NULL, NULL) finds the work done
     if (d->h_state[c] == 2 && (!detached || (d->det_cached[(size_t)c] && d->pf_epoch[(size_t)i] == d->fin_epoch[(size_t)c]))) d->nbp_cache[(size_t)c] = R;
@@ -2761,21 +2831,7 @@ int wfst_decoder_get_prefetched_nbest_paths(wfst_decoder *d, int32_t channel, in
   *total_arcs = 0;
   if (d->pf_nbp_have.empty() || !d->pf_nbp_have[(size_t)channel])
     return fail(WFST_E_STATE, "no harvested detached prefetch with an n-best has covered this channel (or its lattice was beyond the prefetch's bounds)");
-  const wfst_decoder::NbPaths &R = d->pf_nbp[(size_t)channel];
-  const int32_t found = (int32_t)R.tot.size(), total = (int32_t)R.olabel.size();
-  *n_paths = found;
-  *total_arcs = total;
-  if (found > cap_paths || total > cap_arcs) return fail(WFST_E_CAPACITY, "n-best larger than the given capacities");
-  for (int32_t q = 0; q <= found; ++q)
-    if (path_off) path_off[q] = R.off[(size_t)q];
-  for (int32_t q = 0; q < found; ++q)
-    if (path_tot) path_tot[q] = R.tot[(size_t)q];
-  for (int32_t q = 0; q < total; ++q) {
-    if (a_olabel) a_olabel[q] = R.olabel[(size_t)q];
-    if (a_graph) a_graph[q] = R.graph[(size_t)q];
-    if (a_acoustic) a_acoustic[q] = R.ac[(size_t)q];
-  }
-  return WFST_OK;
+  return copy_paths(d->pf_nbp[(size_t)channel], cap_paths, cap_arcs, n_paths, total_arcs, path_off, path_tot, a_olabel, a_graph, a_acoustic);
 }
 
 // Waits for a prefetch in flight and takes its lattices over (what the next prefetch, or any other use of the determinizer, does
@@ -2800,22 +2856,24 @@ int wfst_decoder_get_prefetched_lattice(wfst_decoder *d, int32_t channel, int32_
   *n_arcs = 0;
   if (d->pf_have.empty() || !d->pf_have[(size_t)channel]) return fail(WFST_E_STATE, "no harvested detached prefetch has covered this channel");
   const wfst_decoder::DetLattice &L = d->pf_cache[(size_t)channel];
-  if (L.err & kDetErrCtl) return fail_ctl_error(channel, L.err & ~kDetErrCtl);
-  if (L.err == 2) return fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": raw lattice larger than the determinizer takes");
-  if (L.err) return fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": the subset construction outgrew its workspace (lattice not determinizable within bounds)");
-  *n_states = L.n_states;
-  *n_arcs = (int32_t)L.a.size();
-  if (L.n_states > cap_states || (int32_t)L.a.size() > cap_arcs) return fail(WFST_E_CAPACITY, "lattice larger than the given capacities");
-  for (int32_t s = 0; s < L.n_states; ++s)
-    if (st_final) st_final[s] = s >= L.n_proper ? 1 : 0;
-  for (size_t k = 0; k < L.a.size(); ++k) {
-    if (a_src) a_src[k] = L.a[k].x;
-    if (a_dst) a_dst[k] = L.a[k].y;
-    if (a_ilabel) a_ilabel[k] = 0;
-    if (a_olabel) a_olabel[k] = L.a[k].z;
-    if (a_graph) a_graph[k] = L.w[k].x;
-    if (a_acoustic) a_acoustic[k] = L.w[k].y;
-  }
+  if (L.err) return det_error(d, channel, L.err);
+  return copy_lattice(L.n_states, nullptr, L.n_proper, L.a, L.w, cap_states, cap_arcs, n_states, n_arcs, st_final, a_src, a_dst, a_ilabel,
+                      a_olabel, a_graph, a_acoustic);
+}
+
+// GetLattice's launch over `list` (workspace slot i = list[i]; live: mid-utterance channels, their lattices emitted first); res = the
+// launch's result words, on their way (the stream is not synchronised)
+static int determinize_list(wfst_decoder *d, const std::vector<int32_t> &list, bool live, int32_t use_final_probs, std::vector<int32_t> &res) {
+  const int32_t *dev;
+  int32_t cnt;
+  const int rc = stage_channels(d, list.data(), (int32_t)list.size(), &dev, &cnt);
+  if (rc != WFST_OK) return rc;
+  if (live) launch_lattice_emit(d->D, dev, cnt, use_final_probs ? 1 : 0, d->stream);
+  d->post_dev_list.clear();   // (the slots are about to hold other lattices than the last batched call's)
+  launch_determinize(d->D, d->det, dev, cnt, d->stream);
+  HIP_TRY(hipGetLastError());
+  res.resize((size_t)cnt * 4);
+  HIP_TRY(hipMemcpyAsync(res.data(), d->det.result, res.size() * 4, hipMemcpyDeviceToHost, d->stream));
   return WFST_OK;
 }
 
@@ -2831,77 +2889,36 @@ int wfst_decoder_get_determinized_lattice(wfst_decoder *d, int32_t channel, int3
   *n_states = 0;
   *n_arcs = 0;
   if (!live && !use_final_probs) return WFST_OK;  // as GetRawLattice (base-inl.h:879-884)
-  DetDev &X = d->det;
-  {
-    const int rcw = ensure_det_workspace(d);
-    if (rcw != WFST_OK) return rcw;
-    const int rcp = finish_prefetch(d);   // (the workspace slots are the prefetch's until it is harvested)
-    if (rcp != WFST_OK) return rcp;
-  }
+  int rc = ensure_det_workspace(d);
+  if (rc != WFST_OK) return rc;
+  rc = finish_prefetch(d);   // (the workspace slots are the prefetch's until it is harvested)
+  if (rc != WFST_OK) return rc;
   // a live channel's result is kept for as long as the channel has not moved on (the size query and the fetch of one request
   // are two calls: the second reuses the first's work)
   const bool live_hit = live && d->det_live_nd[(size_t)channel] == d->h_decoded[channel] &&
                         d->det_live_final[(size_t)channel] == (use_final_probs ? 1 : 0);
-  const bool only = d->det_only == channel;   // (determinize_alone: this channel alone, into workspace slot 0, not from a cache)
-  if (only || (live && !live_hit) || (!live && !d->det_cached[channel])) {
+  if ((live && !live_hit) || (!live && !d->det_cached[channel])) {
     // which channels: mid-utterance just this one (its lists are resolved first); after FinalizeDecoding every
     // finalized channel not determinized yet (their lists were resolved by FinalizeDecoding), det_slots per launch
     std::vector<int32_t> all;
-    if (live || only) all.push_back(channel);
+    if (live) all.push_back(channel);
     else
       for (int c = 0; c < d->n_channels; ++c)
         if (d->h_state[c] == 2 && !d->det_cached[c]) all.push_back(c);
     for (size_t first = 0; first < all.size(); first += (size_t)d->det_slots) {
       const std::vector<int32_t> list(all.begin() + (long)first, all.begin() + (long)std::min(all.size(), first + (size_t)d->det_slots));
-      const int32_t *dev;
-      int32_t cnt;
-      int rc = stage_channels(d, list.data(), (int32_t)list.size(), &dev, &cnt);
+      std::vector<int32_t> res;
+      rc = determinize_list(d, list, live, use_final_probs, res);
       if (rc != WFST_OK) return rc;
-      if (live) launch_lattice_emit(d->D, dev, cnt, use_final_probs ? 1 : 0, d->stream);
-      d->post_dev_list.clear();   // (the slots are about to hold other lattices than the last batched call's)
-      launch_determinize(d->D, X, dev, cnt, d->stream);
-      HIP_TRY(hipGetLastError());
-      std::vector<int32_t> res((size_t)cnt * 4);
-      HIP_TRY(hipMemcpyAsync(res.data(), X.result, res.size() * 4, hipMemcpyDeviceToHost, d->stream));
       rc = harvest_determinized(d, list, res, live, use_final_probs);
       if (rc != WFST_OK) return rc;
     }
   }
   const wfst_decoder::DetLattice &L = d->det_cache[(size_t)channel];
-  if (L.err & kDetErrCtl) return fail_ctl_error(channel, L.err & ~kDetErrCtl);
-  if (L.err == 2)
-    return fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": raw lattice larger than the determinizer takes (" +
-                                     std::to_string(X.raw_states_cap) + " states / " + std::to_string(X.raw_arcs_cap) + " arcs)");
-  if (L.err)
-    return fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": the subset construction outgrew its workspace (lattice not determinizable within bounds)");
+  if (L.err) return det_error(d, channel, L.err);
   // the raw lattice's own "no lattice" cases (a frame without tokens, nothing decoded) give an empty result here too
-  *n_states = L.n_states;
-  *n_arcs = (int32_t)L.a.size();
-  if (L.n_states > cap_states || (int32_t)L.a.size() > cap_arcs) return fail(WFST_E_CAPACITY, "lattice larger than the given capacities");
-  for (int32_t s = 0; s < L.n_states; ++s)
-    if (st_final) st_final[s] = s >= L.n_proper ? 1 : 0;
-  for (size_t k = 0; k < L.a.size(); ++k) {
-    if (a_src) a_src[k] = L.a[k].x;
-    if (a_dst) a_dst[k] = L.a[k].y;
-    if (a_ilabel) a_ilabel[k] = 0;
-    if (a_olabel) a_olabel[k] = L.a[k].z;
-    if (a_graph) a_graph[k] = L.w[k].x;
-    if (a_acoustic) a_acoustic[k] = L.w[k].y;
-  }
-  return WFST_OK;
-}
-
-// The determinized lattice of ONE channel into workspace slot 0 (a cached host copy of an earlier batch determinization does not
-// hold the device copy any more): the other finalized channels are hidden from the batch sweep for the call.
-static int determinize_alone(wfst_decoder *d, int32_t channel, int32_t use_final_probs, int32_t *ns, int32_t *na) {
-  d->post_dev_list.clear();   // (slot 0 is about to hold another lattice)
-  // (det_only: the call below determinizes exactly this channel, afresh, whatever is cached and whichever other channels are
-  // finalized -- also when it is the decoder's first determinizer use and the caches do not exist yet)
-  d->det_only = channel;
-  int rc = wfst_decoder_get_determinized_lattice(d, channel, use_final_probs, 0, 0, ns, na, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  d->det_only = -1;
-  if (rc != WFST_OK && !(rc == WFST_E_CAPACITY && *ns > 0)) return rc;
-  return WFST_OK;
+  return copy_lattice(L.n_states, nullptr, L.n_proper, L.a, L.w, cap_states, cap_arcs, n_states, n_arcs, st_final, a_src, a_dst, a_ilabel,
+                      a_olabel, a_graph, a_acoustic);
 }
 
 // ComposeLattice with the old LM and with the new one over the determinized lattices of workspace slots [0, cnt), on the device, in ONE
@@ -2931,11 +2948,145 @@ static int compose_slots(wfst_decoder *d, const wfst_lm *old_lm, const wfst_lm *
   HIP_TRY(hipStreamSynchronize(d->stream));
   return WFST_OK;
 }
-static int compose_slot0(wfst_decoder *d, const wfst_lm *old_lm, const wfst_lm *new_lm, int32_t res[4]) {
-  int rc = compose_slots(d, old_lm, new_lm, 1, res);
-  if (rc != WFST_OK) return rc;
-  if (res[2] != 0) return fail(WFST_E_CAPACITY, "the composed lattice outgrew the composition workspace (" + std::to_string(d->cmp.pair_cap) + " states / " + std::to_string(d->cmp.arc_cap) + " arcs)");
+
+// A caller's bounds on NShortestPath per lattice: the partial-path lists and the paths' arcs at most; the one-wave kernel for lattices
+// of <= small_states states and <= 64 paths (equal-cost paths may come out in another order than the 1024-thread kernel's); where the
+// caller goes when the path workspace does not fit (a capacity then; null: no fallback, a device error)
+struct NbestBounds { int64_t list_cap, out_cap; int32_t small_states; const char *fallback; };
+static constexpr NbestBounds kNbestBatch = {1ll << 24, 1ll << 22, 1024, "ask channel by channel: wfst_decoder_get_nbest_paths"};
+static constexpr NbestBounds kNbestAlone = {1ll << 26, 1ll << 24, 0, nullptr};   // (a gigabyte of partial paths at most)
+
+// NShortestPath (n paths) over the lattices of workspace slots [0, cnt), synchronously: P says where they sit on the device (a, w,
+// res, fin and their strides), lats holds their arcs, fetched; paths[i] = the paths of list[i]'s lattice
+static int nbest_slots(wfst_decoder *d, NbPathsDev P, int32_t n, const std::vector<int32_t> &list,
+                       const std::vector<wfst_decoder::RescLattice> &lats, const NbestBounds &b, std::vector<wfst_decoder::NbPaths> &paths) {
+  const int32_t cnt = (int32_t)list.size();
+  int32_t ns_max = 1, na_max = 1;
+  for (const wfst_decoder::RescLattice &L : lats) { ns_max = std::max(ns_max, L.n_states); na_max = std::max(na_max, (int32_t)L.a.size()); }
+  P.n = n;
+  P.ws_ints = nbest_ws_ints(ns_max, na_max);
+  P.list_cap = std::min<int64_t>((int64_t)ns_max * n + 1, b.list_cap);
+  P.out_cap = (int32_t)std::min<int64_t>((int64_t)n * ns_max, b.out_cap);
+  // (every buffer grows on its own size: callers use them in different shapes.  The batch's workspace is the per-lattice worst case
+  // times the batch; where the device cannot give that much, GpuBatchDecoder::GetNbests asks channel by channel)
+  auto grow = [&](auto &buf, int64_t need) -> bool { return (int64_t)buf.n >= need || buf.alloc((size_t)need) == hipSuccess; };
+  if (!grow(d->np_ws, P.ws_ints * cnt) || !grow(d->np_lists, P.list_cap * cnt) || !grow(d->np_arcs, (int64_t)P.out_cap * cnt) ||
+      !grow(d->np_off, (int64_t)(n + 1) * cnt) || !grow(d->np_tot, (int64_t)n * cnt) || !grow(d->np_out, 4ll * cnt)) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(d->stream);   // (the lattices' fetch into lats may still be under way)
+    const std::string what = "n-best: no device memory for the path workspace of " + std::to_string(cnt) + " lattice(s), " + std::to_string(n) + " paths each";
+    return b.fallback ? fail(WFST_E_CAPACITY, what + ": " + b.fallback) : fail(WFST_E_DEVICE, what);
+  }
+  P.ws = d->np_ws.p; P.lists = d->np_lists.p;
+  P.out = d->np_out.p; P.out_off = d->np_off.p; P.out_tot = d->np_tot.p; P.out_arcs = d->np_arcs.p;
+  launch_nbest_paths(P, cnt, d->stream, (ns_max <= b.small_states && n <= 64) ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> pout((size_t)cnt * 4), poff((size_t)cnt * (size_t)(n + 1));
+  std::vector<float> ptot((size_t)cnt * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(pout.data(), P.out, pout.size() * 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(poff.data(), P.out_off, poff.size() * 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(ptot.data(), P.out_tot, ptot.size() * 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  for (size_t i = 0; i < (size_t)cnt; ++i) {
+    if (lats[i].n_states <= 0) pout[4 * i] = pout[4 * i + 1] = 0;   // (no lattice: no paths)
+    else if (pout[4 * i + 2] == 3) return fail(WFST_E_DEVICE, "n-best: the lattice has a cycle");
+    else if (pout[4 * i + 2] != 0)
+      return fail(WFST_E_CAPACITY, "n-best: channel " + std::to_string(list[i]) + ": " + std::to_string(n) + " paths over " +
+                                       std::to_string(lats[i].n_states) + " states outgrew the path workspace" +
+                                       (b.fallback ? std::string(" (") + b.fallback + ")" : std::string()));
+  }
+  std::vector<std::vector<int32_t>> arcs((size_t)cnt);
+  for (size_t i = 0; i < (size_t)cnt; ++i) {
+    arcs[i].resize((size_t)pout[4 * i + 1]);
+    if (!arcs[i].empty())
+      HIP_TRY(hipMemcpyAsync(arcs[i].data(), P.out_arcs + i * (size_t)P.out_cap, arcs[i].size() * 4, hipMemcpyDeviceToHost, d->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  paths.assign((size_t)cnt, wfst_decoder::NbPaths());
+  for (size_t i = 0; i < (size_t)cnt; ++i)
+    if (!map_paths(pout[4 * i], pout[4 * i + 1], &poff[i * (size_t)(n + 1)], &ptot[i * (size_t)n], arcs[i].data(), lats[i].a, lats[i].w, paths[i]))
+      return fail(WFST_E_DEVICE, "n-best: channel " + std::to_string(list[i]) + ": a path through an arc outside the lattice");
   return WFST_OK;
+}
+
+// The rest of GetLattice and GetNbest for channels whose determinized lattices sit in workspace slots [0, cnt) -- list[i]'s in slot i,
+// dres its result words: with LMs ComposeLattice with the old one and with the new one (unless the slots hold that already), the
+// lattices fetched (lats[i]: list[i]'s; with LMs and no paths asked for, its final flags too), and with n_paths > 0 NShortestPath on
+// them (paths[i]).  The batch runs it per chunk, the per-channel calls on the one lattice postprocess_alone put in slot 0.
+static int postprocess_slots(wfst_decoder *d, const std::vector<int32_t> &list, const std::vector<int32_t> &dres, const wfst_lm *old_lm,
+                             const wfst_lm *new_lm, int32_t n_paths, const NbestBounds &b, std::vector<wfst_decoder::RescLattice> &lats,
+                             std::vector<wfst_decoder::NbPaths> &paths) {
+  const int32_t cnt = (int32_t)list.size();
+  for (int i = 0; i < cnt; ++i)
+    if (dres[(size_t)4 * i + 2]) return det_error(d, list[(size_t)i], dres[(size_t)4 * i + 2]);
+  std::vector<int32_t> cres;
+  if (old_lm) {
+    const bool det_held = slots_hold(d, list);   // (and their composition under these very LMs?)
+    if (det_held && d->post_dev_o == old_lm && d->post_dev_n == new_lm && d->post_dev_cres.size() == (size_t)cnt * 4) {
+      cres = d->post_dev_cres;
+    } else {
+      cres.resize((size_t)cnt * 4);
+      const int rc = compose_slots(d, old_lm, new_lm, cnt, cres.data());
+      if (rc != WFST_OK) return rc;
+      for (int i = 0; i < cnt; ++i)
+        if (cres[(size_t)4 * i + 2] != 0)
+          return fail(WFST_E_CAPACITY, "channel " + std::to_string(list[(size_t)i]) + ": the composed lattice outgrew the composition workspace (" +
+                                           std::to_string(d->cmp.pair_cap) + " states / " + std::to_string(d->cmp.arc_cap) + " arcs)");
+      if (det_held) { d->post_dev_cres = cres; d->post_dev_o = old_lm; d->post_dev_n = new_lm; }
+    }
+  }
+  const std::vector<int32_t> &lres = old_lm ? cres : dres;   // {states, arcs, ...} of the lattices the paths / the fetch are taken from
+  const int4 *la = old_lm ? d->cmp.out_a : d->det.out_a;
+  const float2 *lw = old_lm ? d->cmp.out_w : d->det.out_w;
+  const int64_t lstride = old_lm ? d->cmp.arc_cap : d->det.out_cap;
+  // the lattices' arcs (the paths report labels and costs of their arcs; the lattice fetch returns them)
+  lats.assign((size_t)cnt, wfst_decoder::RescLattice());
+  for (int i = 0; i < cnt; ++i) {
+    wfst_decoder::RescLattice &L = lats[(size_t)i];
+    L.n_states = std::max(0, lres[(size_t)4 * i]);
+    const size_t na = (size_t)std::max(0, lres[(size_t)4 * i + 1]);
+    L.a.resize(na);
+    L.w.resize(na);
+    if (na) {
+      HIP_TRY(hipMemcpyAsync(L.a.data(), la + (size_t)i * (size_t)lstride, na * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
+      HIP_TRY(hipMemcpyAsync(L.w.data(), lw + (size_t)i * (size_t)lstride, na * sizeof(float2), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (old_lm && !n_paths && L.n_states) {
+      L.fin.resize((size_t)L.n_states);
+      HIP_TRY(hipMemcpyAsync(L.fin.data(), d->cmp.out_fin + (size_t)i * (size_t)d->cmp.pair_cap, L.fin.size() * 4, hipMemcpyDeviceToHost, d->stream));
+    }
+  }
+  if (!n_paths) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return WFST_OK;
+  }
+  NbPathsDev P = {};
+  P.a = la; P.w = lw; P.res = old_lm ? d->cmp.result : d->det.result; P.fin = old_lm ? d->cmp.out_fin : nullptr;
+  P.in_stride = lstride; P.fin_stride = old_lm ? d->cmp.pair_cap : 0;
+  return nbest_slots(d, P, n_paths, list, lats, b, paths);
+}
+
+// GetLattice's second pass / GetNbest of ONE channel, computed now (mid-utterance too): its determinized lattice alone into workspace
+// slot 0 (a cached host copy of an earlier batch determinization does not hold the device copy any more), then the batch's chunk body
+// over it.  No lattice: lats stays empty.
+static int postprocess_alone(wfst_decoder *d, int32_t channel, int32_t use_final_probs, const wfst_lm *old_lm, const wfst_lm *new_lm,
+                             int32_t n_paths, std::vector<wfst_decoder::RescLattice> &lats, std::vector<wfst_decoder::NbPaths> &paths) {
+  const bool live = d->h_state[channel] == 1;
+  if (!live && !use_final_probs) return WFST_OK;   // as GetRawLattice (base-inl.h:879-884)
+  HIP_TRY(hipSetDevice(d->device));
+  int rc = ensure_det_workspace(d);
+  if (rc != WFST_OK) return rc;
+  rc = finish_prefetch(d);   // (the workspace slots are the prefetch's until it is harvested)
+  if (rc != WFST_OK) return rc;
+  std::vector<int32_t> res;
+  rc = determinize_list(d, {channel}, live, use_final_probs, res);
+  if (rc != WFST_OK) return rc;
+  rc = harvest_determinized(d, {channel}, res, live, use_final_probs);
+  if (rc != WFST_OK) return rc;
+  const wfst_decoder::DetLattice &L = d->det_cache[(size_t)channel];
+  if (L.err) return det_error(d, channel, L.err);
+  if (L.n_states == 0) return WFST_OK;   // no lattice (as wfst_decoder_get_raw_lattice)
+  return postprocess_slots(d, {channel}, {L.n_states, (int32_t)L.a.size(), 0, L.n_proper}, old_lm, new_lm, n_paths, kNbestAlone, lats, paths);
 }
 
 // ---- the service's post-processing as a BATCH (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:50-105: GetLattice, its second LM pass
@@ -2967,13 +3118,12 @@ static int postprocess_batch(wfst_decoder *d, const int32_t *channels, int32_t n
   if (d->resc_cache.empty()) { d->resc_cache.resize((size_t)d->n_channels); d->nbp_cache.resize((size_t)d->n_channels); }
   wfst_decoder::PostKey key;
   key.o = old_lm; key.n = new_lm; key.use_final = use_final_probs ? 1 : 0; key.n_paths = n_paths; key.valid = true;
-  auto store_empty = [&](int c) {
-    key.decoded = d->h_decoded[c];
-    if (n_paths) { wfst_decoder::NbPaths &R = d->nbp_cache[(size_t)c]; R = wfst_decoder::NbPaths(); R.key = key; R.off.assign(1, 0); }
-    else { wfst_decoder::RescLattice &R = d->resc_cache[(size_t)c]; R = wfst_decoder::RescLattice(); R.key = key; }
-  };
   if (!use_final_probs) {   // a finalized channel without final-probs has no lattice (GetRawLattice, base-inl.h:879-884)
-    for (int c : all) store_empty(c);
+    for (int c : all) {
+      key.decoded = d->h_decoded[c];
+      if (n_paths) d->nbp_cache[(size_t)c] = wfst_decoder::NbPaths{key, {0}, {}, {}, {}, {}};
+      else d->resc_cache[(size_t)c] = wfst_decoder::RescLattice{key, 0, {}, {}, {}};
+    }
     return WFST_OK;
   }
   if (all.empty()) return WFST_OK;
@@ -2981,152 +3131,31 @@ static int postprocess_batch(wfst_decoder *d, const int32_t *channels, int32_t n
   if (rc != WFST_OK) return rc;
   rc = finish_prefetch(d);
   if (rc != WFST_OK) return rc;
-  DetDev &X = d->det;
   const size_t chunk = (size_t)std::max(1, std::min(d->det_slots, 128));
+  std::vector<wfst_decoder::RescLattice> lats;
+  std::vector<wfst_decoder::NbPaths> paths;
   for (size_t first = 0; first < all.size(); first += chunk) {
     const std::vector<int32_t> list(all.begin() + (long)first, all.begin() + (long)std::min(all.size(), first + chunk));
-    int32_t cnt = (int32_t)list.size();
-    std::vector<int32_t> decoded((size_t)cnt);
-    for (int i = 0; i < cnt; ++i) decoded[(size_t)i] = d->h_decoded[list[(size_t)i]];
-    // (the determinizer's slots still hold these very lattices -- a prefetch harvested just before, or the batch of second passes
-    // just before this batch of n-best requests?  The composition's too, under the same LMs?)
-    const bool det_held = list == d->post_dev_list && decoded == d->post_dev_decoded;
-    const bool held = det_held && (!old_lm || (d->post_dev_o == old_lm && d->post_dev_n == new_lm && d->post_dev_cres.size() == (size_t)cnt * 4));
-    std::vector<int32_t> dres, cres;
-    if (held) {
-      dres = d->post_dev_dres;
-      if (old_lm) cres = d->post_dev_cres;
-    } else {
-      if (det_held) {
-        dres = d->post_dev_dres;   // GetLattice is done (wfst_decoder_prefetch_determinized ran it beside the best paths): the second pass starts here
-      } else {
-        d->post_dev_list.clear();
-        const int32_t *dev;
-        rc = stage_channels(d, list.data(), (int32_t)list.size(), &dev, &cnt);
-        if (rc != WFST_OK) return rc;
-        // GetLattice: the determinized lattices of the chunk, list[i] in workspace slot i
-        launch_determinize(d->D, X, dev, cnt, d->stream);
-        HIP_TRY(hipGetLastError());
-        dres.resize((size_t)cnt * 4);
-        HIP_TRY(hipMemcpyAsync(dres.data(), X.result, dres.size() * 4, hipMemcpyDeviceToHost, d->stream));
-        rc = read_ctl(d);  // synchronises the stream
-        if (rc != WFST_OK) return rc;
-        rc = check_ctl_errors(d);
-        if (rc != WFST_OK) return rc;
-      }
-      for (int i = 0; i < cnt; ++i) {
-        if (dres[(size_t)4 * i + 2] == 2)
-          return fail(WFST_E_CAPACITY, "channel " + std::to_string(list[(size_t)i]) + ": raw lattice larger than the determinizer takes");
-        if (dres[(size_t)4 * i + 2])
-          return fail(WFST_E_CAPACITY, "channel " + std::to_string(list[(size_t)i]) + ": the subset construction outgrew its workspace");
-      }
-      // ... the second LM pass: ComposeLattice with the old LM and with the new one
-      if (old_lm) {
-        cres.resize((size_t)cnt * 4);
-        rc = compose_slots(d, old_lm, new_lm, cnt, cres.data());
-        if (rc != WFST_OK) return rc;
-        for (int i = 0; i < cnt; ++i)
-          if (cres[(size_t)4 * i + 2] == 1)
-            return fail(WFST_E_CAPACITY, "channel " + std::to_string(list[(size_t)i]) + ": the composed lattice outgrew the composition workspace");
-      }
-      d->post_dev_list = list; d->post_dev_decoded = decoded; d->post_dev_dres = dres; d->post_dev_cres = cres;
-      d->post_dev_o = old_lm; d->post_dev_n = new_lm;
+    // GetLattice: the determinized lattices of the chunk, list[i] in workspace slot i -- unless the slots hold these very lattices
+    // already (a prefetch harvested just before, or the batch of second passes just before this batch of n-best requests)
+    if (!slots_hold(d, list)) {
+      std::vector<int32_t> dres;
+      rc = determinize_list(d, list, false, use_final_probs, dres);
+      if (rc != WFST_OK) return rc;
+      rc = read_ctl(d);  // synchronises the stream
+      if (rc != WFST_OK) return rc;
+      rc = check_ctl_errors(d);
+      if (rc != WFST_OK) return rc;
+      hold_slots(d, list, dres);
     }
-    const std::vector<int32_t> &lres = old_lm ? cres : dres;   // {states, arcs, ...} of the lattices the paths / the fetch are taken from
-    const int4 *la = old_lm ? d->cmp.out_a : X.out_a;
-    const float2 *lw = old_lm ? d->cmp.out_w : X.out_w;
-    const int64_t lstride = old_lm ? d->cmp.arc_cap : X.out_cap;
-    // the lattices' arcs (the paths report labels and costs of their arcs; the lattice fetch returns them)
-    std::vector<std::vector<int4>> ha((size_t)cnt);
-    std::vector<std::vector<float2>> hw((size_t)cnt);
-    std::vector<std::vector<int32_t>> hfin((size_t)cnt);
-    for (int i = 0; i < cnt; ++i) {
-      const size_t na = (size_t)std::max(0, lres[(size_t)4 * i + 1]), nsi = (size_t)std::max(0, lres[(size_t)4 * i]);
-      ha[(size_t)i].resize(na);
-      hw[(size_t)i].resize(na);
-      if (na) {
-        HIP_TRY(hipMemcpyAsync(ha[(size_t)i].data(), la + (size_t)i * (size_t)lstride, na * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipMemcpyAsync(hw[(size_t)i].data(), lw + (size_t)i * (size_t)lstride, na * sizeof(float2), hipMemcpyDeviceToHost, d->stream));
-      }
-      if (old_lm && !n_paths && nsi) {
-        hfin[(size_t)i].resize(nsi);
-        HIP_TRY(hipMemcpyAsync(hfin[(size_t)i].data(), d->cmp.out_fin + (size_t)i * (size_t)d->cmp.pair_cap, nsi * 4, hipMemcpyDeviceToHost, d->stream));
-      }
-    }
-    if (!n_paths) {
-      HIP_TRY(hipStreamSynchronize(d->stream));
-      for (int i = 0; i < cnt; ++i) {
-        const int c = list[(size_t)i];
-        wfst_decoder::RescLattice &R = d->resc_cache[(size_t)c];
-        key.decoded = d->h_decoded[c];
-        R.key = key;
-        R.n_states = std::max(0, lres[(size_t)4 * i]);
-        R.a.swap(ha[(size_t)i]);
-        R.w.swap(hw[(size_t)i]);
-        R.fin.swap(hfin[(size_t)i]);
-      }
-      continue;
-    }
-    // ... NShortestPath: one workgroup per lattice
-    int32_t ns_max = 1, na_max = 1;
-    for (int i = 0; i < cnt; ++i) { ns_max = std::max(ns_max, lres[(size_t)4 * i]); na_max = std::max(na_max, lres[(size_t)4 * i + 1]); }
-    NbPathsDev P = {};
-    P.a = la; P.w = lw; P.res = old_lm ? d->cmp.result : X.result; P.fin = old_lm ? d->cmp.out_fin : nullptr;
-    P.in_stride = lstride; P.fin_stride = old_lm ? d->cmp.pair_cap : 0;
-    const int64_t nmax = std::max(ns_max, na_max);
-    P.ws_ints = 7ll * ns_max + 4ll * nmax + na_max + 16;
-    P.list_cap = std::min<int64_t>((int64_t)ns_max * n_paths + 1, 1ll << 24);
-    const int64_t out_cap = std::min<int64_t>((int64_t)n_paths * ns_max, 1ll << 22);
-    // (every buffer grows on its OWN size: the batch call and the single-channel call share them with different shapes.  The path
-    // workspace is the per-lattice worst case times the batch: where the device cannot give that much the call reports a capacity,
-    // not a device error -- GpuBatchDecoder::GetNbests then asks channel by channel, which needs one lattice's worth)
-    auto grow = [&](auto &buf, int64_t need) -> bool { return (int64_t)buf.n >= need || buf.alloc((size_t)need) == hipSuccess; };
-    if (!grow(d->np_ws, P.ws_ints * cnt) || !grow(d->np_lists, P.list_cap * cnt) || !grow(d->np_arcs, out_cap * cnt) ||
-        !grow(d->np_off, (int64_t)(n_paths + 1) * cnt) || !grow(d->np_tot, (int64_t)n_paths * cnt) || !grow(d->np_out, 4ll * cnt)) {
-      (void)hipGetLastError();
-      return fail(WFST_E_CAPACITY, "n-best: no device memory for the path workspace of " + std::to_string(cnt) + " lattices at once (" +
-                                       std::to_string(n_paths) + " paths each): ask channel by channel (wfst_decoder_get_nbest_paths)");
-    }
-    P.n = n_paths;
-    P.ws = d->np_ws.p; P.lists = d->np_lists.p;
-    P.out = d->np_out.p; P.out_off = d->np_off.p; P.out_tot = d->np_tot.p;
-    P.out_arcs = d->np_arcs.p; P.out_cap = (int32_t)out_cap;
-    launch_nbest_paths(P, cnt, d->stream, /*small=*/(ns_max <= 1024 && n_paths <= 64) ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> pout((size_t)cnt * 4), poff((size_t)cnt * (size_t)(n_paths + 1));
-    std::vector<float> ptot((size_t)cnt * (size_t)n_paths);
-    HIP_TRY(hipMemcpyAsync(pout.data(), P.out, pout.size() * 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(poff.data(), P.out_off, poff.size() * 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(ptot.data(), P.out_tot, ptot.size() * 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    for (int i = 0; i < cnt; ++i) {
-      const int32_t *o = &pout[(size_t)4 * i];
-      if (lres[(size_t)4 * i] <= 0) continue;   // (no lattice: no paths)
-      if (o[2] == 3) return fail(WFST_E_DEVICE, "n-best: the lattice has a cycle");
-      if (o[2] != 0) return fail(WFST_E_CAPACITY, "n-best: channel " + std::to_string(list[(size_t)i]) + " outgrew the batch's path workspace (ask for it alone: wfst_decoder_get_nbest_paths)");
-    }
-    for (int i = 0; i < cnt; ++i) {
-      const int c = list[(size_t)i];
-      wfst_decoder::NbPaths &R = d->nbp_cache[(size_t)c];
-      R = wfst_decoder::NbPaths();
+    const std::vector<int32_t> dres = d->post_dev_dres;
+    rc = postprocess_slots(d, list, dres, old_lm, new_lm, n_paths, kNbestBatch, lats, paths);
+    if (rc != WFST_OK) return rc;
+    for (size_t i = 0; i < list.size(); ++i) {
+      const int c = list[i];
       key.decoded = d->h_decoded[c];
-      R.key = key;
-      const int32_t found = lres[(size_t)4 * i] > 0 ? pout[(size_t)4 * i] : 0, total = lres[(size_t)4 * i] > 0 ? pout[(size_t)4 * i + 1] : 0;
-      R.off.assign(1, 0);
-      if (found) R.off.assign(poff.begin() + (long)i * (n_paths + 1), poff.begin() + (long)i * (n_paths + 1) + found + 1);
-      R.tot.assign(ptot.begin() + (long)i * n_paths, ptot.begin() + (long)i * n_paths + found);
-      std::vector<int32_t> arcs((size_t)total);
-      if (total) {
-        HIP_TRY(hipMemcpyAsync(arcs.data(), P.out_arcs + (size_t)i * (size_t)P.out_cap, (size_t)total * 4, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipStreamSynchronize(d->stream));
-      }
-      R.olabel.resize((size_t)total); R.graph.resize((size_t)total); R.ac.resize((size_t)total);
-      for (int32_t k = 0; k < total; ++k) {
-        const size_t aidx = (size_t)arcs[(size_t)k];
-        R.olabel[(size_t)k] = ha[(size_t)i][aidx].z;
-        R.graph[(size_t)k] = hw[(size_t)i][aidx].x;
-        R.ac[(size_t)k] = hw[(size_t)i][aidx].y;
-      }
+      if (n_paths) { d->nbp_cache[(size_t)c] = std::move(paths[i]); d->nbp_cache[(size_t)c].key = key; }
+      else { d->resc_cache[(size_t)c] = std::move(lats[i]); d->resc_cache[(size_t)c].key = key; }
     }
   }
   return WFST_OK;
@@ -3149,64 +3178,23 @@ int wfst_decoder_get_rescored_lattice(wfst_decoder *d, int32_t channel, int32_t 
                                       int32_t *a_src, int32_t *a_dst, int32_t *a_ilabel, int32_t *a_olabel, float *a_graph, float *a_acoustic) {
   if (!d || channel < 0 || channel >= d->n_channels || !n_states || !n_arcs || !old_lm || !new_lm) return fail(WFST_E_ARG, "bad argument");
   if (old_lm->device != d->device || new_lm->device != d->device) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
-  // GetLattice of the service under --use-second: the determinized lattice first (its device copy stays in workspace slot 0 when this
-  // channel is determinized alone) ...
-  int32_t ns = 0, na = 0;
   *n_states = 0;
   *n_arcs = 0;
   if (d->h_state[channel] == 0) return fail(WFST_E_STATE, "GetLattice before InitDecoding");
   if (!d->D.lattice) return fail(WFST_E_STATE, "GetLattice needs a decoder created with wfst_limits.lattice_links > 0");
-  if (!d->resc_cache.empty()) {   // a result of wfst_decoder_rescore_lattices for this very request
-    const wfst_decoder::RescLattice &R = d->resc_cache[(size_t)channel];
-    if (R.key.valid && R.key.o == old_lm && R.key.n == new_lm && R.key.use_final == (use_final_probs ? 1 : 0) && R.key.decoded == d->h_decoded[channel] && d->h_state[channel] == 2) {
-      *n_states = R.n_states;
-      *n_arcs = (int32_t)R.a.size();
-      if (R.n_states > cap_states || (int32_t)R.a.size() > cap_arcs) return fail(WFST_E_CAPACITY, "lattice larger than the given capacities");
-      for (int32_t q = 0; q < R.n_states; ++q)
-        if (st_final) st_final[q] = R.fin[(size_t)q];
-      for (size_t q = 0; q < R.a.size(); ++q) {
-        if (a_src) a_src[q] = R.a[q].x;
-        if (a_dst) a_dst[q] = R.a[q].y;
-        if (a_ilabel) a_ilabel[q] = 0;
-        if (a_olabel) a_olabel[q] = R.a[q].z;
-        if (a_graph) a_graph[q] = R.w[q].x;
-        if (a_acoustic) a_acoustic[q] = R.w[q].y;
-      }
-      return WFST_OK;
-    }
+  // a result of wfst_decoder_rescore_lattices for this very request, or else GetLattice of the service under --use-second now: the
+  // determinized lattice, then ComposeLattice with the old LM and with the new one, on the device
+  const wfst_decoder::RescLattice *R = d->resc_cache.empty() ? nullptr : &d->resc_cache[(size_t)channel];
+  std::vector<wfst_decoder::RescLattice> lats;
+  std::vector<wfst_decoder::NbPaths> paths;
+  if (!R || !(R->key.valid && R->key.o == old_lm && R->key.n == new_lm && R->key.use_final == (use_final_probs ? 1 : 0) &&
+              R->key.decoded == d->h_decoded[channel] && d->h_state[channel] == 2)) {
+    const int rc = postprocess_alone(d, channel, use_final_probs, old_lm, new_lm, 0, lats, paths);
+    if (rc != WFST_OK || lats.empty()) return rc;
+    R = &lats[0];
   }
-  int rc = determinize_alone(d, channel, use_final_probs, &ns, &na);
-  if (rc != WFST_OK) return rc;
-  if (ns == 0) return WFST_OK;   // no lattice (as wfst_decoder_get_raw_lattice)
-  HIP_TRY(hipSetDevice(d->device));
-  // ... then ComposeLattice with the old LM and with the new one, on the device
-  int32_t res[4];
-  rc = compose_slot0(d, old_lm, new_lm, res);
-  if (rc != WFST_OK) return rc;
-  CmpDev &Y = d->cmp;
-  *n_states = res[0];
-  *n_arcs = res[1];
-  if (res[0] > cap_states || res[1] > cap_arcs) return fail(WFST_E_CAPACITY, "lattice larger than the given capacities");
-  std::vector<int4> oa((size_t)res[1]);
-  std::vector<float2> ow((size_t)res[1]);
-  std::vector<int32_t> fin((size_t)res[0]);
-  if (res[1]) {
-    HIP_TRY(hipMemcpyAsync(oa.data(), Y.out_a, oa.size() * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(ow.data(), Y.out_w, ow.size() * sizeof(float2), hipMemcpyDeviceToHost, d->stream));
-  }
-  if (res[0]) HIP_TRY(hipMemcpyAsync(fin.data(), Y.out_fin, fin.size() * 4, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  for (int32_t s = 0; s < res[0]; ++s)
-    if (st_final) st_final[s] = fin[(size_t)s];
-  for (int32_t k = 0; k < res[1]; ++k) {
-    if (a_src) a_src[k] = oa[(size_t)k].x;
-    if (a_dst) a_dst[k] = oa[(size_t)k].y;
-    if (a_ilabel) a_ilabel[k] = 0;
-    if (a_olabel) a_olabel[k] = oa[(size_t)k].z;
-    if (a_graph) a_graph[k] = ow[(size_t)k].x;
-    if (a_acoustic) a_acoustic[k] = ow[(size_t)k].y;
-  }
-  return WFST_OK;
+  return copy_lattice(R->n_states, R->fin.data(), 0, R->a, R->w, cap_states, cap_arcs, n_states, n_arcs, st_final, a_src, a_dst, a_ilabel,
+                      a_olabel, a_graph, a_acoustic);
 }
 
 int wfst_decoder_get_nbest_paths(wfst_decoder *d, int32_t channel, int32_t n, int32_t use_final_probs, const wfst_lm *old_lm,
@@ -3219,99 +3207,18 @@ int wfst_decoder_get_nbest_paths(wfst_decoder *d, int32_t channel, int32_t n, in
   *total_arcs = 0;
   if (d->h_state[channel] == 0) return fail(WFST_E_STATE, "GetNbest before InitDecoding");
   if (!d->D.lattice) return fail(WFST_E_STATE, "GetNbest needs a decoder created with wfst_limits.lattice_links > 0");
-  if (!d->nbp_cache.empty()) {   // a result of wfst_decoder_nbest_paths_batch for this very request
-    const wfst_decoder::NbPaths &R = d->nbp_cache[(size_t)channel];
-    if (R.key.valid && R.key.o == old_lm && R.key.n == new_lm && R.key.use_final == (use_final_probs ? 1 : 0) && R.key.n_paths == n &&
-        R.key.decoded == d->h_decoded[channel] && d->h_state[channel] == 2) {
-      const int32_t found = (int32_t)R.tot.size(), total = (int32_t)R.olabel.size();
-      *n_paths = found;
-      *total_arcs = total;
-      if (found > cap_paths || total > cap_arcs) return fail(WFST_E_CAPACITY, "n-best larger than the given capacities");
-      for (int32_t q = 0; q <= found; ++q)
-        if (path_off) path_off[q] = R.off[(size_t)q];
-      for (int32_t q = 0; q < found; ++q)
-        if (path_tot) path_tot[q] = R.tot[(size_t)q];
-      for (int32_t q = 0; q < total; ++q) {
-        if (a_olabel) a_olabel[q] = R.olabel[(size_t)q];
-        if (a_graph) a_graph[q] = R.graph[(size_t)q];
-        if (a_acoustic) a_acoustic[q] = R.ac[(size_t)q];
-      }
-      return WFST_OK;
-    }
+  // a result of wfst_decoder_nbest_paths_batch for this very request, or else now: GetLattice (the determinized lattice; with LMs
+  // its second-pass rescoring), then NShortestPath on the device
+  const wfst_decoder::NbPaths *R = d->nbp_cache.empty() ? nullptr : &d->nbp_cache[(size_t)channel];
+  std::vector<wfst_decoder::RescLattice> lats;
+  std::vector<wfst_decoder::NbPaths> paths;
+  if (!R || !(R->key.valid && R->key.o == old_lm && R->key.n == new_lm && R->key.use_final == (use_final_probs ? 1 : 0) && R->key.n_paths == n &&
+              R->key.decoded == d->h_decoded[channel] && d->h_state[channel] == 2)) {
+    const int rc = postprocess_alone(d, channel, use_final_probs, old_lm, new_lm, n, lats, paths);
+    if (rc != WFST_OK || lats.empty()) return rc;
+    R = &paths[0];
   }
-  // GetLattice (the determinized lattice, into workspace slot 0; with LMs its second-pass rescoring) ...
-  int32_t ns = 0, na = 0;
-  int rc = determinize_alone(d, channel, use_final_probs, &ns, &na);
-  if (rc != WFST_OK) return rc;
-  if (ns == 0) return WFST_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  NbPathsDev P = {};
-  std::vector<int4> oa;
-  std::vector<float2> ow;
-  if (old_lm) {
-    int32_t res[4];
-    rc = compose_slot0(d, old_lm, new_lm, res);
-    if (rc != WFST_OK) return rc;
-    ns = res[0];
-    na = res[1];
-    if (ns == 0) return WFST_OK;   // (nothing reaches a final state of both LMs)
-    P.a = d->cmp.out_a; P.w = d->cmp.out_w; P.res = d->cmp.result; P.fin = d->cmp.out_fin;
-    oa.resize((size_t)na);
-    ow.resize((size_t)na);
-    if (na) {
-      HIP_TRY(hipMemcpyAsync(oa.data(), d->cmp.out_a, oa.size() * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
-      HIP_TRY(hipMemcpyAsync(ow.data(), d->cmp.out_w, ow.size() * sizeof(float2), hipMemcpyDeviceToHost, d->stream));
-    }
-  } else {
-    P.a = d->det.out_a; P.w = d->det.out_w; P.res = d->det.result; P.fin = nullptr;
-  }
-  // ... then NShortestPath on the device
-  const int64_t nmax = std::max(ns, na);
-  const int64_t ws_ints = 7ll * ns + 4ll * nmax + na + 16;
-  const int64_t list_cap = std::min<int64_t>((int64_t)ns * n + 1, 1ll << 26);   // (a gigabyte of partial paths at most)
-  const int64_t out_cap = std::min<int64_t>((int64_t)n * ns, 1ll << 24);
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  if ((int64_t)d->np_ws.n < ws_ints) HIP_TRY(d->np_ws.alloc((size_t)ws_ints));
-  if ((int64_t)d->np_lists.n < list_cap) HIP_TRY(d->np_lists.alloc((size_t)list_cap));
-  if ((int64_t)d->np_arcs.n < out_cap) HIP_TRY(d->np_arcs.alloc((size_t)out_cap));
-  if ((int64_t)d->np_off.n < n + 1) HIP_TRY(d->np_off.alloc((size_t)n + 1));
-  if ((int64_t)d->np_tot.n < n) HIP_TRY(d->np_tot.alloc((size_t)n));   // (its own size: the batch call sizes the two differently)
-  if ((int64_t)d->np_out.n < 4) HIP_TRY(d->np_out.alloc(4));
-  P.n = n;
-  P.ws = d->np_ws.p; P.ws_ints = (int64_t)d->np_ws.n;
-  P.lists = d->np_lists.p; P.list_cap = (int64_t)d->np_lists.n;
-  P.out = d->np_out.p; P.out_off = d->np_off.p; P.out_tot = d->np_tot.p;
-  P.out_arcs = d->np_arcs.p; P.out_cap = (int32_t)std::min<int64_t>((int64_t)d->np_arcs.n, 0x7fffffff);
-  launch_nbest_paths(P, 1, d->stream);
-  HIP_TRY(hipGetLastError());
-  int32_t out[4];
-  HIP_TRY(hipMemcpyAsync(out, P.out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  if (out[2] == 3) return fail(WFST_E_DEVICE, "n-best: the lattice has a cycle");
-  if (out[2] != 0) return fail(WFST_E_CAPACITY, "n-best: " + std::to_string(n) + " paths over " + std::to_string(ns) + " states outgrew the path workspace");
-  *n_paths = out[0];
-  *total_arcs = out[1];
-  if (out[0] > cap_paths || out[1] > cap_arcs) return fail(WFST_E_CAPACITY, "n-best larger than the given capacities");
-  std::vector<int32_t> off((size_t)out[0] + 1), arcs((size_t)out[1]);
-  std::vector<float> tot((size_t)out[0]);
-  HIP_TRY(hipMemcpyAsync(off.data(), P.out_off, off.size() * 4, hipMemcpyDeviceToHost, d->stream));
-  if (out[0]) HIP_TRY(hipMemcpyAsync(tot.data(), P.out_tot, tot.size() * 4, hipMemcpyDeviceToHost, d->stream));
-  if (out[1]) HIP_TRY(hipMemcpyAsync(arcs.data(), P.out_arcs, arcs.size() * 4, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  const wfst_decoder::DetLattice &L = d->det_cache[(size_t)channel];
-  for (int32_t p = 0; p <= out[0]; ++p)
-    if (path_off) path_off[p] = off[(size_t)p];
-  for (int32_t p = 0; p < out[0]; ++p)
-    if (path_tot) path_tot[p] = tot[(size_t)p];
-  for (int32_t k = 0; k < out[1]; ++k) {
-    const size_t a = (size_t)arcs[(size_t)k];
-    const int4 A = old_lm ? oa[a] : L.a[a];
-    const float2 W = old_lm ? ow[a] : L.w[a];
-    if (a_olabel) a_olabel[k] = A.z;
-    if (a_graph) a_graph[k] = W.x;
-    if (a_acoustic) a_acoustic[k] = W.y;
-  }
-  return WFST_OK;
+  return copy_paths(*R, cap_paths, cap_arcs, n_paths, total_arcs, path_off, path_tot, a_olabel, a_graph, a_acoustic);
 }
 
 int wfst_decoder_get_stats(wfst_decoder *d, int32_t channel, int64_t stats[8]) {
