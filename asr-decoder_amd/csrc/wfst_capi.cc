@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <array>
@@ -61,6 +62,7 @@ struct wfst_graph {
   int32_t max_col = 0;  // largest log-likelihood column any arc reads
   int32_t max_olabel = 0, min_olabel = 0;  // over all arcs (biglm: the LMs must know every word)
   std::vector<int32_t> ilabel_host;  // original ilabels (re-mapped when tid2pdf changes)
+  std::vector<int32_t> tid2phone;    // wfst_graph_set_tid2phone (entry 0 unused); empty: none set
   std::vector<uint16_t> code_host;   // degree code of the target state of every arc slot (fused rows; wfst_device.h)
   int32_t packed = 0;                // the arcs' first word = column | code << kColBits (ilabels below 2^20)
   DevBuf<int4> arcs;  // interleaved rows: header + arcs per state
@@ -279,6 +281,15 @@ struct wfst_decoder {
   std::vector<char> lat_cached;
   char *lat_pin = nullptr;  // pinned staging for that fetch
   DevBuf<int32_t> bp_all;   // GetBestPath: {n_hops | ilabel | olabel | graph | acoustic} of the listed channels, one D2H copy
+  // wfst_decoder_set_endpoint_config / _endpoint_detected: the config (its silence list copied), the silence bitmap over
+  // transition-ids on the device, the channel list and the per-channel results {trailing frames, relative cost, error}
+  bool ep_set = false;
+  wfst_endpoint_config ep_cfg;
+  std::vector<int32_t> ep_sil;
+  int32_t ep_ntid = 0;
+  DevBuf<uint32_t> ep_bits;
+  DevBuf<int32_t> ep_chan, ep_out;
+  int32_t *ep_pin = nullptr;   // page-locked: [n_channels] channel list, then [3 n_channels] results
   char *bp_pin = nullptr;   // its pinned staging
   size_t bp_pin_bytes = 0;
   size_t lat_pin_bytes = 0;
@@ -324,6 +335,8 @@ struct wfst_decoder {
     if (pf_ev_done) (void)hipEventDestroy(pf_ev_done);
     if (lat_pin) (void)hipHostFree(lat_pin);
     if (bp_pin) (void)hipHostFree(bp_pin);
+    if (ep_pin) (void)hipHostFree(ep_pin);
+    ep_bits.release(); ep_chan.release(); ep_out.release();
     if (hist_slab) (void)hipFree(hist_slab);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
     for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
@@ -763,6 +776,17 @@ int wfst_graph_set_tid2pdf(wfst_graph *g, const int32_t *tid2pdf, int32_t n_tid)
   if (!g) return fail(WFST_E_ARG, "NULL graph");
   HIP_TRY(hipSetDevice(g->device));
   return upload_columns(g, tid2pdf, n_tid, nullptr);
+}
+
+int wfst_graph_set_tid2phone(wfst_graph *g, const int32_t *tid2phone, int32_t n_tid) {   // TransitionModel::TransitionIdToPhone
+  if (!g || !tid2phone || n_tid < 1) return fail(WFST_E_ARG, "NULL graph / tid2phone, or n_tid < 1");
+  for (int32_t il : g->ilabel_host)
+    if (il != kHeaderLabel && il > n_tid) return fail(WFST_E_ARG, "arc ilabel outside tid2phone range");
+  for (int32_t t = 1; t <= n_tid; ++t)
+    if (tid2phone[t] < 0) return fail(WFST_E_ARG, "negative phone in tid2phone");
+  g->tid2phone.assign(tid2phone, tid2phone + (size_t)n_tid + 1);
+  g->tid2phone[0] = 0;
+  return WFST_OK;
 }
 
 int wfst_graph_info(const wfst_graph *g, int32_t *start, int32_t *final_state, int32_t *n_states,
@@ -3283,6 +3307,122 @@ int wfst_decoder_get_degraded_frames(wfst_decoder *d, int32_t channel, int32_t *
   { const int32_t c = channel; const int rc = results_stream_behind(d, &c, 1, &st); if (rc != WFST_OK) return rc; }   // (behind the channel's own work, not the others')
   HIP_TRY(hipMemcpyAsync(n_frames, d->degraded.p + channel, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return WFST_OK;
+}
+
+// ---- endpoint detection (Kaldi's online2/online-endpoint.{h,cc}) ---------------------------------------------------------------------
+void wfst_endpoint_config_default(wfst_endpoint_config *c) {   // OnlineEndpointConfig's defaults
+  const float inf = std::numeric_limits<float>::infinity();
+  c->rule[0] = {0, 5.0f, inf, 0.0f};
+  c->rule[1] = {1, 0.5f, 2.0f, 0.0f};
+  c->rule[2] = {1, 1.0f, 8.0f, 0.0f};
+  c->rule[3] = {1, 2.0f, inf, 0.0f};
+  c->rule[4] = {0, 0.0f, inf, 20.0f};
+  c->frame_shift = 0.01f;
+  c->n_silence_phones = 0;
+  c->silence_phones = nullptr;
+}
+
+static int check_endpoint_config(const wfst_endpoint_config *c) {
+  if (!c) return fail(WFST_E_ARG, "NULL endpoint config");
+  if (c->n_silence_phones <= 0 || !c->silence_phones) return fail(WFST_E_ARG, "endpoint config: empty silence phone list (--endpoint.silence-phones)");
+  if (!(c->frame_shift > 0.0f)) return fail(WFST_E_ARG, "endpoint config: frame_shift must be > 0");
+  std::vector<int32_t> v(c->silence_phones, c->silence_phones + c->n_silence_phones);
+  std::sort(v.begin(), v.end());
+  if (v[0] <= 0) return fail(WFST_E_ARG, "endpoint config: silence phones must be > 0");
+  if (std::adjacent_find(v.begin(), v.end()) != v.end()) return fail(WFST_E_ARG, "endpoint config: duplicate silence phone");
+  return WFST_OK;
+}
+
+// RuleActivated + EndpointDetected (online-endpoint.cc), f32 throughout
+static int32_t endpoint_rule(const wfst_endpoint_config *c, int32_t num_frames, int32_t trailing_frames, float relative_cost) {
+  if (num_frames == 0) return 0;
+  const float utterance_length = (float)num_frames * c->frame_shift, trailing_silence = (float)trailing_frames * c->frame_shift;
+  const bool contains_nonsilence = utterance_length > trailing_silence;
+  for (int k = 0; k < 5; ++k) {
+    const wfst_endpoint_rule &r = c->rule[k];
+    if ((contains_nonsilence || !r.must_contain_nonsilence) && trailing_silence >= r.min_trailing_silence &&
+        relative_cost <= r.max_relative_cost && utterance_length >= r.min_utterance_length)
+      return k + 1;
+  }
+  return 0;
+}
+
+int wfst_endpoint_rules(const wfst_endpoint_config *cfg, int32_t num_frames_decoded, int32_t trailing_frames, float relative_cost,
+                        int32_t *rule) {
+  if (!rule) return fail(WFST_E_ARG, "NULL rule");
+  const int rc = check_endpoint_config(cfg);
+  if (rc != WFST_OK) return rc;
+  if (num_frames_decoded < 0 || trailing_frames < 0 || trailing_frames > num_frames_decoded)   // online-endpoint.cc: KALDI_ASSERT
+    return fail(WFST_E_ARG, "trailing silence frames outside [0, num_frames_decoded]");
+  *rule = endpoint_rule(cfg, num_frames_decoded, trailing_frames, relative_cost);
+  return WFST_OK;
+}
+
+int wfst_decoder_set_endpoint_config(wfst_decoder *d, const wfst_endpoint_config *cfg) {
+  if (!d) return fail(WFST_E_ARG, "NULL decoder");
+  if (d->D.big) return fail(WFST_E_ARG, "endpoint detection is not supported on biglm decoders (their final costs carry the LM's)");
+  int rc = check_endpoint_config(cfg);
+  if (rc != WFST_OK) return rc;
+  const std::vector<int32_t> &t2p = d->graph->tid2phone;
+  if (t2p.empty()) return fail(WFST_E_STATE, "endpoint config before wfst_graph_set_tid2phone: no transition-id -> phone map");
+  HIP_TRY(hipSetDevice(d->device));
+  const int32_t n_tid = (int32_t)t2p.size() - 1;
+  std::vector<uint32_t> bits((size_t)n_tid / 32 + 1, 0u);
+  for (int32_t t = 1; t <= n_tid; ++t)
+    if (std::find(cfg->silence_phones, cfg->silence_phones + cfg->n_silence_phones, t2p[(size_t)t]) != cfg->silence_phones + cfg->n_silence_phones)
+      bits[(size_t)t >> 5] |= 1u << (t & 31);
+  // (the device may still read the bitmap of an endpoint call of before: every such call has been waited for)
+  if (d->ep_bits.n < bits.size()) HIP_TRY(d->ep_bits.alloc(bits.size()));
+  HIP_TRY(hipMemcpy(d->ep_bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+  if (!d->ep_chan.p) HIP_TRY(d->ep_chan.alloc((size_t)d->n_channels));
+  if (!d->ep_out.p) HIP_TRY(d->ep_out.alloc((size_t)d->n_channels * 3));
+  if (!d->ep_pin) HIP_TRY(hipHostMalloc((void **)&d->ep_pin, (size_t)d->n_channels * 4 * 4, hipHostMallocDefault));
+  d->ep_sil.assign(cfg->silence_phones, cfg->silence_phones + cfg->n_silence_phones);
+  d->ep_cfg = *cfg;
+  d->ep_cfg.silence_phones = d->ep_sil.data();
+  d->ep_ntid = n_tid;
+  d->ep_set = true;
+  return WFST_OK;
+}
+
+int wfst_decoder_endpoint_detected(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t *detected, int32_t *rule,
+                                   int32_t *trailing_frames, float *relative_cost) {
+  if (!d || !channels) return fail(WFST_E_ARG, "NULL decoder / channel list");
+  if (d->D.big) return fail(WFST_E_ARG, "endpoint detection is not supported on biglm decoders (their final costs carry the LM's)");
+  if (!d->ep_set) return fail(WFST_E_STATE, "EndpointDetected before wfst_decoder_set_endpoint_config");
+  if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
+  HIP_TRY(hipSetDevice(d->device));
+  std::vector<char> seen((size_t)d->n_channels, 0);
+  for (int i = 0; i < n; ++i) {
+    const int c = channels[i];
+    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
+    if (seen[(size_t)c]) return fail(WFST_E_ARG, "duplicate channel in list");
+    seen[(size_t)c] = 1;
+    if (d->h_state[(size_t)c] == 0) return fail(WFST_E_STATE, "EndpointDetected before InitDecoding");
+    if (d->h_state[(size_t)c] == 2) return fail(WFST_E_STATE, "EndpointDetected after FinalizeDecoding");
+  }
+  hipStream_t st;
+  int rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
+  if (rc != WFST_OK) return rc;
+  int32_t *pin_chan = d->ep_pin, *pin_out = d->ep_pin + d->n_channels;
+  memcpy(pin_chan, channels, (size_t)n * 4);   // (the last endpoint call has been waited for: its copies are done)
+  HIP_TRY(hipMemcpyAsync(d->ep_chan.p, pin_chan, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  launch_endpoint(d->D, d->ep_chan.p, n, d->ep_bits.p, d->ep_ntid, d->ep_out.p, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(pin_out, d->ep_out.p, (size_t)n * 3 * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i) {
+    const int32_t tr = pin_out[3 * i];
+    float rel;
+    memcpy(&rel, &pin_out[3 * i + 1], 4);
+    const int32_t nd = d->h_decoded[(size_t)channels[i]];
+    const int32_t r = (tr < 0 || pin_out[3 * i + 2]) ? 0 : endpoint_rule(&d->ep_cfg, nd, std::min(tr, nd), rel);
+    if (detected) detected[i] = r != 0;
+    if (rule) rule[i] = r;
+    if (trailing_frames) trailing_frames[i] = pin_out[3 * i + 2] ? -1 : tr;
+    if (relative_cost) relative_cost[i] = pin_out[3 * i + 2] ? std::numeric_limits<float>::infinity() : rel;
+  }
   return WFST_OK;
 }
 

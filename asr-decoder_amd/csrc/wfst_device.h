@@ -486,6 +486,9 @@ void launch_lattice_emit(const DecoderDev &D, const int32_t *chan_list_dev, int 
 void launch_best_path(const DecoderDev &D, const int32_t *chan_list_dev, int n, int use_final,
                       int cap, int32_t *ilabel, int32_t *olabel, float *graph, float *ac,
                       int32_t *n_hops, int32_t *chain_scratch, hipStream_t s);
+// endpoint inputs of the listed channels (endpoint_kernel): out[3 i ..] = {trailing silence frames, final relative cost, error}
+void launch_endpoint(const DecoderDev &D, const int32_t *chan_list_dev, int n, const uint32_t *sil_bits, int n_tid, int32_t *out,
+                     hipStream_t s);
 
 }  // namespace wfst
 #endif

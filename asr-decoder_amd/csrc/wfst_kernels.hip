@@ -4065,6 +4065,112 @@ constexpr int kBpThreads = 256;
 constexpr int kBpChainLds = 4096;   // hops of the backpointer walk kept in LDS (the walk's own list; longer paths go on in HBM)
 constexpr int kBpFrames = 3072;   // utterances up to this many frames keep their frame bounds in LDS (longer ones read them from HBM)
 
+// ---- traceback helpers shared by best_path_kernel and endpoint_kernel ----------------------------------------------------
+// biglm: LM score of arc a taken from the predecessor token's LM state, and the pair state it leads to (-1: a pair no token was
+// ever created with); plain decoders: 0
+template <bool kBig>
+__device__ __forceinline__ int bp_arc_lm(const DecoderDev &D, int c, const int32_t *tok_lm, int prev, int a, float *lm_score) {
+  *lm_score = 0.0f;
+  if constexpr (!kBig) return 0;
+  else {
+    const int ol = D.g.arc_olabel[a];
+    if (ol == 0) return tok_lm[prev];
+    int n1, n2;
+    *lm_score = lm_step(D, c, tok_lm[prev], ol, &n1, &n2);
+    return pair_find(D, c, n1, n2);
+  }
+}
+
+// The predecessor of token t, won by an epsilon arc (kPrevUnresolved): the token of the arc's source state `need` on t's own frame
+// [lo, hi), found by the whole workgroup (kBpThreads lanes) in one scan; written to *found (LDS), left alone if there is none.
+// biglm: several tokens may sit on the source state, one per LM state -- the one whose LM state and cost lead to t over the arc.
+template <bool kBig>
+__device__ __forceinline__ void bp_scan_eps_pred(const DecoderDev &D, int c, const int4 *tok, const int32_t *tok_lm, int lo, int hi,
+                                                 int need, int t, int *found) {
+  const int tid = threadIdx.x;
+  constexpr int kScanU = 4;   // states of the frame in flight per thread
+  for (int i0 = lo + tid; i0 < hi; i0 += kBpThreads * kScanU) {
+    int sx[kScanU];
+#pragma unroll
+    for (int u = 0; u < kScanU; ++u) {
+      const int i = i0 + u * kBpThreads;
+      sx[u] = i < hi ? reinterpret_cast<const int *>(tok + i)[0] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < kScanU; ++u) {
+      const int i = i0 + u * kBpThreads;
+      if (sx[u] != need) continue;
+      [[maybe_unused]] const int4 S = tok[i];
+      if constexpr (kBig) {
+        const int4 T = tok[t];
+        const int a = (int)((uint32_t)T.w & kArcMask);
+        const int ol = D.g.arc_olabel[a];
+        int nlm = tok_lm[i];
+        float lm_score = 0.0f;
+        if (ol != 0) {
+          int n1, n2;
+          lm_score = lm_step(D, c, tok_lm[i], ol, &n1, &n2);
+          nlm = pair_find(D, c, n1, n2);
+        }
+        const float tot = __int_as_float(S.y) + (__int_as_float(D.g.arcs[a].z) + lm_score);
+        if (nlm != tok_lm[t] || __float_as_int(tot) != T.y) continue;
+      }
+      *found = i;
+    }
+  }
+}
+
+// The arc of the hop into token t from its predecessor prev (>= 0) as GetBestPath reports it: TraceBackBestPath takes the FIRST
+// link bp->tok; links are prepended in arc order (base-inl.h:340-341, 1169-1186), so a surviving parallel arc of higher index
+// shadows the winning one.  foff: the channel's frame bounds (nd + 2 of them); m_last: the last PruneActiveTokens pass
+// ((nd - 1) / prune_interval * prune_interval); extra0: the path's extra cost after FinalizeDecoding (biglm; else 0).
+// *eps: the hop is an epsilon arc (its predecessor is on t's own frame); *llrow: the log-likelihood row the arc scored against.
+template <bool kBig>
+__device__ __forceinline__ int bp_resolve_hop(const DecoderDev &D, int c, const ChanCtl *ctl, const int4 *tok, const int32_t *tok_lm,
+                                              const int32_t *foff, int nd, int m_last, float extra0, int t, int prev, bool *eps_out,
+                                              const float **llrow_out) {
+  const float *cut = D.cutoff_hist + (size_t)c * (D.max_frames + 2);
+  const float *ll = D.ll_base[c];
+  const int4 T = tok[t];
+  // frame of t: the f with frame_off[f] <= t < frame_off[f+1]
+  int lo = 0, hi = nd + 1;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (foff[mid] <= t) lo = mid; else hi = mid;
+  }
+  const int fr = lo;
+  const int4 Pt = tok[prev];
+  const float cb = __int_as_float(Pt.y), ct = __int_as_float(T.y);
+  const int warc = (int)((uint32_t)T.w & kArcMask);
+  const bool eps = prev >= foff[fr];  // backpointer on the same frame <=> epsilon hop
+  const int fbp = eps ? fr : fr - 1;
+  const uint2 si = make_uint2((uint32_t)Pt.x + 1u, (uint32_t)D.g.arcs[Pt.x].x);
+  const int ne = (int)(si.y & kEpsMask);
+  const int ahi = eps ? (int)si.x + ne : (int)si.x + ne + (int)(si.y >> kEpsBits);
+  const bool pruned_once = ctl->finalized || m_last >= fbp + 1;
+  const float *llrow = ll + (size_t)(eps ? 0 : fbp) * D.stride;
+  int chosen = warc;
+  for (int a = ahi - 1; a > warc; --a) {
+    const int4 B = D.g.arcs[a];
+    if (B.w != T.x) continue;
+    float alt_g = __int_as_float(B.z);
+    if constexpr (kBig) {
+      float ls;
+      if (bp_arc_lm<kBig>(D, c, tok_lm, prev, a, &ls) != tok_lm[t]) continue;  // leads to another (state, LM state) token
+      alt_g = __int_as_float(B.z) + ls;
+    }
+    const float alt_ac = eps ? 0.f : -llrow[B.x & D.g.col_mask];
+    const float alt_tot = eps ? cb + alt_g : (cb + alt_ac) + alt_g;
+    if (!(alt_tot < cut[fr])) continue;  // link never created
+    if (pruned_once && ((ctl->finalized ? extra0 : 0.0f) + (alt_tot - ct)) > D.lattice_beam) continue;  // base-inl.h:524-532
+    chosen = a;
+    break;
+  }
+  *eps_out = eps;
+  *llrow_out = llrow;
+  return chosen;
+}
+
 // kBig (biglm): final costs carry the LM's (ComputeFinalCosts, biglm.h:160-215), hop graph costs are arc
 // weight + lm_score, an epsilon-won token's predecessor is found by (state, LM pair, cost), and after
 // FinalizeDecoding the reference's final pruning can leave NO token (its final_best_cost ranges over
@@ -4182,39 +4288,7 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
     __syncthreads();
     if (s_need >= 0) {
       ++n_unres;
-      const int need = s_need, t = s_t;
-      constexpr int kScanU = 4;   // states of the frame in flight per thread
-      for (int i0 = s_lo + tid; i0 < s_hi; i0 += kBpThreads * kScanU) {
-        int sx[kScanU];
-#pragma unroll
-        for (int u = 0; u < kScanU; ++u) {
-          const int i = i0 + u * kBpThreads;
-          sx[u] = i < s_hi ? reinterpret_cast<const int *>(tok + i)[0] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < kScanU; ++u) {
-        const int i = i0 + u * kBpThreads;
-        if (sx[u] != need) continue;
-        [[maybe_unused]] const int4 S = tok[i];
-        if constexpr (kBig) {
-          // several tokens may sit on the arc's source state, one per LM state: the predecessor is the
-          // one whose LM state and cost lead to this token over the winning arc
-          const int4 T = tok[t];
-          const int a = (int)((uint32_t)T.w & kArcMask);
-          const int ol = D.g.arc_olabel[a];
-          int nlm = tok_lm[i];
-          float lm_score = 0.0f;
-          if (ol != 0) {
-            int n1, n2;
-            lm_score = lm_step(D, c, tok_lm[i], ol, &n1, &n2);
-            nlm = pair_find(D, c, n1, n2);
-          }
-          const float tot = __int_as_float(S.y) + (__int_as_float(D.g.arcs[a].z) + lm_score);
-          if (nlm != tok_lm[t] || __float_as_int(tot) != T.y) continue;
-        }
-        s_found = i;
-        }
-      }
+      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_lo, s_hi, s_need, s_t, &s_found);
       __syncthreads();
       if (tid == 0) s_t = s_found;  // -1 (never expected) ends the walk
       if (tid == 0 && (D.dbg & 32)) tb_scan += wall_clock64() - tw0;
@@ -4233,8 +4307,6 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
   __syncthreads();
   int32_t *il = o_il + (size_t)bi * cap, *ol = o_ol + (size_t)bi * cap;
   float *og = o_g + (size_t)bi * cap, *oa = o_ac + (size_t)bi * cap;
-  const float *cut = D.cutoff_hist + (size_t)c * (D.max_frames + 2);
-  const float *ll = D.ll_base[c];
   // forward links of frame f have met PruneForwardLinks iff a PruneActiveTokens pass started at
   // NumFramesDecoded() = m >= f+1 (base-inl.h:660-661, 445-476) or FinalizeDecoding ran
   const int m_last = ((nd - 1) / D.prune_interval) * D.prune_interval;
@@ -4242,68 +4314,20 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
   for (int pos = tid; pos < len; pos += kBpThreads) {
     auto hop_at = [&](int q) { const int p = len - 1 - q; return p < kBpChainLds ? s_chain[p] : ch[cap - 1 - p]; };
     const int t = hop_at(pos);
-    const int4 T = tok[t];
     const int prev = pos > 0 ? hop_at(pos - 1) : -1;  // the chain itself holds the resolved backpointers
     if (prev < 0) {  // base-inl.h:1193-1198
       il[pos] = 0; ol[pos] = 0; og[pos] = 0.f; oa[pos] = 0.f;
       continue;
     }
-    // frame of t: the f with frame_off[f] <= t < frame_off[f+1]
-    int lo = 0, hi = nd + 1;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (foff[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int fr = lo;
-    const int4 Pt = tok[prev];
-    const float cb = __int_as_float(Pt.y), ct = __int_as_float(T.y);
-    const int warc = (int)((uint32_t)T.w & kArcMask);
-    const bool eps = prev >= foff[fr];  // backpointer on the same frame <=> epsilon hop
-    const int fbp = eps ? fr : fr - 1;
-    const uint2 si = make_uint2((uint32_t)Pt.x + 1u, (uint32_t)D.g.arcs[Pt.x].x);
-    const int ne = (int)(si.y & kEpsMask);
-    const int ahi = eps ? (int)si.x + ne : (int)si.x + ne + (int)(si.y >> kEpsBits);
-    const bool pruned_once = ctl->finalized || m_last >= fbp + 1;
-    const float *llrow = ll + (size_t)(eps ? 0 : fbp) * D.stride;
-    // biglm: LM score of an arc taken from the predecessor's LM state, and the pair state it leads to
-    // (-1: a pair no token was ever created with)
-    auto arc_lm = [&](int a, float *lm_score) -> int {
-      *lm_score = 0.0f;
-      if constexpr (!kBig) return 0;
-      else {
-        const int ol = D.g.arc_olabel[a];
-        if (ol == 0) return tok_lm[prev];
-        int n1, n2;
-        *lm_score = lm_step(D, c, tok_lm[prev], ol, &n1, &n2);
-        return pair_find(D, c, n1, n2);
-      }
-    };
-    int chosen = warc;
-    // TraceBackBestPath takes the FIRST link bp->tok; links are prepended in arc order
-    // (base-inl.h:340-341, 1169-1186), so a surviving parallel arc of higher index shadows the
-    // winning one.
-    for (int a = ahi - 1; a > warc; --a) {
-      const int4 B = D.g.arcs[a];
-      if (B.w != T.x) continue;
-      float alt_g = __int_as_float(B.z);
-      if constexpr (kBig) {
-        float ls;
-        if (arc_lm(a, &ls) != tok_lm[t]) continue;  // leads to another (state, LM state) token
-        alt_g = __int_as_float(B.z) + ls;
-      }
-      const float alt_ac = eps ? 0.f : -llrow[B.x & D.g.col_mask];
-      const float alt_tot = eps ? cb + alt_g : (cb + alt_ac) + alt_g;
-      if (!(alt_tot < cut[fr])) continue;  // link never created
-      if (pruned_once && ((ctl->finalized ? extra0 : 0.0f) + (alt_tot - ct)) > D.lattice_beam) continue;  // base-inl.h:524-532
-      chosen = a;
-      break;
-    }
+    bool eps;
+    const float *llrow;
+    const int chosen = bp_resolve_hop<kBig>(D, c, ctl, tok, tok_lm, foff, nd, m_last, extra0, t, prev, &eps, &llrow);
     const int4 C = D.g.arcs[chosen];
     il[pos] = D.g.arc_ilabel[chosen];
     ol[pos] = D.g.arc_olabel[chosen];
     if constexpr (kBig) {
       float ls;
-      arc_lm(chosen, &ls);
+      bp_arc_lm<kBig>(D, c, tok_lm, prev, chosen, &ls);
       og[pos] = __int_as_float(C.z) + ls;  // graph_cost = arc weight + lm_score (biglm.h:380,450)
     } else {
       og[pos] = __int_as_float(C.z);
@@ -4311,6 +4335,128 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
     oa[pos] = eps ? 0.f : -llrow[C.x & D.g.col_mask];
   }
   if (tid == 0 && (D.dbg & 32)) atomicAdd(&D.dbg_t[113], wall_clock64() - tb0);
+}
+
+// =========================================================================================
+// endpoint inputs (Kaldi's online2/online-endpoint.cc: TrailingSilenceLength + FinalRelativeCost), one kBpThreads workgroup per
+// listed channel, mid-utterance.  out[3 i .. 3 i + 2] = {trailing_silence_frames, final_relative_cost (f32 bits), device error}:
+//  - the frontier reduction of best_path_kernel: best_all (BestPathEnd(use_final_probs = false)) and best_fin (the cheapest token
+//    on the super-final state, final weight One); final_relative_cost = best_fin - best_all in f32, +inf without a final token
+//    (ComputeFinalCosts, base-inl.h:670-720);
+//  - the trailing walk from best_all, last hop first, in chunks of kEpChunk hops: lane 0 follows the resolved backpointers (an
+//    epsilon-won token's predecessor: the workgroup's frame scan) into LDS, then wave 0 resolves the chunk's hops in parallel
+//    (bp_resolve_hop: GetBestPath's labels, parallel-arc quirk included) and tests each ilabel against the silence bitmap over
+//    transition-ids.  Epsilon hops (ilabel 0) are skipped, silence hops counted; the walk ends in the chunk that holds the first
+//    non-silence hop, or at the root.
+// trailing_silence_frames = -1: no path (no frame decoded, no token on the frontier, or a device error -- out[3 i + 2] says which).
+// =========================================================================================
+constexpr int kEpChunk = 64;   // hops per chunk: one per lane of wave 0
+__global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, const int32_t *chans, const uint32_t *sil_bits, int n_tid,
+                                                              int32_t *out) {
+  const int bi = blockIdx.x;
+  const int c = chans[bi];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ChanCtl *ctl = D.ctl + c;
+  const int n = ctl->front_count, nd = ctl->n_decoded, err = ctl->error;
+  if (err || n == 0 || nd <= 0) {   // (no frame decoded: no path, as best_path_kernel has it, base-inl.h:1104-1108)
+    if (tid == 0) { out[3 * bi] = -1; out[3 * bi + 1] = __float_as_int(__builtin_huge_valf()); out[3 * bi + 2] = err; }
+    return;
+  }
+  __shared__ u64 s_all[kBpThreads / 64], s_fin[kBpThreads / 64];
+  const int4 *tok = D.tok + (size_t)c * D.arena_cap;
+  const int fb = ctl->front_begin;
+  u64 best_all = ~0ull, best_fin = ~0ull;
+  for (int i = tid; i < n; i += kBpThreads) {
+    const int4 t = tok[fb + i];
+    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
+    best_all = v < best_all ? v : best_all;
+    if (t.x == D.g.final_state) best_fin = v < best_fin ? v : best_fin;  // IsFinal, optimize-fst.h:189-192
+  }
+  best_all = wave_min_u64(best_all);
+  best_fin = wave_min_u64(best_fin);
+  if (lane == 0) { s_all[wave] = best_all; s_fin[wave] = best_fin; }
+  const int32_t *foff_g = D.frame_off + (size_t)c * (D.max_frames + 2);
+  __shared__ int32_t s_foff[kBpFrames + 2];
+  const bool foff_lds = nd + 2 <= kBpFrames + 2;
+  if (foff_lds) for (int i = tid; i < nd + 2; i += kBpThreads) s_foff[i] = foff_g[i];
+  const int32_t *foff = foff_lds ? s_foff : foff_g;
+  __shared__ int32_t s_tok[kEpChunk + 1];   // the chunk's tokens, last hop first: hop j is s_tok[j] <- s_tok[j + 1] (-1: the root)
+  __shared__ int s_cur, s_k, s_need, s_lo, s_hi, s_found, s_count, s_done;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < kBpThreads / 64; ++w) {
+      best_all = s_all[w] < best_all ? s_all[w] : best_all;
+      best_fin = s_fin[w] < best_fin ? s_fin[w] : best_fin;
+    }
+    const float rel = best_fin == ~0ull ? __builtin_huge_valf() : o2f((uint32_t)(best_fin >> 32)) - o2f((uint32_t)(best_all >> 32));
+    out[3 * bi + 1] = __float_as_int(rel);
+    out[3 * bi + 2] = 0;
+    s_cur = (int)(uint32_t)best_all;
+    s_count = 0;
+    s_done = 0;
+  }
+  const int m_last = ((nd - 1) / D.prune_interval) * D.prune_interval;
+  const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);   // (a degree code may sit above the index)
+  int guard = 0;   // chunks walked (a damaged arena must not hang the device)
+  for (;;) {
+    __syncthreads();
+    if (s_done) break;
+    // fill: up to kEpChunk hops of the chain into LDS
+    if (tid == 0) { s_tok[0] = s_cur; s_k = 0; }
+    for (;;) {
+      __syncthreads();
+      if (tid == 0) {
+        int t = s_tok[s_k], k = s_k;
+        s_need = -1;
+        while (t >= 0 && k < kEpChunk) {
+          const int4 T = tok[t];
+          if (T.z <= kPrevUnresolved) {
+            int lo = 0, hi = nd + 1;  // frame of t: frame_off[f] <= t < frame_off[f+1]
+            while (hi - lo > 1) {
+              const int mid = (lo + hi) >> 1;
+              if (foff[mid] <= t) lo = mid; else hi = mid;
+            }
+            s_lo = foff[lo];
+            s_hi = foff[lo + 1];
+            s_need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
+            s_found = -1;
+            break;
+          }
+          t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : -1;
+          s_tok[++k] = t;
+        }
+        s_k = k;
+      }
+      __syncthreads();
+      if (s_need < 0) break;
+      bp_scan_eps_pred<false>(D, c, tok, nullptr, s_lo, s_hi, s_need, s_tok[s_k], &s_found);
+      __syncthreads();
+      if (tid == 0) { s_tok[s_k + 1] = s_found; ++s_k; }   // (-1, never expected, ends the walk)
+      __syncthreads();
+      if (s_k >= kEpChunk || s_tok[s_k] < 0) break;
+    }
+    __syncthreads();
+    // resolve: hop j = lane of wave 0; 0 epsilon (or the root's hop), 1 silence, 2 anything else
+    if (wave == 0) {
+      const int k = s_k;
+      int kind = 0;
+      if (lane < k && s_tok[lane + 1] >= 0) {
+        bool eps;
+        const float *llrow;
+        const int a = bp_resolve_hop<false>(D, c, ctl, tok, nullptr, foff, nd, m_last, 0.0f, s_tok[lane], s_tok[lane + 1], &eps, &llrow);
+        const int il = D.g.arc_ilabel[a];
+        if (il != 0) kind = (il > 0 && il <= n_tid && ((sil_bits[il >> 5] >> (il & 31)) & 1u)) ? 1 : 2;
+      }
+      const u64 other = __ballot(kind == 2), sil = __ballot(kind == 1);
+      if (lane == 0) {
+        const u64 before = other ? ((1ull << (__ffsll((long long)other) - 1)) - 1ull) : ~0ull;
+        s_count += __popcll(sil & before);
+        s_cur = s_tok[k];
+        if (other || s_cur < 0 || ++guard >= (1 << 18)) s_done = 1;
+      }
+    }
+  }
+  if (tid == 0) out[3 * bi] = s_count;
 }
 
 // GetRawLattice's raw material: every token and link alive right now, resolved to labels and costs, in the
@@ -4646,6 +4792,9 @@ void launch_best_path(const DecoderDev &D, const int32_t *chans, int n, int use_
   else
     hipLaunchKernelGGL(best_path_kernel<false>, dim3(n), dim3(kBpThreads), 0, s, D, chans, use_final, cap, ilabel, olabel, graph,
                        ac, n_hops, chain);
+}
+void launch_endpoint(const DecoderDev &D, const int32_t *chans, int n, const uint32_t *sil_bits, int n_tid, int32_t *out, hipStream_t s) {
+  hipLaunchKernelGGL(endpoint_kernel, dim3(n), dim3(kBpThreads), 0, s, D, chans, sil_bits, n_tid, out);
 }
 void launch_lattice_emit(const DecoderDev &D, const int32_t *chans, int n, int use_final, hipStream_t s);
 void launch_lattice_prune(const DecoderDev &D, const int32_t *chans, int n, hipStream_t s) {

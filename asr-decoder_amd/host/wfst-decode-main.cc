@@ -50,6 +50,14 @@
 //                  the reference's way -- (graph, config) -- and the objects lease channels of shared C-channel device decoders
 //   --pull         the decodable is a plain DecodableInterface: every score goes through LogLikelihood(frame, index) (without it
 //                  the rows are taken in one piece, MatrixDecodable)
+//   --tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.ruleN.{must-contain-nonsilence,min-trailing-silence,
+//                  max-relative-cost,min-utterance-length}=..] [--endpoint.frame-shift=S] [--print-endpoints]
+//                  endpointing, with --chunk=N and --single-stream or --threads=N [--pool=C]: after every chunk EndpointDetected
+//                  (Kaldi's online2/online-endpoint.cc); on an endpoint the segment is finalized and printed as
+//                  "KEY[t_beg,t_end] word-ids..." (frames of the stream), and the decoder starts again on the stream's next rows, as
+//                  the reference's service loop does (v1-asr/asr-source.h:280-287); the stream's end ends its last segment.
+//                  --print-endpoints: "KEY@t endpoint ruleK" before each segment an endpoint ended.  tid2phone: binary int32 array,
+//                  entry 0 unused (TransitionIdToPhone)
 //   --nbest=N      also print the N-best word sequences of every utterance (the service's
 //                  GetNbestTxt, kaldi-online-nnet3-my-decoder.cc:139-150) as "KEY-k w1 w2 ..." to
 //                  stdout and "LOG KEY-k tot_score .. lm_score .." to stderr (lattice mode)
@@ -98,18 +106,19 @@ bool ReadUtt(std::ifstream &in, Utt *u) {
 // DecodableInterface over a host matrix: the shape every reference caller has.
 class HostMatrixDecodable : public MatrixDecodable {
  public:
-  explicit HostMatrixDecodable(const Utt &u) : _u(u), _ready(u.frames) {}
-  float LogLikelihood(int f, int i) override { return _u.m[(size_t)f * _u.cols + i]; }
-  bool IsLastFrame(int f) const override { return f == _u.frames - 1; }
+  // begin: the stream's rows from this frame on (a segment after an endpoint); frame numbers are relative to it
+  explicit HostMatrixDecodable(const Utt &u, int begin = 0) : _u(u), _begin(begin), _ready(u.frames - begin) {}
+  float LogLikelihood(int f, int i) override { return _u.m[(size_t)(_begin + f) * _u.cols + i]; }
+  bool IsLastFrame(int f) const override { return _begin + f == _u.frames - 1; }
   int NumFramesReady() const override { return _ready; }
-  void SetFramesReady(int n) { _ready = std::min(n, _u.frames); }  // streaming: frames that have "arrived"
+  void SetFramesReady(int n) { _ready = std::min(n, _u.frames) - _begin; }  // streaming: frames of the stream that have "arrived"
   int NumIndices() const override { return _u.cols - 1; }
-  const float *HostRows() const override { return _u.m.data(); }
+  const float *HostRows() const override { return _u.m.data() + (size_t)_begin * _u.cols; }
   int Stride() const override { return _u.cols; }
 
  private:
   const Utt &_u;
-  int _ready;
+  int _begin, _ready;
 };
 // ... and as the reference's callers see a decodable: LogLikelihood(frame, index) only, the index a 1-based TRANSITION-ID.  With
 // --tid2pdf it is Kaldi's DecodableMatrixScaledMapped as the reference CLI builds it (kaldi-nnet3bin/kaldi-hclg-my-decoder.cc:107):
@@ -118,17 +127,17 @@ class HostMatrixDecodable : public MatrixDecodable {
 // transition-id.  Without --tid2pdf: M's columns are the indices themselves.
 class PullDecodable : public DecodableInterface {
  public:
-  PullDecodable(const Utt &u, const std::vector<int32_t> *tid2pdf) : _u(u), _map(tid2pdf), _ready(u.frames) {}
-  float LogLikelihood(int f, int i) override { return _u.m[(size_t)f * _u.cols + (_map ? (*_map)[(size_t)i] : i)]; }
-  bool IsLastFrame(int f) const override { return f == _u.frames - 1; }
+  PullDecodable(const Utt &u, const std::vector<int32_t> *tid2pdf, int begin = 0) : _u(u), _map(tid2pdf), _begin(begin), _ready(u.frames - begin) {}
+  float LogLikelihood(int f, int i) override { return _u.m[(size_t)(_begin + f) * _u.cols + (_map ? (*_map)[(size_t)i] : i)]; }
+  bool IsLastFrame(int f) const override { return _begin + f == _u.frames - 1; }
   int NumFramesReady() const override { return _ready; }
-  void SetFramesReady(int n) { _ready = std::min(n, _u.frames); }
+  void SetFramesReady(int n) { _ready = std::min(n, _u.frames) - _begin; }
   int NumIndices() const override { return _map ? (int)_map->size() - 1 : _u.cols - 1; }
 
  private:
   const Utt &_u;
   const std::vector<int32_t> *_map;   // entry 0 unused
-  int _ready;
+  int _begin, _ready;
 };
 }  // namespace
 
@@ -145,9 +154,15 @@ int main(int argc, char **argv) {
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
     std::vector<int> devices(1, 0);
     std::vector<std::string> pos;
+    std::string tid2phone_file;
+    OnlineEndpointConfig ep_opt;
+    bool endpointing = false, print_endpoints = false;
     for (int i = 1; i < argc; ++i) {
       std::string a = argv[i];
-      if (a.compare(0, 10, "--tid2pdf=") == 0) tid2pdf_file = a.substr(10);
+      if (ep_opt.ParseOption(a)) endpointing = true;
+      else if (a.compare(0, 12, "--tid2phone=") == 0) tid2phone_file = a.substr(12);
+      else if (a == "--print-endpoints") print_endpoints = true;
+      else if (a.compare(0, 10, "--tid2pdf=") == 0) tid2pdf_file = a.substr(10);
       else if (a.compare(0, 8, "--batch=") == 0) batch = atoi(a.c_str() + 8);
       else if (a == "--single-stream") single = true;
       else if (a == "--determinize") determinize = true;
@@ -186,11 +201,20 @@ int main(int argc, char **argv) {
     }
     if (pos.size() < 3) {
       std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
-                   "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
+                   "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
+                   "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
       return 1;
     }
     LatticeFasterDecoderConfig opt;
     opt.ReadConfigFile(pos[0]);
+    if (endpointing || !tid2phone_file.empty() || print_endpoints) {
+      // endpointing (v1-asr/asr-source.h:280-287): --tid2phone and --endpoint.silence-phones, a streaming shape, a search without LMs
+      if (tid2phone_file.empty() || ep_opt.silence_phones.empty()) { std::cerr << "endpointing needs --tid2phone=FILE and --endpoint.silence-phones\n"; return 1; }
+      if (chunk <= 0 || !(single || n_threads > 0)) { std::cerr << "endpointing goes with --chunk=N and --single-stream or --threads=N\n"; return 1; }
+      if (!lm_old_file.empty() || !lm_new_file.empty()) { std::cerr << "endpointing is not supported with --lm-old/--lm-new (biglm)\n"; return 1; }
+      ep_opt.SilencePhones();   // (checked here, before any device work)
+      endpointing = true;
+    }
     if (single && devices.size() > 1) { std::cerr << "--devices lists several devices: batch shape only\n"; return 1; }
     // one graph replica per listed device (fsts[0] also serves --single-stream)
     std::vector<std::unique_ptr<Fst> > fsts;
@@ -209,6 +233,14 @@ int main(int argc, char **argv) {
       // the graph's rows read the pdf columns (what DecodableMatrixScaledMapped does with the transition model); --pull: the
       // decodable ALSO maps, as the reference's does -- the decoder then asks it for one transition-id per pdf (Fst::SetTid2Pdf)
       for (auto &f : fsts) f->SetTid2Pdf(tid2pdf);
+    }
+    if (!tid2phone_file.empty()) {   // TransitionModel::TransitionIdToPhone as a table (binary int32, entry 0 unused)
+      std::ifstream t(tid2phone_file.c_str(), std::ios::binary | std::ios::ate);
+      if (!t) { std::cerr << "cannot open " << tid2phone_file << "\n"; return 1; }
+      std::vector<int32_t> tid2phone((size_t)t.tellg() / 4);
+      t.seekg(0);
+      t.read((char *)tid2phone.data(), tid2phone.size() * 4);
+      for (auto &f : fsts) f->SetTid2Phone(tid2phone);
     }
     std::ifstream in(pos[2].c_str(), std::ios::binary);
     if (!in) { std::cerr << "cannot open " << pos[2] << "\n"; return 1; }
@@ -318,6 +350,47 @@ int main(int argc, char **argv) {
       frame_count += u.frames;
       ++num_success;
     };
+    // One stream decoded as the reference's service loop with endpointing does it (v1-asr/asr-source.h:280-287): the rows arrive
+    // --chunk frames at a time; after every AdvanceDecoding, EndpointDetected -- on an endpoint FinalizeDecoding, the segment's
+    // words "KEY[t_beg,t_end] w1 w2 ..." (frames of the stream), InitDecoding, and the decoder goes on with the stream's next rows.
+    // The end of the stream ends the last segment.  --print-endpoints: also "KEY@t endpoint ruleK" at each endpoint.
+    // Returns the lines; *ok: every segment had a path.
+    auto decode_segmented = [&](GpuLatticeDecoder &dec, const Utt &u, bool pull_rows, bool *ok) {
+      std::string text;
+      *ok = true;
+      int begin = 0;
+      while (begin < u.frames) {
+        HostMatrixDecodable md(u, begin);
+        PullDecodable pd(u, tid2pdf.empty() ? nullptr : &tid2pdf, begin);
+        AmInterface *am = pull_rows ? (AmInterface *)&pd : (AmInterface *)&md;
+        dec.InitDecoding();
+        int end = u.frames, rule = 0;
+        for (int ready = (begin / chunk + 1) * chunk;; ready += chunk) {   // (the rows arrive at multiples of --chunk of the stream)
+          md.SetFramesReady(ready);
+          pd.SetFramesReady(ready);
+          dec.AdvanceDecoding(am);
+          if (ready >= u.frames) break;
+          if (dec.EndpointDetected(ep_opt, &rule)) { end = ready; break; }
+        }
+        dec.FinalizeDecoding();
+        Lattice best;
+        std::vector<int> words, phones;
+        float tot = 0, lm = 0;
+        const bool seg_ok = dec.GetBestPath(&best) && LatticeToVector(best, words, phones, tot, lm);
+        *ok = *ok && seg_ok;
+        if (rule > 0 && print_endpoints) text += u.key + "@" + std::to_string(end) + " endpoint rule" + std::to_string(rule) + "\n";
+        text += u.key + "[" + std::to_string(begin) + "," + std::to_string(end) + "]";
+        for (int w : words) text += " " + std::to_string(w);
+        text += "\n";
+        begin = end;
+      }
+      return text;
+    };
+    auto count_segmented = [&](const Utt &u, bool ok) {
+      if (!ok) { std::cerr << "WARNING Did not successfully decode every segment of utterance " << u.key << ", len = " << u.frames << "\n"; ++num_fail; return; }
+      frame_count += u.frames;
+      ++num_success;
+    };
     if (pull && n_threads == 0) { std::cerr << "--pull goes with --threads\n"; return 1; }
     if (n_threads > 0) {
       // the service's shape: N worker threads, one DecoderItf object each, over a pool's channels or private device decoders
@@ -328,7 +401,7 @@ int main(int argc, char **argv) {
       if (pool_channels > 0)
         pool.reset(biglm ? new GpuChannelPool(&fst, opt, lm1p, lm2p, pool_channels, &limits, linger_us)
                          : new GpuChannelPool(&fst, opt, pool_channels, &limits, linger_us));
-      struct Res { Lattice best; bool ok = false; Lattice lat; bool lat_ok = false; std::vector<Lattice> nbest; };
+      struct Res { Lattice best; bool ok = false; Lattice lat; bool lat_ok = false; std::vector<Lattice> nbest; std::string segments; };
       std::vector<Res> res(utts.size());
       int max_utt_frames = 0, max_utt_cols = 0;
       for (const Utt &u : utts) { max_utt_frames = std::max(max_utt_frames, u.frames); max_utt_cols = std::max(max_utt_cols, u.cols); }
@@ -370,6 +443,14 @@ int main(int argc, char **argv) {
             // an utterance that fails (a capacity limit: the reference's LOG_ERR -> exception) is this utterance's failure, as in the
             // reference CLI (kaldi-hclg-my-decoder.cc:131-136 counts it and goes on): the thread's decoder takes the next one
             try {
+            if (endpointing) {
+              Res scratch;
+              Res &r = first_pass ? res[ui] : scratch;
+              r.segments = decode_segmented(*dp, u, pull, &r.ok);
+              if (uj >= warm_n && warm_n > 0) clocked_frames.fetch_add(r.ok ? u.frames : 0);
+              if (!first_pass) extra_frames.fetch_add(r.ok ? u.frames : 0);
+              continue;
+            }
             decode.InitDecoding();
             if (chunk > 0) {
               for (int ready = chunk;; ready += chunk) {
@@ -413,6 +494,7 @@ int main(int argc, char **argv) {
       for (const std::string &e : errors)
         if (!e.empty()) throw std::runtime_error(e);
       for (size_t i = 0; i < utts.size(); ++i) {
+        if (endpointing) { out << res[i].segments; count_segmented(utts[i], res[i].ok); continue; }
         emit(utts[i], res[i].best, res[i].ok);
         if (want_lattice && (!lattice_file.empty() || !lattice_text.empty())) emit_lattice(utts[i], res[i].lat, res[i].lat_ok);
         if (nbest > 0) emit_nbest(utts[i], res[i].nbest);
@@ -432,6 +514,12 @@ int main(int argc, char **argv) {
                                                         : new GpuLatticeDecoder(&fst, opt, &limits));
       GpuLatticeDecoder &decode = *decode_p;
       for (const Utt &u : utts) {
+        if (endpointing) {
+          bool ok = false;
+          out << decode_segmented(decode, u, false, &ok);
+          count_segmented(u, ok);
+          continue;
+        }
         HostMatrixDecodable decodable(u);
         decode.InitDecoding();
         if (chunk > 0) {  // the service's loop: data arrives, AdvanceDecoding, partial result

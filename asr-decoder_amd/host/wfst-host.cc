@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <iostream>
 #include <sstream>
 
@@ -57,6 +58,7 @@ void LatticeFasterDecoderConfig::ReadConfigFile(const std::string &path) {
     else if (name == "beam-delta") _beam_delta = (float)atof(val.c_str());
     else if (name == "hash-ratio") _hash_ratio = (float)atof(val.c_str());
     else if (name == "determinize-lattice") _determinize_lattice = (val == "true" || val == "1");
+    else if (name.compare(0, 9, "endpoint.") == 0) continue;   // OnlineEndpointConfig's lines (a service keeps one config file)
     else throw std::runtime_error("unknown decoder option --" + name);
   }
 }
@@ -98,6 +100,101 @@ void Fst::SetTid2Pdf(const std::vector<int32_t> &m) {
   if (!_graph) throw std::runtime_error("SetTid2Pdf before ReadFst");
   if (wfst_graph_set_tid2pdf(_graph, m.data(), (int32_t)m.size() - 1) != WFST_OK) Fatal("wfst_graph_set_tid2pdf");
   _tid2pdf = m;
+}
+
+void Fst::SetTid2Phone(const std::vector<int32_t> &m) {
+  if (!_graph) throw std::runtime_error("SetTid2Phone before ReadFst");
+  if (m.size() < 2 || wfst_graph_set_tid2phone(_graph, m.data(), (int32_t)m.size() - 1) != WFST_OK) Fatal("wfst_graph_set_tid2phone");
+}
+
+// ---- OnlineEndpointConfig ---------------------------------------------------------------------
+static bool ParseBool(const std::string &v, const std::string &name) {
+  if (v == "true" || v == "1") return true;
+  if (v == "false" || v == "0") return false;
+  throw std::runtime_error("bad boolean for --" + name + ": " + v);
+}
+static float ParseFloat(const std::string &v, const std::string &name) {
+  if (v == "inf" || v == "+inf" || v == "infinity") return std::numeric_limits<float>::infinity();
+  char *end = nullptr;
+  const float f = strtof(v.c_str(), &end);
+  if (v.empty() || *end) throw std::runtime_error("bad number for --" + name + ": " + v);
+  return f;
+}
+bool OnlineEndpointConfig::ParseOption(const std::string &arg) {
+  if (arg.compare(0, 11, "--endpoint.") != 0) return false;
+  const size_t eq = arg.find('=');
+  if (eq == std::string::npos) throw std::runtime_error("option without '=': " + arg);
+  std::string name = arg.substr(2, eq - 2);
+  const std::string val = arg.substr(eq + 1);
+  std::replace(name.begin(), name.end(), '_', '-');
+  if (name == "endpoint.silence-phones") { silence_phones = val; return true; }
+  if (name == "endpoint.frame-shift") { frame_shift = ParseFloat(val, name); return true; }
+  OnlineEndpointRule *rules[5] = {&rule1, &rule2, &rule3, &rule4, &rule5};
+  if (name.compare(0, 13, "endpoint.rule") == 0 && name.size() > 15 && name[13] >= '1' && name[13] <= '5' && name[14] == '.') {
+    OnlineEndpointRule &r = *rules[name[13] - '1'];
+    const std::string f = name.substr(15);
+    if (f == "must-contain-nonsilence") r.must_contain_nonsilence = ParseBool(val, name);
+    else if (f == "min-trailing-silence") r.min_trailing_silence = ParseFloat(val, name);
+    else if (f == "max-relative-cost") r.max_relative_cost = ParseFloat(val, name);
+    else if (f == "min-utterance-length") r.min_utterance_length = ParseFloat(val, name);
+    else throw std::runtime_error("unknown endpoint option --" + name);
+    return true;
+  }
+  throw std::runtime_error("unknown endpoint option --" + name);
+}
+void OnlineEndpointConfig::ReadConfigFile(const std::string &path) {
+  std::ifstream in(path.c_str());
+  if (!in) throw std::runtime_error("cannot open config file " + path);
+  std::string line;
+  while (std::getline(in, line)) {
+    size_t h = line.find('#');
+    if (h != std::string::npos) line.erase(h);
+    size_t b = line.find_first_not_of(" \t\r\n");
+    if (b == std::string::npos) continue;
+    line = line.substr(b, line.find_last_not_of(" \t\r\n") - b + 1);
+    if (line.compare(0, 2, "--") != 0) throw std::runtime_error("bad config line: " + line);
+    (void)ParseOption(line);
+  }
+}
+std::vector<int32_t> OnlineEndpointConfig::SilencePhones() const {
+  std::vector<int32_t> v;
+  size_t p = 0;
+  while (p <= silence_phones.size() && !silence_phones.empty()) {
+    size_t q = silence_phones.find(':', p);
+    if (q == std::string::npos) q = silence_phones.size();
+    const std::string tok = silence_phones.substr(p, q - p);
+    char *end = nullptr;
+    const long x = strtol(tok.c_str(), &end, 10);
+    if (tok.empty() || *end) throw std::runtime_error("bad --endpoint.silence-phones: " + silence_phones);
+    v.push_back((int32_t)x);
+    p = q + 1;
+  }
+  wfst_endpoint_config c = ToCRaw(v);
+  int32_t rule = 0;
+  if (wfst_endpoint_rules(&c, 0, 0, 0.0f, &rule) != WFST_OK) Fatal("OnlineEndpointConfig");   // (the library's checks)
+  return v;
+}
+wfst_endpoint_config OnlineEndpointConfig::ToCRaw(const std::vector<int32_t> &phones) const {
+  wfst_endpoint_config c;
+  const OnlineEndpointRule *rules[5] = {&rule1, &rule2, &rule3, &rule4, &rule5};
+  for (int k = 0; k < 5; ++k)
+    c.rule[k] = {rules[k]->must_contain_nonsilence ? 1 : 0, rules[k]->min_trailing_silence, rules[k]->max_relative_cost,
+                 rules[k]->min_utterance_length};
+  c.frame_shift = frame_shift;
+  c.n_silence_phones = (int32_t)phones.size();
+  c.silence_phones = phones.empty() ? nullptr : phones.data();
+  return c;
+}
+wfst_endpoint_config OnlineEndpointConfig::ToC(std::vector<int32_t> *phones) const {
+  *phones = SilencePhones();
+  return ToCRaw(*phones);
+}
+// the bytes that tell two configs apart (what a decoder has set on the device is set again only when it changes)
+static std::string EndpointKey(const wfst_endpoint_config &c) {
+  std::string k((const char *)c.rule, sizeof(c.rule));
+  k.append((const char *)&c.frame_shift, sizeof(c.frame_shift));
+  k.append((const char *)c.silence_phones, (size_t)c.n_silence_phones * sizeof(int32_t));
+  return k;
 }
 
 // ---- LatticeToVector --------------------------------------------------------------------------
@@ -272,10 +369,10 @@ GpuChannelPool::~GpuChannelPool() {
   if (_slab) wfst_host_free(_slab);
   if (!_trace_file.empty()) {
     if (FILE *f = fopen(_trace_file.c_str(), "w")) {
-      fprintf(f, "# ms since the pool started: first request, batch closed, pass done | requests init advance finalize best-path calls | ms of each | device busy at close\n");
+      fprintf(f, "# ms since the pool started: first request, batch closed, pass done | requests init advance finalize best-path calls endpoint | ms of each | device busy at close\n");
       for (const TracePass &t : _trace)
-        fprintf(f, "%.3f %.3f %.3f | %d %d %d %d %d | %.3f %.3f %.3f %.3f %.3f | %d\n", t.t_first, t.t_closed, t.t_end, t.n[0], t.n[1], t.n[2], t.n[3], t.n[4],
-                t.ms[0], t.ms[1], t.ms[2], t.ms[3], t.ms[4], t.busy);
+        fprintf(f, "%.3f %.3f %.3f | %d %d %d %d %d %d | %.3f %.3f %.3f %.3f %.3f %.3f | %d\n", t.t_first, t.t_closed, t.t_end, t.n[0], t.n[1], t.n[2], t.n[3], t.n[4],
+                t.n[5], t.ms[0], t.ms[1], t.ms[2], t.ms[3], t.ms[4], t.ms[5], t.busy);
       fclose(f);
     }
   }
@@ -459,6 +556,7 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
     StartBestPaths();
     ms[kBestPath] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  clocked(kEndpoint, [&] { ExecuteEndpoint(by_kind[kEndpoint]); });
   clocked(kCall, [&] {
     for (Request *r : by_kind[kCall]) {
       try {
@@ -470,10 +568,63 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
   });
   {
     std::lock_guard<std::mutex> lk(_mu);
-    for (int k = 0; k < kKinds; ++k) _stats.ms_by_kind[k] += ms[k];
+    for (int k = 0; k <= kCall; ++k) _stats.ms_by_kind[k] += ms[k];
+    _stats.ms_endpoint += ms[kEndpoint];
   }
   if (!_trace_file.empty() && !_trace.empty())
     for (int k = 0; k < kKinds; ++k) _trace.back().ms[k] = ms[k];
+}
+// EndpointDetected of every waiting channel: one wfst_decoder_endpoint_detected per distinct config (a service has one); a list the
+// library refuses is retried request by request, each with its own verdict
+void GpuChannelPool::ExecuteEndpoint(std::vector<Request *> &requests) {
+  // each distinct config object is checked and converted once per pass (a service's threads share one); requests whose configs
+  // convert to the same bytes form one group
+  struct Conf { std::vector<int32_t> phones; wfst_endpoint_config c; std::string key; std::exception_ptr error; };
+  std::map<const OnlineEndpointConfig *, Conf> confs;
+  std::map<std::string, std::vector<Request *> > groups;
+  std::map<std::string, const Conf *> group_conf;
+  for (Request *r : requests) {
+    auto it = confs.find(r->endpoint_config);
+    if (it == confs.end()) {
+      Conf &cf = confs[r->endpoint_config];
+      try {
+        cf.c = r->endpoint_config->ToC(&cf.phones);
+        cf.key = EndpointKey(cf.c);
+      } catch (...) {
+        cf.error = std::current_exception();
+      }
+      it = confs.find(r->endpoint_config);
+    }
+    if (it->second.error) { r->error = it->second.error; continue; }
+    groups[it->second.key].push_back(r);
+    group_conf[it->second.key] = &it->second;
+  }
+  for (auto &gr : groups) {
+    std::vector<Request *> &group = gr.second;
+    if (gr.first != _ep_key) {
+      if (wfst_decoder_set_endpoint_config(_dec, &group_conf[gr.first]->c) != WFST_OK) {
+        const std::string m = std::string("EndpointDetected: ") + wfst_last_error();
+        for (Request *r : group) r->error = std::make_exception_ptr(std::runtime_error(m));
+        continue;
+      }
+      _ep_key = gr.first;
+    }
+    auto call = [&](const std::vector<Request *> &rs) {
+      std::vector<int32_t> ch, rule(rs.size());
+      for (Request *r : rs) ch.push_back(r->channel);
+      const int rc = wfst_decoder_endpoint_detected(_dec, ch.data(), (int32_t)ch.size(), nullptr, rule.data(), nullptr, nullptr);
+      if (rc == WFST_OK)
+        for (size_t i = 0; i < rs.size(); ++i) rs[i]->endpoint_rule = rule[i];
+      std::lock_guard<std::mutex> lk(_mu);
+      _stats.endpoint_calls += 1;
+      _stats.endpoint_requests += (long long)rs.size();
+      return rc;
+    };
+    if (call(group) == WFST_OK) continue;
+    for (Request *r : group)
+      if (call(std::vector<Request *>(1, r)) != WFST_OK)
+        r->error = std::make_exception_ptr(std::runtime_error(std::string("EndpointDetected: ") + wfst_last_error()));
+  }
 }
 void GpuChannelPool::ExecuteAdvance(std::vector<Request *> &requests) {
   // one call per (stride, max_num_frames): in a service every stream has the same model, i.e. one call
@@ -857,6 +1008,34 @@ void GpuLatticeDecoder::FinalizeDecoding() {
     return;
   }
   if (wfst_decoder_finalize(_dec, nullptr, 0) != WFST_OK) Fatal("FinalizeDecoding");
+}
+
+void GpuLatticeDecoder::SetEndpointConfig(wfst_decoder *dec, const OnlineEndpointConfig &config, std::string *key) {
+  std::vector<int32_t> phones;
+  const wfst_endpoint_config c = config.ToC(&phones);
+  const std::string k = EndpointKey(c);
+  if (k == *key) return;
+  if (wfst_decoder_set_endpoint_config(dec, &c) != WFST_OK) Fatal("EndpointDetected");
+  *key = k;
+}
+
+bool GpuLatticeDecoder::EndpointDetected(const OnlineEndpointConfig &config, int *rule) {
+  int r = 0;
+  if (_pool) {
+    GpuChannelPool::Request q;
+    q.kind = GpuChannelPool::kEndpoint;
+    q.channel = _chan;
+    q.endpoint_config = &config;
+    _pool->Submit(&q);
+    _decoded = q.decoded;
+    r = q.endpoint_rule;
+  } else {
+    SetEndpointConfig(_dec, config, &_ep_key);
+    const int32_t c = 0;
+    if (wfst_decoder_endpoint_detected(_dec, &c, 1, nullptr, &r, nullptr, nullptr) != WFST_OK) Fatal("EndpointDetected");
+  }
+  if (rule) *rule = r;
+  return r != 0;
 }
 
 int32 GpuLatticeDecoder::NumFramesDecoded() const { return _pool ? _decoded : wfst_decoder_num_frames_decoded(_dec, 0); }
@@ -1267,6 +1446,31 @@ void GpuBatchDecoder::GetBestPaths(const std::vector<int> &channels, std::vector
     }
     return;
   }
+}
+
+void GpuBatchDecoder::EndpointDetected(const std::vector<int> &channels, const OnlineEndpointConfig &config, std::vector<bool> *detected,
+                                       std::vector<int> *rule) {
+  std::vector<int32_t> phones;
+  const wfst_endpoint_config c = config.ToC(&phones);
+  const std::string k = EndpointKey(c);
+  if (k != _ep_key) {
+    if (wfst_decoder_set_endpoint_config(_dec, &c) != WFST_OK) Fatal("EndpointDetected");
+    _ep_key = k;
+  }
+  std::vector<int32_t> ch(channels.begin(), channels.end()), r(channels.size());
+  if (!ch.empty() && wfst_decoder_endpoint_detected(_dec, ch.data(), (int32_t)ch.size(), nullptr, r.data(), nullptr, nullptr) != WFST_OK)
+    Fatal("EndpointDetected");
+  detected->assign(channels.size(), false);
+  for (size_t i = 0; i < r.size(); ++i) (*detected)[i] = r[i] != 0;
+  if (rule) rule->assign(r.begin(), r.end());
+}
+
+bool GpuBatchDecoder::EndpointDetected(int channel, const OnlineEndpointConfig &config, int *rule) {
+  std::vector<bool> d;
+  std::vector<int> r;
+  EndpointDetected(std::vector<int>(1, channel), config, &d, &r);
+  if (rule) *rule = r[0];
+  return d[0];
 }
 
 bool GpuBatchDecoder::GetBestPath(int channel, Lattice *ofst, bool use_final_probs) {

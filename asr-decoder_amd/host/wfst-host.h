@@ -92,6 +92,38 @@ struct LatticeFasterDecoderConfig {
   wfst_config ToC() const;
 };
 
+// ---- endpointing (Kaldi's online2/online-endpoint.h) -------------------------------------------------------------------
+// OnlineEndpointRule / OnlineEndpointConfig with Kaldi's option names: --endpoint.silence-phones=a:b:c and
+// --endpoint.ruleN.{must-contain-nonsilence,min-trailing-silence,max-relative-cost,min-utterance-length} (N = 1..5), plus
+// --endpoint.frame-shift (seconds per decoded frame; Kaldi takes it from the decodable: 0.01, 0.03 for frame-subsampled models).
+struct OnlineEndpointRule {
+  bool must_contain_nonsilence;
+  float min_trailing_silence;
+  float max_relative_cost;
+  float min_utterance_length;
+  OnlineEndpointRule(bool must_contain_nonsilence = true, float min_trailing_silence = 1.0f,
+                     float max_relative_cost = std::numeric_limits<float>::infinity(), float min_utterance_length = 0.0f)
+      : must_contain_nonsilence(must_contain_nonsilence), min_trailing_silence(min_trailing_silence),
+        max_relative_cost(max_relative_cost), min_utterance_length(min_utterance_length) {}
+};
+struct OnlineEndpointConfig {
+  std::string silence_phones;   // colon-separated phone ids; must be set
+  OnlineEndpointRule rule1, rule2, rule3, rule4, rule5;
+  float frame_shift;
+  OnlineEndpointConfig()   // Kaldi's defaults
+      : rule1(false, 5.0f, std::numeric_limits<float>::infinity(), 0.0f), rule2(true, 0.5f, 2.0f, 0.0f), rule3(true, 1.0f, 8.0f, 0.0f),
+        rule4(true, 2.0f, std::numeric_limits<float>::infinity(), 0.0f), rule5(false, 0.0f, std::numeric_limits<float>::infinity(), 20.0f),
+        frame_shift(0.01f) {}
+  // one "--endpoint.name=value" argument: true if it is one of these options (a bad value throws), false for any other argument
+  bool ParseOption(const std::string &arg);
+  // "--name=value" lines as LatticeFasterDecoderConfig::ReadConfigFile reads them; the --endpoint.* lines are taken (an unknown
+  // --endpoint.* name throws), the others are left to the other configs that read the same file
+  void ReadConfigFile(const std::string &path);
+  std::vector<int32_t> SilencePhones() const;   // parsed and checked (non-empty, no duplicates, every phone > 0); throws
+  wfst_endpoint_config ToC(std::vector<int32_t> *phones) const;   // (the C struct points into *phones)
+  wfst_endpoint_config ToCRaw(const std::vector<int32_t> &phones) const;   // (unchecked)
+};
+
 // ---- graph ----------------------------------------------------------------------------------
 class Fst {
  public:
@@ -106,6 +138,8 @@ class Fst {
   // (every Kaldi decodable).
   void SetTid2Pdf(const std::vector<int32_t> &tid2pdf);
   const std::vector<int32_t> &Tid2Pdf() const { return _tid2pdf; }
+  // TransitionModel::TransitionIdToPhone as a table (entry 0 unused): what EndpointDetected's silence phones are looked up in
+  void SetTid2Phone(const std::vector<int32_t> &tid2phone);
   StateId Start() const { return _start; }
   bool IsFinal(StateId id) const { return id == _final; }
   StateId TotState() const { return _states; }
@@ -248,6 +282,9 @@ class GpuChannelPool {
     long long frames;             // frames handed to the device
     double ms_by_kind[5];         // batcher time in the C-ABI calls: init, advance, finalize, best path, one-off calls
     double ms_waiting;            // ... and waiting for requests (idle, or letting a batch form)
+    long long endpoint_calls;     // wfst_decoder_endpoint_detected calls issued ...
+    long long endpoint_requests;  // ... for this many EndpointDetected requests
+    double ms_endpoint;           // batcher time in them
   };
   Stats GetStats();
   wfst_decoder *Handle() { return _dec; }
@@ -256,7 +293,7 @@ class GpuChannelPool {
   friend class GpuLatticeDecoder;
   GpuChannelPool(const GpuChannelPool &);
   GpuChannelPool &operator=(const GpuChannelPool &);
-  enum Kind { kInit = 0, kAdvance, kFinalize, kBestPath, kCall, kKinds };
+  enum Kind { kInit = 0, kAdvance, kFinalize, kBestPath, kCall, kEndpoint, kKinds };
   struct Request {
     Kind kind;
     int channel;
@@ -267,6 +304,9 @@ class GpuChannelPool {
     std::vector<int32_t> il, ol; std::vector<float> g, ac; int n_hops, degraded;
     // kCall
     std::function<void(wfst_decoder *)> call;
+    // kEndpoint: the config asked with; the rule that fired (0: none)
+    const OnlineEndpointConfig *endpoint_config = nullptr;
+    int endpoint_rule = 0;
     // outcome
     int decoded;                  // NumFramesDecoded of the channel after the request
     std::exception_ptr error;
@@ -286,6 +326,8 @@ class GpuChannelPool {
   void Run();
   void Execute(std::vector<Request *> &batch);
   void ExecuteAdvance(std::vector<Request *> &rs);
+  void ExecuteEndpoint(std::vector<Request *> &rs);   // one wfst_decoder_endpoint_detected per distinct config
+  std::string _ep_key;                                 // the config last set on the device decoder (its C struct's bytes + phones)
   void ExecuteBestPath(std::vector<Request *> &rs);   // synchronous (the fall-back when a list is refused: request by request)
   // best paths WITHOUT the batcher standing still: the waiting requests of one kind (with / without final-probs) go to the device as
   // one list (wfst_decoder_best_path_enqueue), the batcher goes on feeding the device, and takes the results when they have landed
@@ -317,7 +359,7 @@ class GpuChannelPool {
   Stats _stats;
   // WFST_POOL_TRACE=<file>: one line per batcher pass (when its first request arrived, when it was closed, what it held, how long each
   // kind's device calls took, whether the device was still busy when it closed), written when the pool goes
-  struct TracePass { double t_first, t_closed, t_end; int n[5]; double ms[5]; int busy; };
+  struct TracePass { double t_first, t_closed, t_end; int n[kKinds]; double ms[kKinds]; int busy; };
   std::vector<TracePass> _trace;
   std::string _trace_file;
   std::chrono::steady_clock::time_point _t_origin, _t_first;
@@ -382,9 +424,15 @@ class GpuLatticeDecoder : public DecoderItf {
   // word sequences and totals; each path's FIRST arc carries its whole weight (graph = lm_score, acoustic = tot - lm), so that
   // LatticeToVector gives words, tot_score and lm_score
   bool GetNbestShortlist(std::vector<Lattice> &nbest_paths, int n);
+  // EndpointDetected (kaldi-online-nnet3-my-decoder.h:360-362; Kaldi's online2/online-endpoint.cc) after AdvanceDecoding: the
+  // trailing silence of the best path and FinalRelativeCost on the device, the rules on the host.  *rule: the rule that fired
+  // (1..5, 0: none).  Needs the graph's SetTid2Phone; throws for a biglm decoder, before InitDecoding or after FinalizeDecoding.
+  // Over a pool, the requests of many threads go to the device as one call per batcher pass.
+  bool EndpointDetected(const OnlineEndpointConfig &config, int *rule = nullptr);
 
  private:
   void Pull(AmInterface *decodable);
+  static void SetEndpointConfig(wfst_decoder *dec, const OnlineEndpointConfig &config, std::string *key);
   template <class F> void OnDevice(F &&f);   // f(): C-ABI calls on (_dec, _chan) -- in the pool's batcher thread where there is a pool
   wfst_decoder *_dec;
   void Share(Fst *graph, const LatticeFasterDecoderConfig &config, ArpaLm *oldlm, ArpaLm *newlm, const wfst_limits *limits);
@@ -399,6 +447,7 @@ class GpuLatticeDecoder : public DecoderItf {
   void GrowRows(size_t floats);
   void SetColumns(const Fst *graph);   // the graph's tid2pdf -> one representative transition-id per pdf (Pull)
   std::vector<int32_t> _rep;           // [pdf] a transition-id of that pdf; empty: the rows are indexed by the decodable's own indices
+  std::string _ep_key;                 // private decoder: the endpoint config last set
   int _stride, _rows_ready;
   bool _inited;
 };
@@ -449,11 +498,16 @@ class GpuBatchDecoder {
                    bool use_final_probs = true);
   void GetNbests(const std::vector<int> &channels, std::vector<std::vector<Lattice> > *nbests, std::vector<bool> *ok, int n,
                  ArpaLm *oldlm = nullptr, ArpaLm *newlm = nullptr);
+  // EndpointDetected of many channels in one device call ((*rule)[i]: 1..5, 0 none); the one-channel form
+  void EndpointDetected(const std::vector<int> &channels, const OnlineEndpointConfig &config, std::vector<bool> *detected,
+                        std::vector<int> *rule = nullptr);
+  bool EndpointDetected(int channel, const OnlineEndpointConfig &config, int *rule = nullptr);
   wfst_decoder *Handle() { return _dec; }
 
  private:
   wfst_decoder *_dec;
   int _n;
+  std::string _ep_key;
 };
 
 // the reference's name for the biglm decoder (biglm.h:570): `OnlineLatticeDecoderMempoolBiglm decode(&fst, opt, &lm1, &lm2);`

@@ -35,6 +35,8 @@ SYMBOLS = [
     "wfst_decoder_get_degraded_frames", "wfst_decoder_get_prune_raw_abandoned", "wfst_host_alloc", "wfst_host_free", "wfst_decoder_busy", "wfst_decoder_calls_in_flight", "wfst_decoder_get_determinizer_ms", "wfst_decoder_best_path_enqueue", "wfst_decoder_best_path_ready", "wfst_decoder_best_path_fetch", "wfst_decoder_prefetch_nbest", "wfst_decoder_get_prefetched_nbest_paths", "wfst_decoder_get_path_flags", "wfst_decoder_rescore_lattices", "wfst_decoder_nbest_paths_batch",
     "wfst_decoder_prefetch_determinized", "wfst_lattice_labels_batch",
     "wfst_decoder_prefetch_determinized_detached", "wfst_decoder_get_prefetched_lattice", "wfst_decoder_harvest_prefetched",
+    "wfst_endpoint_config_default", "wfst_graph_set_tid2phone", "wfst_decoder_set_endpoint_config", "wfst_decoder_endpoint_detected",
+    "wfst_endpoint_rules",
 ]
 
 
@@ -118,6 +120,53 @@ class Config(C.Structure):
                  prune_interval=25, beam_delta=0.5, hash_ratio=2.0, prune_scale=0.1):
         super().__init__(beam, max_active, min_active, lattice_beam, prune_interval, beam_delta,
                          hash_ratio, prune_scale)
+
+
+class EndpointRule(C.Structure):
+    """wfst_endpoint_rule == Kaldi's OnlineEndpointRule."""
+
+    _fields_ = [("must_contain_nonsilence", C.c_int32), ("min_trailing_silence", C.c_float), ("max_relative_cost", C.c_float),
+                ("min_utterance_length", C.c_float)]
+
+
+class _EndpointConfigC(C.Structure):
+    _fields_ = [("rule", EndpointRule * 5), ("frame_shift", C.c_float), ("n_silence_phones", C.c_int32),
+                ("silence_phones", C.POINTER(C.c_int32))]
+
+
+class EndpointConfig(object):
+    """wfst_endpoint_config == Kaldi's OnlineEndpointConfig: rules[0..4] are rule1..rule5 (dicts of must_contain_nonsilence,
+    min_trailing_silence, max_relative_cost, min_utterance_length), frame_shift in seconds, silence_phones a non-empty list.
+    Defaults from the library (Kaldi's)."""
+
+    def __init__(self, silence_phones=(), frame_shift=None, rules=None):
+        c = _EndpointConfigC()
+        lib().wfst_endpoint_config_default(C.byref(c))
+        self.rules = [dict(must_contain_nonsilence=bool(r.must_contain_nonsilence), min_trailing_silence=r.min_trailing_silence,
+                           max_relative_cost=r.max_relative_cost, min_utterance_length=r.min_utterance_length) for r in c.rule]
+        self.frame_shift = c.frame_shift if frame_shift is None else float(frame_shift)
+        for k, r in (rules or {}).items():   # {rule index 0..4: {field: value}}
+            self.rules[k].update(r)
+        self.silence_phones = [int(p) for p in silence_phones]
+
+    def as_c(self):
+        """The C struct; its silence list is kept alive on the returned object."""
+        c = _EndpointConfigC()
+        for k, r in enumerate(self.rules):
+            c.rule[k] = EndpointRule(int(bool(r["must_contain_nonsilence"])), r["min_trailing_silence"], r["max_relative_cost"],
+                                     r["min_utterance_length"])
+        c.frame_shift = self.frame_shift
+        c._sil = np.ascontiguousarray(self.silence_phones, dtype=np.int32)
+        c.n_silence_phones = int(c._sil.shape[0])
+        c.silence_phones = _i32(c._sil) if c._sil.shape[0] else None
+        return c
+
+    def rule_fired(self, num_frames_decoded, trailing_frames, relative_cost):
+        """wfst_endpoint_rules: the first rule (1..5) that fires for these inputs, 0 if none -- on the host."""
+        r = C.c_int32()
+        c = self.as_c()
+        _check(lib().wfst_endpoint_rules(C.byref(c), int(num_frames_decoded), int(trailing_frames), C.c_float(relative_cost), C.byref(r)))
+        return r.value
 
 
 class Limits(C.Structure):
@@ -226,6 +275,11 @@ class Graph:
     def set_tid2pdf(self, tid2pdf):
         m = np.ascontiguousarray(tid2pdf, dtype=np.int32)
         _check(lib().wfst_graph_set_tid2pdf(self.h, _i32(m), int(m.shape[0] - 1)))
+
+    def set_tid2phone(self, tid2phone):
+        """TransitionIdToPhone as a table (entry 0 unused): what the endpoint's silence phones are looked up in."""
+        m = np.ascontiguousarray(tid2phone, dtype=np.int32)
+        _check(lib().wfst_graph_set_tid2phone(self.h, _i32(m), int(m.shape[0] - 1)))
 
     def info(self):
         s, f, ns, na = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -661,6 +715,20 @@ class BatchDecoder:
         _check(lib().wfst_decoder_get_profile_busy(self.h, busy))
         return dict(expand_ms=ms[0], expand_launches=n[0], insert_ms=ms[1], insert_launches=n[1],
                     closure_ms=ms[2], closure_launches=n[2], expand_busy_ms=busy[0], insert_busy_ms=busy[1], closure_busy_ms=busy[2])
+
+    def set_endpoint_config(self, cfg):
+        c = cfg.as_c()
+        _check(lib().wfst_decoder_set_endpoint_config(self.h, C.byref(c)))
+
+    def endpoint(self, channels=None):
+        """EndpointDetected of the listed channels (all if None) in one device call: (detected bool[n], rule int32[n] (1..5, 0 none),
+        trailing_frames int32[n] (-1: no path), relative_cost float32[n])."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        n = int(ch.shape[0])
+        det, rule, tr = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        rel = np.zeros(n, np.float32)
+        _check(lib().wfst_decoder_endpoint_detected(self.h, _i32(ch), n, _i32(det), _i32(rule), _i32(tr), _f32(rel)))
+        return det.astype(bool), rule, tr, rel
 
     def frontier(self, channel, cap=1 << 20):
         st = np.zeros(cap, np.int32)

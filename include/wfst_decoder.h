@@ -545,6 +545,60 @@ int wfst_decoder_get_degraded_frames(wfst_decoder *d, int32_t channel, int32_t *
 int wfst_decoder_get_frontier(wfst_decoder *d, int32_t channel, int32_t cap, int32_t *states,
                               float *costs);
 
+/* ---- endpoint detection (streaming) --------------------------------------------------------------------------------------
+ * Kaldi's online2/online-endpoint.{h,cc}, which the reference's online decoder calls after every AdvanceDecoding
+ * (EndpointDetected(const OnlineEndpointConfig&), kaldi-nnet3/kaldi-online-nnet3-my-decoder.h:360-362; the service loop:
+ * v1-asr/asr-source.h:280-287).  A rule fires iff
+ *   (utterance_length > trailing_silence || !must_contain_nonsilence) && trailing_silence >= min_trailing_silence &&
+ *   relative_cost <= max_relative_cost && utterance_length >= min_utterance_length
+ * with utterance_length = num_frames_decoded * frame_shift and trailing_silence = trailing_silence_frames * frame_shift (f32);
+ * rules 1..5 are tried in order, the first that fires is reported.  No frames decoded: not detected. */
+typedef struct {                  /* OnlineEndpointRule */
+  int32_t must_contain_nonsilence;
+  float min_trailing_silence;     /* seconds */
+  float max_relative_cost;        /* +inf: no limit */
+  float min_utterance_length;     /* seconds */
+} wfst_endpoint_rule;
+
+typedef struct {                  /* OnlineEndpointConfig (--endpoint.*) */
+  wfst_endpoint_rule rule[5];     /* rule1 .. rule5 */
+  float frame_shift;              /* seconds per decoded frame: 0.01, or 0.03 for frame-subsampled chain models */
+  int32_t n_silence_phones;       /* --endpoint.silence-phones=a:b:c -- non-empty, no duplicates, every phone > 0 */
+  const int32_t *silence_phones;  /* (copied by the calls that take a config) */
+} wfst_endpoint_config;
+
+/* Kaldi's defaults: rule1 {0, 5.0, inf, 0}, rule2 {1, 0.5, 2.0, 0}, rule3 {1, 1.0, 8.0, 0}, rule4 {1, 2.0, inf, 0},
+ * rule5 {0, 0, inf, 20.0}; frame_shift 0.01; no silence phones (the caller must name them). */
+void wfst_endpoint_config_default(wfst_endpoint_config *cfg);
+
+/* TransitionModel::TransitionIdToPhone as a table: tid2phone[tid] for tid 1..n_tid (entry 0 unused, the layout of
+ * wfst_graph_set_tid2pdf).  WFST_E_ARG if an arc's ilabel exceeds n_tid or a phone is negative.  Host-side only. */
+int wfst_graph_set_tid2phone(wfst_graph *g, const int32_t *tid2phone, int32_t n_tid);
+
+/* The endpoint configuration of a decoder: checked (WFST_E_ARG: empty or duplicate silence list, a phone <= 0,
+ * frame_shift <= 0), then the silence set is turned into a bitmap over transition-ids (through the graph's tid2phone) in
+ * device memory.  WFST_E_STATE: the graph has no tid2phone; WFST_E_ARG: a biglm decoder (not supported). */
+int wfst_decoder_set_endpoint_config(wfst_decoder *d, const wfst_endpoint_config *cfg);
+
+/* EndpointDetected (kaldi-online-nnet3-my-decoder.h:360-362) for a LIST of channels mid-utterance, one launch: per listed
+ * channel trailing_frames[i] = TrailingSilenceLength (the silence hops at the end of the best path GetBestPath(use_final_probs =
+ * false) reports, epsilon hops skipped), relative_cost[i] = FinalRelativeCost (ComputeFinalCosts, base-inl.h:670-720: cost of
+ * the best token on the final state - cost of the best token, +inf without one), rule[i] = the rule that fired (1..5, 0: none)
+ * and detected[i] = rule[i] != 0.  Enqueued behind the listed channels' own work (as wfst_decoder_best_path_enqueue), then
+ * waited for.  WFST_E_ARG: a biglm decoder (not supported); WFST_E_STATE: no endpoint config set, or a listed channel not
+ * initialised or already finalized.  A channel with no frame decoded yet has no path (trailing_frames[i] = -1, relative_cost[i] = +inf,
+ * not detected, as Kaldi's EndpointDetected returns false there).  A channel whose utterance ended in a device error has no path: trailing_frames[i] = -1,
+ * relative_cost[i] = +inf, not detected -- the others' results stand and the call returns WFST_OK (the error itself is
+ * reported by the channel's next advance / sync / best path).  Any output pointer may be NULL. */
+int wfst_decoder_endpoint_detected(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t *detected, int32_t *rule,
+                                   int32_t *trailing_frames, float *relative_cost);
+
+/* The rules alone, on the host (no device): *rule = the first of rules 1..5 that fires for these inputs, 0 if none (and 0 for
+ * num_frames_decoded == 0).  The config is checked as wfst_decoder_set_endpoint_config checks it; WFST_E_ARG also for
+ * trailing_frames outside [0, num_frames_decoded]. */
+int wfst_endpoint_rules(const wfst_endpoint_config *cfg, int32_t num_frames_decoded, int32_t trailing_frames, float relative_cost,
+                        int32_t *rule);
+
 #ifdef __cplusplus
 }
 #endif
