@@ -17,12 +17,20 @@ kaldi-nnet3bin/kaldi-hclg-my-decoder.cc:97-129).  Log-likelihoods are resident i
 timed region starts.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what its headline figure needs and nothing else: it builds the inputs, warms up, times the steps, writes
+--dump-outputs if asked and prints the line (the contract's keys and the decoder's own counters of the timed steps).  --full adds
+everything else this script measures or checks: the live parity sample and the CPU baselines, the instrumented roofline step and the
+rocprofv3 counter passes, the service-point workloads, the legs (other BASELINE configurations as child runs) and bench_detail.json.
+No run reads what an earlier run wrote: the graph and the LMs are generated in the run, and a --full run hands them to its child runs
+through a directory of its own (--work-dir).
 
 N > 1: utterances shard embarrassingly (128 per GPU, graph replicated, weak scaling); the only
 collective is the gather of the final word-id results per step (RCCL).
-Rank 0 prints ONE JSON line, under 4 KB (summary_line(): metric, value, config, roofline, cpu_baseline and one dict of scalars
-per leg); everything else -- curves, counts, notes, every leg's own config and roofline -- goes to bench_detail.json.
+Rank 0 prints ONE JSON line, under 4 KB (summary_line(): metric, value, config and, with --full, roofline, cpu_baseline and one dict
+of scalars per leg); everything else -- curves, counts, notes, every leg's own config and roofline -- goes to bench_detail.json.
 
 roofline.achieved: algorithmic bytes (SURVEY.md 8(d) per-unit figures x the units processed) of the slowest
 kernel / its time, from hipEvent pairs around every launch on the stream it is launched on.  The decoder runs
@@ -37,10 +45,13 @@ Other BASELINE configs through the same script (not the headline; `metric` says 
     --host-feed                      PCIe-inclusive (host matrices handed over inside the step)
 """
 import argparse
+import atexit
 import importlib
 import json
 import os
+import shutil
 import sys
+import tempfile
 import threading
 import time
 
@@ -63,6 +74,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else this script measures or checks: the "
+                    "parity sample and CPU baselines, the roofline step and counter passes, the service-point workloads, the legs and the "
+                    "detail file (--cpu-sample, --cpu-seconds, --cpu-threads, --no-cpu-baseline, --no-service-point, --no-legs, --only-legs, "
+                    "--no-traffic and --no-profile-step refine it); a plain run writes a detail file only where --detail-out names one")
     ap.add_argument("--batch", type=int, default=128, help="utterances per GPU")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--states", type=int, default=2850000)
@@ -132,7 +147,9 @@ def parse():
     ap.add_argument("--lm-old", default="20000,5,0,0", help="old LM: bigram contexts, successors, trigram contexts, successors")
     ap.add_argument("--lm-new", default="40000,6,100000,3", help="new LM: same four numbers")
     ap.add_argument("--lm-pairs", type=int, default=1 << 20, help="LM pair states per utterance (wfst_limits.lm_pairs)")
-    ap.add_argument("--graph-cache", default="/tmp/wfst_bench_graph_%d.bin")
+    ap.add_argument("--work-dir", default="", help="directory of the files this run hands to its CPU checkers and child runs (graph, LMs); a "
+                    "--full run passes its own to its child runs, which read what it holds.  Default: a new temporary directory, removed "
+                    "at the end of the run")
     ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child runs of this script, "
                     "FETCH_SIZE and WRITE_SIZE, one step each with the kernels enqueued one by one): quote the stored passes of profiles/traffic_latest.json")
     ap.add_argument("--no-profile-step", action="store_true", help="skip the extra instrumented step behind the timed region (the rocprofv3 --pmc "
@@ -881,19 +898,25 @@ def main():
               prune_interval=a.prune_interval, beam_delta=0.5)
 
     # ---- inputs (untimed) -------------------------------------------------------------------
+    # (the files this run hands to its CPU checkers and child runs live in a directory of the run's own: a child of a --full run is
+    # handed its parent's and reads what the parent wrote there; nothing is read from an earlier run)
+    work = a.work_dir or tempfile.mkdtemp(prefix="wfst_bench_")
+    if not a.work_dir:
+        atexit.register(shutil.rmtree, work, True)
     t0 = time.time()
-    gpath = (a.graph_cache % a.states) + (".r%d" % rank if world > 1 else "")
-    g = None
-    if os.path.exists(gpath):
-        try:
-            g = synth.Graph.read(gpath)
-        except (IOError, ValueError):
-            g = None  # a partial file from an interrupted run: rebuild
-    if g is None:
+    gpath = os.path.join(work, "graph_%d.bin" % a.states)
+    if a.work_dir and os.path.exists(gpath):
+        g = synth.Graph.read(gpath)
+    else:
         g = synth.make_hclg_like(a.states, seed=7, n_tid=n_tid)
-        g.write(gpath + ".tmp%d" % os.getpid())
-        os.replace(gpath + ".tmp%d" % os.getpid(), gpath)
     log("[rank %d] graph: %d states, %d arcs (%.1fs)" % (rank, g.n_states, g.n_arcs, time.time() - t0))
+
+    def graph_file():
+        """the graph as the file the CPU decoders, the drop-in CLI and the child runs load: written on first use"""
+        if not os.path.exists(gpath):
+            g.write(gpath + ".tmp")
+            os.replace(gpath + ".tmp", gpath)
+        return gpath
     t0 = time.time()
     mats = make_utts(synth, g, m, rank * B, B, T, P, a)
     if os.environ.get("WFST_BENCH_SAME_UTT"):  # experiment: every channel decodes the same utterance (no load imbalance)
@@ -913,8 +936,8 @@ def main():
         big = []
         for tag, spec, order, seed in (("old", a.lm_old, 2, 41), ("new", a.lm_new, 3, 42)):
             nb, s2, nt, s3 = (int(x) for x in spec.split(","))
-            lp = "/tmp/wfst_bench_lm_%s_%d_%s.bin%s" % (tag, V, spec.replace(",", "_"), ".r%d" % rank if world > 1 else "")
-            if not os.path.exists(lp):
+            lp = os.path.join(work, "lm_%s_%d_%s.bin" % (tag, V, spec.replace(",", "_")))
+            if not os.path.exists(lp):   # (an earlier child of the same --full run may have written it)
                 lm = lmsynth.make_lm(V, 3 if nt > 0 else 2, nb, s2, nt, s3, seed=seed)
                 lm.to_fsa().write(lp + ".tmp%d" % os.getpid())
                 os.replace(lp + ".tmp%d" % os.getpid(), lp)
@@ -1131,10 +1154,10 @@ def main():
                         "wfst_decoder_get_nbest_paths(11) of one channel alone (determinize + ComposeLattice x 2 + NShortestPath), median of three"}
     else:
         post = None
-    # ---- roofline pass: one more step with HIP events around every kernel launch -----------
+    # ---- roofline pass (--full): one more step with HIP events around every kernel launch -----------
     gstats = [dec.stats(c) for c in range(B)]
     profiled_step_ms = 0.0
-    if not a.no_profile_step:
+    if a.full and not a.no_profile_step:
         dec.set_profiling(True)
         torch.cuda.synchronize(dev)
         tp0 = time.perf_counter()
@@ -1143,8 +1166,8 @@ def main():
             step.drain(res_p)
         torch.cuda.synchronize(dev)
         profiled_step_ms = 1e3 * (time.perf_counter() - tp0)   # the instrumented step itself (slower than a timed one: event pairs, no hipGraph)
-    prof = dec.profile()
-    if not a.no_profile_step:
+    prof = dec.profile() if a.full else None
+    if a.full and not a.no_profile_step:
         dec.set_profiling(False)
 
     regime = ("beam-only pruning (max_active never binds, min_active 0): bit-exact best-path parity with the reference CPU decoder"
@@ -1183,7 +1206,7 @@ def main():
     out["config"]["decoder_paths"] = pf
     if post is not None:
         out["postprocess"] = post
-    if world > 1:
+    if world > 1 and a.full:
         # N > 1: every rank runs the configuration rank 0 reports (the kernel paths a decoder takes follow from its limits)
         tv = torch.tensor([pf[k] for k in sorted(pf)], dtype=torch.int64, device="cpu" if share else dev)
         tmin, tmax = tv.clone(), tv.clone()
@@ -1198,7 +1221,7 @@ def main():
             pyoracle.build_oracle()
         dist.barrier()
         orc = pyoracle.OracleDecoder()
-        h = orc.load_graph(gpath)
+        h = orc.load_graph(graph_file())
         okr = 0
         for i in range(min(2, B)):
             o = orc.decode(h, pyoracle.Config(**cd), mats[i], m)
@@ -1214,7 +1237,7 @@ def main():
 
         pyoracle.build_oracle()
         orc = pyoracle.OracleDecoder()
-        h = orc.load_graph(gpath)
+        h = orc.load_graph(graph_file())
         sa = argparse.Namespace(**vars(a))
         ok = 0
         for u, r in enumerate(gathered):
@@ -1254,6 +1277,8 @@ def main():
         if a.lattice_links == 0 and not a.biglm:
             out["config"]["degraded_frames"] = int(sum(dec.degraded_frames(c) for c in range(B)))
         out["config"]["utterances_with_path"] = int(sum(1 for r in res if r["ok"]))
+    if rank == 0 and a.full:
+        graph_file()   # (the CPU decoders, the drop-in CLI and the child runs below load the graph from its file)
         if getattr(res, "nbest_lazy", None) is not None:   # (outside the timed region: the n-best lists as per-utterance entries)
             for i, r in enumerate(res):
                 if res.nbest_lazy[i] is not None:
@@ -1472,7 +1497,7 @@ def main():
             wl = ["--batch", str(B), "--frames", str(T), "--states", str(a.states), "--pdfs", str(P), "--beam", str(a.beam), "--max-active", str(a.max_active),
                   "--min-active", str(a.min_active), "--workload", a.workload, "--paths", str(a.paths), "--mu", str(a.mu), "--sigma", str(a.sigma),
                   "--max-tokens", str(a.max_tokens), "--arena-per-frame", str(a.arena_per_frame), "--lattice-beam", str(a.lattice_beam),
-                  "--prune-interval", str(a.prune_interval)]
+                  "--prune-interval", str(a.prune_interval), "--work-dir", work]
             if a.biglm:
                 wl += ["--biglm", "--lm-old", a.lm_old, "--lm-new", a.lm_new, "--lm-pairs", str(a.lm_pairs)]
             if a.lattice_links > 0:
@@ -1535,7 +1560,7 @@ def main():
             R["achieved_definition"] = ("algorithmic bytes of all %s launches of one step / time during which at least one of them was "
                                         "executing (the groups' launches overlap; per-launch figures under per_launch)" % (dom + "_kernel"))
     # ---- second workload: SURVEY 8(d) generator at the reference service's operating point ----
-    if rank == 0 and world == 1 and not a.no_service_point and a.lattice_links == 0 and not a.host_feed and a.workload == "multi" and not a.biglm:
+    if a.full and rank == 0 and world == 1 and not a.no_service_point and a.lattice_links == 0 and not a.host_feed and a.workload == "multi" and not a.biglm:
         if dec is not None:
             dec.free()
         dec = None
@@ -1637,7 +1662,7 @@ def main():
         L["reference_default_limits"] = rdl
         log("[rank 0] service point: %.1fs" % (time.time() - t0))
     headline_run = (not a.biglm and a.lattice_links == 0 and not a.host_feed and a.workload == "multi")
-    if rank == 0 and world == 1 and headline_run and not a.no_legs:
+    if a.full and rank == 0 and world == 1 and headline_run and not a.no_legs:
         # ---- the other BASELINE configurations, driver-observed: configs[3] (biglm) and configs[4] (lattice-generating decode at
         # beam 15 + the determinized lattices), each a child process running this script on the same graph and utterances
         # for a few steps, with its own live parity sample, token counts, per-kernel times and roofline; the child's line
@@ -1650,8 +1675,8 @@ def main():
         del ll_dev
         torch.cuda.empty_cache()
         n2 = max(2, a.steps // 5)
-        common = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--warmup", "1", "--no-service-point", "--no-legs", "--no-traffic",
-                  "--batch", str(B), "--frames", str(T), "--states", str(a.states), "--pdfs", str(P)]
+        common = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--warmup", "1", "--full", "--no-service-point", "--no-legs", "--no-traffic",
+                  "--batch", str(B), "--frames", str(T), "--states", str(a.states), "--pdfs", str(P), "--work-dir", work]
         # the reference's own CPU path timed beside configs[3] and configs[4] (1 / 32 / all host threads): its biglm decoder
         # (kaldi-hclg-my-decoder-biglm.cc:80-102) and its lattice pipeline (decode, GetRawLattice, DeterminizeLatticeWrapper,
         # NShortestPath: kaldi-online-nnet3-my-decoder.cc:50-105); the other legs vary the same two configurations and carry none
@@ -1714,8 +1739,9 @@ def main():
             if name in L and sib in L and "cpu_baseline" not in L[name] and "cpu_baseline" in L[sib]:
                 L[name]["cpu_baseline"] = dict(L[sib]["cpu_baseline"], measured_in_leg=sib)
     if rank == 0:
-        # the full result to bench_detail.json, its summary -- strict JSON under 4 KB, scalars only -- as the ONE stdout line
-        where = write_detail(out, a.detail_out)
+        # the full result to bench_detail.json (--full, or the file --detail-out names), its summary -- strict JSON under 4 KB, scalars
+        # only -- as the ONE stdout line
+        where = write_detail(out, a.detail_out) if (a.full or a.detail_out) else None
         print(summary_line(out, os.path.basename(where) if where else None), flush=True)
     if dec is not None:
         dec.free()

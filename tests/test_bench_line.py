@@ -161,3 +161,25 @@ def test_gpus_n_launches_its_own_ranks(monkeypatch, capsys):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" or "HSA_ENABLE_IPC_MODE_LEGACY" in os.environ
     out = capsys.readouterr().out.strip().splitlines()
     assert json.loads(out[-1])["n_gpus"] == 8 and len(out) == 1
+
+
+def test_plain_run_line(monkeypatch):
+    """A plain run (no --full) fills the contract's keys and its own counters only: the line then carries no roofline, CPU baseline,
+    legs or detail file, and is still strict JSON."""
+    import sys
+
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.work_dir == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert b.parse().full is True
+    o = _canned()
+    plain = {k: o[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                               "vs_baseline", "dtype", "data")}
+    plain["config"] = {k: o["config"][k] for k in ("workload", "global_batch", "frames_per_utt", "rtfx", "utterances_with_path")}
+    d = _strict(b.summary_line(plain, None))
+    assert d["value"] == o["value"] and d["ms_per_step"] == o["ms_per_step"] and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["config"]["global_batch"] == o["config"]["global_batch"]
+    for k in ("roofline", "cpu_baseline", "legs", "detail"):
+        assert k not in d, k

@@ -27,8 +27,7 @@ def test_two_ranks_share_one_gpu_and_gather_real_results():
     env = dict(os.environ, WFST_BENCH_SHARE_GPU="1", WFST_BENCH_CHECK_GATHER="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "6", "--frames", "60", "--states", "20000", "--pdfs", "1000", "--cpu-sample", "0", "--no-service-point",
-           "--graph-cache", "/tmp/wfst_mr_graph_%d.bin"]
+           "--batch", "6", "--frames", "60", "--states", "20000", "--pdfs", "1000", "--cpu-sample", "0", "--no-service-point", "--full"]
     detail = "/tmp/wfst_mr_detail_%d.json" % os.getpid()
     p = subprocess.run(cmd + ["--detail-out", detail], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -58,8 +57,7 @@ def test_two_ranks_gather_real_determinized_lattices():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--batch", "6", "--frames", "60", "--states", "20000", "--pdfs", "1000", "--cpu-sample", "0", "--no-service-point",
-           "--lattice-links", "1000000", "--determinize", "--max-tokens", "32768", "--graph-cache", "/tmp/wfst_mr_graph_%d.bin",
-           "--detail-out", detail]
+           "--lattice-links", "1000000", "--determinize", "--max-tokens", "32768", "--full", "--detail-out", detail]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -77,7 +75,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(WFST_BENCH_SHARE_GPU="1", WFST_BENCH_CHECK_GATHER="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "6", "--frames", "60",
-           "--states", "20000", "--pdfs", "1000", "--cpu-sample", "0", "--no-service-point", "--graph-cache", "/tmp/wfst_mr_graph_%d.bin"]
+           "--states", "20000", "--pdfs", "1000", "--cpu-sample", "0", "--no-service-point"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

@@ -5,7 +5,7 @@
 R="${GRAFT_REPO_ROOT:-$PWD}"   # (A/B switches of wfst_options.debug need a library built with -DWFST_AB_SWITCHES)
 cd "$R"
 mkdir -p gpurun_out/ab
-COMMON="${AB_COMMON:---steps 10 --warmup 3 --no-service-point --no-legs --cpu-sample 4 --no-cpu-baseline}"
+COMMON="--full ${AB_COMMON:---steps 10 --warmup 3 --no-service-point --no-legs --cpu-sample 4 --no-cpu-baseline}"
 i=0
 for rep in $(seq 1 ${REPS:-2}); do
   i=0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the biglm leg (BASELINE configs[3]) under several argument sets, one box:   bash tools/ab_biglm.sh "" "--groups 4" ...
 R="${GRAFT_REPO_ROOT:-$PWD}"; cd "$R"; mkdir -p gpurun_out/ab
-ARGS="--biglm --max-tokens 131072 --steps ${STEPS:-10} --cpu-sample 2 --warmup 3 --no-service-point --no-traffic --no-legs --no-cpu-baseline"
+ARGS="--biglm --max-tokens 131072 --steps ${STEPS:-10} --cpu-sample 2 --warmup 3 --no-service-point --no-traffic --no-legs --no-cpu-baseline --full"
 for rep in $(seq 1 ${REPS:-1}); do
   i=0
   for v in "$@"; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the beam-15 lattice leg (pipelined determinizer) at several channel-group counts, one box
 R="${GRAFT_REPO_ROOT:-$PWD}"; cd "$R"; mkdir -p gpurun_out/ab
-ARGS="--beam 15 --lattice-beam 8 --lattice-links 25165824 --arena-per-frame 60000 --max-tokens 262144 --determinize --pipeline-determinizer --steps 6 --cpu-sample 2 --warmup 2 --no-service-point --no-traffic --no-legs --no-cpu-baseline"
+ARGS="--beam 15 --lattice-beam 8 --lattice-links 25165824 --arena-per-frame 60000 --max-tokens 262144 --determinize --pipeline-determinizer --steps 6 --cpu-sample 2 --warmup 2 --no-service-point --no-traffic --no-legs --no-cpu-baseline --full"
 for g in "$@"; do
   timeout 200 python bench.py $ARGS --groups $g --detail-out gpurun_out/ab/groups_$g.json > /dev/null 2> gpurun_out/ab/groups_$g.err || tail -3 gpurun_out/ab/groups_$g.err
   python - $g <<'PY'

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on one box: the beam-13 lattice leg with and without the several-workgroup raw pass (debug 0x40000 = off), variant "ab"
 R="${GRAFT_REPO_ROOT:-$PWD}"; cd "$R"; mkdir -p gpurun_out/ab
-ARGS="--lattice-links 25165824 --steps 6 --cpu-sample 2 --warmup 2 --no-service-point --no-traffic --no-legs --no-cpu-baseline"
+ARGS="--lattice-links 25165824 --steps 6 --cpu-sample 2 --warmup 2 --no-service-point --no-traffic --no-legs --no-cpu-baseline --full"
 for rep in 1 2; do
   for dbg in 0 262144; do
     WFST_LIB_VARIANT=ab timeout 150 python bench.py $ARGS --debug $dbg --detail-out gpurun_out/ab/p13_${dbg}_$rep.json > /dev/null 2> gpurun_out/ab/p13_${dbg}_$rep.err || tail -3 gpurun_out/ab/p13_${dbg}_$rep.err

@@ -2,7 +2,7 @@
 # the beam-15 lattice leg (pipelined determinizer, or AB_LATTICE_ARGS) with several LIBRARY VARIANTS (build.py --variant NAME;
 # "" = the product library), one box, interleaved:   bash tools/ab_variant.sh base ""
 R="${GRAFT_REPO_ROOT:-$PWD}"; cd "$R"; mkdir -p gpurun_out/ab
-ARGS="${AB_LATTICE_ARGS:---beam 15 --lattice-beam 8 --lattice-links 25165824 --arena-per-frame 60000 --max-tokens 262144 --determinize --pipeline-determinizer} --steps ${STEPS:-6} --cpu-sample 2 --warmup 2 --no-service-point --no-traffic --no-legs --no-cpu-baseline"
+ARGS="${AB_LATTICE_ARGS:---beam 15 --lattice-beam 8 --lattice-links 25165824 --arena-per-frame 60000 --max-tokens 262144 --determinize --pipeline-determinizer} --steps ${STEPS:-6} --cpu-sample 2 --warmup 2 --no-service-point --no-traffic --no-legs --no-cpu-baseline --full"
 for rep in $(seq 1 ${REPS:-2}); do
   i=0
   for v in "$@"; do

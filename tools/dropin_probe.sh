@@ -1,5 +1,5 @@
 #!/bin/bash
-# the drop-in leg's CLI runs by hand (timing experiments): needs /tmp/wfst_bench_graph_2850000.bin (any bench.py run leaves it)
+# the drop-in leg's CLI runs by hand (timing experiments): writes the bench graph and utterances as files for it (bench.py keeps none)
 R="${GRAFT_REPO_ROOT:-$PWD}"; cd "$R"
 python - <<'P'
 import importlib, os, struct, sys, numpy as np
