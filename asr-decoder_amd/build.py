@@ -48,8 +48,44 @@ def build_variant(name, defines):
     return out
 
 
+def kernel_resources(extra=()):
+    """What the compiler made of the decode kernels (wfst_kernels.hip, device code only, the library's own flags):
+    {kernel name: {"vgprs", "agprs", "sgprs", "vgpr_spill", "sgpr_spill", "scratch", "occupancy", "lds"}} from
+    -Rpass-analysis=kernel-resource-usage; "lds" is the static LDS in bytes.  Template instantiations keep their mangled names,
+    plain kernels go by their function name.  (tests/test_kernel_resources.py; `python build.py --resources` prints the lines.)"""
+    import re
+    import tempfile
+    flags = [f for f in FLAGS if f not in ("-shared", "-fPIC")]
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([HIPCC] + flags + list(extra) + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
+                                                           "-o", os.path.join(tmp, "kernels.o"), SRCS[0]],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])
+    keys = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
+            "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
+    out, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark: +(.*?): (\S+) \[-Rpass-analysis=kernel-resource-usage\]", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            name = m.group(2)
+            plain = re.match(r"_ZN4wfstL?(\d+)", name)   # wfst::<name>(...): the plain kernels
+            if plain and "I" not in name[len(plain.group(0)) + int(plain.group(1)):][:1]:
+                a = len(plain.group(0))
+                name = name[a:a + int(plain.group(1))]
+            cur = out.setdefault(name, {})
+        elif cur is not None and m.group(1) in keys:
+            cur[keys[m.group(1)]] = int(m.group(2))
+    return out
+
+
 if __name__ == "__main__":
-    if "--variant" in sys.argv:
+    if "--resources" in sys.argv:
+        for k, v in sorted(kernel_resources().items()):
+            print(k, " ".join("%s=%d" % kv for kv in sorted(v.items())))
+    elif "--variant" in sys.argv:
         i = sys.argv.index("--variant")
         print(build_variant(sys.argv[i + 1], [a for a in sys.argv[i + 2:] if a.startswith("-D")]))
     else:

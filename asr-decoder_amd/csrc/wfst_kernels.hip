@@ -709,7 +709,8 @@ __global__ __launch_bounds__(kExpandThreads) void expand_kernel_biglm_timed(Deco
 // per TILE.  The records go to their bucket slots straight from the LDS image (rank within the tile's share of the
 // bucket): neighbouring lanes write to different partitions, the lines fill in L2.
 // A tile is kStTokens = 256 frontier tokens (one per thread); its slots beyond kStSlots are staged in further passes.
-// LDS: 24 KB slots + 6 KB log-likelihoods + 4 KB per-token scan = 34.5 KB: four workgroups per CU.
+// LDS: 24 KB slots + 6 KB log-likelihoods + 4 KB per-token scan + 1 KB compacting-tile index + 0.5 KB counters = 35.6 KB
+// (36 408 bytes): four workgroups per CU.
 // Arithmetic, pruning and record layout are those of the round-2 expansion of the fused rows (retired in round 4), to the bit.
 // =========================================================================================
 constexpr int kStThreads = 256;
@@ -720,7 +721,11 @@ constexpr int kStSlotsGather = 1536;   // (1392 slots at five workgroups per CU 
 // 16-byte DMA per four columns, asked for with the tile's tokens -- instead of one 4-byte gather per arc slot (a request each at
 // the memory side: 1.9 M per frame of 128 utterances against 0.9 M row lines; the gathers were a round trip of their own
 // between the arcs and the pricing).  Rows of up to kStRowFloats columns, a multiple of four, 16-byte aligned (what
-// wfst_decoder_advance checks); 22 KB slots + 12 KB row + 4 KB scan = 38.5 KB: still four workgroups per CU.
+// wfst_decoder_advance checks); 22 KB slots + 12 KB row + 4 KB scan + 1 KB compacting-tile index + 0.5 KB counters = 39.6 KB
+// (40 504 bytes, of 40 960 for four workgroups in a CU's 160 KB): LDS is what bounds this kernel's residency, alone and beside the
+// insert kernel (4096 table slots = 49 KB: 1 insert + 2 expansion workgroups are 128 KB, 2 + 1 are 137.5 KB).  Its registers
+// stay below the 96 that a fourth workgroup on such a CU would need -- tests/test_kernel_resources.py -- should the insert
+// table ever shrink (2048 slots measured: NOTES.md, "a fourth workgroup per CU").
 constexpr int kStSlotsRow = 1408;
 constexpr int kStSuper = 4;   // a compacting tile holds up to kStSuper x kStTokens frontier tokens (frame_boundary_fused / prep_frame size it)
 // Tokens per compacting tile of a frame of n tokens of which about n_live lie at or below the cutoff: as many as hold ~7/8 of a
@@ -737,7 +742,12 @@ template <bool kTimers, bool kRow>
 __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int group, int par) {
   constexpr int kStSlots = kRow ? kStSlotsRow : kStSlotsGather;
   constexpr int kStIter = (kStSlots + kStThreads - 1) / kStThreads;   // slots per thread and pass
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid0 = threadIdx.x;
+  int tid = tid0, lane = tid & 63, wave = tid >> 6;
+  // A FRESH thread index per phase: what a phase derives from the index (slot numbers, LDS addresses, six of each) is computed
+  // in the phase and dies with it.  Derived from the one index of the kernel's entry, some fifty such values were loop invariants
+  // of the tile loop, held in registers across every pass; the wave number is a scalar.
+#define ST_FRESH_TID() do { tid = tid0; asm volatile("" : "+v"(tid)); lane = tid & 63; wave = __builtin_amdgcn_readfirstlane(tid >> 6); } while (0)
   unsigned long long tq = kTimers ? wall_clock64() : 0ull;
   FrameCtl *fc = D.fctl + group;
   // XCD-aware static assignment: workgroups b and b + 8 share an XCD (round-robin dispatch), the tile list holds a channel's tiles
@@ -819,6 +829,7 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
       for (int rnd = 0; rnd * kStTokens < n_live; ++rnd) {
       // ---- the round's tokens: one per thread; its row slots = emitting arcs + two per pseudo arc -------------------
       {
+        ST_FRESH_TID();
         int my_i = tid;   // the token's index within the tile
         if (super) {   // (uniform)
           // the tile's live tokens, numbered in token order; this round takes numbers [rnd * kStTokens, + kStTokens).  (Counted afresh
@@ -907,6 +918,7 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
         const int S = min(kStSlots, total - s0);
         // ---- (a) every slot of the pass: one lane's 16-byte DMA into the LDS image (64 consecutive slots per instruction) ----
         int lo[kStIter];
+        ST_FRESH_TID();
         {
           // the owner of each of this thread's slots: kStIter binary searches over the scanned offsets, run in LOCKSTEP (a search is
           // a chain of dependent LDS reads; one after the other they were ~2 us in front of the pass's last DMA)
@@ -980,6 +992,7 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
         if constexpr (kRow && kTimers) { if (tid == 0) dbg_phase(D, 12, tq); }
         if constexpr (kTimers) { if (tid == 0) dbg_phase(D, 13, tq); }
         // ---- (c) price every candidate; its record takes the place of its slot ------------------------------------------
+        ST_FRESH_TID();
         float tmin = kInf;
         u64 cbest = ~0ull;        // best_exp: this thread's cheapest candidate (emitting or epsilon arrival)
         uint32_t cand_mask = 0;   // bit i: slot i of this thread is a candidate (not a pseudo arc's second slot, not padding)
@@ -1084,6 +1097,7 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
         }
         if constexpr (kTimers) { if (tid == 0) dbg_phase(D, 14, tq); }
         // ---- (d) survivors: rank within the tile's share of their hash partition -------------------------------------
+        ST_FRESH_TID();
         int pr[kStIter];
 #pragma unroll
         for (int i = 0; i < kStIter; ++i) {
@@ -1111,6 +1125,7 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
         }
         lds_barrier();
         if constexpr (kTimers) { if (tid == 0) dbg_phase(D, 15, tq); }
+        ST_FRESH_TID();
         // ---- (e) the records, straight from the LDS image to their bucket slots ------------------------------------------
 #pragma unroll
         for (int i = 0; i < kStIter; ++i) {
@@ -1135,6 +1150,7 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
       }   // (rounds)
     }
     {
+      ST_FRESH_TID();
       // (a token's closure paths priced = its pseudo arcs = (slots - emitting arcs) / 2; tokens beyond the round's count carry +inf)
       const bool exp = counted && s_cost[tid] <= cutoff;
       const int nem = exp ? s_nemit[tid] : 0, zt = exp ? (s_base[tid + 1] - s_base[tid] - nem) >> 1 : 0;
@@ -1152,9 +1168,15 @@ __device__ __forceinline__ void expand_staged_body(const DecoderDev &D, int grou
     if constexpr (kTimers) tq = wall_clock64();
   }
 }
+#undef ST_FRESH_TID
 __global__ __launch_bounds__(kStThreads, 4) void expand_kernel_staged(DecoderDev D, int group, int par) { expand_staged_body<false, false>(D, group, par); }
 __global__ __launch_bounds__(kStThreads, 4) void expand_kernel_staged_timed(DecoderDev D, int group, int par) { expand_staged_body<true, false>(D, group, par); }
-__global__ __launch_bounds__(kStThreads, 4) void expand_kernel_staged_row(DecoderDev D, int group, int par) { expand_staged_body<false, true>(D, group, par); }
+// (five waves per SIMD is this kernel's REGISTER ceiling -- 96 VGPRs, what a CU shared with insert workgroups would leave it; its
+// own LDS admits four workgroups, which the compiler remarks on)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"
+__global__ __launch_bounds__(kStThreads, 5) void expand_kernel_staged_row(DecoderDev D, int group, int par) { expand_staged_body<false, true>(D, group, par); }
+#pragma clang diagnostic pop
 __global__ __launch_bounds__(kStThreads, 4) void expand_kernel_staged_row_timed(DecoderDev D, int group, int par) { expand_staged_body<true, true>(D, group, par); }
 
 // =========================================================================================
