@@ -9,12 +9,14 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <memory>
 #include <string>
 #include <array>
 #include <vector>
 
 #include "../../include/wfst_decoder.h"
 #include "wfst_device.h"
+#include "wfst_hip_own.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -34,25 +36,6 @@ int fail(int code, const std::string &msg) {
     if (e_ != hipSuccess)                                                                       \
       return fail(WFST_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));            \
   } while (0)
-
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    release();
-    const hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { p = nullptr; return e; }   // (n stays 0: a failed buffer is never taken for a large enough one)
-    n = count;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  size_t bytes() const { return n * sizeof(T); }
-};
 
 }  // namespace
 
@@ -95,16 +78,6 @@ struct wfst_graph {
     g.n_arcs = n_arcs;
     return g;
   }
-  ~wfst_graph() {
-    arcs.release();
-    arc_ilabel.release();
-    arc_olabel.release();
-    arc_src.release();
-    eps_target_state.release();
-    eps_flat.release();
-    pseudo.release();
-    pseudo_w.release();
-  }
 };
 
 struct wfst_lm {
@@ -130,23 +103,18 @@ struct wfst_lm {
     L.hmask = hmask;
     return L;
   }
-  ~wfst_lm() {
-    st.release();
-    words.release();
-    wt.release();
-    hash.release();
-  }
 };
 
 struct wfst_decoder {
+  // Every HIP resource below is an owner (wfst_hip_own.h) and goes with the decoder; the order of the members matters for `stream`
+  // alone, which is declared first so that it is destroyed last: it outlives the buffers its work reads.
+  Stream stream;   // the decoder's own, or the caller's (borrowed)
   const wfst_graph *graph = nullptr;
   int device = 0;
   wfst_config cfg;
   wfst_limits lim = {0, 0, 0, 0, 0, 0, 0, 0};   // as resolved by create
   int32_t n_channels = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  DecoderDev D;
+  DecoderDev D = {};
   DevBuf<ChanCtl> ctl;
   DevBuf<int4> tok;
   DevBuf<int32_t> emit_cnt, prune_par;
@@ -173,36 +141,36 @@ struct wfst_decoder {
   std::vector<int32_t> h_decoded, h_target, h_state;  // state: 0 = never inited, 1 = decoding, 2 = finalized
   std::vector<const float *> h_ll_base;
   // pinned staging
-  int32_t *p_target = nullptr, *p_chan = nullptr;   // p_target / p_ll: kStage sets, used in rotation (advance_device)
-  const float **p_ll = nullptr;
+  PinBuf<int32_t> p_target, p_chan;   // p_target / p_ll: kStage sets, used in rotation (advance_device)
+  PinBuf<const float *> p_ll;
   static constexpr int kStage = 4;
-  hipEvent_t stage_ev[kStage] = {nullptr, nullptr, nullptr, nullptr};   // set k's upload has been consumed
+  Event stage_ev[kStage];   // set k's upload has been consumed
   int stage_next = 0;
-  hipEvent_t chan_stage_ev[kStage] = {nullptr, nullptr, nullptr, nullptr};   // (stage_channels' sets of p_chan)
+  Event chan_stage_ev[kStage];   // (stage_channels' sets of p_chan)
   int chan_stage_next = 0;
   // RESULTS beside the search: a best path asked for a LIST of channels (the channel pool's shape: some utterances have ended, the
   // others go on) runs on a stream of its own behind the listed channels' last enqueued work -- an event recorded on the decoder's
   // stream by every init / advance / finalize, in a ring; a slot recorded again marks a later point of the stream: still behind the
   // channel's work -- instead of behind everything the decoder's stream holds (the frames of the other channels enqueued since).
   static constexpr int kMarkRing = 16;
-  hipEvent_t mark_ev[kMarkRing] = {};
+  Event mark_ev[kMarkRing];
   int mark_next = 0;
   long long mark_count = 0;            // marks recorded so far
   bool mark_frames[kMarkRing] = {};    // the mark stands behind an advance call (frames to decode), not behind an init / finalize
   std::vector<int> chan_mark;          // [channel] ring slot of the event behind the channel's last enqueued work, -1: none
-  hipStream_t res_stream = nullptr;
+  Stream res_stream;
   std::vector<int32_t> bp_out;         // wfst_decoder_best_path_enqueue: the outstanding request's channels ...
   int32_t bp_out_n = 0, bp_out_cap = 0;   // ... their number (0: nothing outstanding) and the hop capacity
-  ChanCtl *bp_ctl_pin = nullptr;       // ... and its own page-locked copy of the control blocks (p_ctl is the synchronous getters')
-  int32_t *bp_deg_pin = nullptr;       // ... and of the degraded-frame counts, which a fetch leaves in deg_cache for its channels
+  PinBuf<ChanCtl> bp_ctl_pin;          // ... and its own page-locked copy of the control blocks (p_ctl is the synchronous getters')
+  PinBuf<int32_t> bp_deg_pin;          // ... and of the degraded-frame counts, which a fetch leaves in deg_cache for its channels
   std::vector<long long> chan_serial, bp_out_serial;   // [channel] calls enqueued for it so far; [list position] ... when the list was enqueued
   std::vector<int32_t> deg_cache;      // [channel] wfst_decoder_get_degraded_frames without a device round trip; -1: not held (any later init / advance / finalize of the channel)
-  int32_t *res_chan_pin = nullptr;
+  PinBuf<int32_t> res_chan_pin;
   DevBuf<int32_t> res_chan_list;
-  hipEvent_t copy_ev = nullptr;        // advance_host: the rows of page-locked buffers are on their way (the decode stream waits for it, the host does not)
+  Event copy_ev;                       // advance_host: the rows of page-locked buffers are on their way (the decode stream waits for it, the host does not)
   std::vector<const float *> hist_src; // [channel] the host buffer of the channel's last hand-over ...
   std::vector<char> hist_src_pinned;   // ... and whether it is page-locked (asked once per buffer)
-  ChanCtl *p_ctl = nullptr;
+  PinBuf<ChanCtl> p_ctl;
   // best-path output buffers (device), grown on demand
   DevBuf<int32_t> bp_chain;
   DevBuf<NbEntry> nb_list;  // n-best scratch, allocated by the first wfst_decoder_get_nbest
@@ -244,8 +212,7 @@ struct wfst_decoder {
   // a batch's determinized lattices packed back to back on the device (det_pack_kernel) and their pinned landing place on the host
   DevBuf<int4> det_pack_a;
   DevBuf<float2> det_pack_w;
-  void *det_pack_pin = nullptr;
-  size_t det_pack_pin_bytes = 0;
+  PinBuf<char> det_pack_pin;
   // wfst_decoder_prefetch_determinized: a determinize launch in flight on a side stream (its channels, its result words)
   int stagger_us = 0;   // lattice decoders with several channel groups: group g starts its frame chain g x this many microseconds late
   bool pf_pending = false;
@@ -263,23 +230,22 @@ struct wfst_decoder {
   DevBuf<NbPathEntry> pf_np_lists;
   DevBuf<float> pf_np_tot;
   int32_t pf_np_slots = 0, pf_np_n = 0;
-  void *pf_np_pin = nullptr;
-  size_t pf_np_pin_bytes = 0;
+  PinBuf<char> pf_np_pin;
   std::vector<NbPaths> pf_nbp;        // [channel] detached prefetches: the paths of the utterance the prefetched lattice belongs to
   std::vector<char> pf_nbp_have;
-  int32_t *pf_pin = nullptr;          // [2][n_channels * 4] pinned: the channel list going up, the launch's result words coming down (a copy from or
+  PinBuf<int32_t> pf_pin;             // [2][n_channels * 4] pinned: the channel list going up, the launch's result words coming down (a copy from or
                                       // to pageable memory would hold the calling thread until the launch is over)
   DevBuf<int32_t> pf_dev;
-  hipStream_t det_stream = nullptr;   // (a decoder without channel groups; otherwise the second group's stream, idle between advances)
-  hipEvent_t pf_ev_start = nullptr, pf_ev_done = nullptr;
+  Stream det_stream;                  // (a decoder without channel groups; otherwise the second group's stream, idle between advances)
+  Event pf_ev_start, pf_ev_done;
   // host-fed log-likelihood history (advance_host)
-  hipStream_t copy_stream = nullptr;  // host -> device uploads of advance_host
+  Stream copy_stream;                 // host -> device uploads of advance_host
   // pruned lattices fetched from the device (lattice mode): filled for ALL finalized channels by the
   // first wfst_decoder_get_raw_lattice after a FinalizeDecoding, dropped by init / finalize
   std::vector<std::vector<int4> > lat_cache_tok;
   std::vector<std::vector<LatArc> > lat_cache_arc;
   std::vector<char> lat_cached;
-  char *lat_pin = nullptr;  // pinned staging for that fetch
+  PinBuf<char> lat_pin;     // pinned staging for that fetch
   DevBuf<int32_t> bp_all;   // GetBestPath: {n_hops | ilabel | olabel | graph | acoustic} of the listed channels, one D2H copy
   // wfst_decoder_set_endpoint_config / _endpoint_detected: the config (its silence list copied), the silence bitmap over
   // transition-ids on the device, the channel list and the per-channel results {trailing frames, relative cost, error}
@@ -289,12 +255,10 @@ struct wfst_decoder {
   int32_t ep_ntid = 0;
   DevBuf<uint32_t> ep_bits;
   DevBuf<int32_t> ep_chan, ep_out;
-  int32_t *ep_pin = nullptr;   // page-locked: [n_channels] channel list, then [3 n_channels] results
-  char *bp_pin = nullptr;   // its pinned staging
-  size_t bp_pin_bytes = 0;
-  size_t lat_pin_bytes = 0;
+  PinBuf<int32_t> ep_pin;      // page-locked: [n_channels] channel list, then [3 n_channels] results
+  PinBuf<char> bp_pin;      // its pinned staging
   std::vector<int32_t> lat_cache_nd;
-  float *hist_slab = nullptr;          // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
+  DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
   int32_t hist_slab_stride = 0;        // ... of this many floats
   size_t hist_cap = 0;                 // (uniform pitch: equally spaced page-locked rows of many channels go up as one 2-D copy)
   std::vector<float *> hist_dev;       // [channel] = hist_slab + channel * hist_cap * hist_stride
@@ -305,68 +269,30 @@ struct wfst_decoder {
   int upload_slice = 48;  // wfst_options.upload_slice_frames
   // the frame loop of one advance call, captured once per (frames per group, stride) and replayed
   bool use_graph = true;
-  std::map<std::vector<int>, hipGraphExec_t> graphs;
+  GraphExecCache graphs;
   // channel groups: each runs its frame loop on its own stream (fork/join around the main stream)
   int n_groups = 1;
-  std::vector<hipStream_t> gstreams;
-  std::vector<hipEvent_t> gevents;  // [0] fork, [1..] join per group
+  std::vector<Stream> gstreams;   // ([0] stays empty: group 0 runs on the decoder's stream)
+  std::vector<Event> gevents;     // [0] fork, [1..] join per group
   // optional kernel timing (wfst_decoder_set_profiling)
   bool profiling = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   std::vector<std::pair<int, int>> ev_pairs[4];  // [kernel class] -> (start, stop) event indices
   std::vector<std::array<int, 4>> ev_log;        // the same launches in order: {kind, channel group, start, stop} (WFST_PROFILE_DUMP of a WFST_AB_SWITCHES build)
   size_t ev_used = 0;
   int ev_get() {
     if (ev_used == ev_pool.size()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return -1;
-      ev_pool.push_back(e);
+      Event e;
+      if (e.create(hipEventDefault) != hipSuccess) return -1;
+      ev_pool.push_back(std::move(e));
     }
     return (int)ev_used++;
   }
 
-  ~wfst_decoder() {
+  ~wfst_decoder() {   // (the waits only: they come before any member gives its resource back)
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     if (pf_pending && pf_ev_done) (void)hipEventSynchronize(pf_ev_done);   // (a prefetching determinizer still reads the decoder's buffers)
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (det_stream) (void)hipStreamDestroy(det_stream);
-    if (pf_ev_start) (void)hipEventDestroy(pf_ev_start);
-    if (pf_ev_done) (void)hipEventDestroy(pf_ev_done);
-    if (lat_pin) (void)hipHostFree(lat_pin);
-    if (bp_pin) (void)hipHostFree(bp_pin);
-    if (ep_pin) (void)hipHostFree(ep_pin);
-    ep_bits.release(); ep_chan.release(); ep_out.release();
-    if (hist_slab) (void)hipFree(hist_slab);
-    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
-    for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
-    for (hipStream_t st : gstreams) if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t ev : gevents) (void)hipEventDestroy(ev);
-    if (p_target) (void)hipHostFree(p_target);
-    for (hipEvent_t ev : stage_ev) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : chan_stage_ev) if (ev) (void)hipEventDestroy(ev);
-    if (copy_ev) (void)hipEventDestroy(copy_ev);
-    for (hipEvent_t ev : mark_ev) if (ev) (void)hipEventDestroy(ev);
-    if (res_stream) (void)hipStreamDestroy(res_stream);
-    if (res_chan_pin) (void)hipHostFree(res_chan_pin);
-    if (bp_ctl_pin) (void)hipHostFree(bp_ctl_pin);
-    if (bp_deg_pin) (void)hipHostFree(bp_deg_pin);
-    res_chan_list.release();
-    if (p_chan) (void)hipHostFree(p_chan);
-    if (p_ll) (void)hipHostFree((void *)p_ll);
-    if (p_ctl) (void)hipHostFree(p_ctl);
-    if (pf_pin) (void)hipHostFree(pf_pin);
-    if (pf_np_pin) (void)hipHostFree(pf_np_pin);
-    pf_np_ws.release(); pf_np_arcs.release(); pf_np_off.release(); pf_np_out.release(); pf_np_lists.release(); pf_np_tot.release();
-    if (det_pack_pin) (void)hipHostFree(det_pack_pin);
-    pair_keys.release(); pair_list.release(); eps_keys.release(); tok_lm.release(); bucket_lm.release(); remap.release();
-    det_ws.release(); det_result.release(); det_ticks.release(); det_out_a.release(); det_out_w.release(); det_pack_a.release(); det_pack_w.release(); pf_dev.release();
-    cmp_ws.release(); cmp_result.release(); cmp_fin.release(); cmp_out_a.release(); cmp_out_w.release();
-    np_ws.release(); np_out.release(); np_off.release(); np_arcs.release(); np_tot.release(); np_lists.release();
-    ctl.release(); tok.release(); frame_off.release(); bucket_cnt.release(); emit_cnt.release(); prune_par.release();
-    eps_toki.release(); eps_occ_list.release(); eps_won_list.release(); worklist.release(); target.release(); chan_list.release();
-    bucket.release(); links.release(); lat_toks.release(); lat_arcs.release(); lat_stats.release(); link_off.release(); link_mid.release(); extra.release(); fctl.release(); dbg_t.release(); items.release(); item_pref.release(); degraded.release(); tiles.release(); cutoff_hist.release(); eps_vals.release(); ll_base.release(); nb_list.release(); nb_scratch.release(); nb_out_i.release(); nb_out_f.release(); bp_chain.release(); bp_all.release();
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
 
@@ -701,7 +627,7 @@ int wfst_graph_from_arrays_ex(int32_t start, int32_t final_state, int32_t n_stat
       }
     }
 
-  wfst_graph *g = new wfst_graph();
+  std::unique_ptr<wfst_graph> g(new wfst_graph());
   g->device = device;
   g->fused = fused ? 1 : 0;
   g->start = pos[start];
@@ -725,10 +651,8 @@ int wfst_graph_from_arrays_ex(int32_t start, int32_t final_state, int32_t n_stat
       (e = g->eps_target_state.alloc(h_targets.size())) != hipSuccess ||
       (e = g->eps_flat.alloc(std::max<size_t>(1, h_flat.size()))) != hipSuccess ||
       (e = g->pseudo.alloc(std::max<size_t>(1, h_pseudo.size()))) != hipSuccess ||
-      (e = g->pseudo_w.alloc(h_pseudo_w.size())) != hipSuccess) {
-    delete g;
+      (e = g->pseudo_w.alloc(h_pseudo_w.size())) != hipSuccess)
     return fail(WFST_E_DEVICE, std::string("hipMalloc(graph): ") + hipGetErrorString(e));
-  }
   int rc = WFST_OK;
   if (hipMemcpy(g->arc_src.p, h_src.data(), h_src.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(g->arc_olabel.p, h_ol.data(), h_ol.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -738,12 +662,9 @@ int wfst_graph_from_arrays_ex(int32_t start, int32_t final_state, int32_t n_stat
       hipMemcpy(g->pseudo_w.p, h_pseudo_w.data(), h_pseudo_w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(g->arc_ilabel.p, g->ilabel_host.data(), g->ilabel_host.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
     rc = fail(WFST_E_DEVICE, "hipMemcpy(graph) failed");
-  if (rc == WFST_OK) rc = upload_columns(g, nullptr, 0, &ext);
-  if (rc != WFST_OK) {
-    delete g;
-    return rc;
-  }
-  *out = g;
+  if (rc == WFST_OK) rc = upload_columns(g.get(), nullptr, 0, &ext);
+  if (rc != WFST_OK) return rc;
+  *out = g.release();
   return WFST_OK;
 }
 
@@ -877,7 +798,7 @@ int wfst_lm_from_arrays(int32_t bos, int32_t eos, int32_t unk, int32_t n_states,
     }
   }
   HIP_TRY(hipSetDevice(device));
-  wfst_lm *lm = new wfst_lm();
+  std::unique_ptr<wfst_lm> lm(new wfst_lm());
   lm->device = device;
   lm->bos = bos;
   lm->eos = eos;
@@ -894,11 +815,9 @@ int wfst_lm_from_arrays(int32_t bos, int32_t eos, int32_t unk, int32_t n_states,
       (e = hipMemcpy(lm->words.p, words.data(), words.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(lm->wt.p, wt.data(), wt.size() * sizeof(int2), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = lm->hash.alloc(htab.size())) != hipSuccess ||
-      (e = hipMemcpy(lm->hash.p, htab.data(), htab.size() * sizeof(int4), hipMemcpyHostToDevice)) != hipSuccess) {
-    delete lm;
+      (e = hipMemcpy(lm->hash.p, htab.data(), htab.size() * sizeof(int4), hipMemcpyHostToDevice)) != hipSuccess)
     return fail(WFST_E_DEVICE, std::string("LM upload: ") + hipGetErrorString(e));
-  }
-  *out = lm;
+  *out = lm.release();
   return WFST_OK;
 }
 
@@ -1038,21 +957,14 @@ int wfst_decoder_create_biglm(const wfst_graph *g, const wfst_config *cfg, int32
   const int n_part = 1 << log2part;
   const int64_t bucket_cap = std::max<int64_t>(2048, 8 * M / n_part);
 
-  wfst_decoder *d = new wfst_decoder();
+  std::unique_ptr<wfst_decoder> d(new wfst_decoder());
   d->graph = g;
   d->device = g->device;
   d->cfg = *cfg;
   d->lim = L;
   d->n_channels = n_channels;
-  if (hip_stream) {
-    d->stream = (hipStream_t)hip_stream;
-  } else {
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete d;
-      return fail(WFST_E_DEVICE, "hipStreamCreate failed");
-    }
-    d->own_stream = true;
-  }
+  if (hip_stream) d->stream.borrow((hipStream_t)hip_stream);
+  else if (d->stream.create() != hipSuccess) return fail(WFST_E_DEVICE, "hipStreamCreate failed");
   size_t pair_cap = 0;
   const size_t B = (size_t)n_channels;
   size_t ecap = (size_t)std::max(1, g->n_eps_targets);
@@ -1064,112 +976,86 @@ int wfst_decoder_create_biglm(const wfst_graph *g, const wfst_config *cfg, int32
   }
   int64_t lat_arc_cap = 0, lat_tok_cap = 0;
   const size_t fo = (size_t)L.max_frames + 2;
+  DecoderDev &D = d->D;
   hipError_t e = hipSuccess;
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  A(d->ctl.alloc(B));
-  A(d->tok.alloc(B * (size_t)L.arena_tokens));
-  A(d->frame_off.alloc(B * fo));
-  A(d->cutoff_hist.alloc(B * fo));
-  A(d->bucket.alloc(B * (size_t)n_part * (size_t)bucket_cap));
-  A(d->bucket_cnt.alloc(B * (size_t)n_part));
-  A(d->emit_cnt.alloc(B * 32));
-  A(d->prune_par.alloc(B * kPruneParInts));
-  A(d->eps_vals.alloc(B * ecap));
-  A(d->eps_toki.alloc(B * ecap));
-  A(d->eps_occ_list.alloc(B * (size_t)L.max_tokens_per_frame));
-  A(d->eps_won_list.alloc(B * (size_t)L.max_tokens_per_frame));
-  A(d->worklist.alloc(B * 2 * (size_t)L.max_tokens_per_frame));
+  // A decode buffer is named ONCE: own() allocates it, keeps the first error, queues its initial fill (0x00 / 0xFF, done below when
+  // everything is allocated) and returns the pointer for DecoderDev.  A buffer this kind of decoder does not have stays null in D.
+  struct Fill { void *p; size_t bytes; int value; };
+  std::vector<Fill> fills;
+  auto own = [&](auto &buf, size_t count, int fill = -1) {
+    A(buf.alloc(count));
+    if (fill >= 0) fills.push_back({(void *)buf.p, buf.bytes(), fill});
+    return buf.p;
+  };
+  D.ctl = own(d->ctl, B, 0x00);
+  D.tok = own(d->tok, B * (size_t)L.arena_tokens);
+  D.frame_off = own(d->frame_off, B * fo);
+  D.cutoff_hist = own(d->cutoff_hist, B * fo);
+  D.bucket = own(d->bucket, B * (size_t)n_part * (size_t)bucket_cap);
+  D.bucket_cnt = own(d->bucket_cnt, B * (size_t)n_part, 0x00);
+  D.emit_cnt = own(d->emit_cnt, B * 32, 0x00);
+  D.prune_par = own(d->prune_par, B * kPruneParInts, 0x00);
+  D.eps_vals = own(d->eps_vals, B * ecap, 0xFF);
+  D.eps_toki = own(d->eps_toki, B * ecap);
+  D.eps_occ_list = own(d->eps_occ_list, B * (size_t)L.max_tokens_per_frame);
+  D.eps_won_list = own(d->eps_won_list, B * (size_t)L.max_tokens_per_frame);
+  D.worklist = own(d->worklist, B * 2 * (size_t)L.max_tokens_per_frame);
   if (big) {
-    A(d->pair_keys.alloc(B * pair_cap));
-    A(d->pair_list.alloc(B * pair_cap));
-    A(d->eps_keys.alloc(B * ecap));
-    A(d->tok_lm.alloc(B * (size_t)L.arena_tokens));
-    A(d->bucket_lm.alloc(B * (size_t)n_part * (size_t)bucket_cap));
+    D.pair_keys = own(d->pair_keys, B * pair_cap, 0xFF);
+    D.pair_list = own(d->pair_list, B * pair_cap);
+    D.eps_keys = own(d->eps_keys, B * ecap, 0xFF);
+    D.tok_lm = own(d->tok_lm, B * (size_t)L.arena_tokens);
+    D.bucket_lm = own(d->bucket_lm, B * (size_t)n_part * (size_t)bucket_cap);
   }
   // new indices while the arena is compacted: the back-pruning of lattice mode, the token collection of best-path mode
-  A(d->remap.alloc(B * (size_t)L.arena_tokens));
+  D.remap = own(d->remap, B * (size_t)L.arena_tokens);
   if (L.lattice_links > 0) {
-    A(d->links.alloc(B * (size_t)L.lattice_links));
-    A(d->link_off.alloc(B * ((size_t)L.max_frames + 3)));
-    A(d->link_mid.alloc(B * ((size_t)L.max_frames + 3)));
-    A(d->extra.alloc(B * (size_t)L.arena_tokens));
+    D.links = own(d->links, B * (size_t)L.lattice_links);
+    D.link_off = own(d->link_off, B * ((size_t)L.max_frames + 3));
+    D.link_mid = own(d->link_mid, B * ((size_t)L.max_frames + 3));
+    D.extra = own(d->extra, B * (size_t)L.arena_tokens);
     // GetRawLattice may be asked for at any time (base-inl.h:869-975): everything alive -- the pruned
     // history and the raw frames since the last PruneActiveTokens pass -- must fit the resolved lists
     lat_arc_cap = L.lattice_links;
     lat_tok_cap = L.arena_tokens;
-    A(d->lat_arcs.alloc(B * (size_t)lat_arc_cap));
-    A(d->lat_toks.alloc(B * (size_t)lat_tok_cap));
-    A(d->lat_stats.alloc(B * 4));
+    D.lat_arcs = own(d->lat_arcs, B * (size_t)lat_arc_cap);
+    D.lat_toks = own(d->lat_toks, B * (size_t)lat_tok_cap);
+    D.lat_stats = own(d->lat_stats, B * 4);
   }
   // tiles of 128 tokens at least (prep_frame); a frame of a soft-limit decoder may hold several times the per-frame limit (every
   // candidate the buckets took can be a token: 8 x the limit): room for every channel at twice the limit and then some
   const size_t tile_cap = B * ((size_t)L.max_tokens_per_frame / 64 + 2) + (size_t)L.max_tokens_per_frame / 16;
-  A(d->fctl.alloc(8));
-  A(d->dbg_t.alloc(128));
-  A(d->tiles.alloc(8 * tile_cap));
+  D.fctl = own(d->fctl, 8, 0x00);
+  D.dbg_t = own(d->dbg_t, 128, 0x00);
+  D.tiles = own(d->tiles, 8 * tile_cap);
   const size_t item_cap = 2 * B * (size_t)n_part;  // two lists (heavy from the front, light from the back), each sized for the worst case
-  A(d->items.alloc(8 * item_cap));
-  A(d->item_pref.alloc(8 * item_cap * 64));   // the record prefix of every listed item, beside it (plan_channel)
-  A(d->degraded.alloc(B));
-  A(d->target.alloc(B));
-  A(d->chan_list.alloc(B));
-  A(d->ll_base.alloc(B));
-  A(hipHostMalloc((void **)&d->p_target, wfst_decoder::kStage * B * 4));
-  A(hipHostMalloc((void **)&d->p_chan, wfst_decoder::kStage * B * 4));
-  for (int k = 0; k < wfst_decoder::kStage; ++k) A(hipEventCreateWithFlags(&d->chan_stage_ev[k], hipEventDisableTiming));
-  A(hipHostMalloc((void **)&d->p_ll, wfst_decoder::kStage * B * sizeof(float *)));
-  for (int k = 0; k < wfst_decoder::kStage; ++k) A(hipEventCreateWithFlags(&d->stage_ev[k], hipEventDisableTiming));
-  A(hipEventCreateWithFlags(&d->copy_ev, hipEventDisableTiming));
-  for (int k = 0; k < wfst_decoder::kMarkRing; ++k) A(hipEventCreateWithFlags(&d->mark_ev[k], hipEventDisableTiming));
+  D.items = own(d->items, 8 * item_cap);
+  D.item_pref = own(d->item_pref, 8 * item_cap * 64);   // the record prefix of every listed item, beside it (plan_channel)
+  D.degraded = own(d->degraded, B, 0x00);
+  own(d->target, B, 0x00);
+  own(d->chan_list, B);
+  D.ll_base = own(d->ll_base, B, 0x00);
+  own(d->res_chan_list, B);
+  A(d->p_target.alloc(wfst_decoder::kStage * B));
+  A(d->p_chan.alloc(wfst_decoder::kStage * B));
+  A(d->p_ll.alloc(wfst_decoder::kStage * B));
+  A(d->res_chan_pin.alloc(B));
+  A(d->p_ctl.alloc(B));
+  for (Event &ev : d->chan_stage_ev) A(ev.create());
+  for (Event &ev : d->stage_ev) A(ev.create());
+  A(d->copy_ev.create());
+  for (Event &ev : d->mark_ev) A(ev.create());
   d->chan_mark.assign(B, -1);
-  A(hipHostMalloc((void **)&d->res_chan_pin, B * 4));
-  A(d->res_chan_list.alloc(B));
-  A(hipHostMalloc((void **)&d->p_ctl, B * sizeof(ChanCtl)));
-  if (e == hipSuccess) A(hipMemsetAsync(d->ctl.p, 0, d->ctl.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->bucket_cnt.p, 0, d->bucket_cnt.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->emit_cnt.p, 0, d->emit_cnt.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->prune_par.p, 0, d->prune_par.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->fctl.p, 0, d->fctl.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->dbg_t.p, 0, d->dbg_t.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->eps_vals.p, 0xFF, d->eps_vals.bytes(), d->stream));
-  if (e == hipSuccess && big) A(hipMemsetAsync(d->eps_keys.p, 0xFF, d->eps_keys.bytes(), d->stream));
-  if (e == hipSuccess && big) A(hipMemsetAsync(d->pair_keys.p, 0xFF, d->pair_keys.bytes(), d->stream));
+  for (const Fill &f : fills)
+    if (e == hipSuccess) A(hipMemsetAsync(f.p, f.value, f.bytes, d->stream));
   {
     const int per_slot = (L.lattice_links > 0 && big) ? 20 : (L.lattice_links > 0 || big) ? 16 : 12;
     if (e == hipSuccess && lds_slots * per_slot > 65536) A((hipError_t)insert_kernel_set_lds(lds_slots * per_slot));
   }
-
-  if (e == hipSuccess) A(hipMemsetAsync(d->degraded.p, 0, d->degraded.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->target.p, 0, d->target.bytes(), d->stream));
-  if (e == hipSuccess) A(hipMemsetAsync(d->ll_base.p, 0, d->ll_base.bytes(), d->stream));
   if (e == hipSuccess) A(hipStreamSynchronize(d->stream));
-  if (e != hipSuccess) {
-    delete d;
-    return fail(WFST_E_DEVICE, std::string("decoder allocation failed: ") + hipGetErrorString(e));
-  }
-  DecoderDev &D = d->D;
+  if (e != hipSuccess) return fail(WFST_E_DEVICE, std::string("decoder allocation failed: ") + hipGetErrorString(e));
   D.g = g->view();
-  D.ctl = d->ctl.p;
-  D.tok = d->tok.p;
-  D.frame_off = d->frame_off.p;
-  D.cutoff_hist = d->cutoff_hist.p;
-  D.bucket = d->bucket.p;
-  D.bucket_cnt = d->bucket_cnt.p;
-  D.emit_cnt = d->emit_cnt.p;
-  D.prune_par = d->prune_par.p;
-  D.eps_vals = d->eps_vals.p;
-  D.eps_toki = d->eps_toki.p;
-  D.eps_occ_list = d->eps_occ_list.p;
-  D.eps_won_list = d->eps_won_list.p;
-  D.worklist = d->worklist.p;
-  D.links = d->links.p;
-  D.link_off = d->link_off.p;
-  D.link_mid = d->link_mid.p;
-  D.extra = d->extra.p;
-  D.remap = d->remap.p;
-  D.lat_arcs = d->lat_arcs.p;
-  D.lat_toks = d->lat_toks.p;
-  D.lat_stats = d->lat_stats.p;
   D.lat_arc_cap = (int32_t)lat_arc_cap;
   D.lat_tok_cap = (int32_t)lat_tok_cap;
   D.link_cap = L.lattice_links;
@@ -1238,21 +1124,9 @@ int wfst_decoder_create_biglm(const wfst_graph *g, const wfst_config *cfg, int32
       if (stride >= 1) { D.two_launch = 1; D.gc_stride = (int32_t)std::min<int64_t>(stride, 16); }
     }
   }
-  D.pair_keys = d->pair_keys.p;
-  D.pair_list = d->pair_list.p;
   D.pair_cap = (int32_t)pair_cap;
-  D.tok_lm = d->tok_lm.p;
-  D.bucket_lm = d->bucket_lm.p;
-  D.eps_keys = d->eps_keys.p;
-  D.fctl = d->fctl.p;
-  D.dbg_t = d->dbg_t.p;
-  D.tiles = d->tiles.p;
   D.tile_cap = (int32_t)tile_cap;
-  D.items = d->items.p;
-  D.item_pref = d->item_pref.p;
-  D.degraded = d->degraded.p;
   D.item_cap = (int32_t)item_cap;
-  D.ll_base = d->ll_base.p;
   D.n_channels = n_channels;
   D.stride = 0;
   D.n_part = n_part;
@@ -1304,10 +1178,9 @@ int wfst_decoder_create_biglm(const wfst_graph *g, const wfst_config *cfg, int32
     d->gstreams.resize(d->n_groups);
     d->gevents.resize(d->n_groups + 1);
     hipError_t ge = hipSuccess;
-    d->gstreams[0] = nullptr;  // group 0 runs on the decoder's own stream
-    for (size_t g = 1; g < d->gstreams.size(); ++g) if (ge == hipSuccess) ge = hipStreamCreateWithFlags(&d->gstreams[g], hipStreamNonBlocking);
-    for (auto &ev : d->gevents) if (ge == hipSuccess) ge = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (ge != hipSuccess) { delete d; return fail(WFST_E_DEVICE, "stream/event creation failed"); }
+    for (size_t g = 1; g < d->gstreams.size(); ++g) if (ge == hipSuccess) ge = d->gstreams[g].create();  // group 0 runs on the decoder's own stream
+    for (Event &ev : d->gevents) if (ge == hipSuccess) ge = ev.create();
+    if (ge != hipSuccess) return fail(WFST_E_DEVICE, "stream/event creation failed");
   }
   if (d->D.lattice && d->D.prune_raw) {
     // the raw launch's workgroups wait for each other: taken only where every workgroup of all the groups' launches is resident at
@@ -1318,7 +1191,7 @@ int wfst_decoder_create_biglm(const wfst_graph *g, const wfst_config *cfg, int32
   d->expand_wgs = O.expand_workgroups;
   d->insert_wgs = O.insert_workgroups;
   d->gpar.assign(8, 0);
-  *out = d;
+  *out = d.release();
   return WFST_OK;
 }
 
@@ -1385,7 +1258,7 @@ static int mark_channels(wfst_decoder *d, const int32_t *channels, int32_t cnt, 
 }
 // The results stream, made to wait for the listed channels' last enqueued work (and nothing newer).
 static int results_stream_behind(wfst_decoder *d, const int32_t *channels, int32_t cnt, hipStream_t *out) {
-  if (!d->res_stream) HIP_TRY(hipStreamCreateWithFlags(&d->res_stream, hipStreamNonBlocking));
+  if (!d->res_stream) HIP_TRY(d->res_stream.create());
   bool waited[wfst_decoder::kMarkRing] = {};
   for (int i = 0; i < cnt; ++i) {
     const int k = d->chan_mark[(size_t)channels[i]];
@@ -1414,7 +1287,7 @@ static int stage_channels(wfst_decoder *d, const int32_t *channels, int32_t n, c
   const int stage = d->chan_stage_next;
   d->chan_stage_next = (d->chan_stage_next + 1) % wfst_decoder::kStage;
   HIP_TRY(hipEventSynchronize(d->chan_stage_ev[stage]));
-  int32_t *p_chan = d->p_chan + (size_t)stage * d->n_channels;
+  int32_t *p_chan = d->p_chan.p + (size_t)stage * d->n_channels;
   memcpy(p_chan, channels, (size_t)n * 4);
   HIP_TRY(hipMemcpyAsync(d->chan_list.p, p_chan, (size_t)n * 4, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipEventRecord(d->chan_stage_ev[stage], d->stream));
@@ -1496,8 +1369,8 @@ static int advance_device(wfst_decoder *d, const int32_t *channels, int32_t n, c
   const int stage = d->stage_next;
   d->stage_next = (d->stage_next + 1) % wfst_decoder::kStage;
   HIP_TRY(hipEventSynchronize(d->stage_ev[stage]));   // (never recorded: returns at once)
-  int32_t *p_target = d->p_target + (size_t)stage * d->n_channels;
-  const float **p_ll = d->p_ll + (size_t)stage * d->n_channels;
+  int32_t *p_target = d->p_target.p + (size_t)stage * d->n_channels;
+  const float **p_ll = d->p_ll.p + (size_t)stage * d->n_channels;
   for (int i = 0; i < cnt; ++i) {
     const int c = channels ? channels[i] : i;
     int target = n_frames_ready[i];
@@ -1608,23 +1481,20 @@ static int advance_device(wfst_decoder *d, const int32_t *channels, int32_t n, c
     std::vector<int> key = {g, gsteps[g], (int)stride, gpar0[g], (int)d->D.ll_row, s_lo, s_hi};
     for (int s = -1; s < gsteps[g]; ++s)
       if (prune_step(g, s)) key.push_back(s);   // (the launch sequence differs with the steps that prune)
-    auto it = d->graphs.find(key);
-    if (it == d->graphs.end()) {
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
+    auto it = d->graphs.m.find(key);
+    hipGraphExec_t exec = it == d->graphs.m.end() ? nullptr : it->second;
+    if (!exec) {
+      Graph graph;   // (the capture: gone once the executable is made of it)
       HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       enqueue_group(g, st, s_lo, s_hi);
-      HIP_TRY(hipStreamEndCapture(st, &graph));
-      HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-      HIP_TRY(hipGraphDestroy(graph));
-      if (d->graphs.size() >= 64) {  // bounded cache
+      HIP_TRY(hipStreamEndCapture(st, &graph.h));
+      if (d->graphs.m.size() >= 64) {  // bounded cache
         HIP_TRY(hipDeviceSynchronize());
-        for (auto &kv : d->graphs) (void)hipGraphExecDestroy(kv.second);
-        d->graphs.clear();
+        d->graphs.destroy_all();
       }
-      it = d->graphs.emplace(key, exec).first;
+      HIP_TRY(d->graphs.add(key, graph.h, &exec));
     }
-    HIP_TRY(hipGraphLaunch(it->second, st));
+    HIP_TRY(hipGraphLaunch(exec, st));
     return WFST_OK;
   };
   if (G == 1) {
@@ -1688,25 +1558,26 @@ int wfst_decoder_advance_host(wfst_decoder *d, const int32_t *channels, int32_t 
     if (want > have && !loglikes_host[i]) return fail(WFST_E_ARG, "NULL log-likelihood matrix");
     need_rows = std::max(need_rows, (size_t)want);
   }
-  if (need_rows > d->hist_cap || (d->hist_slab && d->hist_slab_stride != stride)) {
+  if (need_rows > d->hist_cap || (d->hist_slab.p && d->hist_slab_stride != stride)) {
     // The histories of all channels are one allocation of uniform pitch.  (A decoder created with a small wfst_limits.max_frames --
     // a caller that sizes its utterances -- gets the whole history at once: regrowing costs an allocation, a device copy and a free
     // that waits for the device.)
     size_t ncap = std::max<size_t>(need_rows, std::max<size_t>(d->hist_cap * 2, 256));
     if (d->D.max_frames <= 1024) ncap = std::max<size_t>(ncap, (size_t)d->D.max_frames);
     ncap = std::min<size_t>(ncap, std::max<size_t>(need_rows, (size_t)d->D.max_frames));   // (no utterance is longer than max_frames)
-    float *np = nullptr;
+    DevBuf<float> slab;   // the new history: the decoder's once the old one's rows are in it and every channel points at it
     if (d->copy_stream) HIP_TRY(hipStreamSynchronize(d->copy_stream));   // (rows of page-locked buffers may still be on their way into the old history)
-    HIP_TRY(hipMalloc((void **)&np, (size_t)d->n_channels * ncap * (size_t)stride * 4));
+    HIP_TRY(slab.alloc((size_t)d->n_channels * ncap * (size_t)stride));
+    float *const np = slab.p;
     size_t keep = 0;
     for (int c = 0; c < d->n_channels; ++c) keep = std::max(keep, (size_t)d->hist_rows[c]);
-    if (d->hist_slab && keep > 0 && d->hist_slab_stride == stride) {
+    if (d->hist_slab.p && keep > 0 && d->hist_slab_stride == stride) {
       // (on the decoder's own stream, not the legacy one: another decoder of the process may be capturing its frame loop in
       // another thread -- the service's one-decoder-per-thread shape -- and the legacy stream refuses to work beside a capture)
-      HIP_TRY(hipMemcpy2DAsync(np, ncap * (size_t)stride * 4, d->hist_slab, d->hist_cap * (size_t)stride * 4, keep * (size_t)stride * 4,
+      HIP_TRY(hipMemcpy2DAsync(np, ncap * (size_t)stride * 4, d->hist_slab.p, d->hist_cap * (size_t)stride * 4, keep * (size_t)stride * 4,
                                (size_t)d->n_channels, hipMemcpyDeviceToDevice, d->stream));
     }
-    if (d->hist_slab) {
+    if (d->hist_slab.p) {
       HIP_TRY(hipStreamSynchronize(d->stream));
       // channels that read their rows from the old allocation follow it: the listed ones through advance_device (which sees their
       // pointers move and uploads ALL row pointers), the others here
@@ -1714,9 +1585,8 @@ int wfst_decoder_advance_host(wfst_decoder *d, const int32_t *channels, int32_t 
       for (int i = 0; i < cnt; ++i) listed[(size_t)(channels ? channels[i] : i)] = 1;
       for (int c = 0; c < d->n_channels; ++c)
         if (!listed[(size_t)c] && d->h_ll_base[c] == d->hist_dev[c] && d->hist_dev[c]) d->h_ll_base[c] = np + (size_t)c * ncap * (size_t)stride;
-      HIP_TRY(hipFree(d->hist_slab));
     }
-    d->hist_slab = np;
+    d->hist_slab = std::move(slab);   // (frees the old one: the stream is idle)
     d->hist_cap = ncap;
     d->hist_slab_stride = stride;
     for (int c = 0; c < d->n_channels; ++c) {
@@ -1728,7 +1598,7 @@ int wfst_decoder_advance_host(wfst_decoder *d, const int32_t *channels, int32_t 
   // Upload and decode in slices of kSlice frames: the host copies slice k+1 (pageable memory: the
   // copy call returns when the caller's buffer is consumed) while the GPU decodes slice k, so the
   // PCIe time of a long hand-over hides behind the search instead of preceding it.
-  if (!d->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
+  if (!d->copy_stream) HIP_TRY(d->copy_stream.create());
   const int kSlice = std::max(1, d->upload_slice);
   int longest = 0;
   for (int i = 0; i < cnt; ++i) longest = std::max(longest, n_frames_ready[i] - d->hist_rows[channels ? channels[i] : i]);
@@ -1853,7 +1723,7 @@ int wfst_decoder_finalize(wfst_decoder *d, const int32_t *channels, int32_t n) {
 }
 
 static int read_ctl(wfst_decoder *d) {
-  HIP_TRY(hipMemcpyAsync(d->p_ctl, d->ctl.p, d->ctl.bytes(), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->p_ctl.p, d->ctl.p, d->ctl.bytes(), hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return WFST_OK;
 }
@@ -1876,7 +1746,7 @@ static int fail_ctl_error(int c, int e) {
 
 static int check_ctl_errors(wfst_decoder *d) {
   for (int c = 0; c < d->n_channels; ++c)
-    if (d->p_ctl[c].error) return fail_ctl_error(c, d->p_ctl[c].error);
+    if (d->p_ctl.p[c].error) return fail_ctl_error(c, d->p_ctl.p[c].error);
   return WFST_OK;
 }
 
@@ -1940,13 +1810,7 @@ static int bp_buffers(wfst_decoder *d, size_t words, size_t need, int32_t cap = 
     HIP_TRY(d->bp_all.alloc(words));
     HIP_TRY(d->bp_chain.alloc(need));
   }
-  if (d->bp_pin_bytes < words * 4) {
-    if (d->bp_pin) (void)hipHostFree(d->bp_pin);
-    d->bp_pin = nullptr;
-    d->bp_pin_bytes = 0;
-    HIP_TRY(hipHostMalloc((void **)&d->bp_pin, words * 4, hipHostMallocDefault));
-    d->bp_pin_bytes = words * 4;
-  }
+  HIP_TRY(d->bp_pin.reserve(words * 4));
   return WFST_OK;
 }
 
@@ -1971,18 +1835,18 @@ int wfst_decoder_best_path_enqueue(wfst_decoder *d, const int32_t *channels, int
   const size_t need = (size_t)n * (size_t)cap, head = ((size_t)n + 3) & ~(size_t)3, words = head + 4 * need;
   rc = bp_buffers(d, words, need, cap);
   if (rc != WFST_OK) return rc;
-  if (!d->bp_ctl_pin) HIP_TRY(hipHostMalloc((void **)&d->bp_ctl_pin, d->ctl.bytes(), hipHostMallocDefault));
-  memcpy(d->res_chan_pin, channels, (size_t)n * 4);   // (the results stream is idle here: nothing is outstanding)
-  HIP_TRY(hipMemcpyAsync(d->res_chan_list.p, d->res_chan_pin, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  if (!d->bp_ctl_pin.p) HIP_TRY(d->bp_ctl_pin.alloc(d->ctl.n));
+  memcpy(d->res_chan_pin.p, channels, (size_t)n * 4);   // (the results stream is idle here: nothing is outstanding)
+  HIP_TRY(hipMemcpyAsync(d->res_chan_list.p, d->res_chan_pin.p, (size_t)n * 4, hipMemcpyHostToDevice, st));
   int32_t *dn = d->bp_all.p, *dil = dn + head, *dol = dil + need;
   float *dg = reinterpret_cast<float *>(dol + need), *dac = dg + need;
   launch_best_path(d->D, d->res_chan_list.p, n, use_final_probs ? 1 : 0, cap, dil, dol, dg, dac, dn, d->bp_chain.p, st);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(d->bp_pin, d->bp_all.p, words * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(d->bp_pin.p, d->bp_all.p, words * 4, hipMemcpyDeviceToHost, st));
   // (the listed channels' control blocks are final behind their marks; the others' are not looked at)
-  HIP_TRY(hipMemcpyAsync(d->bp_ctl_pin, d->ctl.p, d->ctl.bytes(), hipMemcpyDeviceToHost, st));
-  if (!d->bp_deg_pin) HIP_TRY(hipHostMalloc((void **)&d->bp_deg_pin, d->degraded.bytes(), hipHostMallocDefault));
-  HIP_TRY(hipMemcpyAsync(d->bp_deg_pin, d->degraded.p, d->degraded.bytes(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(d->bp_ctl_pin.p, d->ctl.p, d->ctl.bytes(), hipMemcpyDeviceToHost, st));
+  if (!d->bp_deg_pin.p) HIP_TRY(d->bp_deg_pin.alloc(d->degraded.n));
+  HIP_TRY(hipMemcpyAsync(d->bp_deg_pin.p, d->degraded.p, d->degraded.bytes(), hipMemcpyDeviceToHost, st));
   d->bp_out.assign(channels, channels + n);
   if (d->chan_serial.empty()) d->chan_serial.assign((size_t)d->n_channels, 0);
   d->bp_out_serial.resize((size_t)n);
@@ -2010,7 +1874,7 @@ int wfst_decoder_best_path_fetch(wfst_decoder *d, int32_t *ilabel, int32_t *olab
   d->bp_out_n = 0;   // (taken, whatever it turns out to hold)
   HIP_TRY(hipStreamSynchronize(d->res_stream));
   const size_t need = (size_t)cnt * (size_t)cap, head = ((size_t)cnt + 3) & ~(size_t)3;
-  const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin);
+  const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin.p);
   memcpy(n_hops, hp, (size_t)cnt * 4);
   memcpy(ilabel, hp + head, need * 4);
   memcpy(olabel, hp + head + need, need * 4);
@@ -2019,13 +1883,13 @@ int wfst_decoder_best_path_fetch(wfst_decoder *d, int32_t *ilabel, int32_t *olab
   // a device error of ANOTHER channel's utterance is that channel's, not this request's
   for (int i = 0; i < cnt; ++i) {
     const int c = d->bp_out[(size_t)i];
-    if (d->bp_ctl_pin[c].error) return fail_ctl_error(c, d->bp_ctl_pin[c].error);
+    if (d->bp_ctl_pin.p[c].error) return fail_ctl_error(c, d->bp_ctl_pin.p[c].error);
   }
   // (the listed channels' counts of frames on which the token limit bound: read behind their own work, like the paths)
   if (d->deg_cache.empty()) d->deg_cache.assign((size_t)d->n_channels, -1);
   for (int i = 0; i < cnt; ++i) {
     const size_t c = (size_t)d->bp_out[(size_t)i];
-    if (d->chan_serial[c] == d->bp_out_serial[(size_t)i]) d->deg_cache[c] = d->bp_deg_pin[c];   // (no call for the channel since the list went up)
+    if (d->chan_serial[c] == d->bp_out_serial[(size_t)i]) d->deg_cache[c] = d->bp_deg_pin.p[c];   // (no call for the channel since the list went up)
   }
   for (int i = 0; i < cnt; ++i)
     if (n_hops[i] > cap) return fail(WFST_E_CAPACITY, "best path longer than cap hops; n_hops holds the needed size");
@@ -2063,11 +1927,11 @@ int wfst_decoder_get_best_path(wfst_decoder *d, const int32_t *channels, int32_t
   float *dg = reinterpret_cast<float *>(dol + need), *dac = dg + need;
   launch_best_path(d->D, dev, cnt, use_final_probs ? 1 : 0, cap, dil, dol, dg, dac, dn, d->bp_chain.p, d->stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(d->bp_pin, d->bp_all.p, words * 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->bp_pin.p, d->bp_all.p, words * 4, hipMemcpyDeviceToHost, d->stream));
   rc = read_ctl(d);   // synchronises the stream
   if (rc != WFST_OK) return rc;
   {
-    const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin);
+    const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin.p);
     memcpy(n_hops, hp, (size_t)cnt * 4);
     memcpy(ilabel, hp + head, need * 4);
     memcpy(olabel, hp + head + need, need * 4);
@@ -2349,7 +2213,7 @@ int wfst_decoder_get_raw_lattice(wfst_decoder *d, int32_t channel, int32_t use_f
     if (rc != WFST_OK) return rc;
     rc = check_ctl_errors(d);
     if (rc != WFST_OK) return rc;
-    const ChanCtl &cc = d->p_ctl[channel];
+    const ChanCtl &cc = d->p_ctl.p[channel];
     d->lat_cache_nd[channel] = cc.n_decoded;
     d->lat_cache_tok[channel].resize((size_t)cc.lat_toks);
     d->lat_cache_arc[channel].resize((size_t)cc.lat_arcs);
@@ -2373,35 +2237,29 @@ int wfst_decoder_get_raw_lattice(wfst_decoder *d, int32_t channel, int32_t use_f
     size_t need = 0;
     for (int c = 0; c < d->n_channels; ++c) {
       if (d->h_state[c] != 2 || d->lat_cached[c]) continue;
-      need += (size_t)d->p_ctl[c].lat_toks * sizeof(int4) + (size_t)d->p_ctl[c].lat_arcs * sizeof(LatArc);
+      need += (size_t)d->p_ctl.p[c].lat_toks * sizeof(int4) + (size_t)d->p_ctl.p[c].lat_arcs * sizeof(LatArc);
     }
-    if (need > d->lat_pin_bytes) {
-      if (d->lat_pin) (void)hipHostFree(d->lat_pin);
-      d->lat_pin = nullptr;
-      d->lat_pin_bytes = 0;
-      HIP_TRY(hipHostMalloc((void **)&d->lat_pin, need + need / 4, hipHostMallocDefault));
-      d->lat_pin_bytes = need + need / 4;
-    }
+    HIP_TRY(d->lat_pin.reserve(need, need / 4));
     size_t off = 0;
     for (int c = 0; c < d->n_channels; ++c) {
       if (d->h_state[c] != 2 || d->lat_cached[c]) continue;
-      const ChanCtl &cc = d->p_ctl[c];
+      const ChanCtl &cc = d->p_ctl.p[c];
       const size_t tb = (size_t)cc.lat_toks * sizeof(int4), ab = (size_t)cc.lat_arcs * sizeof(LatArc);
-      if (tb) HIP_TRY(hipMemcpyAsync(d->lat_pin + off, d->lat_toks.p + (size_t)c * (size_t)d->D.lat_tok_cap, tb, hipMemcpyDeviceToHost, d->stream));
-      if (ab) HIP_TRY(hipMemcpyAsync(d->lat_pin + off + tb, d->lat_arcs.p + (size_t)c * (size_t)d->D.lat_arc_cap, ab, hipMemcpyDeviceToHost, d->stream));
+      if (tb) HIP_TRY(hipMemcpyAsync(d->lat_pin.p + off, d->lat_toks.p + (size_t)c * (size_t)d->D.lat_tok_cap, tb, hipMemcpyDeviceToHost, d->stream));
+      if (ab) HIP_TRY(hipMemcpyAsync(d->lat_pin.p + off + tb, d->lat_arcs.p + (size_t)c * (size_t)d->D.lat_arc_cap, ab, hipMemcpyDeviceToHost, d->stream));
       off += tb + ab;
     }
     HIP_TRY(hipStreamSynchronize(d->stream));
     off = 0;
     for (int c = 0; c < d->n_channels; ++c) {
       if (d->h_state[c] != 2 || d->lat_cached[c]) continue;
-      const ChanCtl &cc = d->p_ctl[c];
+      const ChanCtl &cc = d->p_ctl.p[c];
       const size_t tb = (size_t)cc.lat_toks * sizeof(int4), ab = (size_t)cc.lat_arcs * sizeof(LatArc);
       d->lat_cache_nd[c] = cc.n_decoded;
       d->lat_cache_tok[c].resize((size_t)cc.lat_toks);
       d->lat_cache_arc[c].resize((size_t)cc.lat_arcs);
-      if (tb) memcpy(d->lat_cache_tok[c].data(), d->lat_pin + off, tb);
-      if (ab) memcpy(d->lat_cache_arc[c].data(), d->lat_pin + off + tb, ab);
+      if (tb) memcpy(d->lat_cache_tok[c].data(), d->lat_pin.p + off, tb);
+      if (ab) memcpy(d->lat_cache_arc[c].data(), d->lat_pin.p + off + tb, ab);
       off += tb + ab;
       d->lat_cached[c] = 1;
     }
@@ -2563,17 +2421,11 @@ static int harvest_determinized(wfst_decoder *d, const std::vector<int32_t> &lis
       HIP_TRY(d->det_pack_w.alloc(kPackCap));
     }
     const size_t need = total * (sizeof(int4) + sizeof(float2));
-    if (d->det_pack_pin_bytes < need) {
-      if (d->det_pack_pin) (void)hipHostFree(d->det_pack_pin);
-      d->det_pack_pin = nullptr;
-      d->det_pack_pin_bytes = 0;
-      HIP_TRY(hipHostMalloc(&d->det_pack_pin, need + need / 2, hipHostMallocDefault));
-      d->det_pack_pin_bytes = need + need / 2;
-    }
+    HIP_TRY(d->det_pack_pin.reserve(need, need / 2));
     launch_det_pack(X, (int)list.size(), d->det_pack_a.p, d->det_pack_w.p, (int64_t)kPackCap, d->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d->det_pack_pin, d->det_pack_a.p, total * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync((char *)d->det_pack_pin + total * sizeof(int4), d->det_pack_w.p, total * sizeof(float2), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->det_pack_pin.p, d->det_pack_a.p, total * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->det_pack_pin.p + total * sizeof(int4), d->det_pack_w.p, total * sizeof(float2), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
   }
   std::vector<unsigned long long> ticks(list.size(), 0ull);
@@ -2587,7 +2439,7 @@ static int harvest_determinized(wfst_decoder *d, const std::vector<int32_t> &lis
     L.n_states = 0; L.n_proper = 0; L.a.clear(); L.w.clear();
     L.ticks = ticks[(size_t)i];
     L.err = res[4 * i + 2];   // reported when THIS channel's lattice is asked for
-    if (!detached && d->p_ctl[list[i]].error) L.err = kDetErrCtl | d->p_ctl[list[i]].error;
+    if (!detached && d->p_ctl.p[list[i]].error) L.err = kDetErrCtl | d->p_ctl.p[list[i]].error;
     if (detached) d->pf_have[(size_t)list[i]] = 1;
     else {
       d->det_cached[(size_t)list[i]] = live ? 0 : 1;
@@ -2601,8 +2453,8 @@ static int harvest_determinized(wfst_decoder *d, const std::vector<int32_t> &lis
     L.w.resize(na);
     if (!na) continue;
     if (packed) {
-      memcpy(L.a.data(), (const int4 *)d->det_pack_pin + off, na * sizeof(int4));
-      memcpy(L.w.data(), (const float2 *)((const char *)d->det_pack_pin + total * sizeof(int4)) + off, na * sizeof(float2));
+      memcpy(L.a.data(), (const int4 *)d->det_pack_pin.p + off, na * sizeof(int4));
+      memcpy(L.w.data(), (const float2 *)(d->det_pack_pin.p + total * sizeof(int4)) + off, na * sizeof(float2));
       off += na;
     } else {
       HIP_TRY(hipMemcpyAsync(L.a.data(), X.out_a + (size_t)i * X.out_cap, na * sizeof(int4), hipMemcpyDeviceToHost, d->stream));
@@ -2620,7 +2472,7 @@ static int harvest_determinized(wfst_decoder *d, const std::vector<int32_t> &lis
     }
   }
   for (int i = 0; i < (int)list.size(); ++i)
-    all_current = all_current && d->h_state[list[i]] == 2 && res[4 * i + 2] == 0 && (detached || !d->p_ctl[list[i]].error);
+    all_current = all_current && d->h_state[list[i]] == 2 && res[4 * i + 2] == 0 && (detached || !d->p_ctl.p[list[i]].error);
   if (all_current) {
     // the workspace slots hold these lattices: a batched second pass / n-best right behind starts from them (postprocess_batch)
     hold_slots(d, list, res);
@@ -2734,25 +2586,25 @@ static int prefetch_determinized(wfst_decoder *d, bool detached, int32_t n_paths
   for (int c = 0; c < d->n_channels && (int32_t)list.size() < d->det_slots; ++c)   // (one launch's worth; the rest on request)
     if (d->h_state[c] == 2 && !d->det_cached[c]) list.push_back(c);
   if (list.empty()) return WFST_OK;
-  hipStream_t side = (d->n_groups > 1 && !detached) ? d->gstreams[1] : d->det_stream;   // (detached: a stream the frame loop never uses)
+  hipStream_t side = (d->n_groups > 1 && !detached) ? d->gstreams[1].h : d->det_stream.h;   // (detached: a stream the frame loop never uses)
   if (!side) {
-    HIP_TRY(hipStreamCreateWithFlags(&d->det_stream, hipStreamNonBlocking));
+    HIP_TRY(d->det_stream.create());
     side = d->det_stream;
   }
   if (d->fin_epoch.empty()) d->fin_epoch.assign((size_t)d->n_channels, 0);
   d->pf_epoch.resize(list.size());
   for (size_t i = 0; i < list.size(); ++i) d->pf_epoch[i] = d->fin_epoch[(size_t)list[i]];
   if (!d->pf_ev_start) {
-    HIP_TRY(hipEventCreateWithFlags(&d->pf_ev_start, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d->pf_ev_done, hipEventDisableTiming));
+    HIP_TRY(d->pf_ev_start.create());
+    HIP_TRY(d->pf_ev_done.create());
   }
   if (!d->pf_dev.p) {
     HIP_TRY(hipStreamSynchronize(d->stream));
     HIP_TRY(d->pf_dev.alloc((size_t)d->n_channels));
-    HIP_TRY(hipHostMalloc((void **)&d->pf_pin, (size_t)d->n_channels * 8 * 4, hipHostMallocDefault));
+    HIP_TRY(d->pf_pin.alloc((size_t)d->n_channels * 8));
   }
   d->pf_list = list;
-  int32_t *pin_list = d->pf_pin, *pin_res = d->pf_pin + (size_t)d->n_channels * 4;
+  int32_t *pin_list = d->pf_pin.p, *pin_res = d->pf_pin.p + (size_t)d->n_channels * 4;
   for (size_t i = 0; i < list.size(); ++i) pin_list[i] = list[i];
   d->post_dev_list.clear();   // (the slots are about to hold other lattices than the last batched call's)
   HIP_TRY(hipMemcpyAsync(d->pf_dev.p, pin_list, list.size() * 4, hipMemcpyHostToDevice, d->stream));
@@ -2789,16 +2641,10 @@ static int prefetch_determinized(wfst_decoder *d, bool detached, int32_t n_paths
     P.out_arcs = d->pf_np_arcs.p;
     const size_t b_out = (size_t)cnt * 4 * 4, b_off = (size_t)cnt * (size_t)(n_paths + 1) * 4, b_tot = (size_t)cnt * (size_t)n_paths * 4,
                  b_arcs = (size_t)cnt * (size_t)P.out_cap * 4;
-    if (d->pf_np_pin_bytes < b_out + b_off + b_tot + b_arcs) {
-      if (d->pf_np_pin) (void)hipHostFree(d->pf_np_pin);
-      d->pf_np_pin = nullptr;
-      d->pf_np_pin_bytes = 0;
-      HIP_TRY(hipHostMalloc(&d->pf_np_pin, b_out + b_off + b_tot + b_arcs, hipHostMallocDefault));
-      d->pf_np_pin_bytes = b_out + b_off + b_tot + b_arcs;
-    }
+    HIP_TRY(d->pf_np_pin.reserve(b_out + b_off + b_tot + b_arcs));
     launch_nbest_paths(P, cnt, side, /*small=*/1);   // (determinized lattices of utterances: a hundred states each)
     HIP_TRY(hipGetLastError());
-    char *pin = (char *)d->pf_np_pin;
+    char *pin = d->pf_np_pin.p;
     HIP_TRY(hipMemcpyAsync(pin, P.out, b_out, hipMemcpyDeviceToHost, side));
     HIP_TRY(hipMemcpyAsync(pin + b_out, P.out_off, b_off, hipMemcpyDeviceToHost, side));
     HIP_TRY(hipMemcpyAsync(pin + b_out + b_off, P.out_tot, b_tot, hipMemcpyDeviceToHost, side));
@@ -2817,13 +2663,13 @@ static int finish_prefetch(wfst_decoder *d) {
   d->pf_pending = false;   // (the launch is over: from here on its lattices are either taken over below or lost with the error returned)
   const bool detached = d->pf_detached;
   d->pf_detached = false;
-  d->pf_res.assign(d->pf_pin + (size_t)d->n_channels * 4, d->pf_pin + (size_t)d->n_channels * 4 + d->pf_list.size() * 4);
+  d->pf_res.assign(d->pf_pin.p + (size_t)d->n_channels * 4, d->pf_pin.p + (size_t)d->n_channels * 4 + d->pf_list.size() * 4);
   // (a channel initialised or finalized anew since the launch: hooks in front of those calls came here first)
   const int rc = harvest_determinized(d, d->pf_list, d->pf_res, false, 1, detached);
   if (rc != WFST_OK || d->pf_npaths <= 0) return rc;
   // ... and the paths NShortestPath found on those lattices: arc indices -> the labels and costs of the lattices just fetched
   const int32_t n_paths = d->pf_npaths, cnt = (int32_t)d->pf_list.size(), out_cap = n_paths * 1024;
-  const char *pin = (const char *)d->pf_np_pin;
+  const char *pin = d->pf_np_pin.p;
   const int32_t *pout = (const int32_t *)pin;
   const int32_t *poff = (const int32_t *)(pin + (size_t)cnt * 16);
   const float *ptot = (const float *)(pin + (size_t)cnt * 16 + (size_t)cnt * (size_t)(n_paths + 1) * 4);
@@ -3250,7 +3096,7 @@ int wfst_decoder_get_stats(wfst_decoder *d, int32_t channel, int64_t stats[8]) {
   HIP_TRY(hipSetDevice(d->device));
   int rc = read_ctl(d);
   if (rc != WFST_OK) return rc;
-  const ChanCtl &c = d->p_ctl[channel];
+  const ChanCtl &c = d->p_ctl.p[channel];
   stats[0] = c.n_decoded;
   stats[1] = (int64_t)c.cnt_N;
   stats[2] = (int64_t)c.cnt_E;
@@ -3377,7 +3223,7 @@ int wfst_decoder_set_endpoint_config(wfst_decoder *d, const wfst_endpoint_config
   HIP_TRY(hipMemcpy(d->ep_bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
   if (!d->ep_chan.p) HIP_TRY(d->ep_chan.alloc((size_t)d->n_channels));
   if (!d->ep_out.p) HIP_TRY(d->ep_out.alloc((size_t)d->n_channels * 3));
-  if (!d->ep_pin) HIP_TRY(hipHostMalloc((void **)&d->ep_pin, (size_t)d->n_channels * 4 * 4, hipHostMallocDefault));
+  if (!d->ep_pin.p) HIP_TRY(d->ep_pin.alloc((size_t)d->n_channels * 4));
   d->ep_sil.assign(cfg->silence_phones, cfg->silence_phones + cfg->n_silence_phones);
   d->ep_cfg = *cfg;
   d->ep_cfg.silence_phones = d->ep_sil.data();
@@ -3405,7 +3251,7 @@ int wfst_decoder_endpoint_detected(wfst_decoder *d, const int32_t *channels, int
   hipStream_t st;
   int rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
   if (rc != WFST_OK) return rc;
-  int32_t *pin_chan = d->ep_pin, *pin_out = d->ep_pin + d->n_channels;
+  int32_t *pin_chan = d->ep_pin.p, *pin_out = d->ep_pin.p + d->n_channels;
   memcpy(pin_chan, channels, (size_t)n * 4);   // (the last endpoint call has been waited for: its copies are done)
   HIP_TRY(hipMemcpyAsync(d->ep_chan.p, pin_chan, (size_t)n * 4, hipMemcpyHostToDevice, st));
   launch_endpoint(d->D, d->ep_chan.p, n, d->ep_bits.p, d->ep_ntid, d->ep_out.p, st);
@@ -3431,7 +3277,7 @@ int wfst_decoder_get_frontier(wfst_decoder *d, int32_t channel, int32_t cap, int
   HIP_TRY(hipSetDevice(d->device));
   int rc = read_ctl(d);
   if (rc != WFST_OK) return rc;
-  const ChanCtl &c = d->p_ctl[channel];
+  const ChanCtl &c = d->p_ctl.p[channel];
   const int n = c.front_count, k = std::min(n, cap);
   if (k > 0) {
     std::vector<int4> t((size_t)k);
