@@ -21,6 +21,7 @@
 
 using namespace wfst;
 namespace wfst { int insert_kernel_set_lds(int bytes); }
+namespace wfst { launch_partial_fn launch_partial = nullptr; }   // set by wfst_kernels.hip (wfst_device.h)
 static const int32_t kHeaderLabel = -2;  // ilabel_host marker of a header slot
 
 namespace {
@@ -165,6 +166,8 @@ struct wfst_decoder {
   PinBuf<int32_t> bp_deg_pin;          // ... and of the degraded-frame counts, which a fetch leaves in deg_cache for its channels
   std::vector<long long> chan_serial, bp_out_serial;   // [channel] calls enqueued for it so far; [list position] ... when the list was enqueued
   std::vector<int32_t> deg_cache;      // [channel] wfst_decoder_get_degraded_frames without a device round trip; -1: not held (any later init / advance / finalize of the channel)
+  Event bp_ev;                         // ... and the event behind its copies: what _ready polls and _fetch waits for (the results stream may
+                                       // hold a partial-words request behind them, which is not theirs to wait for)
   PinBuf<int32_t> res_chan_pin;
   DevBuf<int32_t> res_chan_list;
   Event copy_ev;                       // advance_host: the rows of page-locked buffers are on their way (the decode stream waits for it, the host does not)
@@ -257,6 +260,15 @@ struct wfst_decoder {
   DevBuf<int32_t> ep_chan, ep_out;
   PinBuf<int32_t> ep_pin;      // page-locked: [n_channels] channel list, then [3 n_channels] results
   PinBuf<char> bp_pin;      // its pinned staging
+  // wfst_decoder_partial_enqueue / _ready / _fetch: the per-channel workspace of partial_kernel (commit state, committed words, scratch:
+  // allocated by the first request), the outstanding request's list, its device and page-locked blocks ([n_channels] list entries,
+  // then per entry {n_words, n_stable, stable_frame, error} + cap words) and the event behind its copies
+  DevBuf<int32_t> pt_ws, pt_chan, pt_out;
+  PinBuf<int32_t> pt_pin;
+  Event pt_ev;
+  std::vector<int32_t> pt_list;
+  int32_t pt_n = 0, pt_cap = 0;        // (0: nothing outstanding)
+  std::vector<char> pt_reset;          // [channel] InitDecoding since the channel's last request: its commit state starts from zero
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
   int32_t hist_slab_stride = 0;        // ... of this many floats
@@ -1316,6 +1328,7 @@ int wfst_decoder_init(wfst_decoder *d, const int32_t *channels, int32_t n) {
     d->h_state[c] = 1;
     d->h_ll_base[c] = nullptr;
     d->hist_rows[c] = 0;
+    if (!d->pt_reset.empty()) d->pt_reset[(size_t)c] = 1;
     if (!d->lat_cached.empty()) d->lat_cached[c] = 0;
     if (!d->det_cached.empty()) { d->det_cached[c] = 0; d->det_live_nd[c] = -1; }
     if (!d->resc_cache.empty()) { d->resc_cache[(size_t)c].key.valid = false; d->nbp_cache[(size_t)c].key.valid = false; }
@@ -1836,7 +1849,8 @@ int wfst_decoder_best_path_enqueue(wfst_decoder *d, const int32_t *channels, int
   rc = bp_buffers(d, words, need, cap);
   if (rc != WFST_OK) return rc;
   if (!d->bp_ctl_pin.p) HIP_TRY(d->bp_ctl_pin.alloc(d->ctl.n));
-  memcpy(d->res_chan_pin.p, channels, (size_t)n * 4);   // (the results stream is idle here: nothing is outstanding)
+  if (!d->bp_ev) HIP_TRY(d->bp_ev.create());
+  memcpy(d->res_chan_pin.p, channels, (size_t)n * 4);   // (no best-path request is outstanding: the last one's copy from here was waited for)
   HIP_TRY(hipMemcpyAsync(d->res_chan_list.p, d->res_chan_pin.p, (size_t)n * 4, hipMemcpyHostToDevice, st));
   int32_t *dn = d->bp_all.p, *dil = dn + head, *dol = dil + need;
   float *dg = reinterpret_cast<float *>(dol + need), *dac = dg + need;
@@ -1847,6 +1861,7 @@ int wfst_decoder_best_path_enqueue(wfst_decoder *d, const int32_t *channels, int
   HIP_TRY(hipMemcpyAsync(d->bp_ctl_pin.p, d->ctl.p, d->ctl.bytes(), hipMemcpyDeviceToHost, st));
   if (!d->bp_deg_pin.p) HIP_TRY(d->bp_deg_pin.alloc(d->degraded.n));
   HIP_TRY(hipMemcpyAsync(d->bp_deg_pin.p, d->degraded.p, d->degraded.bytes(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(d->bp_ev, st));
   d->bp_out.assign(channels, channels + n);
   if (d->chan_serial.empty()) d->chan_serial.assign((size_t)d->n_channels, 0);
   d->bp_out_serial.resize((size_t)n);
@@ -1860,10 +1875,10 @@ int wfst_decoder_best_path_ready(wfst_decoder *d) {
   if (!d) return fail(WFST_E_ARG, "NULL decoder");
   if (d->bp_out_n <= 0) return fail(WFST_E_STATE, "no best-path request is outstanding");
   HIP_TRY(hipSetDevice(d->device));
-  const hipError_t e = hipStreamQuery(d->res_stream);
+  const hipError_t e = hipEventQuery(d->bp_ev);
   if (e == hipSuccess) return 1;
   if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-  return fail(WFST_E_DEVICE, std::string("hipStreamQuery: ") + hipGetErrorString(e));
+  return fail(WFST_E_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(e));
 }
 
 int wfst_decoder_best_path_fetch(wfst_decoder *d, int32_t *ilabel, int32_t *olabel, float *graph_cost, float *acoustic_cost, int32_t *n_hops) {
@@ -1872,7 +1887,7 @@ int wfst_decoder_best_path_fetch(wfst_decoder *d, int32_t *ilabel, int32_t *olab
   HIP_TRY(hipSetDevice(d->device));
   const int32_t cnt = d->bp_out_n, cap = d->bp_out_cap;
   d->bp_out_n = 0;   // (taken, whatever it turns out to hold)
-  HIP_TRY(hipStreamSynchronize(d->res_stream));
+  HIP_TRY(hipEventSynchronize(d->bp_ev));
   const size_t need = (size_t)cnt * (size_t)cap, head = ((size_t)cnt + 3) & ~(size_t)3;
   const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin.p);
   memcpy(n_hops, hp, (size_t)cnt * 4);
@@ -3270,6 +3285,98 @@ int wfst_decoder_endpoint_detected(wfst_decoder *d, const int32_t *channels, int
     if (relative_cost) relative_cost[i] = pin_out[3 * i + 2] ? std::numeric_limits<float>::infinity() : rel;
   }
   return WFST_OK;
+}
+
+// ---- partial words with a stable prefix (the service's per-chunk callback) ---------------------------------------------------------
+static const char *kPartialBiglm = "partial words are not supported on biglm decoders (a hop's extra cost changes at FinalizeDecoding there)";
+int wfst_decoder_partial_enqueue(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t cap_words) {
+  if (!d || !channels || cap_words <= 0) return fail(WFST_E_ARG, "NULL decoder / channel list, or cap_words <= 0");
+  if (d->D.big) return fail(WFST_E_ARG, kPartialBiglm);
+  if (d->pt_n > 0) return fail(WFST_E_STATE, "a partial request is outstanding (wfst_decoder_partial_fetch takes it)");
+  if (!launch_partial) return fail(WFST_E_DEVICE, "partial_kernel is not part of this build");   // (never a fall-back: an error)
+  if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
+  HIP_TRY(hipSetDevice(d->device));
+  std::vector<char> seen((size_t)d->n_channels, 0);
+  for (int i = 0; i < n; ++i) {
+    const int c = channels[i];
+    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
+    if (seen[(size_t)c]) return fail(WFST_E_ARG, "duplicate channel in list");
+    seen[(size_t)c] = 1;
+    if (d->h_state[(size_t)c] == 0) return fail(WFST_E_STATE, "partial words before InitDecoding");
+    if (d->h_state[(size_t)c] == 2) return fail(WFST_E_STATE, "partial words after FinalizeDecoding");
+  }
+  const int64_t stride = partial_ws_ints(d->D.max_frames);
+  if (d->pt_reset.empty()) {   // the first request: a decoder that never asks pays nothing
+    // (all of it or none: what a failure leaves behind goes with these locals, and the next request starts over)
+    DevBuf<int32_t> ws, chan;
+    Event ev;
+    HIP_TRY(ws.alloc((size_t)d->n_channels * (size_t)stride));
+    HIP_TRY(chan.alloc((size_t)d->n_channels));
+    HIP_TRY(ev.create());
+    d->pt_ws = std::move(ws);
+    d->pt_chan = std::move(chan);
+    d->pt_ev = std::move(ev);
+    d->pt_reset.assign((size_t)d->n_channels, 1);
+  }
+  const size_t words = (size_t)n * (size_t)(4 + cap_words), all = (size_t)d->n_channels * (size_t)(4 + cap_words);
+  if (d->pt_out.n < words) HIP_TRY(d->pt_out.alloc(all));   // (room for every channel at this capacity, once; nothing of ours is outstanding)
+  HIP_TRY(d->pt_pin.reserve((size_t)d->n_channels + all));
+  hipStream_t st;
+  const int rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
+  if (rc != WFST_OK) return rc;
+  int32_t *pin_chan = d->pt_pin.p, *pin_out = d->pt_pin.p + d->n_channels;
+  for (int i = 0; i < n; ++i) pin_chan[i] = channels[i] | (d->pt_reset[(size_t)channels[i]] ? kPartialResetBit : 0);
+  HIP_TRY(hipMemcpyAsync(d->pt_chan.p, pin_chan, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  launch_partial(d->D, d->pt_chan.p, n, d->pt_ws.p, stride, cap_words, d->pt_out.p, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(pin_out, d->pt_out.p, words * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(d->pt_ev, st));
+  for (int i = 0; i < n; ++i) d->pt_reset[(size_t)channels[i]] = 0;
+  d->pt_list.assign(channels, channels + n);
+  d->pt_n = n;
+  d->pt_cap = cap_words;
+  return WFST_OK;
+}
+
+int wfst_decoder_partial_ready(wfst_decoder *d) {
+  if (!d) return fail(WFST_E_ARG, "NULL decoder");
+  if (d->pt_n <= 0) return fail(WFST_E_STATE, "no partial request is outstanding");
+  HIP_TRY(hipSetDevice(d->device));
+  const hipError_t e = hipEventQuery(d->pt_ev);
+  if (e == hipSuccess) return 1;
+  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
+  return fail(WFST_E_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(e));
+}
+
+int wfst_decoder_partial_fetch(wfst_decoder *d, int32_t *words, int32_t *n_words, int32_t *n_stable, int32_t *stable_frame) {
+  if (!d) return fail(WFST_E_ARG, "NULL decoder");
+  if (d->pt_n <= 0) return fail(WFST_E_STATE, "no partial request is outstanding");
+  HIP_TRY(hipSetDevice(d->device));
+  const int32_t cnt = d->pt_n, cap = d->pt_cap;
+  d->pt_n = 0;   // (taken, whatever it turns out to hold)
+  HIP_TRY(hipEventSynchronize(d->pt_ev));
+  const int32_t *pin_out = d->pt_pin.p + d->n_channels;
+  bool too_long = false;
+  for (int i = 0; i < cnt; ++i) {
+    const int32_t *o = pin_out + (size_t)i * (size_t)(4 + cap);
+    // (o[3] > 0: the channel's utterance ended in a device error -- no words; the error itself is reported by the channel's next
+    // advance / sync / best path, and the others' results stand)
+    if (n_words) n_words[i] = o[0];
+    if (n_stable) n_stable[i] = o[1];
+    if (stable_frame) stable_frame[i] = o[2];
+    // (o[3] < 0: more words than the decoder's max_frames -- the kernel wrote none, and no cap_words would hold them)
+    if (words && o[3] >= 0) memcpy(words + (size_t)i * (size_t)cap, o + 4, (size_t)std::min(std::max(o[0], 0), cap) * 4);
+    if (o[3] < 0 || o[0] > cap) too_long = true;
+  }
+  if (too_long) return fail(WFST_E_CAPACITY, "partial result longer than cap_words (n_words holds the needed size), or than the decoder's max_frames words");
+  return WFST_OK;
+}
+
+int wfst_decoder_get_partial(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t cap_words, int32_t *words, int32_t *n_words,
+                             int32_t *n_stable, int32_t *stable_frame) {
+  const int rc = wfst_decoder_partial_enqueue(d, channels, n, cap_words);
+  if (rc != WFST_OK) return rc;
+  return wfst_decoder_partial_fetch(d, words, n_words, n_stable, stable_frame);
 }
 
 int wfst_decoder_get_frontier(wfst_decoder *d, int32_t channel, int32_t cap, int32_t *states, float *costs) {

@@ -489,6 +489,16 @@ void launch_best_path(const DecoderDev &D, const int32_t *chan_list_dev, int n, 
 // endpoint inputs of the listed channels (endpoint_kernel): out[3 i ..] = {trailing silence frames, final relative cost, error}
 void launch_endpoint(const DecoderDev &D, const int32_t *chan_list_dev, int n, const uint32_t *sil_bits, int n_tid, int32_t *out,
                      hipStream_t s);
+// partial words with a stable prefix of the listed channels (partial_kernel): list entries may carry kPartialResetBit (the channel's
+// commit state starts from zero); ws: partial_ws_ints(max_frames) ints per channel; out[i]: {n_words, n_stable, stable_frame, error}
+// and cap_words words
+constexpr int32_t kPartialResetBit = 1 << 30;
+inline int64_t partial_ws_ints(int32_t max_frames) { return 8 + 2 * (int64_t)max_frames; }
+// (a pointer, null in wfst_capi.cc and set by wfst_kernels.hip when that is linked in: the host half of the library also links
+// without the kernels -- against the HIP test double --, where nothing asks for partial words; null at a request is an error)
+using launch_partial_fn = void (*)(const DecoderDev &D, const int32_t *chan_list_dev, int n, int32_t *ws, int64_t ws_stride, int cap_words,
+                                   int32_t *out, hipStream_t s);
+extern launch_partial_fn launch_partial;
 
 }  // namespace wfst
 #endif

@@ -4481,6 +4481,307 @@ __global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, cons
   if (tid == 0) out[3 * bi] = s_count;
 }
 
+// =========================================================================================
+// partial hypothesis with a stable word prefix (the reference service's per-chunk callback (best_str, partial, ...),
+// gpu-asr/v1-gpu-asr-task.h:70-76; kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:122-137), one kBpThreads workgroup per listed
+// channel, mid-utterance.  The words are those of GetBestPath(use_final_probs = false) + LatticeToVector now; the first n_stable of
+// them never change again.  Three steps:
+//  - the frontier reduction of endpoint_kernel (best_all); the same pass marks every frontier token's predecessor on frame nd - 1;
+//  - the ancestor sweep, frame by frame backwards: the ancestors of the frontier on frame f are a bitmap in LDS over the frame's
+//    arena range.  A marked token with a backpointer marks it (previous frame, or -- an epsilon hop a token collection has
+//    resolved -- its own frame); a marked token won by an epsilon arc (kPrevUnresolved) wants the frame's token on its arc's
+//    source state: those states go into an LDS hash and ONE scan of the frame marks them all; to the frame's fixpoint.  The
+//    first frame f < m_last ((nd - 1) / prune_interval * prune_interval: behind it bp_resolve_hop's inputs are frozen) that
+//    receives exactly ONE mark from frame f + 1 holds the commit token R -- every frontier token descends from it -- and ends the
+//    sweep; so does the channel's previous commit frame, which is never passed: the cost of a call follows the commit lag, not
+//    the utterance.  A frame or its predecessor beyond the bitmap ends the sweep with no new commit (never a wrong one);
+//  - the walk from best_all back to the PREVIOUS commit token (the root if there is none), in chunks of kEpChunk hops exactly as
+//    endpoint_kernel walks; wave 0 resolves the hops (bp_resolve_hop) and keeps the non-zero olabels, newest first, in the
+//    channel's scratch.  Those of the hops up to and including the hop into R are appended to the channel's committed words; the
+//    rest is the unstable tail.
+// ws, per channel: {commit frame (0: none), commit state (graph row), committed words, -, ...}, then max_frames committed words,
+// then max_frames words of scratch.  The commit token is remembered as (frame, state): collections and compactions move tokens
+// but keep frames, and a state has one token per frame.  A list entry with kPartialResetBit set starts the channel from zero (the first
+// request after InitDecoding).  out, per list entry: {n_words, n_stable, stable_frame, error (device error bits; -1: more words
+// than max_frames)} and cap_words words.
+// =========================================================================================
+constexpr int kPtBits = 65536;               // tokens of one frame an ancestor bitmap covers
+constexpr int kPtWords = kPtBits / 32;
+constexpr int kPtNeedLog2 = 12, kPtNeedSlots = 1 << kPtNeedLog2;   // LDS hash of the source states wanted in one scan
+constexpr int kPtStateInts = 8;   // (partial_ws_ints)
+__global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const int32_t *chans, int32_t *ws, long long ws_stride,
+                                                             int cap_words, int32_t *out) {
+  const int bi = blockIdx.x;
+  const bool reset = (chans[bi] & kPartialResetBit) != 0;
+  const int c = chans[bi] & ~kPartialResetBit;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int32_t *st = ws + (size_t)c * ws_stride, *committed = st + kPtStateInts, *rev = committed + D.max_frames;
+  int32_t *o = out + (size_t)bi * (4 + cap_words);
+  const ChanCtl *ctl = D.ctl + c;
+  const int cf = reset ? 0 : st[0], cs = reset ? -1 : st[1], nc = reset ? 0 : st[2];
+  const int n = ctl->front_count, nd = ctl->n_decoded, err = ctl->error;
+  if (err || n == 0 || nd <= 0) {   // no path (as best_path_kernel has it, base-inl.h:1104-1108), or the utterance ended in an error
+    if (tid == 0) {
+      o[0] = 0; o[1] = 0; o[2] = 0; o[3] = err;
+      if (reset) { st[0] = 0; st[1] = -1; st[2] = 0; }
+    }
+    return;
+  }
+  __shared__ u64 s_all[kBpThreads / 64];
+  __shared__ int32_t s_foff[kBpFrames + 2];
+  __shared__ uint32_t s_bm[3][kPtWords];
+  __shared__ int32_t s_key[kPtNeedSlots];
+  __shared__ int32_t s_tok[kEpChunk + 1];   // the chunk's tokens, last hop first: hop j is s_tok[j] <- s_tok[j + 1] (-1: the root)
+  __shared__ int s_cur, s_k, s_need, s_lo, s_hi, s_found, s_done, s_cnt, s_more, s_nneed, s_abort, s_R, s_nrev, s_ntail;
+  const int4 *tok = D.tok + (size_t)c * D.arena_cap;
+  const int fb = ctl->front_begin;
+  const int32_t *foff_g = D.frame_off + (size_t)c * (D.max_frames + 2);
+  const bool foff_lds = nd + 2 <= kBpFrames + 2;
+  if (foff_lds) for (int i = tid; i < nd + 2; i += kBpThreads) s_foff[i] = foff_g[i];
+  const int32_t *foff = foff_lds ? s_foff : foff_g;
+  const int m_last = ((nd - 1) / D.prune_interval) * D.prune_interval;
+  const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);   // (a degree code may sit above the index)
+  uint32_t *bm_cur = s_bm[0], *bm_prev = s_bm[1], *bm_todo = s_bm[2];
+  // a sweep can only commit on a frame f with cf < f < m_last
+  int lo = foff_g[nd - 1], hi = fb;   // frame nd - 1
+  const bool sweep = m_last - 1 > cf && hi - lo <= kPtBits;
+  if (sweep) for (int j = tid; j < ((hi - lo + 31) >> 5); j += kBpThreads) bm_cur[j] = 0u;
+  if (tid == 0) { s_abort = 0; s_R = -1; s_found = -1; s_nneed = 0; s_more = 0; }
+  __syncthreads();
+  u64 best_all = ~0ull;
+  for (int i = tid; i < n; i += kBpThreads) {
+    const int4 t = tok[fb + i];
+    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
+    best_all = v < best_all ? v : best_all;
+    if (sweep && t.z >= 0) {   // (a predecessor on the frontier itself is marked already: the whole frontier is)
+      const int zi = (int)((uint32_t)t.z & idx_mask);
+      if (zi < fb) {
+        const int b = zi - lo;
+        if ((uint32_t)b < (uint32_t)(hi - lo)) atomicOr(&bm_cur[b >> 5], 1u << (b & 31));
+        else s_abort = 1;
+      }
+    }
+  }
+  best_all = wave_min_u64(best_all);
+  if (lane == 0) s_all[wave] = best_all;
+  // ---- ancestor sweep ----------------------------------------------------------------------------------------------------------
+  int R = -1, Rf = 0;
+  if (sweep) {
+    bool keys_clean = false;
+    for (int f = nd - 1;; --f) {
+      __syncthreads();   // the marks of frame f have landed in bm_cur
+      if (s_abort || f <= cf) break;
+      const int nf = hi - lo, nw = (nf + 31) >> 5;
+      if (tid == 0) s_cnt = 0;
+      __syncthreads();
+      {
+        int my = 0, first = -1;
+        for (int j = tid; j < nw; j += kBpThreads) {
+          const uint32_t w = bm_cur[j];
+          if (w) { my += __popc(w); first = lo + j * 32 + (__ffs((int)w) - 1); }
+        }
+        if (my) { atomicAdd(&s_cnt, my); s_R = first; }   // (the token itself where the count turns out to be one)
+      }
+      __syncthreads();
+      const int cnt = s_cnt;
+      if (cnt == 0) break;   // never expected
+      if (cnt == 1 && f < m_last) { R = s_R; Rf = f; break; }
+      if (f - 1 <= cf) break;   // the previous commit frame comes next: nothing newer to commit
+      const int pl = foff[f - 1], np = lo - pl;
+      if (np > kPtBits) break;
+      for (int j = tid; j < ((np + 31) >> 5); j += kBpThreads) bm_prev[j] = 0u;
+      for (int j = tid; j < nw; j += kBpThreads) bm_todo[j] = 0u;
+      if (!keys_clean) { for (int j = tid; j < kPtNeedSlots; j += kBpThreads) s_key[j] = -1; keys_clean = true; }
+      __syncthreads();
+      auto mark_own = [&](int b) {   // a token of this frame joins the ancestors
+        const uint32_t bit = 1u << (b & 31);
+        if (!(atomicOr(&bm_cur[b >> 5], bit) & bit)) { atomicOr(&bm_todo[b >> 5], bit); s_more = 1; }
+      };
+      auto visit = [&](int i) {   // marked token lo + i: its predecessor
+        const int2 zw = reinterpret_cast<const int2 *>(tok + lo + i)[1];
+        if (zw.x <= kPrevUnresolved) {
+          const int need = D.g.arc_src[(uint32_t)zw.y & kArcMask] & 0x7FFFFFFF;
+          bool done = false;
+          if (atomicAdd(&s_nneed, 0) < (kPtNeedSlots * 3) / 4) {
+            uint32_t slot = hash32(need) >> (32 - kPtNeedLog2);
+            for (int q = 0; q < kPtNeedSlots; ++q) {
+              const int k = atomicCAS(&s_key[slot], -1, need);
+              if (k == -1) { atomicAdd(&s_nneed, 1); done = true; break; }
+              if (k == need) { done = true; break; }
+              slot = (slot + 1) & (kPtNeedSlots - 1);
+            }
+          }
+          if (!done) { atomicOr(&bm_todo[i >> 5], 1u << (i & 31)); s_more = 1; }   // a full table: the next pass
+        } else if (zw.x >= 0) {
+          const int zi = (int)((uint32_t)zw.x & idx_mask);
+          if (zi >= lo) {   // on this same frame (an epsilon hop resolved by a token collection)
+            if (zi - lo < nf) mark_own(zi - lo); else s_abort = 1;
+          } else {
+            const int b = zi - pl;
+            if ((uint32_t)b < (uint32_t)np) atomicOr(&bm_prev[b >> 5], 1u << (b & 31));
+            else s_abort = 1;
+          }
+        }
+      };
+      for (bool first_pass = true;; first_pass = false) {
+        if (first_pass && cnt * 4 > nf) {   // many marks: a token per thread
+          for (int i = tid; i < nf; i += kBpThreads)
+            if ((bm_cur[i >> 5] >> (i & 31)) & 1u) visit(i);
+        } else {
+          for (int j = tid; j < nw; j += kBpThreads) {
+            uint32_t w = first_pass ? bm_cur[j] : bm_todo[j];
+            if (!w) continue;
+            if (!first_pass) w = atomicExch(&bm_todo[j], 0u);
+            while (w) {
+              const int b = __ffs((int)w) - 1;
+              w &= w - 1u;
+              visit(j * 32 + b);
+            }
+          }
+        }
+        __syncthreads();
+        if (s_nneed > 0) {   // one scan of the frame for the tokens on the wanted states
+          constexpr int kScanU = 4;
+          for (int i0 = tid; i0 < nf; i0 += kBpThreads * kScanU) {
+            int sx[kScanU];
+#pragma unroll
+            for (int u = 0; u < kScanU; ++u) {
+              const int i = i0 + u * kBpThreads;
+              sx[u] = i < nf ? reinterpret_cast<const int *>(tok + lo + i)[0] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < kScanU; ++u) {
+              if (sx[u] < 0) continue;
+              uint32_t slot = hash32(sx[u]) >> (32 - kPtNeedLog2);
+              for (int q = 0; q < kPtNeedSlots; ++q) {
+                const int k = s_key[slot];
+                if (k == -1) break;
+                if (k == sx[u]) { mark_own(i0 + u * kBpThreads); break; }
+                slot = (slot + 1) & (kPtNeedSlots - 1);
+              }
+            }
+          }
+          __syncthreads();
+          for (int j = tid; j < kPtNeedSlots; j += kBpThreads) s_key[j] = -1;
+          if (tid == 0) s_nneed = 0;
+        }
+        __syncthreads();
+        const int more = s_more;
+        __syncthreads();   // (everyone has read the flag before it is reset)
+        if (!more || s_abort) break;
+        if (tid == 0) s_more = 0;
+        __syncthreads();
+      }
+      uint32_t *sw = bm_cur; bm_cur = bm_prev; bm_prev = sw;
+      hi = lo;
+      lo = pl;
+    }
+  }
+  __syncthreads();
+  // ---- the walk's end: the previous commit token, found by its state on its frame ----------------------------------------------
+  int stop = -1;   // (the root)
+  if (cf > 0) {
+    bp_scan_eps_pred<false>(D, c, tok, nullptr, foff[cf], foff[cf + 1], cs, 0, &s_found);
+    __syncthreads();
+    stop = s_found;
+    if (stop < 0) {   // never expected: the commit token is an ancestor of every living token
+      if (tid == 0) { o[0] = 0; o[1] = 0; o[2] = 0; o[3] = kErrInternal; }
+      return;
+    }
+  }
+  if (tid == 0) {
+    for (int w = 1; w < kBpThreads / 64; ++w) best_all = s_all[w] < best_all ? s_all[w] : best_all;
+    s_cur = (int)(uint32_t)best_all;
+    s_done = s_cur == stop ? 1 : 0;
+    s_nrev = 0;
+    s_ntail = -1;
+  }
+  int guard = 0;   // chunks walked (a damaged arena must not hang the device)
+  for (;;) {
+    __syncthreads();
+    if (s_done) break;
+    if (tid == 0) { s_tok[0] = s_cur; s_k = 0; }
+    for (;;) {
+      __syncthreads();
+      if (tid == 0) {
+        int t = s_tok[s_k], k = s_k;
+        s_need = -1;
+        while (t >= 0 && t != stop && k < kEpChunk) {
+          const int4 T = tok[t];
+          if (T.z <= kPrevUnresolved) {
+            int flo = 0, fhi = nd + 1;  // frame of t: frame_off[f] <= t < frame_off[f+1]
+            while (fhi - flo > 1) {
+              const int mid = (flo + fhi) >> 1;
+              if (foff[mid] <= t) flo = mid; else fhi = mid;
+            }
+            s_lo = foff[flo];
+            s_hi = foff[flo + 1];
+            s_need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
+            s_found = -1;
+            break;
+          }
+          t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : -1;
+          s_tok[++k] = t;
+        }
+        s_k = k;
+      }
+      __syncthreads();
+      if (s_need < 0) break;
+      bp_scan_eps_pred<false>(D, c, tok, nullptr, s_lo, s_hi, s_need, s_tok[s_k], &s_found);
+      __syncthreads();
+      if (tid == 0) { s_tok[s_k + 1] = s_found; ++s_k; }   // (-1, never expected, ends the walk)
+      __syncthreads();
+      if (s_k >= kEpChunk || s_tok[s_k] < 0 || s_tok[s_k] == stop) break;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const int k = s_k, base = s_nrev;
+      int word = 0;
+      if (lane < k && s_tok[lane + 1] >= 0) {
+        bool eps;
+        const float *llrow;
+        const int a = bp_resolve_hop<false>(D, c, ctl, tok, nullptr, foff, nd, m_last, 0.0f, s_tok[lane], s_tok[lane + 1], &eps, &llrow);
+        word = D.g.arc_olabel[a];
+      }
+      const u64 has = __ballot(word != 0), at_r = __ballot(lane < k && s_tok[lane] == R);
+      if (word != 0) {
+        const int pos = base + lane_rank(has);
+        if (pos < D.max_frames) rev[pos] = word;
+      }
+      if (lane == 0) {
+        // the hop INTO R is committed with everything before it: the tail is what the walk met first
+        if (at_r && s_ntail < 0) s_ntail = base + __popcll(has & ((1ull << (__ffsll((long long)at_r) - 1)) - 1ull));
+        s_nrev = base + __popcll(has);
+        s_cur = s_tok[k];
+        if (s_cur < 0 || s_cur == stop || ++guard >= (1 << 18)) s_done = 1;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- commit and report ---------------------------------------------------------------------------------------------------------
+  const int nrev = s_nrev;
+  const bool commit = R >= 0 && s_ntail >= 0;
+  const int ntail = commit ? s_ntail : nrev;
+  const int nc_new = nc + (nrev - ntail);
+  if (nrev > D.max_frames || nc_new > D.max_frames) {   // more words than the workspace holds: the commit state stays as it was
+    if (tid == 0) {
+      o[0] = nc + nrev; o[1] = nc; o[2] = cf; o[3] = -1;
+      if (reset) { st[0] = 0; st[1] = -1; st[2] = 0; }
+    }
+    return;
+  }
+  for (int p = nc + tid; p < nc_new; p += kBpThreads) committed[p] = rev[nrev - 1 - (p - nc)];
+  __syncthreads();
+  const int n_words = nc_new + ntail;
+  for (int p = tid; p < min(n_words, cap_words); p += kBpThreads) o[4 + p] = p < nc_new ? committed[p] : rev[ntail - 1 - (p - nc_new)];
+  if (tid == 0) {
+    st[0] = commit ? Rf : cf;
+    st[1] = commit ? tok[R].x : cs;
+    st[2] = nc_new;
+    o[0] = n_words; o[1] = nc_new; o[2] = commit ? Rf : cf; o[3] = 0;
+  }
+}
+
 // GetRawLattice's raw material: every token and link alive right now, resolved to labels and costs, in the
 // channel's compact lat_toks[] / lat_arcs[].  use_final != 0: final states by ComputeFinalCosts (base-inl.h:
 // 670-720, 924-940): the graph-final tokens of the newest frame if there are any, else all of it.
@@ -4818,6 +5119,11 @@ void launch_best_path(const DecoderDev &D, const int32_t *chans, int n, int use_
 void launch_endpoint(const DecoderDev &D, const int32_t *chans, int n, const uint32_t *sil_bits, int n_tid, int32_t *out, hipStream_t s) {
   hipLaunchKernelGGL(endpoint_kernel, dim3(n), dim3(kBpThreads), 0, s, D, chans, sil_bits, n_tid, out);
 }
+static void launch_partial_kernel(const DecoderDev &D, const int32_t *chans, int n, int32_t *ws, int64_t ws_stride, int cap_words, int32_t *out,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(partial_kernel, dim3(n), dim3(kBpThreads), 0, s, D, chans, ws, (long long)ws_stride, cap_words, out);
+}
+[[maybe_unused]] static const bool partial_registered = (launch_partial = launch_partial_kernel, true);   // (wfst_device.h: launch_partial)
 void launch_lattice_emit(const DecoderDev &D, const int32_t *chans, int n, int use_final, hipStream_t s);
 void launch_lattice_prune(const DecoderDev &D, const int32_t *chans, int n, hipStream_t s) {
   hipLaunchKernelGGL(lattice_finalize_kernel, dim3(n), dim3(kBT), 0, s, D, chans);

@@ -22,6 +22,10 @@
 //                  AdvanceDecoding call; after every call the partial result GetBestPath(use_final_probs = false) is
 //                  printed as "KEY@frames word-ids..." (GetBestPathTxt(..., false), :122-137); with --nbest also the
 //                  partial n-best (lattice mode serves GetNbest mid-utterance)
+//   --partial-words  with --chunk=N (and --single-stream or --threads=N): the partial result after every chunk comes from
+//                  GetPartialWords -- the incremental form, whose device work follows the frames since the last commit, not the
+//                  utterance -- and is printed as "KEY@frames n_stable word-ids...": the first n_stable words are final (the partial
+//                  n-best lines of --nbest follow it as they follow the plain partial line)
 //   --inflight=K   batch shape only: K batches in flight, each on its own GpuBatchDecoder (own HIP
 //                  stream) driven by its own host thread -- the reference service's model of one
 //                  decoder object per thread (v2-asrbin/v2-asr-service.cc:95-105); the GPU overlaps
@@ -149,7 +153,7 @@ int main(int argc, char **argv) {
     std::string lattice_file, lattice_text;
     long long lattice_links = 1ll << 22;
     int nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
-    bool pull = false;
+    bool pull = false, partial_words = false;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
     std::vector<int> devices(1, 0);
@@ -176,6 +180,7 @@ int main(int argc, char **argv) {
       else if (a.compare(0, 7, "--pool=") == 0) pool_channels = std::max(0, atoi(a.c_str() + 7));
       else if (a.compare(0, 12, "--linger-us=") == 0) linger_us = std::max(0, atoi(a.c_str() + 12));
       else if (a == "--pull") pull = true;
+      else if (a == "--partial-words") partial_words = true;
       else if (a.compare(0, 9, "--repeat=") == 0) repeat = std::max(1, atoi(a.c_str() + 9));
       else if (a.compare(0, 7, "--warm=") == 0) warm = std::max(0, atoi(a.c_str() + 7));
       else if (a.compare(0, 9, "--ragged=") == 0) ragged = std::min(100, std::max(1, atoi(a.c_str() + 9)));
@@ -200,7 +205,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words]]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
       return 1;
@@ -214,6 +219,10 @@ int main(int argc, char **argv) {
       if (!lm_old_file.empty() || !lm_new_file.empty()) { std::cerr << "endpointing is not supported with --lm-old/--lm-new (biglm)\n"; return 1; }
       ep_opt.SilencePhones();   // (checked here, before any device work)
       endpointing = true;
+    }
+    if (partial_words && (!(single || n_threads > 0) || chunk <= 0 || endpointing || !lm_old_file.empty())) {
+      std::cerr << "--partial-words goes with --chunk=N and --single-stream or --threads=N (no endpointing, no --lm-old/--lm-new)\n";
+      return 1;
     }
     if (single && devices.size() > 1) { std::cerr << "--devices lists several devices: batch shape only\n"; return 1; }
     // one graph replica per listed device (fsts[0] also serves --single-stream)
@@ -401,7 +410,7 @@ int main(int argc, char **argv) {
       if (pool_channels > 0)
         pool.reset(biglm ? new GpuChannelPool(&fst, opt, lm1p, lm2p, pool_channels, &limits, linger_us)
                          : new GpuChannelPool(&fst, opt, pool_channels, &limits, linger_us));
-      struct Res { Lattice best; bool ok = false; Lattice lat; bool lat_ok = false; std::vector<Lattice> nbest; std::string segments; };
+      struct Res { Lattice best; bool ok = false; Lattice lat; bool lat_ok = false; std::vector<Lattice> nbest; std::string segments, partials; };
       std::vector<Res> res(utts.size());
       int max_utt_frames = 0, max_utt_cols = 0;
       for (const Utt &u : utts) { max_utt_frames = std::max(max_utt_frames, u.frames); max_utt_cols = std::max(max_utt_cols, u.cols); }
@@ -458,6 +467,17 @@ int main(int argc, char **argv) {
                 pd.SetFramesReady(ready);
                 decode.AdvanceDecoding(am);
                 if (ready >= u.frames) break;
+                if (partial_words) {   // (over the pool: one list per batcher pass for all the threads that ask)
+                  std::vector<int> w;
+                  int n_stable = 0;
+                  dp->GetPartialWords(&w, &n_stable);
+                  if (first_pass) {
+                    std::string &o = res[ui].partials;
+                    o += u.key + "@" + std::to_string(decode.NumFramesDecoded()) + " " + std::to_string(n_stable);
+                    for (size_t q = 0; q < w.size(); ++q) o += " " + std::to_string(w[q]);
+                    o += "\n";
+                  }
+                }
               }
             } else {
               decode.AdvanceDecoding(am);
@@ -495,6 +515,7 @@ int main(int argc, char **argv) {
         if (!e.empty()) throw std::runtime_error(e);
       for (size_t i = 0; i < utts.size(); ++i) {
         if (endpointing) { out << res[i].segments; count_segmented(utts[i], res[i].ok); continue; }
+        out << res[i].partials;
         emit(utts[i], res[i].best, res[i].ok);
         if (want_lattice && (!lattice_file.empty() || !lattice_text.empty())) emit_lattice(utts[i], res[i].lat, res[i].lat_ok);
         if (nbest > 0) emit_nbest(utts[i], res[i].nbest);
@@ -530,10 +551,18 @@ int main(int argc, char **argv) {
             Lattice part;
             std::vector<int> w, ph;
             float tot = 0, lm = 0;
-            out << u.key << "@" << decode.NumFramesDecoded();
-            if (decode.GetBestPath(&part, false) && LatticeToVector(part, w, ph, tot, lm))
+            if (partial_words) {   // key@frames n_stable w1 w2 ...: the incremental partial result, its first n_stable words final
+              int n_stable = 0;
+              decode.GetPartialWords(&w, &n_stable);
+              out << u.key << "@" << decode.NumFramesDecoded() << " " << n_stable;
               for (size_t k = 0; k < w.size(); ++k) out << " " << w[k];
-            out << "\n";
+              out << "\n";
+            } else {
+              out << u.key << "@" << decode.NumFramesDecoded();
+              if (decode.GetBestPath(&part, false) && LatticeToVector(part, w, ph, tot, lm))
+                for (size_t k = 0; k < w.size(); ++k) out << " " << w[k];
+              out << "\n";
+            }
             if (nbest > 0) {
               // (partial lists come from the raw lattice: its unpruned last frames make the mid-utterance lattice expensive to
               // determinize, for the reference as much as here)

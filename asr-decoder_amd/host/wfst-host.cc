@@ -369,10 +369,10 @@ GpuChannelPool::~GpuChannelPool() {
   if (_slab) wfst_host_free(_slab);
   if (!_trace_file.empty()) {
     if (FILE *f = fopen(_trace_file.c_str(), "w")) {
-      fprintf(f, "# ms since the pool started: first request, batch closed, pass done | requests init advance finalize best-path calls endpoint | ms of each | device busy at close\n");
+      fprintf(f, "# ms since the pool started: first request, batch closed, pass done | requests init advance finalize best-path calls endpoint partial | ms of each | device busy at close\n");
       for (const TracePass &t : _trace)
-        fprintf(f, "%.3f %.3f %.3f | %d %d %d %d %d %d | %.3f %.3f %.3f %.3f %.3f %.3f | %d\n", t.t_first, t.t_closed, t.t_end, t.n[0], t.n[1], t.n[2], t.n[3], t.n[4],
-                t.n[5], t.ms[0], t.ms[1], t.ms[2], t.ms[3], t.ms[4], t.ms[5], t.busy);
+        fprintf(f, "%.3f %.3f %.3f | %d %d %d %d %d %d %d | %.3f %.3f %.3f %.3f %.3f %.3f %.3f | %d\n", t.t_first, t.t_closed, t.t_end, t.n[0], t.n[1], t.n[2], t.n[3],
+                t.n[4], t.n[5], t.n[6], t.ms[0], t.ms[1], t.ms[2], t.ms[3], t.ms[4], t.ms[5], t.ms[6], t.busy);
       fclose(f);
     }
   }
@@ -447,16 +447,18 @@ void GpuChannelPool::Run() {
     const auto t_wait = std::chrono::steady_clock::now();
     // wait for requests; a best-path list on the device is looked after meanwhile (its results are taken as soon as they have landed)
     while (!_stop && _queue.empty()) {
-      if (_bp_flight.empty() && _bp_wait.empty()) { _cv_work.wait(lk); continue; }
+      if (_bp_flight.empty() && _bp_wait.empty() && _pt_flight.empty() && _pt_wait.empty()) { _cv_work.wait(lk); continue; }
       lk.unlock();
-      const bool progressed = PollBestPaths(false);
-      if (!progressed && _bp_flight.empty()) StartBestPaths();
+      const bool bp_taken = PollBestPaths(false), pt_taken = PollPartials(false), progressed = bp_taken || pt_taken;
+      if (!bp_taken && _bp_flight.empty()) StartBestPaths();
+      if (!pt_taken && _pt_flight.empty()) StartPartials();
       lk.lock();
       if (!progressed && _queue.empty() && !_stop) _cv_work.wait_until(lk, std::chrono::system_clock::now() + std::chrono::microseconds(30));
     }
     if (_queue.empty()) {   // (_stop: what is on the device is taken, what waits is served, then out)
       lk.unlock();
       while (!_bp_flight.empty() || !_bp_wait.empty()) { PollBestPaths(true); StartBestPaths(); }
+      while (!_pt_flight.empty() || !_pt_wait.empty()) { PollPartials(true); StartPartials(); }
       return;
     }
     // the other leased channels' requests are on their way more often than not (their threads were released together): a short
@@ -469,7 +471,7 @@ void GpuChannelPool::Run() {
     // ... and with three advance calls outstanding the batch waits in any case: a fourth would stand in wfst_decoder_advance_host
     // until the device has caught up (its staging sets are used in rotation), and the batcher with it -- finished utterances' best
     // paths would lie on the device untaken, their threads idle
-    auto arrived = [&] { return (int)(_queue.size() + _bp_wait.size() + _bp_flight.size()); };
+    auto arrived = [&] { return (int)(_queue.size() + _bp_wait.size() + _bp_flight.size() + _pt_wait.size() + _pt_flight.size()); };
     {
       const auto t_first = std::chrono::steady_clock::now();
       for (;;) {
@@ -484,6 +486,7 @@ void GpuChannelPool::Run() {
           lk.unlock();
           const int depth = wfst_decoder_calls_in_flight(_dec);
           if (!_bp_flight.empty()) PollBestPaths(false);
+          if (!_pt_flight.empty()) PollPartials(false);
           lk.lock();
           if (depth < 3) break;   // (2: the same, measured)
         }
@@ -532,7 +535,7 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
       if (call(&c, 1) != WFST_OK) r->error = std::make_exception_ptr(std::runtime_error(std::string(what) + ": " + wfst_last_error()));
     }
   };
-  double ms[kKinds] = {0, 0, 0, 0, 0};
+  double ms[kKinds] = {0, 0, 0, 0, 0, 0, 0};
   // a kind's requesters go on as soon as that kind is served: the threads whose chunks have just been enqueued pull their next
   // chunks while the batcher fetches other channels' best paths (which waits for the device)
   auto clocked = [&](int kind, auto &&f) {
@@ -556,6 +559,20 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
     StartBestPaths();
     ms[kBestPath] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  // partial words: the same shape -- the pass's requests join the waiting list and go to the device as ONE list
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (Request *r : by_kind[kPartial]) _pt_wait.push_back(r);
+    CountBestPaths();
+    PollPartials(false);
+    const long long before = _stats.partial_calls;   // (written by this thread alone)
+    StartPartials();
+    if (_stats.partial_calls - before > _stats.partial_max_per_pass) {
+      std::lock_guard<std::mutex> lk(_mu);
+      _stats.partial_max_per_pass = _stats.partial_calls - before;
+    }
+    ms[kPartial] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
   clocked(kEndpoint, [&] { ExecuteEndpoint(by_kind[kEndpoint]); });
   clocked(kCall, [&] {
     for (Request *r : by_kind[kCall]) {
@@ -570,6 +587,7 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
     std::lock_guard<std::mutex> lk(_mu);
     for (int k = 0; k <= kCall; ++k) _stats.ms_by_kind[k] += ms[k];
     _stats.ms_endpoint += ms[kEndpoint];
+    _stats.ms_partial += ms[kPartial];
   }
   if (!_trace_file.empty() && !_trace.empty())
     for (int k = 0; k < kKinds; ++k) _trace.back().ms[k] = ms[k];
@@ -708,6 +726,65 @@ bool GpuChannelPool::PollBestPaths(bool block) {
   }
   Finish(rs);
   return true;
+}
+void GpuChannelPool::StartPartials() {
+  if (!_pt_flight.empty() || _pt_wait.empty()) return;
+  _pt_flight.swap(_pt_wait);
+  std::vector<int32_t> ch;
+  int maxf = 1;
+  for (Request *r : _pt_flight) { ch.push_back(r->channel); maxf = std::max(maxf, wfst_decoder_num_frames_decoded(_dec, r->channel)); }
+  _pt_cap = maxf + 64;
+  {
+    std::lock_guard<std::mutex> lk(_mu);
+    _stats.partial_calls += 1;
+    _stats.partial_requests += (long long)ch.size();
+  }
+  if (wfst_decoder_partial_enqueue(_dec, ch.data(), (int32_t)ch.size(), _pt_cap) != WFST_OK) {
+    // refused (one of the channels: before InitDecoding, after FinalizeDecoding ...): request by request, each its own verdict
+    std::vector<Request *> rs;
+    rs.swap(_pt_flight);
+    CountBestPaths();
+    ExecutePartial(rs);
+    Finish(rs);
+  }
+}
+// true: a list's results were taken (its requesters are released)
+bool GpuChannelPool::PollPartials(bool block) {
+  if (_pt_flight.empty()) return false;
+  if (!block && wfst_decoder_partial_ready(_dec) != 1) return false;
+  const int cnt = (int)_pt_flight.size(), cap = _pt_cap;
+  std::vector<int32_t> w((size_t)cnt * cap), nw((size_t)cnt, 0), ns((size_t)cnt, 0);
+  const int rc = wfst_decoder_partial_fetch(_dec, w.data(), nw.data(), ns.data(), nullptr);
+  std::vector<Request *> rs;
+  rs.swap(_pt_flight);
+  CountBestPaths();
+  if (rc != WFST_OK) {
+    ExecutePartial(rs);   // (more words than the capacity: request by request, with the size it needs)
+    Finish(rs);
+    return true;
+  }
+  for (int i = 0; i < cnt; ++i) {
+    Request *r = rs[(size_t)i];
+    r->words.assign(w.begin() + (long)((size_t)i * cap), w.begin() + (long)((size_t)i * cap) + nw[(size_t)i]);
+    r->n_stable = ns[(size_t)i];
+  }
+  Finish(rs);
+  return true;
+}
+void GpuChannelPool::ExecutePartial(std::vector<Request *> &rs) {
+  for (Request *r : rs) {
+    const int32_t c = r->channel;
+    int32_t cap = std::max(1, wfst_decoder_num_frames_decoded(_dec, c)) + 64, nw = 0, ns = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      std::vector<int32_t> w((size_t)cap);
+      const int rc = wfst_decoder_get_partial(_dec, &c, 1, cap, w.data(), &nw, &ns, nullptr);
+      if (rc == WFST_E_CAPACITY && nw > cap && attempt == 0) { cap = nw; continue; }
+      if (rc != WFST_OK) { r->error = std::make_exception_ptr(std::runtime_error(std::string("GetPartialWords: ") + wfst_last_error())); break; }
+      r->words.assign(w.begin(), w.begin() + nw);
+      r->n_stable = ns;
+      break;
+    }
+  }
 }
 void GpuChannelPool::ExecuteBestPath(std::vector<Request *> &all) {
   for (int ufp = 0; ufp < 2; ++ufp) {
@@ -1036,6 +1113,34 @@ bool GpuLatticeDecoder::EndpointDetected(const OnlineEndpointConfig &config, int
   }
   if (rule) *rule = r;
   return r != 0;
+}
+
+bool GpuLatticeDecoder::GetPartialWords(std::vector<int> *words, int *n_stable) {
+  words->clear();
+  int ns = 0;
+  if (_pool) {
+    GpuChannelPool::Request q;
+    q.kind = GpuChannelPool::kPartial;
+    q.channel = _chan;
+    _pool->Submit(&q);
+    _decoded = q.decoded;
+    words->assign(q.words.begin(), q.words.end());
+    ns = q.n_stable;
+  } else {
+    const int32_t c = 0;
+    int32_t cap = std::max(1, NumFramesDecoded()) + 64, nw = 0, s32 = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      std::vector<int32_t> w((size_t)cap);
+      const int rc = wfst_decoder_get_partial(_dec, &c, 1, cap, w.data(), &nw, &s32, nullptr);
+      if (rc == WFST_E_CAPACITY && nw > cap && attempt == 0) { cap = nw; continue; }
+      if (rc != WFST_OK) Fatal("GetPartialWords");
+      words->assign(w.begin(), w.begin() + nw);
+      break;
+    }
+    ns = s32;
+  }
+  if (n_stable) *n_stable = ns;
+  return NumFramesDecoded() > 0;
 }
 
 int32 GpuLatticeDecoder::NumFramesDecoded() const { return _pool ? _decoded : wfst_decoder_num_frames_decoded(_dec, 0); }
@@ -1465,6 +1570,37 @@ void GpuBatchDecoder::EndpointDetected(const std::vector<int> &channels, const O
   if (rule) rule->assign(r.begin(), r.end());
 }
 
+void GpuBatchDecoder::GetPartialWords(const std::vector<int> &channels, std::vector<std::vector<int> > *words, std::vector<int> *n_stable,
+                                      std::vector<int> *stable_frame) {
+  const int cnt = (int)channels.size();
+  words->assign((size_t)cnt, std::vector<int>());
+  if (n_stable) n_stable->assign((size_t)cnt, 0);
+  if (stable_frame) stable_frame->assign((size_t)cnt, 0);
+  if (cnt == 0) return;
+  std::vector<int32_t> ch(channels.begin(), channels.end()), nw((size_t)cnt, 0), ns((size_t)cnt, 0), sf((size_t)cnt, 0);
+  int32_t cap = 65;
+  for (int c : channels) cap = std::max(cap, (c >= 0 && c < _n ? wfst_decoder_num_frames_decoded(_dec, c) : 0) + 64);
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    std::vector<int32_t> w((size_t)cnt * (size_t)cap);
+    const int rc = wfst_decoder_get_partial(_dec, ch.data(), cnt, cap, w.data(), nw.data(), ns.data(), sf.data());
+    if (rc == WFST_E_CAPACITY && *std::max_element(nw.begin(), nw.end()) > cap && attempt == 0) { cap = *std::max_element(nw.begin(), nw.end()); continue; }
+    if (rc != WFST_OK) Fatal("GetPartialWords");
+    for (int i = 0; i < cnt; ++i) {
+      (*words)[(size_t)i].assign(w.begin() + (long)((size_t)i * cap), w.begin() + (long)((size_t)i * cap) + nw[(size_t)i]);
+      if (n_stable) (*n_stable)[(size_t)i] = ns[(size_t)i];
+      if (stable_frame) (*stable_frame)[(size_t)i] = sf[(size_t)i];
+    }
+    return;
+  }
+}
+bool GpuBatchDecoder::GetPartialWords(int channel, std::vector<int> *words, int *n_stable) {
+  std::vector<std::vector<int> > w;
+  std::vector<int> ns;
+  GetPartialWords(std::vector<int>(1, channel), &w, &ns);
+  *words = w[0];
+  if (n_stable) *n_stable = ns[0];
+  return NumFramesDecoded(channel) > 0;
+}
 bool GpuBatchDecoder::EndpointDetected(int channel, const OnlineEndpointConfig &config, int *rule) {
   std::vector<bool> d;
   std::vector<int> r;

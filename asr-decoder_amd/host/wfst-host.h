@@ -285,6 +285,11 @@ class GpuChannelPool {
     long long endpoint_calls;     // wfst_decoder_endpoint_detected calls issued ...
     long long endpoint_requests;  // ... for this many EndpointDetected requests
     double ms_endpoint;           // batcher time in them
+    long long partial_calls;      // wfst_decoder_partial_enqueue calls issued ...
+    long long partial_requests;   // ... for this many GetPartialWords requests
+    double ms_partial;            // batcher time in them (enqueueing and fetching; the device works beside the batcher)
+    long long partial_max_per_pass;   // the most of those LIST calls one batcher pass issued (one).  Not counted here or in partial_calls: the
+                                      // synchronous request-by-request calls after a refused list or a capacity too small, which hold the batcher
   };
   Stats GetStats();
   wfst_decoder *Handle() { return _dec; }
@@ -293,7 +298,7 @@ class GpuChannelPool {
   friend class GpuLatticeDecoder;
   GpuChannelPool(const GpuChannelPool &);
   GpuChannelPool &operator=(const GpuChannelPool &);
-  enum Kind { kInit = 0, kAdvance, kFinalize, kBestPath, kCall, kEndpoint, kKinds };
+  enum Kind { kInit = 0, kAdvance, kFinalize, kBestPath, kCall, kEndpoint, kPartial, kKinds };
   struct Request {
     Kind kind;
     int channel;
@@ -307,6 +312,9 @@ class GpuChannelPool {
     // kEndpoint: the config asked with; the rule that fired (0: none)
     const OnlineEndpointConfig *endpoint_config = nullptr;
     int endpoint_rule = 0;
+    // kPartial: the words of the partial best path, the first n_stable of them final
+    std::vector<int32_t> words;
+    int n_stable = 0;
     // outcome
     int decoded;                  // NumFramesDecoded of the channel after the request
     std::exception_ptr error;
@@ -334,6 +342,13 @@ class GpuChannelPool {
   void StartBestPaths();
   bool PollBestPaths(bool block);
   void Finish(std::vector<Request *> &rs);
+  // partial words the same way: ONE wfst_decoder_partial_enqueue per batcher pass for every waiting request, polled with _ready
+  // (the synchronous endpoint call holds the batcher until the device has answered; this one does not)
+  void StartPartials();
+  bool PollPartials(bool block);
+  void ExecutePartial(std::vector<Request *> &rs);    // synchronous, request by request (a refused list, a capacity too small)
+  std::vector<Request *> _pt_wait, _pt_flight;   // (the batcher thread's own)
+  int _pt_cap = 0;
   // The decoder objects' row buffers as slots of ONE page-locked allocation, equally spaced: rows of consecutive channels that cover
   // the same frames then go to the device as one 2-D copy (wfst_decoder_advance_host).  Allocated by the first object that asks, every
   // slot as large as that request (a service reserves its longest utterance: ReserveRows); nullptr: no room for `floats` in a slot --
@@ -345,7 +360,7 @@ class GpuChannelPool {
   std::vector<Request *> _bp_wait, _bp_flight;   // (the batcher thread's own)
   int _bp_cap = 0, _bp_ufp = 1;
   std::atomic<int> _n_bp_outstanding{0};         // their number, for the submitting threads (which one completes a batch)
-  void CountBestPaths() { _n_bp_outstanding.store((int)(_bp_wait.size() + _bp_flight.size())); }
+  void CountBestPaths() { _n_bp_outstanding.store((int)(_bp_wait.size() + _bp_flight.size() + _pt_wait.size() + _pt_flight.size())); }   // (and partial words)
   wfst_decoder *_dec;
   Fst *_graph;
   int _n, _linger_us;
@@ -429,6 +444,14 @@ class GpuLatticeDecoder : public DecoderItf {
   // (1..5, 0: none).  Needs the graph's SetTid2Phone; throws for a biglm decoder, before InitDecoding or after FinalizeDecoding.
   // Over a pool, the requests of many threads go to the device as one call per batcher pass.
   bool EndpointDetected(const OnlineEndpointConfig &config, int *rule = nullptr);
+  // The words of the partial result after AdvanceDecoding -- what the reference's services hand to their per-chunk callback
+  // (gpu-asr/v1-gpu-asr-task.h:70-76; GetBestPathTxt, kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:122-137): *words = the words of
+  // GetBestPath(use_final_probs = false) now, the first *n_stable of them a prefix of every later result of the utterance
+  // (wfst_decoder_get_partial).  The device work follows the frames since the last commit, not the utterance.  false: no frame
+  // decoded yet, or no token.  Throws for a biglm decoder, before InitDecoding or after FinalizeDecoding, and for a result of more
+  // words than the decoder's max_frames (the call is retried once with the size it asks for; that limit no size satisfies).  Over a pool, the
+  // requests of many threads go to the device as one list per batcher pass, and the batcher goes on feeding the device meanwhile.
+  bool GetPartialWords(std::vector<int> *words, int *n_stable = nullptr);
 
  private:
   void Pull(AmInterface *decodable);
@@ -502,6 +525,10 @@ class GpuBatchDecoder {
   void EndpointDetected(const std::vector<int> &channels, const OnlineEndpointConfig &config, std::vector<bool> *detected,
                         std::vector<int> *rule = nullptr);
   bool EndpointDetected(int channel, const OnlineEndpointConfig &config, int *rule = nullptr);
+  // GetPartialWords (see GpuLatticeDecoder) of many channels in one device call; the one-channel form
+  void GetPartialWords(const std::vector<int> &channels, std::vector<std::vector<int> > *words, std::vector<int> *n_stable = nullptr,
+                       std::vector<int> *stable_frame = nullptr);
+  bool GetPartialWords(int channel, std::vector<int> *words, int *n_stable = nullptr);
   wfst_decoder *Handle() { return _dec; }
 
  private:

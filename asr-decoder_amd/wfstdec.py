@@ -37,6 +37,7 @@ SYMBOLS = [
     "wfst_decoder_prefetch_determinized_detached", "wfst_decoder_get_prefetched_lattice", "wfst_decoder_harvest_prefetched",
     "wfst_endpoint_config_default", "wfst_graph_set_tid2phone", "wfst_decoder_set_endpoint_config", "wfst_decoder_endpoint_detected",
     "wfst_endpoint_rules",
+    "wfst_decoder_partial_enqueue", "wfst_decoder_partial_ready", "wfst_decoder_partial_fetch", "wfst_decoder_get_partial",
 ]
 
 
@@ -729,6 +730,32 @@ class BatchDecoder:
         rel = np.zeros(n, np.float32)
         _check(lib().wfst_decoder_endpoint_detected(self.h, _i32(ch), n, _i32(det), _i32(rule), _i32(tr), _f32(rel)))
         return det.astype(bool), rule, tr, rel
+
+    def partial_enqueue(self, channels=None, cap_words=256):
+        """First half of partial(): the work goes on the results stream behind the listed channels' own; returns at once."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        _check(lib().wfst_decoder_partial_enqueue(self.h, _i32(ch), int(ch.shape[0]), int(cap_words)))
+        self._partial_req = (int(ch.shape[0]), int(cap_words))
+
+    def partial_ready(self):
+        rc = lib().wfst_decoder_partial_ready(self.h)
+        if rc < 0:
+            _check(rc)
+        return bool(rc)
+
+    def partial_fetch(self):
+        n, cap = self._partial_req
+        words = np.zeros((n, cap), np.int32)
+        nw, ns, sf = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(lib().wfst_decoder_partial_fetch(self.h, _i32(words), _i32(nw), _i32(ns), _i32(sf)))
+        return [words[i, : nw[i]].copy() for i in range(n)], ns, sf
+
+    def partial(self, channels=None, cap_words=256):
+        """Partial words of the listed channels (all if None) mid-utterance (wfst_decoder_get_partial): (words: one int32 array per
+        channel -- those of best_paths(use_final_probs=False) now --, n_stable int32[n]: how many of them can no longer change,
+        stable_frame int32[n]: the frame of the commit token, 0 if none yet)."""
+        self.partial_enqueue(channels, cap_words)
+        return self.partial_fetch()
 
     def frontier(self, channel, cap=1 << 20):
         st = np.zeros(cap, np.int32)

@@ -599,6 +599,39 @@ int wfst_decoder_endpoint_detected(wfst_decoder *d, const int32_t *channels, int
 int wfst_endpoint_rules(const wfst_endpoint_config *cfg, int32_t num_frames_decoded, int32_t trailing_frames, float relative_cost,
                         int32_t *rule);
 
+/* ---- partial results with a stable word prefix (streaming) ------------------------------------------------------------------
+ * What the reference's services hand to their per-chunk callback (best_str, partial, endpoint_detected)
+ * (gpu-asr/v1-gpu-asr-task.h:70-76, option print-partial-hypotheses, gpu-asr/gpu-worker-pool-itf.h:19-48; the CPU service after
+ * every AdvanceDecoding: GetBestPathTxt, kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:122-137) -- without a traceback of the
+ * whole utterance per chunk, and with the part of it that can no longer change told apart.
+ *
+ * For every listed channel (initialised, not finalized), with nd frames decoded:
+ *   words[i * cap_words .. + n_words[i])  the non-zero olabels of the path wfst_decoder_get_best_path(use_final_probs = 0) reports
+ *                       now, start -> end: wfst_lattice_to_vector's words on that call's hops;
+ *   n_stable[i] <= n_words[i]: the first n_stable[i] words are a prefix of the words of every later partial result of the utterance
+ *                       and of its best path after FinalizeDecoding, with either value of use_final_probs;
+ *   stable_frame[i]     the frame of the commit token (0: none yet): the newest token below the last PruneActiveTokens pass
+ *                       ((nd - 1) / prune_interval * prune_interval) that every token of the frontier descends from.
+ * n_stable and stable_frame never decrease within an utterance; wfst_decoder_init starts a channel from zero.  The device work of a
+ * call follows nd - stable_frame, not nd.
+ *
+ * wfst_decoder_partial_enqueue puts the work on the results stream behind the listed channels' own enqueued work and returns at
+ * once; _ready says (never blocks) whether the results have landed; _fetch waits if need be and writes them out;
+ * wfst_decoder_get_partial is the halves in a row.  One partial request may be outstanding per decoder (a second _enqueue:
+ * WFST_E_STATE), beside an outstanding best-path request or none; the listed channels must not be advanced or initialised in
+ * between.  WFST_E_ARG: a biglm decoder (not supported), cap_words <= 0, a bad list; WFST_E_STATE: a listed channel not initialised
+ * or already finalized; WFST_E_CAPACITY: a result longer than cap_words (n_words[i] is then the needed size, the first cap_words
+ * words are written), or longer than the decoder's max_frames words -- the per-channel workspace's limit: no word of that
+ * channel is written then, n_words[i] exceeds max_frames and no cap_words helps; the channel's commit state stays as it was.  No frame decoded: n_words[i] = n_stable[i] = 0.  A channel whose
+ * utterance ended in a device error reports n_words[i] = 0; the others' results stand and the call returns WFST_OK.  Any output
+ * pointer may be NULL. */
+int wfst_decoder_partial_enqueue(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t cap_words);
+int wfst_decoder_partial_ready(wfst_decoder *d);
+int wfst_decoder_partial_fetch(wfst_decoder *d, int32_t *words /* [n][cap_words] */, int32_t *n_words, int32_t *n_stable,
+                               int32_t *stable_frame);
+int wfst_decoder_get_partial(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t cap_words, int32_t *words,
+                             int32_t *n_words, int32_t *n_stable, int32_t *stable_frame);
+
 #ifdef __cplusplus
 }
 #endif
