@@ -21,7 +21,6 @@
 
 using namespace wfst;
 namespace wfst { int insert_kernel_set_lds(int bytes); }
-namespace wfst { launch_partial_fn launch_partial = nullptr; }   // set by wfst_kernels.hip (wfst_device.h)
 static const int32_t kHeaderLabel = -2;  // ilabel_host marker of a header slot
 
 namespace {
@@ -1809,21 +1808,62 @@ int wfst_decoder_num_frames_decoded(wfst_decoder *d, int32_t channel) {
 // channels' own work, the batcher goes on feeding the device, and the results are taken when they have landed.  One request may be
 // outstanding per decoder; the state it holds (the list, the result block in page-locked memory, a copy of the control blocks of
 // its own) is touched by nothing else meanwhile.
-static int bp_buffers(wfst_decoder *d, size_t words, size_t need, int32_t cap = 0) {
-  if (cap > 0) {
-    // (list requests: room for EVERY channel at this capacity, once -- lists of growing length would otherwise regrow the buffers
-    // call after call, and a regrowth waits for the device)
-    const size_t all_need = (size_t)d->n_channels * (size_t)cap, all_head = ((size_t)d->n_channels + 3) & ~(size_t)3;
-    need = std::max(need, all_need);
-    words = std::max(words, all_head + 4 * all_need);
+// A caller's list of n channels: every index in range, none twice, every channel past InitDecoding ("<what> before InitDecoding");
+// then the caller's own rule for a finalized channel (finalized_msg: its WFST_E_STATE message, or nullptr: allowed).
+static int check_channel_list(const wfst_decoder *d, const int32_t *channels, int32_t n, const char *what, const char *finalized_msg) {
+  std::vector<char> seen((size_t)d->n_channels, 0);
+  for (int i = 0; i < n; ++i) {
+    const int c = channels[i];
+    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
+    if (seen[(size_t)c]) return fail(WFST_E_ARG, "duplicate channel in list");
+    seen[(size_t)c] = 1;
+    if (d->h_state[(size_t)c] == 0) return fail(WFST_E_STATE, std::string(what) + " before InitDecoding");
+    if (d->h_state[(size_t)c] == 2 && finalized_msg) return fail(WFST_E_STATE, finalized_msg);
   }
-  if (d->bp_all.n < words || d->bp_chain.n < need) {
+  return WFST_OK;
+}
+
+// what a _ready call answers: 1 the event behind the outstanding request's copies has passed, 0 not yet
+static int poll_event(wfst_decoder *d, hipEvent_t ev) {
+  HIP_TRY(hipSetDevice(d->device));
+  const hipError_t e = hipEventQuery(ev);
+  if (e == hipSuccess) return 1;
+  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
+  return fail(WFST_E_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(e));
+}
+
+// The best-path result block of `count` channels at `cap` hops: {n_hops[count] (padded to 4 words) | ilabel | olabel | graph |
+// acoustic}, one device block -> one copy into pinned host memory -> the caller's arrays (five copies into pageable memory cost
+// five staging round trips).  need: hops of all channels (also the walk's scratch); words: the block's size.
+struct BpBlock {
+  size_t count, need, head, words;
+  BpBlock(int32_t count_, int32_t cap) : count((size_t)count_), need(count * (size_t)cap), head((count + 3) & ~(size_t)3), words(head + 4 * need) {}
+  void launch(wfst_decoder *d, const int32_t *chans_dev, int32_t use_final_probs, int32_t cap, hipStream_t st) const {
+    int32_t *dn = d->bp_all.p, *dil = dn + head, *dol = dil + need;
+    float *dg = reinterpret_cast<float *>(dol + need), *dac = dg + need;
+    launch_best_path(d->D, chans_dev, (int)count, use_final_probs ? 1 : 0, cap, dil, dol, dg, dac, dn, d->bp_chain.p, st);
+  }
+  void unpack(const void *pin, int32_t *n_hops, int32_t *ilabel, int32_t *olabel, float *graph_cost, float *acoustic_cost) const {
+    const int32_t *hp = static_cast<const int32_t *>(pin);
+    memcpy(n_hops, hp, count * 4);
+    memcpy(ilabel, hp + head, need * 4);
+    memcpy(olabel, hp + head + need, need * 4);
+    memcpy(graph_cost, hp + head + 2 * need, need * 4);
+    memcpy(acoustic_cost, hp + head + 3 * need, need * 4);
+  }
+};
+
+// room for EVERY channel's best path at this capacity, once: lists of growing length would otherwise regrow the buffers call after
+// call, and a regrowth waits for the device
+static int bp_buffers(wfst_decoder *d, int32_t cap) {
+  const BpBlock all(d->n_channels, cap);
+  if (d->bp_all.n < all.words || d->bp_chain.n < all.need) {
     HIP_TRY(hipStreamSynchronize(d->stream));
     if (d->res_stream) HIP_TRY(hipStreamSynchronize(d->res_stream));
-    HIP_TRY(d->bp_all.alloc(words));
-    HIP_TRY(d->bp_chain.alloc(need));
+    HIP_TRY(d->bp_all.alloc(all.words));
+    HIP_TRY(d->bp_chain.alloc(all.need));
   }
-  HIP_TRY(d->bp_pin.reserve(words * 4));
+  HIP_TRY(d->bp_pin.reserve(all.words * 4));
   return WFST_OK;
 }
 
@@ -1832,31 +1872,22 @@ int wfst_decoder_best_path_enqueue(wfst_decoder *d, const int32_t *channels, int
   if (d->bp_out_n > 0) return fail(WFST_E_STATE, "a best-path request is outstanding (wfst_decoder_best_path_fetch takes it)");
   HIP_TRY(hipSetDevice(d->device));
   if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
-  std::vector<char> seen((size_t)d->n_channels, 0);
-  for (int i = 0; i < n; ++i) {
-    if (channels[i] < 0 || channels[i] >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
-    if (seen[(size_t)channels[i]]) return fail(WFST_E_ARG, "duplicate channel in list");
-    seen[(size_t)channels[i]] = 1;
-    const int c = channels[i];
-    if (d->h_state[c] == 0) return fail(WFST_E_STATE, "GetBestPath before InitDecoding");
-    if (d->h_state[c] == 2 && !use_final_probs)  // base-inl.h:1100-1102 (LOG_ERR)
-      return fail(WFST_E_STATE, "You cannot call FinalizeDecoding() and then GetBestPath with use_final_probs == false");
-  }
-  hipStream_t st;
-  int rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
+  int rc = check_channel_list(d, channels, n, "GetBestPath",   // base-inl.h:1100-1102 (LOG_ERR)
+                              use_final_probs ? nullptr : "You cannot call FinalizeDecoding() and then GetBestPath with use_final_probs == false");
   if (rc != WFST_OK) return rc;
-  const size_t need = (size_t)n * (size_t)cap, head = ((size_t)n + 3) & ~(size_t)3, words = head + 4 * need;
-  rc = bp_buffers(d, words, need, cap);
+  hipStream_t st;
+  rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
+  if (rc != WFST_OK) return rc;
+  const BpBlock B(n, cap);
+  rc = bp_buffers(d, cap);
   if (rc != WFST_OK) return rc;
   if (!d->bp_ctl_pin.p) HIP_TRY(d->bp_ctl_pin.alloc(d->ctl.n));
   if (!d->bp_ev) HIP_TRY(d->bp_ev.create());
   memcpy(d->res_chan_pin.p, channels, (size_t)n * 4);   // (no best-path request is outstanding: the last one's copy from here was waited for)
   HIP_TRY(hipMemcpyAsync(d->res_chan_list.p, d->res_chan_pin.p, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  int32_t *dn = d->bp_all.p, *dil = dn + head, *dol = dil + need;
-  float *dg = reinterpret_cast<float *>(dol + need), *dac = dg + need;
-  launch_best_path(d->D, d->res_chan_list.p, n, use_final_probs ? 1 : 0, cap, dil, dol, dg, dac, dn, d->bp_chain.p, st);
+  B.launch(d, d->res_chan_list.p, use_final_probs, cap, st);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(d->bp_pin.p, d->bp_all.p, words * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(d->bp_pin.p, d->bp_all.p, B.words * 4, hipMemcpyDeviceToHost, st));
   // (the listed channels' control blocks are final behind their marks; the others' are not looked at)
   HIP_TRY(hipMemcpyAsync(d->bp_ctl_pin.p, d->ctl.p, d->ctl.bytes(), hipMemcpyDeviceToHost, st));
   if (!d->bp_deg_pin.p) HIP_TRY(d->bp_deg_pin.alloc(d->degraded.n));
@@ -1874,11 +1905,7 @@ int wfst_decoder_best_path_enqueue(wfst_decoder *d, const int32_t *channels, int
 int wfst_decoder_best_path_ready(wfst_decoder *d) {
   if (!d) return fail(WFST_E_ARG, "NULL decoder");
   if (d->bp_out_n <= 0) return fail(WFST_E_STATE, "no best-path request is outstanding");
-  HIP_TRY(hipSetDevice(d->device));
-  const hipError_t e = hipEventQuery(d->bp_ev);
-  if (e == hipSuccess) return 1;
-  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-  return fail(WFST_E_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(e));
+  return poll_event(d, d->bp_ev);
 }
 
 int wfst_decoder_best_path_fetch(wfst_decoder *d, int32_t *ilabel, int32_t *olabel, float *graph_cost, float *acoustic_cost, int32_t *n_hops) {
@@ -1888,13 +1915,7 @@ int wfst_decoder_best_path_fetch(wfst_decoder *d, int32_t *ilabel, int32_t *olab
   const int32_t cnt = d->bp_out_n, cap = d->bp_out_cap;
   d->bp_out_n = 0;   // (taken, whatever it turns out to hold)
   HIP_TRY(hipEventSynchronize(d->bp_ev));
-  const size_t need = (size_t)cnt * (size_t)cap, head = ((size_t)cnt + 3) & ~(size_t)3;
-  const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin.p);
-  memcpy(n_hops, hp, (size_t)cnt * 4);
-  memcpy(ilabel, hp + head, need * 4);
-  memcpy(olabel, hp + head + need, need * 4);
-  memcpy(graph_cost, hp + head + 2 * need, need * 4);
-  memcpy(acoustic_cost, hp + head + 3 * need, need * 4);
+  BpBlock(cnt, cap).unpack(d->bp_pin.p, n_hops, ilabel, olabel, graph_cost, acoustic_cost);
   // a device error of ANOTHER channel's utterance is that channel's, not this request's
   for (int i = 0; i < cnt; ++i) {
     const int c = d->bp_out[(size_t)i];
@@ -1932,27 +1953,15 @@ int wfst_decoder_get_best_path(wfst_decoder *d, const int32_t *channels, int32_t
     if (d->h_state[c] == 2 && !use_final_probs)  // base-inl.h:1100-1102 (LOG_ERR)
       return fail(WFST_E_STATE, "You cannot call FinalizeDecoding() and then GetBestPath with use_final_probs == false");
   }
-  const size_t need = (size_t)cnt * (size_t)cap;
-  // one device block {n_hops[cnt] (padded to 4 words) | ilabel | olabel | graph | acoustic} -> one copy into pinned
-  // host memory -> the caller's arrays (five copies into pageable memory cost five staging round trips)
-  const size_t head = ((size_t)cnt + 3) & ~(size_t)3, words = head + 4 * need;
-  rc = bp_buffers(d, words, need);
+  const BpBlock B(cnt, cap);
+  rc = bp_buffers(d, cap);
   if (rc != WFST_OK) return rc;
-  int32_t *dn = d->bp_all.p, *dil = dn + head, *dol = dil + need;
-  float *dg = reinterpret_cast<float *>(dol + need), *dac = dg + need;
-  launch_best_path(d->D, dev, cnt, use_final_probs ? 1 : 0, cap, dil, dol, dg, dac, dn, d->bp_chain.p, d->stream);
+  B.launch(d, dev, use_final_probs, cap, d->stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(d->bp_pin.p, d->bp_all.p, words * 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->bp_pin.p, d->bp_all.p, B.words * 4, hipMemcpyDeviceToHost, d->stream));
   rc = read_ctl(d);   // synchronises the stream
   if (rc != WFST_OK) return rc;
-  {
-    const int32_t *hp = reinterpret_cast<const int32_t *>(d->bp_pin.p);
-    memcpy(n_hops, hp, (size_t)cnt * 4);
-    memcpy(ilabel, hp + head, need * 4);
-    memcpy(olabel, hp + head + need, need * 4);
-    memcpy(graph_cost, hp + head + 2 * need, need * 4);
-    memcpy(acoustic_cost, hp + head + 3 * need, need * 4);
-  }
+  B.unpack(d->bp_pin.p, n_hops, ilabel, olabel, graph_cost, acoustic_cost);
   rc = check_ctl_errors(d);
   if (rc != WFST_OK) return rc;
   for (int i = 0; i < cnt; ++i)
@@ -3254,17 +3263,10 @@ int wfst_decoder_endpoint_detected(wfst_decoder *d, const int32_t *channels, int
   if (!d->ep_set) return fail(WFST_E_STATE, "EndpointDetected before wfst_decoder_set_endpoint_config");
   if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
   HIP_TRY(hipSetDevice(d->device));
-  std::vector<char> seen((size_t)d->n_channels, 0);
-  for (int i = 0; i < n; ++i) {
-    const int c = channels[i];
-    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
-    if (seen[(size_t)c]) return fail(WFST_E_ARG, "duplicate channel in list");
-    seen[(size_t)c] = 1;
-    if (d->h_state[(size_t)c] == 0) return fail(WFST_E_STATE, "EndpointDetected before InitDecoding");
-    if (d->h_state[(size_t)c] == 2) return fail(WFST_E_STATE, "EndpointDetected after FinalizeDecoding");
-  }
+  int rc = check_channel_list(d, channels, n, "EndpointDetected", "EndpointDetected after FinalizeDecoding");
+  if (rc != WFST_OK) return rc;
   hipStream_t st;
-  int rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
+  rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
   if (rc != WFST_OK) return rc;
   int32_t *pin_chan = d->ep_pin.p, *pin_out = d->ep_pin.p + d->n_channels;
   memcpy(pin_chan, channels, (size_t)n * 4);   // (the last endpoint call has been waited for: its copies are done)
@@ -3293,18 +3295,10 @@ int wfst_decoder_partial_enqueue(wfst_decoder *d, const int32_t *channels, int32
   if (!d || !channels || cap_words <= 0) return fail(WFST_E_ARG, "NULL decoder / channel list, or cap_words <= 0");
   if (d->D.big) return fail(WFST_E_ARG, kPartialBiglm);
   if (d->pt_n > 0) return fail(WFST_E_STATE, "a partial request is outstanding (wfst_decoder_partial_fetch takes it)");
-  if (!launch_partial) return fail(WFST_E_DEVICE, "partial_kernel is not part of this build");   // (never a fall-back: an error)
   if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
   HIP_TRY(hipSetDevice(d->device));
-  std::vector<char> seen((size_t)d->n_channels, 0);
-  for (int i = 0; i < n; ++i) {
-    const int c = channels[i];
-    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
-    if (seen[(size_t)c]) return fail(WFST_E_ARG, "duplicate channel in list");
-    seen[(size_t)c] = 1;
-    if (d->h_state[(size_t)c] == 0) return fail(WFST_E_STATE, "partial words before InitDecoding");
-    if (d->h_state[(size_t)c] == 2) return fail(WFST_E_STATE, "partial words after FinalizeDecoding");
-  }
+  int rc = check_channel_list(d, channels, n, "partial words", "partial words after FinalizeDecoding");
+  if (rc != WFST_OK) return rc;
   const int64_t stride = partial_ws_ints(d->D.max_frames);
   if (d->pt_reset.empty()) {   // the first request: a decoder that never asks pays nothing
     // (all of it or none: what a failure leaves behind goes with these locals, and the next request starts over)
@@ -3322,7 +3316,7 @@ int wfst_decoder_partial_enqueue(wfst_decoder *d, const int32_t *channels, int32
   if (d->pt_out.n < words) HIP_TRY(d->pt_out.alloc(all));   // (room for every channel at this capacity, once; nothing of ours is outstanding)
   HIP_TRY(d->pt_pin.reserve((size_t)d->n_channels + all));
   hipStream_t st;
-  const int rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
+  rc = results_stream_behind(d, channels, n, &st);   // behind these channels' own work only (see mark_ev)
   if (rc != WFST_OK) return rc;
   int32_t *pin_chan = d->pt_pin.p, *pin_out = d->pt_pin.p + d->n_channels;
   for (int i = 0; i < n; ++i) pin_chan[i] = channels[i] | (d->pt_reset[(size_t)channels[i]] ? kPartialResetBit : 0);
@@ -3341,11 +3335,7 @@ int wfst_decoder_partial_enqueue(wfst_decoder *d, const int32_t *channels, int32
 int wfst_decoder_partial_ready(wfst_decoder *d) {
   if (!d) return fail(WFST_E_ARG, "NULL decoder");
   if (d->pt_n <= 0) return fail(WFST_E_STATE, "no partial request is outstanding");
-  HIP_TRY(hipSetDevice(d->device));
-  const hipError_t e = hipEventQuery(d->pt_ev);
-  if (e == hipSuccess) return 1;
-  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-  return fail(WFST_E_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(e));
+  return poll_event(d, d->pt_ev);
 }
 
 int wfst_decoder_partial_fetch(wfst_decoder *d, int32_t *words, int32_t *n_words, int32_t *n_stable, int32_t *stable_frame) {

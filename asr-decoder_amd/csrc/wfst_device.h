@@ -494,11 +494,8 @@ void launch_endpoint(const DecoderDev &D, const int32_t *chan_list_dev, int n, c
 // and cap_words words
 constexpr int32_t kPartialResetBit = 1 << 30;
 inline int64_t partial_ws_ints(int32_t max_frames) { return 8 + 2 * (int64_t)max_frames; }
-// (a pointer, null in wfst_capi.cc and set by wfst_kernels.hip when that is linked in: the host half of the library also links
-// without the kernels -- against the HIP test double --, where nothing asks for partial words; null at a request is an error)
-using launch_partial_fn = void (*)(const DecoderDev &D, const int32_t *chan_list_dev, int n, int32_t *ws, int64_t ws_stride, int cap_words,
-                                   int32_t *out, hipStream_t s);
-extern launch_partial_fn launch_partial;
+void launch_partial(const DecoderDev &D, const int32_t *chan_list_dev, int n, int32_t *ws, int64_t ws_stride, int cap_words, int32_t *out,
+                    hipStream_t s);
 
 }  // namespace wfst
 #endif

@@ -4087,7 +4087,107 @@ constexpr int kBpThreads = 256;
 constexpr int kBpChainLds = 4096;   // hops of the backpointer walk kept in LDS (the walk's own list; longer paths go on in HBM)
 constexpr int kBpFrames = 3072;   // utterances up to this many frames keep their frame bounds in LDS (longer ones read them from HBM)
 
-// ---- traceback helpers shared by best_path_kernel and endpoint_kernel ----------------------------------------------------
+constexpr int kEpChunk = 64;   // hops per chunk of the chunked walk: one per lane of wave 0
+
+// ---- traceback helpers shared by best_path_kernel, endpoint_kernel and partial_kernel -------------------------------------
+// frame of token t: the f with frame_off[f] <= t < frame_off[f+1]
+__device__ __forceinline__ int bp_frame_of(const int32_t *foff, int nd, int t) {
+  int lo = 0, hi = nd + 1;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (foff[mid] <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// the arena index of a resolved backpointer (a degree code may sit above the index)
+__device__ __forceinline__ uint32_t bp_idx_mask(const DecoderDev &D) {
+  return D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);
+}
+
+// The channel's frame bounds (nd + 2 of them) for the walk and the hop pass to search: staged into s_foff[kBpFrames + 2] (from HBM
+// a search was nine dependent loads); longer utterances read them from HBM.  The caller's barrier makes the LDS copy visible.
+__device__ __forceinline__ const int32_t *bp_stage_foff(const DecoderDev &D, int c, int nd, int32_t *s_foff) {
+  const int32_t *foff_g = D.frame_off + (size_t)c * (D.max_frames + 2);
+  if (nd > kBpFrames) return foff_g;
+  for (int i = threadIdx.x; i < nd + 2; i += kBpThreads) s_foff[i] = foff_g[i];
+  return s_foff;
+}
+
+// The frontier reduction: minima over the n tokens from fb on, packed (f2o(cost) << 32 | arena index) so that a tie goes to the
+// lower index; ~0: none.  kWhat says how many are wanted:
+//   kFrAll  all: the cheapest token (BestPathEnd(use_final_probs = false));
+//   kFrFin  + fin: the cheapest token on the super-final state (IsFinal, optimize-fst.h:189-192; final weight One);
+//   kFrWf   + wf: biglm -- costs carry the LM's final cost (ComputeFinalCosts, biglm.h:160-215; diff-lm.h:48-53): fin with it, and
+//             wf the minimum of cost + LM final cost over ALL tokens.
+// per_token(token, arena index) runs on every frontier token in the same pass.  Every thread calls (one barrier inside); the
+// result is thread 0's.
+enum { kFrAll = 0, kFrFin = 1, kFrWf = 2 };
+struct BpFrontier { u64 all, fin, wf; };
+template <int kWhat>
+struct BpFrontierLds { u64 v[kWhat + 1][kBpThreads / 64]; };
+template <int kWhat, class F>
+__device__ __forceinline__ BpFrontier bp_frontier(const DecoderDev &D, int c, const int4 *tok, const int32_t *tok_lm, int fb, int n,
+                                                  BpFrontierLds<kWhat> *lds, F &&per_token) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  u64 b[3] = {~0ull, ~0ull, ~0ull};
+  for (int i = tid; i < n; i += kBpThreads) {
+    const int4 t = tok[fb + i];
+    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
+    b[0] = v < b[0] ? v : b[0];
+    if constexpr (kWhat == kFrWf) {
+      const u64 pk = D.pair_keys[(size_t)c * D.pair_cap + tok_lm[fb + i]];
+      const float lm_final = lm_final_cost(D.lm_old, (int)(uint32_t)pk) + lm_final_cost(D.lm_new, (int)(uint32_t)(pk >> 32));
+      const u64 w = ((u64)f2o(__int_as_float(t.y) + lm_final) << 32) | (uint32_t)(fb + i);
+      b[2] = w < b[2] ? w : b[2];
+      if (t.x == D.g.final_state) b[1] = w < b[1] ? w : b[1];
+    } else if constexpr (kWhat == kFrFin) {
+      if (t.x == D.g.final_state) b[1] = v < b[1] ? v : b[1];
+    }
+    per_token(t, fb + i);
+  }
+#pragma unroll
+  for (int j = 0; j <= kWhat; ++j) {
+    b[j] = wave_min_u64(b[j]);
+    if (lane == 0) lds->v[j][wave] = b[j];
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int j = 0; j <= kWhat; ++j)
+      for (int w = 1; w < kBpThreads / 64; ++w) b[j] = lds->v[j][w] < b[j] ? lds->v[j][w] : b[j];
+  }
+  return BpFrontier{b[0], b[1], b[2]};
+}
+
+// A token won by an epsilon arc carries kPrevUnresolved; its predecessor is the token of the arc's source state `need` on its
+// own frame [lo, hi), which the whole workgroup looks for (bp_scan_eps_pred, answer in `found`).  LDS; need < 0: nothing asked.
+struct BpScanReq { int need, lo, hi, found; };
+
+// The walk's lane-0 step: from token t follow resolved backpointers in one go (a dependent load per hop, nothing else on the
+// chain), handing each visited token to sink(t), until the root (-1 returned), the token `stop` (-1: none) or `bound` tokens
+// (a damaged arena must not hang the device).  At an epsilon-won token it stops, asks for the scan (*rq) and returns that token.
+template <class Sink>
+__device__ __forceinline__ int bp_follow(const DecoderDev &D, const int4 *tok, const int32_t *foff, int nd, int t, int bound, int stop,
+                                         BpScanReq *rq, Sink &&sink) {
+  const uint32_t idx_mask = bp_idx_mask(D);
+  rq->need = -1;
+  for (int n = 0; t >= 0 && t != stop && n < bound; ++n) {
+    const int4 T = tok[t];
+    sink(t);
+    if (T.z <= kPrevUnresolved) {
+      const int fr = bp_frame_of(foff, nd, t);
+      rq->lo = foff[fr];
+      rq->hi = foff[fr + 1];
+      rq->need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
+      rq->found = -1;
+      break;
+    }
+    t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : -1;
+  }
+  return t;
+}
+
 // biglm: LM score of arc a taken from the predecessor token's LM state, and the pair state it leads to (-1: a pair no token was
 // ever created with); plain decoders: 0
 template <bool kBig>
@@ -4154,13 +4254,7 @@ __device__ __forceinline__ int bp_resolve_hop(const DecoderDev &D, int c, const 
   const float *cut = D.cutoff_hist + (size_t)c * (D.max_frames + 2);
   const float *ll = D.ll_base[c];
   const int4 T = tok[t];
-  // frame of t: the f with frame_off[f] <= t < frame_off[f+1]
-  int lo = 0, hi = nd + 1;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (foff[mid] <= t) lo = mid; else hi = mid;
-  }
-  const int fr = lo;
+  const int fr = bp_frame_of(foff, nd, t);
   const int4 Pt = tok[prev];
   const float cb = __int_as_float(Pt.y), ct = __int_as_float(T.y);
   const int warc = (int)((uint32_t)T.w & kArcMask);
@@ -4193,6 +4287,39 @@ __device__ __forceinline__ int bp_resolve_hop(const DecoderDev &D, int c, const 
   return chosen;
 }
 
+// The chunked walk of endpoint_kernel and partial_kernel (plain decoders, mid-utterance), last hop first: from W->cur up to
+// kEpChunk hops into LDS -- tok[0 .. k], hop j is tok[j] <- tok[j + 1] (-1: the root) -- lane 0 following the backpointers and
+// the workgroup's frame scan finding an epsilon-won token's predecessor (-1, never expected, ends the walk).  The chunk ends at
+// kEpChunk hops, at the root or at the token `stop` (-1: none); W->cur = tok[k] is where the next chunk starts.  Every thread
+// calls, after a barrier behind the write of W->cur; the chunk is visible on return.  Wave 0 then resolves the hops in parallel.
+struct BpChunk {
+  int32_t tok[kEpChunk + 1];
+  int cur, k;
+  BpScanReq rq;
+};
+__device__ __forceinline__ void bp_walk_chunk(const DecoderDev &D, int c, const int4 *tok, const int32_t *foff, int nd, BpChunk *W,
+                                              int stop) {
+  const int tid = threadIdx.x;
+  if (tid == 0) W->k = 0;
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) {
+      int k = W->k;
+      W->cur = bp_follow(D, tok, foff, nd, W->cur, kEpChunk - k, stop, &W->rq, [&](int t) { W->tok[k++] = t; });
+      W->tok[k] = W->cur;
+      W->k = k;
+    }
+    __syncthreads();
+    if (W->rq.need < 0) break;
+    bp_scan_eps_pred<false>(D, c, tok, nullptr, W->rq.lo, W->rq.hi, W->rq.need, W->cur, &W->rq.found);
+    __syncthreads();
+    if (tid == 0) W->tok[W->k] = W->cur = W->rq.found;
+    __syncthreads();
+    if (W->k >= kEpChunk || W->cur < 0 || W->cur == stop) break;
+  }
+  __syncthreads();
+}
+
 // kBig (biglm): final costs carry the LM's (ComputeFinalCosts, biglm.h:160-215), hop graph costs are arc
 // weight + lm_score, an epsilon-won token's predecessor is found by (state, LM pair, cost), and after
 // FinalizeDecoding the reference's final pruning can leave NO token (its final_best_cost ranges over
@@ -4203,64 +4330,35 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
                                                                int32_t *n_hops, int32_t *chain) {
   const int bi = blockIdx.x;
   const int c = chans ? chans[bi] : bi;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const ChanCtl *ctl = D.ctl + c;
   const int n = ctl->front_count, nd = ctl->n_decoded;
   if (nd <= 0 || n == 0) {  // base-inl.h:1104-1108 / 1148-1154: no path
     if (tid == 0) n_hops[bi] = 0;
     return;
   }
-  __shared__ u64 s_all[kBpThreads / 64], s_fin[kBpThreads / 64], s_wf[kBpThreads / 64];
+  __shared__ BpFrontierLds<kBig ? kFrWf : kFrFin> s_red;
   __shared__ int s_len;
   const int4 *tok = D.tok + (size_t)c * D.arena_cap;
   const int32_t *tok_lm = kBig ? D.tok_lm + (size_t)c * D.arena_cap : nullptr;
-  const int fb = ctl->front_begin;
-  u64 best_all = ~0ull, best_fin = ~0ull, best_wf = ~0ull;  // best_wf: min cost + LM final cost over ALL tokens (biglm)
   unsigned long long tb0 = (D.dbg & 32) ? wall_clock64() : 0ull, tb_walk = 0, tb_scan = 0;
   int n_unres = 0;
-  for (int i = tid; i < n; i += kBpThreads) {
-    const int4 t = tok[fb + i];
-    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
-    best_all = v < best_all ? v : best_all;
-    if constexpr (kBig) {
-      const u64 pk = D.pair_keys[(size_t)c * D.pair_cap + tok_lm[fb + i]];
-      const float lm_final = lm_final_cost(D.lm_old, (int)(uint32_t)pk) + lm_final_cost(D.lm_new, (int)(uint32_t)(pk >> 32));  // diff-lm.h:48-53
-      const u64 w = ((u64)f2o(__int_as_float(t.y) + lm_final) << 32) | (uint32_t)(fb + i);
-      best_wf = w < best_wf ? w : best_wf;
-      if (t.x == D.g.final_state) best_fin = w < best_fin ? w : best_fin;
-    } else {
-      if (t.x == D.g.final_state) best_fin = v < best_fin ? v : best_fin;  // IsFinal, optimize-fst.h:189-192
-    }
-  }
-  best_all = wave_min_u64(best_all);
-  best_fin = wave_min_u64(best_fin);
-  best_wf = wave_min_u64(best_wf);
-  if (lane == 0) { s_all[wave] = best_all; s_fin[wave] = best_fin; s_wf[wave] = best_wf; }
-  __syncthreads();
+  const BpFrontier best = bp_frontier(D, c, tok, tok_lm, ctl->front_begin, n, &s_red, [](const int4 &, int) {});
   int32_t *ch = chain + (size_t)bi * cap;
-  const int32_t *foff_g = D.frame_off + (size_t)c * (D.max_frames + 2);
-  // the frame bounds of the utterance in LDS (both the walk and the hop pass search them; from HBM a search was nine dependent loads)
   __shared__ int32_t s_foff[kBpFrames + 2];
-  const bool foff_lds = nd + 2 <= kBpFrames + 2;
-  if (foff_lds) for (int i = tid; i < nd + 2; i += kBpThreads) s_foff[i] = foff_g[i];
-  const int32_t *foff = foff_lds ? s_foff : foff_g;
+  const int32_t *foff = bp_stage_foff(D, c, nd, s_foff);
   __shared__ int32_t s_chain[kBpChainLds];   // the walk's hops, last hop first
-  __shared__ int s_t, s_need, s_lo, s_hi, s_found;
+  __shared__ int s_t;
+  __shared__ BpScanReq s_rq;
   __shared__ float s_extra0;   // extra cost of the best path's tokens after FinalizeDecoding (0 except in biglm, below)
   if (tid == 0) {
     s_extra0 = 0.0f;
-    for (int w = 1; w < kBpThreads / 64; ++w) {
-      best_all = s_all[w] < best_all ? s_all[w] : best_all;
-      best_fin = s_fin[w] < best_fin ? s_fin[w] : best_fin;
-      best_wf = s_wf[w] < best_wf ? s_wf[w] : best_wf;
-    }
-    const u64 best = (use_final && best_fin != ~0ull) ? best_fin : best_all;
-    s_t = (int)(uint32_t)best;
+    s_t = (int)(uint32_t)((use_final && best.fin != ~0ull) ? best.fin : best.all);
     if (kBig && ctl->finalized) {
       // PruneForwardLinksFinal (biglm.h:468-568): tok_extra_cost = tot_cost + final_cost - final_best_cost
       // of the cheapest candidate; above lattice_beam it -- and with it every token -- is pruned away
-      const float fbc = o2f((uint32_t)(best_wf >> 32));
-      const float own = (best_fin != ~0ull) ? o2f((uint32_t)(best_fin >> 32)) : (o2f((uint32_t)(best_all >> 32)) + 0.0f);
+      const float fbc = o2f((uint32_t)(best.wf >> 32));
+      const float own = (best.fin != ~0ull) ? o2f((uint32_t)(best.fin >> 32)) : (o2f((uint32_t)(best.all >> 32)) + 0.0f);
       if ((own - fbc) > D.lattice_beam) s_t = -1;
       // final_best_cost ranges over non-final tokens too (biglm.h:186-188), so the best final token -- and with it every
       // token of its path, whose links to their successors cost nothing extra -- carries this extra cost, and a parallel
@@ -4269,50 +4367,31 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
     }
     s_len = 0;
   }
-  // Walk the backpointer chain (last hop first, packed against the end of ch[]).  One thread
-  // follows resolved backpointers; a token won by an epsilon arc carries kPrevUnresolved and the
-  // whole workgroup scans its frame for the token of the arc's source state.
+  // Walk the backpointer chain (last hop first, packed against the end of ch[]): lane 0's follow step and the workgroup's scan
+  // for an epsilon-won token's predecessor take turns.
   if (tid == 0 && (D.dbg & 32)) { const unsigned long long now = wall_clock64(); atomicAdd(&D.dbg_t[110], now - tb0); tb0 = now; }
   for (;;) {
     __syncthreads();
     if (s_t < 0) break;
     unsigned long long tw0 = (tid == 0 && (D.dbg & 32)) ? wall_clock64() : 0ull;
     if (tid == 0) {
-      // resolved backpointers are followed in one go (a dependent load per hop, nothing else on the chain); the walk stops at a
-      // token won by an epsilon arc, whose predecessor the whole workgroup looks for
-      int t = s_t, len = s_len;
-      const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);   // (a degree code may sit above the index)
-      s_need = -1;
-      while (t >= 0 && len < (1 << 24)) {   // (the bound: a damaged arena must not hang the device)
-        const int4 T = tok[t];
+      int len = s_len;
+      s_t = bp_follow(D, tok, foff, nd, s_t, (1 << 24) - len, -1, &s_rq, [&](int t) {
         // (the hop list stays in LDS until the walk is over: on this target a load issued behind a global store waits for the store)
         if (len < kBpChainLds) s_chain[len] = t;
         else if (len < cap) ch[cap - 1 - len] = t;
         ++len;
-        if (T.z <= kPrevUnresolved) {
-          int lo = 0, hi = nd + 1;  // frame of t: frame_off[f] <= t < frame_off[f+1]
-          while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (foff[mid] <= t) lo = mid; else hi = mid;
-          }
-          s_lo = foff[lo];
-          s_hi = foff[lo + 1];
-          s_need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
-          s_found = -1;
-          break;
-        }
-        t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : T.z;
-      }
-      s_t = t;
+      });
+      if (len >= (1 << 24)) { s_t = -1; s_rq.need = -1; }   // (the bound met: the walk ends here)
       s_len = len;
       if (D.dbg & 32) { const unsigned long long now = wall_clock64(); tb_walk += now - tw0; tw0 = now; }
     }
     __syncthreads();
-    if (s_need >= 0) {
+    if (s_rq.need >= 0) {
       ++n_unres;
-      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_lo, s_hi, s_need, s_t, &s_found);
+      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_rq.lo, s_rq.hi, s_rq.need, s_t, &s_rq.found);
       __syncthreads();
-      if (tid == 0) s_t = s_found;  // -1 (never expected) ends the walk
+      if (tid == 0) s_t = s_rq.found;  // -1 (never expected) ends the walk
       if (tid == 0 && (D.dbg & 32)) tb_scan += wall_clock64() - tw0;
     }
   }
@@ -4362,17 +4441,13 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
 // =========================================================================================
 // endpoint inputs (Kaldi's online2/online-endpoint.cc: TrailingSilenceLength + FinalRelativeCost), one kBpThreads workgroup per
 // listed channel, mid-utterance.  out[3 i .. 3 i + 2] = {trailing_silence_frames, final_relative_cost (f32 bits), device error}:
-//  - the frontier reduction of best_path_kernel: best_all (BestPathEnd(use_final_probs = false)) and best_fin (the cheapest token
-//    on the super-final state, final weight One); final_relative_cost = best_fin - best_all in f32, +inf without a final token
-//    (ComputeFinalCosts, base-inl.h:670-720);
-//  - the trailing walk from best_all, last hop first, in chunks of kEpChunk hops: lane 0 follows the resolved backpointers (an
-//    epsilon-won token's predecessor: the workgroup's frame scan) into LDS, then wave 0 resolves the chunk's hops in parallel
-//    (bp_resolve_hop: GetBestPath's labels, parallel-arc quirk included) and tests each ilabel against the silence bitmap over
-//    transition-ids.  Epsilon hops (ilabel 0) are skipped, silence hops counted; the walk ends in the chunk that holds the first
-//    non-silence hop, or at the root.
+//  - the frontier reduction (bp_frontier): final_relative_cost = fin - all in f32, +inf without a final token (ComputeFinalCosts,
+//    base-inl.h:670-720);
+//  - the trailing walk from `all` in chunks (bp_walk_chunk): wave 0 resolves a chunk's hops (bp_resolve_hop: GetBestPath's labels,
+//    parallel-arc quirk included) and tests each ilabel against the silence bitmap over transition-ids.  Epsilon hops (ilabel 0)
+//    are skipped, silence hops counted; the walk ends in the chunk that holds the first non-silence hop, or at the root.
 // trailing_silence_frames = -1: no path (no frame decoded, no token on the frontier, or a device error -- out[3 i + 2] says which).
 // =========================================================================================
-constexpr int kEpChunk = 64;   // hops per chunk: one per lane of wave 0
 __global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, const int32_t *chans, const uint32_t *sil_bits, int n_tid,
                                                               int32_t *out) {
   const int bi = blockIdx.x;
@@ -4384,88 +4459,35 @@ __global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, cons
     if (tid == 0) { out[3 * bi] = -1; out[3 * bi + 1] = __float_as_int(__builtin_huge_valf()); out[3 * bi + 2] = err; }
     return;
   }
-  __shared__ u64 s_all[kBpThreads / 64], s_fin[kBpThreads / 64];
-  const int4 *tok = D.tok + (size_t)c * D.arena_cap;
-  const int fb = ctl->front_begin;
-  u64 best_all = ~0ull, best_fin = ~0ull;
-  for (int i = tid; i < n; i += kBpThreads) {
-    const int4 t = tok[fb + i];
-    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
-    best_all = v < best_all ? v : best_all;
-    if (t.x == D.g.final_state) best_fin = v < best_fin ? v : best_fin;  // IsFinal, optimize-fst.h:189-192
-  }
-  best_all = wave_min_u64(best_all);
-  best_fin = wave_min_u64(best_fin);
-  if (lane == 0) { s_all[wave] = best_all; s_fin[wave] = best_fin; }
-  const int32_t *foff_g = D.frame_off + (size_t)c * (D.max_frames + 2);
+  __shared__ BpFrontierLds<kFrFin> s_red;
   __shared__ int32_t s_foff[kBpFrames + 2];
-  const bool foff_lds = nd + 2 <= kBpFrames + 2;
-  if (foff_lds) for (int i = tid; i < nd + 2; i += kBpThreads) s_foff[i] = foff_g[i];
-  const int32_t *foff = foff_lds ? s_foff : foff_g;
-  __shared__ int32_t s_tok[kEpChunk + 1];   // the chunk's tokens, last hop first: hop j is s_tok[j] <- s_tok[j + 1] (-1: the root)
-  __shared__ int s_cur, s_k, s_need, s_lo, s_hi, s_found, s_count, s_done;
-  __syncthreads();
+  __shared__ BpChunk s_w;
+  __shared__ int s_count, s_done;
+  const int4 *tok = D.tok + (size_t)c * D.arena_cap;
+  const BpFrontier best = bp_frontier(D, c, tok, nullptr, ctl->front_begin, n, &s_red, [](const int4 &, int) {});
+  const int32_t *foff = bp_stage_foff(D, c, nd, s_foff);
   if (tid == 0) {
-    for (int w = 1; w < kBpThreads / 64; ++w) {
-      best_all = s_all[w] < best_all ? s_all[w] : best_all;
-      best_fin = s_fin[w] < best_fin ? s_fin[w] : best_fin;
-    }
-    const float rel = best_fin == ~0ull ? __builtin_huge_valf() : o2f((uint32_t)(best_fin >> 32)) - o2f((uint32_t)(best_all >> 32));
+    const float rel = best.fin == ~0ull ? __builtin_huge_valf() : o2f((uint32_t)(best.fin >> 32)) - o2f((uint32_t)(best.all >> 32));
     out[3 * bi + 1] = __float_as_int(rel);
     out[3 * bi + 2] = 0;
-    s_cur = (int)(uint32_t)best_all;
+    s_w.cur = (int)(uint32_t)best.all;
     s_count = 0;
     s_done = 0;
   }
   const int m_last = ((nd - 1) / D.prune_interval) * D.prune_interval;
-  const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);   // (a degree code may sit above the index)
   int guard = 0;   // chunks walked (a damaged arena must not hang the device)
   for (;;) {
     __syncthreads();
     if (s_done) break;
-    // fill: up to kEpChunk hops of the chain into LDS
-    if (tid == 0) { s_tok[0] = s_cur; s_k = 0; }
-    for (;;) {
-      __syncthreads();
-      if (tid == 0) {
-        int t = s_tok[s_k], k = s_k;
-        s_need = -1;
-        while (t >= 0 && k < kEpChunk) {
-          const int4 T = tok[t];
-          if (T.z <= kPrevUnresolved) {
-            int lo = 0, hi = nd + 1;  // frame of t: frame_off[f] <= t < frame_off[f+1]
-            while (hi - lo > 1) {
-              const int mid = (lo + hi) >> 1;
-              if (foff[mid] <= t) lo = mid; else hi = mid;
-            }
-            s_lo = foff[lo];
-            s_hi = foff[lo + 1];
-            s_need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
-            s_found = -1;
-            break;
-          }
-          t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : -1;
-          s_tok[++k] = t;
-        }
-        s_k = k;
-      }
-      __syncthreads();
-      if (s_need < 0) break;
-      bp_scan_eps_pred<false>(D, c, tok, nullptr, s_lo, s_hi, s_need, s_tok[s_k], &s_found);
-      __syncthreads();
-      if (tid == 0) { s_tok[s_k + 1] = s_found; ++s_k; }   // (-1, never expected, ends the walk)
-      __syncthreads();
-      if (s_k >= kEpChunk || s_tok[s_k] < 0) break;
-    }
-    __syncthreads();
-    // resolve: hop j = lane of wave 0; 0 epsilon (or the root's hop), 1 silence, 2 anything else
+    bp_walk_chunk(D, c, tok, foff, nd, &s_w, -1);
+    // hop j = lane of wave 0; 0 epsilon (or the root's hop), 1 silence, 2 anything else
     if (wave == 0) {
-      const int k = s_k;
+      const int k = s_w.k;
       int kind = 0;
-      if (lane < k && s_tok[lane + 1] >= 0) {
+      if (lane < k && s_w.tok[lane + 1] >= 0) {
         bool eps;
         const float *llrow;
-        const int a = bp_resolve_hop<false>(D, c, ctl, tok, nullptr, foff, nd, m_last, 0.0f, s_tok[lane], s_tok[lane + 1], &eps, &llrow);
+        const int a = bp_resolve_hop<false>(D, c, ctl, tok, nullptr, foff, nd, m_last, 0.0f, s_w.tok[lane], s_w.tok[lane + 1], &eps, &llrow);
         const int il = D.g.arc_ilabel[a];
         if (il != 0) kind = (il > 0 && il <= n_tid && ((sil_bits[il >> 5] >> (il & 31)) & 1u)) ? 1 : 2;
       }
@@ -4473,8 +4495,7 @@ __global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, cons
       if (lane == 0) {
         const u64 before = other ? ((1ull << (__ffsll((long long)other) - 1)) - 1ull) : ~0ull;
         s_count += __popcll(sil & before);
-        s_cur = s_tok[k];
-        if (other || s_cur < 0 || ++guard >= (1 << 18)) s_done = 1;
+        if (other || s_w.cur < 0 || ++guard >= (1 << 18)) s_done = 1;
       }
     }
   }
@@ -4486,7 +4507,7 @@ __global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, cons
 // gpu-asr/v1-gpu-asr-task.h:70-76; kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:122-137), one kBpThreads workgroup per listed
 // channel, mid-utterance.  The words are those of GetBestPath(use_final_probs = false) + LatticeToVector now; the first n_stable of
 // them never change again.  Three steps:
-//  - the frontier reduction of endpoint_kernel (best_all); the same pass marks every frontier token's predecessor on frame nd - 1;
+//  - the frontier reduction (bp_frontier: all); the same pass marks every frontier token's predecessor on frame nd - 1;
 //  - the ancestor sweep, frame by frame backwards: the ancestors of the frontier on frame f are a bitmap in LDS over the frame's
 //    arena range.  A marked token with a backpointer marks it (previous frame, or -- an epsilon hop a token collection has
 //    resolved -- its own frame); a marked token won by an epsilon arc (kPrevUnresolved) wants the frame's token on its arc's
@@ -4495,9 +4516,8 @@ __global__ __launch_bounds__(kBpThreads) void endpoint_kernel(DecoderDev D, cons
 //    receives exactly ONE mark from frame f + 1 holds the commit token R -- every frontier token descends from it -- and ends the
 //    sweep; so does the channel's previous commit frame, which is never passed: the cost of a call follows the commit lag, not
 //    the utterance.  A frame or its predecessor beyond the bitmap ends the sweep with no new commit (never a wrong one);
-//  - the walk from best_all back to the PREVIOUS commit token (the root if there is none), in chunks of kEpChunk hops exactly as
-//    endpoint_kernel walks; wave 0 resolves the hops (bp_resolve_hop) and keeps the non-zero olabels, newest first, in the
-//    channel's scratch.  Those of the hops up to and including the hop into R are appended to the channel's committed words; the
+//  - the walk from `all` back to the PREVIOUS commit token (the root if there is none) in chunks (bp_walk_chunk); wave 0
+//    resolves a chunk's hops (bp_resolve_hop) and keeps the non-zero olabels, newest first, in the channel's scratch.  Those of the hops up to and including the hop into R are appended to the channel's committed words; the
 //    rest is the unstable tail.
 // ws, per channel: {commit frame (0: none), commit state (graph row), committed words, -, ...}, then max_frames committed words,
 // then max_frames words of scratch.  The commit token is remembered as (frame, state): collections and compactions move tokens
@@ -4527,32 +4547,25 @@ __global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const
     }
     return;
   }
-  __shared__ u64 s_all[kBpThreads / 64];
+  __shared__ BpFrontierLds<kFrAll> s_red;
   __shared__ int32_t s_foff[kBpFrames + 2];
   __shared__ uint32_t s_bm[3][kPtWords];
   __shared__ int32_t s_key[kPtNeedSlots];
-  __shared__ int32_t s_tok[kEpChunk + 1];   // the chunk's tokens, last hop first: hop j is s_tok[j] <- s_tok[j + 1] (-1: the root)
-  __shared__ int s_cur, s_k, s_need, s_lo, s_hi, s_found, s_done, s_cnt, s_more, s_nneed, s_abort, s_R, s_nrev, s_ntail;
+  __shared__ BpChunk s_w;
+  __shared__ int s_done, s_cnt, s_more, s_nneed, s_abort, s_R, s_nrev, s_ntail;
   const int4 *tok = D.tok + (size_t)c * D.arena_cap;
   const int fb = ctl->front_begin;
-  const int32_t *foff_g = D.frame_off + (size_t)c * (D.max_frames + 2);
-  const bool foff_lds = nd + 2 <= kBpFrames + 2;
-  if (foff_lds) for (int i = tid; i < nd + 2; i += kBpThreads) s_foff[i] = foff_g[i];
-  const int32_t *foff = foff_lds ? s_foff : foff_g;
+  const int32_t *foff = bp_stage_foff(D, c, nd, s_foff);
   const int m_last = ((nd - 1) / D.prune_interval) * D.prune_interval;
-  const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);   // (a degree code may sit above the index)
+  const uint32_t idx_mask = bp_idx_mask(D);
   uint32_t *bm_cur = s_bm[0], *bm_prev = s_bm[1], *bm_todo = s_bm[2];
   // a sweep can only commit on a frame f with cf < f < m_last
-  int lo = foff_g[nd - 1], hi = fb;   // frame nd - 1
+  int lo = D.frame_off[(size_t)c * (D.max_frames + 2) + nd - 1], hi = fb;   // frame nd - 1 (from HBM: the LDS copy is behind the barrier)
   const bool sweep = m_last - 1 > cf && hi - lo <= kPtBits;
   if (sweep) for (int j = tid; j < ((hi - lo + 31) >> 5); j += kBpThreads) bm_cur[j] = 0u;
-  if (tid == 0) { s_abort = 0; s_R = -1; s_found = -1; s_nneed = 0; s_more = 0; }
+  if (tid == 0) { s_abort = 0; s_R = -1; s_w.rq.found = -1; s_nneed = 0; s_more = 0; }
   __syncthreads();
-  u64 best_all = ~0ull;
-  for (int i = tid; i < n; i += kBpThreads) {
-    const int4 t = tok[fb + i];
-    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
-    best_all = v < best_all ? v : best_all;
+  const BpFrontier best = bp_frontier(D, c, tok, nullptr, fb, n, &s_red, [&](const int4 &t, int) {
     if (sweep && t.z >= 0) {   // (a predecessor on the frontier itself is marked already: the whole frontier is)
       const int zi = (int)((uint32_t)t.z & idx_mask);
       if (zi < fb) {
@@ -4561,9 +4574,7 @@ __global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const
         else s_abort = 1;
       }
     }
-  }
-  best_all = wave_min_u64(best_all);
-  if (lane == 0) s_all[wave] = best_all;
+  });
   // ---- ancestor sweep ----------------------------------------------------------------------------------------------------------
   int R = -1, Rf = 0;
   if (sweep) {
@@ -4681,18 +4692,17 @@ __global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const
   // ---- the walk's end: the previous commit token, found by its state on its frame ----------------------------------------------
   int stop = -1;   // (the root)
   if (cf > 0) {
-    bp_scan_eps_pred<false>(D, c, tok, nullptr, foff[cf], foff[cf + 1], cs, 0, &s_found);
+    bp_scan_eps_pred<false>(D, c, tok, nullptr, foff[cf], foff[cf + 1], cs, 0, &s_w.rq.found);
     __syncthreads();
-    stop = s_found;
+    stop = s_w.rq.found;
     if (stop < 0) {   // never expected: the commit token is an ancestor of every living token
       if (tid == 0) { o[0] = 0; o[1] = 0; o[2] = 0; o[3] = kErrInternal; }
       return;
     }
   }
   if (tid == 0) {
-    for (int w = 1; w < kBpThreads / 64; ++w) best_all = s_all[w] < best_all ? s_all[w] : best_all;
-    s_cur = (int)(uint32_t)best_all;
-    s_done = s_cur == stop ? 1 : 0;
+    s_w.cur = (int)(uint32_t)best.all;
+    s_done = s_w.cur == stop ? 1 : 0;
     s_nrev = 0;
     s_ntail = -1;
   }
@@ -4700,50 +4710,17 @@ __global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const
   for (;;) {
     __syncthreads();
     if (s_done) break;
-    if (tid == 0) { s_tok[0] = s_cur; s_k = 0; }
-    for (;;) {
-      __syncthreads();
-      if (tid == 0) {
-        int t = s_tok[s_k], k = s_k;
-        s_need = -1;
-        while (t >= 0 && t != stop && k < kEpChunk) {
-          const int4 T = tok[t];
-          if (T.z <= kPrevUnresolved) {
-            int flo = 0, fhi = nd + 1;  // frame of t: frame_off[f] <= t < frame_off[f+1]
-            while (fhi - flo > 1) {
-              const int mid = (flo + fhi) >> 1;
-              if (foff[mid] <= t) flo = mid; else fhi = mid;
-            }
-            s_lo = foff[flo];
-            s_hi = foff[flo + 1];
-            s_need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
-            s_found = -1;
-            break;
-          }
-          t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : -1;
-          s_tok[++k] = t;
-        }
-        s_k = k;
-      }
-      __syncthreads();
-      if (s_need < 0) break;
-      bp_scan_eps_pred<false>(D, c, tok, nullptr, s_lo, s_hi, s_need, s_tok[s_k], &s_found);
-      __syncthreads();
-      if (tid == 0) { s_tok[s_k + 1] = s_found; ++s_k; }   // (-1, never expected, ends the walk)
-      __syncthreads();
-      if (s_k >= kEpChunk || s_tok[s_k] < 0 || s_tok[s_k] == stop) break;
-    }
-    __syncthreads();
+    bp_walk_chunk(D, c, tok, foff, nd, &s_w, stop);
     if (wave == 0) {
-      const int k = s_k, base = s_nrev;
+      const int k = s_w.k, base = s_nrev;
       int word = 0;
-      if (lane < k && s_tok[lane + 1] >= 0) {
+      if (lane < k && s_w.tok[lane + 1] >= 0) {
         bool eps;
         const float *llrow;
-        const int a = bp_resolve_hop<false>(D, c, ctl, tok, nullptr, foff, nd, m_last, 0.0f, s_tok[lane], s_tok[lane + 1], &eps, &llrow);
+        const int a = bp_resolve_hop<false>(D, c, ctl, tok, nullptr, foff, nd, m_last, 0.0f, s_w.tok[lane], s_w.tok[lane + 1], &eps, &llrow);
         word = D.g.arc_olabel[a];
       }
-      const u64 has = __ballot(word != 0), at_r = __ballot(lane < k && s_tok[lane] == R);
+      const u64 has = __ballot(word != 0), at_r = __ballot(lane < k && s_w.tok[lane] == R);
       if (word != 0) {
         const int pos = base + lane_rank(has);
         if (pos < D.max_frames) rev[pos] = word;
@@ -4752,8 +4729,7 @@ __global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const
         // the hop INTO R is committed with everything before it: the tail is what the walk met first
         if (at_r && s_ntail < 0) s_ntail = base + __popcll(has & ((1ull << (__ffsll((long long)at_r) - 1)) - 1ull));
         s_nrev = base + __popcll(has);
-        s_cur = s_tok[k];
-        if (s_cur < 0 || s_cur == stop || ++guard >= (1 << 18)) s_done = 1;
+        if (s_w.cur < 0 || s_w.cur == stop || ++guard >= (1 << 18)) s_done = 1;
       }
     }
   }
@@ -5119,11 +5095,9 @@ void launch_best_path(const DecoderDev &D, const int32_t *chans, int n, int use_
 void launch_endpoint(const DecoderDev &D, const int32_t *chans, int n, const uint32_t *sil_bits, int n_tid, int32_t *out, hipStream_t s) {
   hipLaunchKernelGGL(endpoint_kernel, dim3(n), dim3(kBpThreads), 0, s, D, chans, sil_bits, n_tid, out);
 }
-static void launch_partial_kernel(const DecoderDev &D, const int32_t *chans, int n, int32_t *ws, int64_t ws_stride, int cap_words, int32_t *out,
-                                  hipStream_t s) {
+void launch_partial(const DecoderDev &D, const int32_t *chans, int n, int32_t *ws, int64_t ws_stride, int cap_words, int32_t *out, hipStream_t s) {
   hipLaunchKernelGGL(partial_kernel, dim3(n), dim3(kBpThreads), 0, s, D, chans, ws, (long long)ws_stride, cap_words, out);
 }
-[[maybe_unused]] static const bool partial_registered = (launch_partial = launch_partial_kernel, true);   // (wfst_device.h: launch_partial)
 void launch_lattice_emit(const DecoderDev &D, const int32_t *chans, int n, int use_final, hipStream_t s);
 void launch_lattice_prune(const DecoderDev &D, const int32_t *chans, int n, hipStream_t s) {
   hipLaunchKernelGGL(lattice_finalize_kernel, dim3(n), dim3(kBT), 0, s, D, chans);

@@ -191,4 +191,5 @@ void launch_lattice_emit(const DecoderDev &, const int32_t *, int, int, hipStrea
 void launch_best_path(const DecoderDev &, const int32_t *, int, int, int, int32_t *, int32_t *, float *, float *, int32_t *, int32_t *,
                       hipStream_t) {}
 void launch_endpoint(const DecoderDev &, const int32_t *, int, const uint32_t *, int, int32_t *, hipStream_t) {}
+void launch_partial(const DecoderDev &, const int32_t *, int, int32_t *, int64_t, int, int32_t *, hipStream_t) {}
 }  // namespace wfst

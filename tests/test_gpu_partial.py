@@ -319,7 +319,61 @@ def test_long_utterance(synth, oracle, tmp_path, lattice):
         graph.free()
 
 
-# ---- 7: the halves, and the errors -------------------------------------------------------------------------------------------------
+# ---- 7: the walk's stop token on a chunk edge ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lattice", [False, True])
+def test_stop_token_on_a_chunk_edge(synth, oracle, tmp_path, lattice):
+    """A chain graph (one path, no input-epsilon arcs: one hop is one frame, one token per frame), a word on every third arc.  Every
+    frame holds one token, so a call at nd frames commits on frame m_last - 1 = (nd - 1) / prune_interval * prune_interval - 1, and
+    the next call walks from its frontier back to that token: nd' - stable_frame hops.  Calls spaced so that this is 63, 64, 65 and
+    128 hops -- the stop token inside partial_kernel's 64-hop chunk, as its last entry, as the first of the next chunk, and at the
+    end of a second full chunk."""
+    import gpu_util as G
+
+    n_states, n_tid, interval = 400, 100, 10
+    rng = np.random.default_rng(3)
+    arcs = {s: [(int(rng.integers(1, n_tid + 1)), 1 + s if s % 3 == 1 else 0, float(rng.uniform(0.1, 3.0)), (s + 1) % n_states)]
+            for s in range(n_states)}
+    g = synth.graph_from_arc_lists(n_states, 0, arcs, {n_states - 1: 0.5})
+    path = str(tmp_path / "chain.bin")
+    g.write(path)
+    m = synth.default_tid2pdf(n_tid)
+    graph = G.wfstdec.Graph.load(path)
+    graph.set_tid2pdf(m)
+    h = oracle.load_graph(path)
+    cd = dict(beam=9.0, max_active=1000000, min_active=0, lattice_beam=5.0, prune_interval=interval)
+    cfg = pyoracle.Config(**cd)
+    frames = [30, 82, 143, 204, 327]
+    x = rng.normal(-2.0, 1.0, size=(340, n_tid // 2)).astype(np.float32)
+    try:
+        dec = make_decoder(G, graph, cd, 1, lattice, max_frames=384, arena=1 << 16, max_tok=4096, links=1 << 16)
+        dev = G.upload([x])
+        dec.init()
+        hist, walked = History("chain"), []
+        for fr in frames:
+            dec.advance([dev[0].data_ptr()], [fr], n_tid // 2)
+            if hist.calls:
+                walked.append(fr - hist.calls[-1][3])
+            words, ns, sf = dec.partial(cap_words=256)
+            o = oracle.decode(h, cfg, x[:fr], m, finalize=False, use_final_probs=False)
+            assert np.array_equal(words[0], o.words), "@%d: partial words != the oracle's" % fr
+            hist.add(fr, words[0], ns[0], sf[0])
+            assert sf[0] == ((fr - 1) // interval) * interval - 1, "@%d: stable_frame" % fr
+            emitting = np.cumsum(o.path_ilabel != 0)
+            assert ns[0] == int(np.sum((o.path_olabel != 0) & (o.path_ilabel != 0) & (emitting <= sf[0]))), "@%d: n_stable" % fr
+        assert walked == [63, 64, 65, 128]
+        dec.advance([dev[0].data_ptr()], [340], n_tid // 2)
+        dec.finalize()
+        fin = dec.best_paths(cap=1024)[0]["words"]
+        dec.free()
+        o = oracle.decode(h, cfg, x, m)
+        assert np.array_equal(fin, o.words)
+        hist.check_final(o.words, "the oracle's final words")
+    finally:
+        oracle.free_graph(h)
+        graph.free()
+
+
+# ---- 8: the halves, and the errors -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("lattice", [False, True])
 def test_halves_and_errors(synth, oracle, tmp_path, lattice):
     import gpu_util as G
