@@ -17,6 +17,7 @@
 #include "../../include/wfst_decoder.h"
 #include "wfst_device.h"
 #include "wfst_hip_own.h"
+#include "wfst_capi_words.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -268,6 +269,11 @@ struct wfst_decoder {
   std::vector<int32_t> pt_list;
   int32_t pt_n = 0, pt_cap = 0;        // (0: nothing outstanding)
   std::vector<char> pt_reset;          // [channel] InitDecoding since the channel's last request: its commit state starts from zero
+  // wfst_decoder_set_silence_phones: the silence bitmap over transition-ids words_kernel trims word ends with (sil_set: there is one)
+  bool sil_set = false;
+  int32_t sil_ntid = 0;
+  DevBuf<uint32_t> sil_bits;
+  WordsState wd;   // wfst_decoder_words_enqueue / _ready / _fetch (wfst_capi_words.cc)
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
   int32_t hist_slab_stride = 0;        // ... of this many floats
@@ -3193,15 +3199,20 @@ void wfst_endpoint_config_default(wfst_endpoint_config *c) {   // OnlineEndpoint
   c->silence_phones = nullptr;
 }
 
+// a non-empty silence phone list: every phone > 0, none twice
+static int check_silence_list(const int32_t *phones, int32_t n, const char *what) {
+  std::vector<int32_t> v(phones, phones + n);
+  std::sort(v.begin(), v.end());
+  if (v[0] <= 0) return fail(WFST_E_ARG, std::string(what) + ": silence phones must be > 0");
+  if (std::adjacent_find(v.begin(), v.end()) != v.end()) return fail(WFST_E_ARG, std::string(what) + ": duplicate silence phone");
+  return WFST_OK;
+}
+
 static int check_endpoint_config(const wfst_endpoint_config *c) {
   if (!c) return fail(WFST_E_ARG, "NULL endpoint config");
   if (c->n_silence_phones <= 0 || !c->silence_phones) return fail(WFST_E_ARG, "endpoint config: empty silence phone list (--endpoint.silence-phones)");
   if (!(c->frame_shift > 0.0f)) return fail(WFST_E_ARG, "endpoint config: frame_shift must be > 0");
-  std::vector<int32_t> v(c->silence_phones, c->silence_phones + c->n_silence_phones);
-  std::sort(v.begin(), v.end());
-  if (v[0] <= 0) return fail(WFST_E_ARG, "endpoint config: silence phones must be > 0");
-  if (std::adjacent_find(v.begin(), v.end()) != v.end()) return fail(WFST_E_ARG, "endpoint config: duplicate silence phone");
-  return WFST_OK;
+  return check_silence_list(c->silence_phones, c->n_silence_phones, "endpoint config");
 }
 
 // RuleActivated + EndpointDetected (online-endpoint.cc), f32 throughout
@@ -3229,6 +3240,24 @@ int wfst_endpoint_rules(const wfst_endpoint_config *cfg, int32_t num_frames_deco
   return WFST_OK;
 }
 
+// the silence set as a bitmap over transition-ids 1..n_tid (t2p: the graph's tid2phone, entry 0 unused)
+static std::vector<uint32_t> silence_bitmap(const std::vector<int32_t> &t2p, const int32_t *phones, int32_t n) {
+  const int32_t n_tid = (int32_t)t2p.size() - 1;
+  std::vector<uint32_t> bits((size_t)n_tid / 32 + 1, 0u);
+  for (int32_t t = 1; t <= n_tid; ++t)
+    if (std::find(phones, phones + n, t2p[(size_t)t]) != phones + n) bits[(size_t)t >> 5] |= 1u << (t & 31);
+  return bits;
+}
+
+// the bitmap words_kernel reads (no words request is outstanding: the last one's launch has been waited for)
+static int set_words_silence(wfst_decoder *d, const std::vector<uint32_t> &bits, int32_t n_tid) {
+  if (d->sil_bits.n < bits.size()) HIP_TRY(d->sil_bits.alloc(bits.size()));
+  HIP_TRY(hipMemcpy(d->sil_bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+  d->sil_ntid = n_tid;
+  d->sil_set = true;
+  return WFST_OK;
+}
+
 int wfst_decoder_set_endpoint_config(wfst_decoder *d, const wfst_endpoint_config *cfg) {
   if (!d) return fail(WFST_E_ARG, "NULL decoder");
   if (d->D.big) return fail(WFST_E_ARG, "endpoint detection is not supported on biglm decoders (their final costs carry the LM's)");
@@ -3236,15 +3265,15 @@ int wfst_decoder_set_endpoint_config(wfst_decoder *d, const wfst_endpoint_config
   if (rc != WFST_OK) return rc;
   const std::vector<int32_t> &t2p = d->graph->tid2phone;
   if (t2p.empty()) return fail(WFST_E_STATE, "endpoint config before wfst_graph_set_tid2phone: no transition-id -> phone map");
+  if (d->wd.n > 0) return fail(WFST_E_STATE, kWordsOutstanding);   // (it reads the silence list this call replaces)
   HIP_TRY(hipSetDevice(d->device));
   const int32_t n_tid = (int32_t)t2p.size() - 1;
-  std::vector<uint32_t> bits((size_t)n_tid / 32 + 1, 0u);
-  for (int32_t t = 1; t <= n_tid; ++t)
-    if (std::find(cfg->silence_phones, cfg->silence_phones + cfg->n_silence_phones, t2p[(size_t)t]) != cfg->silence_phones + cfg->n_silence_phones)
-      bits[(size_t)t >> 5] |= 1u << (t & 31);
+  const std::vector<uint32_t> bits = silence_bitmap(t2p, cfg->silence_phones, cfg->n_silence_phones);
   // (the device may still read the bitmap of an endpoint call of before: every such call has been waited for)
   if (d->ep_bits.n < bits.size()) HIP_TRY(d->ep_bits.alloc(bits.size()));
   HIP_TRY(hipMemcpy(d->ep_bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+  rc = set_words_silence(d, bits, n_tid);   // (the word times' list too)
+  if (rc != WFST_OK) return rc;
   if (!d->ep_chan.p) HIP_TRY(d->ep_chan.alloc((size_t)d->n_channels));
   if (!d->ep_out.p) HIP_TRY(d->ep_out.alloc((size_t)d->n_channels * 3));
   if (!d->ep_pin.p) HIP_TRY(d->ep_pin.alloc((size_t)d->n_channels * 4));
@@ -3368,6 +3397,42 @@ int wfst_decoder_get_partial(wfst_decoder *d, const int32_t *channels, int32_t n
   if (rc != WFST_OK) return rc;
   return wfst_decoder_partial_fetch(d, words, n_words, n_stable, stable_frame);
 }
+
+// ---- words, word times and scores of an utterance in one launch (words_kernel) -----------------------------------------------------
+int wfst_decoder_set_silence_phones(wfst_decoder *d, const int32_t *phones, int32_t n) {
+  if (!d) return fail(WFST_E_ARG, "NULL decoder");
+  if (n < 0 || (n > 0 && !phones)) return fail(WFST_E_ARG, "silence phones: n < 0, or n > 0 without a list");
+  if (d->wd.n > 0) return fail(WFST_E_STATE, kWordsOutstanding);
+  if (n == 0) {
+    d->sil_set = false;
+    return WFST_OK;
+  }
+  const int rc = check_silence_list(phones, n, "silence phones");
+  if (rc != WFST_OK) return rc;
+  const std::vector<int32_t> &t2p = d->graph->tid2phone;
+  if (t2p.empty()) return fail(WFST_E_STATE, "silence phones before wfst_graph_set_tid2phone: no transition-id -> phone map");
+  HIP_TRY(hipSetDevice(d->device));
+  return set_words_silence(d, silence_bitmap(t2p, phones, n), (int32_t)t2p.size() - 1);
+}
+
+// What wfst_capi_words.cc -- the entry points that launch words_kernel, a translation unit of their own -- needs of a decoder.
+extern "C++" {
+namespace wfst {
+int capi_fail(int code, const std::string &msg) { return fail(code, msg); }
+int capi_fail_ctl(int channel, int error_word) { return fail_ctl_error(channel, error_word); }
+int capi_poll_event(wfst_decoder *d, hipEvent_t ev) { return poll_event(d, ev); }
+WordsView words_view(wfst_decoder *d) {
+  return WordsView{d->device, d->n_channels, &d->D, &d->wd, d->sil_set ? d->sil_bits.p : nullptr, d->sil_ntid};
+}
+int words_begin(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs, hipStream_t *st) {
+  HIP_TRY(hipSetDevice(d->device));
+  const int rc = check_channel_list(d, channels, n, "GetBestPath",   // base-inl.h:1100-1102 (LOG_ERR)
+                                    use_final_probs ? nullptr : "You cannot call FinalizeDecoding() and then GetBestPath with use_final_probs == false");
+  if (rc != WFST_OK) return rc;
+  return results_stream_behind(d, channels, n, st);   // behind these channels' own work only (see mark_ev)
+}
+}  // namespace wfst
+}  // extern "C++"
 
 int wfst_decoder_get_frontier(wfst_decoder *d, int32_t channel, int32_t cap, int32_t *states, float *costs) {
   if (!d || channel < 0 || channel >= d->n_channels || cap < 0) return fail(WFST_E_ARG, "bad argument");

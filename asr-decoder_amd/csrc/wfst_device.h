@@ -486,6 +486,13 @@ void launch_lattice_emit(const DecoderDev &D, const int32_t *chan_list_dev, int 
 void launch_best_path(const DecoderDev &D, const int32_t *chan_list_dev, int n, int use_final,
                       int cap, int32_t *ilabel, int32_t *olabel, float *graph, float *ac,
                       int32_t *n_hops, int32_t *chain_scratch, hipStream_t s);
+// words, word times and scores of the listed channels' best paths (words_kernel): out[i] = {n_hops, n_words, tot, lm, 1: the path
+// outgrew the scratch, the channel's error word, 0, 0} + cap_words words, begin frames and end frames; chain: cap_chain ints per list entry for the hops
+// of the walk beyond words_chain_lds(); sil_bits: the silence bitmap over transition-ids 1..n_tid, or nullptr
+constexpr int32_t kWordsHead = 8;
+int words_chain_lds();
+void launch_words(const DecoderDev &D, const int32_t *chan_list_dev, int n, int use_final, const uint32_t *sil_bits, int n_tid,
+                  int cap_words, int cap_chain, int32_t *chain, int32_t *out, hipStream_t s);
 // endpoint inputs of the listed channels (endpoint_kernel): out[3 i ..] = {trailing silence frames, final relative cost, error}
 void launch_endpoint(const DecoderDev &D, const int32_t *chan_list_dev, int n, const uint32_t *sil_bits, int n_tid, int32_t *out,
                      hipStream_t s);

@@ -78,6 +78,17 @@ __device__ __forceinline__ int wave_incl_scan(int v0) {
   v += WFST_DPP(0, v, 0x143, 0xc, 0xf);
   return v;
 }
+// inclusive prefix maximum over the wave's 64 lanes, of values >= 0
+__device__ __forceinline__ int wave_incl_max(int v0) {
+  int v = max(v0, WFST_DPP(0, v0, 0x111, 0xf, 0xf));
+  v = max(v, WFST_DPP(0, v0, 0x112, 0xf, 0xf));
+  v = max(v, WFST_DPP(0, v0, 0x113, 0xf, 0xf));
+  v = max(v, WFST_DPP(0, v, 0x114, 0xf, 0xe));
+  v = max(v, WFST_DPP(0, v, 0x118, 0xf, 0xc));
+  v = max(v, WFST_DPP(0, v, 0x142, 0xa, 0xf));
+  v = max(v, WFST_DPP(0, v, 0x143, 0xc, 0xf));
+  return v;
+}
 // the wave's total, in every lane (uniform)
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane(wave_incl_scan((int)x), 63); }
 __device__ __forceinline__ float wave_min_f(float x) {
@@ -4287,6 +4298,21 @@ __device__ __forceinline__ int bp_resolve_hop(const DecoderDev &D, int c, const 
   return chosen;
 }
 
+// The costs of the hop over arc a (bp_resolve_hop's answer, with its eps and llrow) from token prev, as GetBestPath reports them
+template <bool kBig>
+__device__ __forceinline__ void bp_hop_costs(const DecoderDev &D, int c, const int32_t *tok_lm, int prev, int a, bool eps, const float *llrow,
+                                             float *graph, float *acoustic) {
+  const int4 C = D.g.arcs[a];
+  if constexpr (kBig) {
+    float ls;
+    bp_arc_lm<kBig>(D, c, tok_lm, prev, a, &ls);
+    *graph = __int_as_float(C.z) + ls;  // graph_cost = arc weight + lm_score (biglm.h:380,450)
+  } else {
+    *graph = __int_as_float(C.z);
+  }
+  *acoustic = eps ? 0.f : -llrow[C.x & D.g.col_mask];
+}
+
 // The chunked walk of endpoint_kernel and partial_kernel (plain decoders, mid-utterance), last hop first: from W->cur up to
 // kEpChunk hops into LDS -- tok[0 .. k], hop j is tok[j] <- tok[j + 1] (-1: the root) -- lane 0 following the backpointers and
 // the workgroup's frame scan finding an epsilon-won token's predecessor (-1, never expected, ends the walk).  The chunk ends at
@@ -4320,6 +4346,63 @@ __device__ __forceinline__ void bp_walk_chunk(const DecoderDev &D, int c, const 
   __syncthreads();
 }
 
+// The token GetBestPath starts its traceback from (BestPathEnd, base-inl.h:1096-1160), thread 0's: the cheapest final token if
+// use_final and there is one, else the cheapest token.  biglm after FinalizeDecoding: -1 if the final pruning left no token, and
+// *extra0 = the extra cost the path's tokens carry (0 otherwise).
+template <bool kBig>
+__device__ __forceinline__ int bp_end_token(const DecoderDev &D, const ChanCtl *ctl, const BpFrontier &best, int use_final, float *extra0) {
+  *extra0 = 0.0f;
+  int t = (int)(uint32_t)((use_final && best.fin != ~0ull) ? best.fin : best.all);
+  if (kBig && ctl->finalized) {
+    // PruneForwardLinksFinal (biglm.h:468-568): tok_extra_cost = tot_cost + final_cost - final_best_cost
+    // of the cheapest candidate; above lattice_beam it -- and with it every token -- is pruned away
+    const float fbc = o2f((uint32_t)(best.wf >> 32));
+    const float own = (best.fin != ~0ull) ? o2f((uint32_t)(best.fin >> 32)) : (o2f((uint32_t)(best.all >> 32)) + 0.0f);
+    if ((own - fbc) > D.lattice_beam) t = -1;
+    // final_best_cost ranges over non-final tokens too (biglm.h:186-188), so the best final token -- and with it every
+    // token of its path, whose links to their successors cost nothing extra -- carries this extra cost, and a parallel
+    // arc survives the final pruning only with it counted (the hop pass)
+    *extra0 = own - fbc;
+  }
+  return t;
+}
+
+// The whole walk from *s_t (LDS, set by thread 0 with *s_len = 0; -1: no path) to the root, last hop first: lane 0's follow step
+// and the workgroup's scan for an epsilon-won token's predecessor take turns.  Hop p < kBpChainLds goes to s_chain[p], a later
+// one to spill(p, token); *s_len counts them all.  Every thread calls; the caller's next barrier makes *s_len visible.
+// dbg: count into w thread 0's clock ticks in the follow steps and the scans, and the number of scans.
+struct BpWalkDbg { unsigned long long walk, scan; int n_unres; };
+template <bool kBig, class Spill>
+__device__ __forceinline__ void bp_walk(const DecoderDev &D, int c, const int4 *tok, const int32_t *tok_lm, const int32_t *foff, int nd,
+                                        int32_t *s_chain, int *s_t, int *s_len, BpScanReq *s_rq, bool dbg, BpWalkDbg &w, Spill &&spill) {
+  const int tid = threadIdx.x;
+  for (;;) {
+    __syncthreads();
+    if (*s_t < 0) break;
+    unsigned long long tw0 = (tid == 0 && dbg) ? wall_clock64() : 0ull;
+    if (tid == 0) {
+      int len = *s_len;
+      *s_t = bp_follow(D, tok, foff, nd, *s_t, (1 << 24) - len, -1, s_rq, [&](int t) {
+        // (the hop list stays in LDS until the walk is over: on this target a load issued behind a global store waits for the store)
+        if (len < kBpChainLds) s_chain[len] = t;
+        else spill(len, t);
+        ++len;
+      });
+      if (len >= (1 << 24)) { *s_t = -1; s_rq->need = -1; }   // (the bound met: the walk ends here)
+      *s_len = len;
+      if (dbg) { const unsigned long long now = wall_clock64(); w.walk += now - tw0; tw0 = now; }
+    }
+    __syncthreads();
+    if (s_rq->need >= 0) {
+      if (dbg) ++w.n_unres;
+      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_rq->lo, s_rq->hi, s_rq->need, *s_t, &s_rq->found);
+      __syncthreads();
+      if (tid == 0) *s_t = s_rq->found;  // -1 (never expected) ends the walk
+      if (tid == 0 && dbg) w.scan += wall_clock64() - tw0;
+    }
+  }
+}
+
 // kBig (biglm): final costs carry the LM's (ComputeFinalCosts, biglm.h:160-215), hop graph costs are arc
 // weight + lm_score, an epsilon-won token's predecessor is found by (state, LM pair, cost), and after
 // FinalizeDecoding the reference's final pruning can leave NO token (its final_best_cost ranges over
@@ -4341,8 +4424,8 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
   __shared__ int s_len;
   const int4 *tok = D.tok + (size_t)c * D.arena_cap;
   const int32_t *tok_lm = kBig ? D.tok_lm + (size_t)c * D.arena_cap : nullptr;
-  unsigned long long tb0 = (D.dbg & 32) ? wall_clock64() : 0ull, tb_walk = 0, tb_scan = 0;
-  int n_unres = 0;
+  unsigned long long tb0 = (D.dbg & 32) ? wall_clock64() : 0ull;
+  BpWalkDbg wd = {0ull, 0ull, 0};
   const BpFrontier best = bp_frontier(D, c, tok, tok_lm, ctl->front_begin, n, &s_red, [](const int4 &, int) {});
   int32_t *ch = chain + (size_t)bi * cap;
   __shared__ int32_t s_foff[kBpFrames + 2];
@@ -4352,52 +4435,18 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
   __shared__ BpScanReq s_rq;
   __shared__ float s_extra0;   // extra cost of the best path's tokens after FinalizeDecoding (0 except in biglm, below)
   if (tid == 0) {
-    s_extra0 = 0.0f;
-    s_t = (int)(uint32_t)((use_final && best.fin != ~0ull) ? best.fin : best.all);
-    if (kBig && ctl->finalized) {
-      // PruneForwardLinksFinal (biglm.h:468-568): tok_extra_cost = tot_cost + final_cost - final_best_cost
-      // of the cheapest candidate; above lattice_beam it -- and with it every token -- is pruned away
-      const float fbc = o2f((uint32_t)(best.wf >> 32));
-      const float own = (best.fin != ~0ull) ? o2f((uint32_t)(best.fin >> 32)) : (o2f((uint32_t)(best.all >> 32)) + 0.0f);
-      if ((own - fbc) > D.lattice_beam) s_t = -1;
-      // final_best_cost ranges over non-final tokens too (biglm.h:186-188), so the best final token -- and with it every
-      // token of its path, whose links to their successors cost nothing extra -- carries this extra cost, and a parallel
-      // arc survives the final pruning only with it counted (the hop loop below)
-      s_extra0 = own - fbc;
-    }
+    float extra0;
+    s_t = bp_end_token<kBig>(D, ctl, best, use_final, &extra0);
+    s_extra0 = extra0;
     s_len = 0;
   }
-  // Walk the backpointer chain (last hop first, packed against the end of ch[]): lane 0's follow step and the workgroup's scan
-  // for an epsilon-won token's predecessor take turns.
+  // Walk the backpointer chain (last hop first; what LDS does not hold is packed against the end of ch[])
   if (tid == 0 && (D.dbg & 32)) { const unsigned long long now = wall_clock64(); atomicAdd(&D.dbg_t[110], now - tb0); tb0 = now; }
-  for (;;) {
-    __syncthreads();
-    if (s_t < 0) break;
-    unsigned long long tw0 = (tid == 0 && (D.dbg & 32)) ? wall_clock64() : 0ull;
-    if (tid == 0) {
-      int len = s_len;
-      s_t = bp_follow(D, tok, foff, nd, s_t, (1 << 24) - len, -1, &s_rq, [&](int t) {
-        // (the hop list stays in LDS until the walk is over: on this target a load issued behind a global store waits for the store)
-        if (len < kBpChainLds) s_chain[len] = t;
-        else if (len < cap) ch[cap - 1 - len] = t;
-        ++len;
-      });
-      if (len >= (1 << 24)) { s_t = -1; s_rq.need = -1; }   // (the bound met: the walk ends here)
-      s_len = len;
-      if (D.dbg & 32) { const unsigned long long now = wall_clock64(); tb_walk += now - tw0; tw0 = now; }
-    }
-    __syncthreads();
-    if (s_rq.need >= 0) {
-      ++n_unres;
-      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_rq.lo, s_rq.hi, s_rq.need, s_t, &s_rq.found);
-      __syncthreads();
-      if (tid == 0) s_t = s_rq.found;  // -1 (never expected) ends the walk
-      if (tid == 0 && (D.dbg & 32)) tb_scan += wall_clock64() - tw0;
-    }
-  }
+  bp_walk<kBig>(D, c, tok, tok_lm, foff, nd, s_chain, &s_t, &s_len, &s_rq, (D.dbg & 32) != 0, wd,
+                [&](int p, int t) { if (p < cap) ch[cap - 1 - p] = t; });
   if (tid == 0 && (D.dbg & 32)) {
-    atomicAdd(&D.dbg_t[111], tb_walk); atomicAdd(&D.dbg_t[112], tb_scan); atomicAdd(&D.dbg_t[114], (unsigned long long)s_len);
-    atomicAdd(&D.dbg_t[115], (unsigned long long)n_unres); atomicAdd(&D.dbg_t[116], 1ull);
+    atomicAdd(&D.dbg_t[111], wd.walk); atomicAdd(&D.dbg_t[112], wd.scan); atomicAdd(&D.dbg_t[114], (unsigned long long)s_len);
+    atomicAdd(&D.dbg_t[115], (unsigned long long)wd.n_unres); atomicAdd(&D.dbg_t[116], 1ull);
     tb0 = wall_clock64();
   }
   if (tid == 0) n_hops[bi] = s_len;
@@ -4423,19 +4472,134 @@ __global__ __launch_bounds__(kBpThreads) void best_path_kernel(DecoderDev D, con
     bool eps;
     const float *llrow;
     const int chosen = bp_resolve_hop<kBig>(D, c, ctl, tok, tok_lm, foff, nd, m_last, extra0, t, prev, &eps, &llrow);
-    const int4 C = D.g.arcs[chosen];
     il[pos] = D.g.arc_ilabel[chosen];
     ol[pos] = D.g.arc_olabel[chosen];
-    if constexpr (kBig) {
-      float ls;
-      bp_arc_lm<kBig>(D, c, tok_lm, prev, chosen, &ls);
-      og[pos] = __int_as_float(C.z) + ls;  // graph_cost = arc weight + lm_score (biglm.h:380,450)
-    } else {
-      og[pos] = __int_as_float(C.z);
-    }
-    oa[pos] = eps ? 0.f : -llrow[C.x & D.g.col_mask];
+    bp_hop_costs<kBig>(D, c, tok_lm, prev, chosen, eps, llrow, &og[pos], &oa[pos]);
   }
   if (tid == 0 && (D.dbg & 32)) atomicAdd(&D.dbg_t[113], wall_clock64() - tb0);
+}
+
+// =========================================================================================
+// an utterance's result in one launch: the words of the best path, each word's begin and end frame, and LatticeToVector's two
+// scores (what the reference's services deliver: OnebestLatticeToString's words, tot_score and lm_score,
+// kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:107-121; AlignStruct's (start, end) per word, gpu-asr/gpu-worker-pool-itf.h:85-97).
+// One kBpThreads workgroup per listed channel; the path is best_path_kernel's -- the same frontier reduction, end token and walk,
+// every hop resolved by bp_resolve_hop -- but no hop leaves the device.  out[i] = {n_hops, n_words, tot_score, lm_score (f32
+// bits), 1: the walk outgrew the chain scratch and nothing else is valid, the channel's error word, 0, 0} | words[cap_words] | begin[cap_words] |
+// end[cap_words].
+//  - The walk keeps its first kBpChainLds hops in LDS; the rest go to chain[i * cap_chain ..] (cap_chain may be 0).
+//  - The hop pass takes the path in tiles of kBpThreads hops, start -> final.  With F(hop) = the frames consumed before it (from
+//    the frame of its token: fr - 1 for an emitting hop, fr for an epsilon hop), a word hop (olabel != 0) begins at F.  Three
+//    scans across the tile (a ballot's rank and two DPP prefix maxima per wave, the waves' totals through LDS, the tiles' carried
+//    in registers) give a word hop its index k, the begin frame of word k - 1 and the last frame + 1 of an emitting hop before it
+//    that is not silence (sil_bits over transition-ids; nullptr: no hop is silence, and the end is the next word's begin): the
+//    thread of word k writes word k - 1's end, thread 0 the last word's.  F never decreases along the path, so both prefix maxima
+//    are "the newest such hop" and the end of a word without such a hop of its own falls back to its begin through max().
+//  - Thread 0 adds the tile's costs up in hop order (LatticeToVector's float sums, newfst/lattice-functions.cc:179-217).
+// =========================================================================================
+template <bool kBig>
+__global__ __launch_bounds__(kBpThreads) void words_kernel(DecoderDev D, const int32_t *chans, int use_final, const uint32_t *sil_bits,
+                                                           int n_tid, int cap_words, int cap_chain, int32_t *chain, int32_t *out) {
+  const int bi = blockIdx.x;
+  const int c = chans[bi];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ChanCtl *ctl = D.ctl + c;
+  const int n = ctl->front_count, nd = ctl->n_decoded;
+  int32_t *o = out + (size_t)bi * (kWordsHead + 3 * (size_t)cap_words);
+  if (nd <= 0 || n == 0) {  // base-inl.h:1104-1108 / 1148-1154: no path
+    if (tid < kWordsHead) o[tid] = tid == 5 ? ctl->error : 0;
+    return;
+  }
+  __shared__ BpFrontierLds<kBig ? kFrWf : kFrFin> s_red;
+  __shared__ int32_t s_foff[kBpFrames + 2];
+  __shared__ int32_t s_chain[kBpChainLds];   // the walk's hops, last hop first
+  __shared__ int s_t, s_len;
+  __shared__ BpScanReq s_rq;
+  __shared__ float s_extra0;
+  __shared__ float s_g[kBpThreads], s_ac[kBpThreads];   // a tile's costs
+  __shared__ int s_wave[3][kBpThreads / 64];            // a tile's words, newest non-silence end and newest word begin, per wave
+  const int4 *tok = D.tok + (size_t)c * D.arena_cap;
+  const int32_t *tok_lm = kBig ? D.tok_lm + (size_t)c * D.arena_cap : nullptr;
+  const BpFrontier best = bp_frontier(D, c, tok, tok_lm, ctl->front_begin, n, &s_red, [](const int4 &, int) {});
+  int32_t *ch = chain + (size_t)bi * cap_chain;
+  const int32_t *foff = bp_stage_foff(D, c, nd, s_foff);
+  if (tid == 0) {
+    float extra0;
+    s_t = bp_end_token<kBig>(D, ctl, best, use_final, &extra0);
+    s_extra0 = extra0;
+    s_len = 0;
+  }
+  BpWalkDbg no_dbg = {0ull, 0ull, 0};
+  bp_walk<kBig>(D, c, tok, tok_lm, foff, nd, s_chain, &s_t, &s_len, &s_rq, false, no_dbg,
+                [&](int p, int t) { if (p - kBpChainLds < cap_chain) ch[p - kBpChainLds] = t; });
+  __syncthreads();
+  const int len = s_len;
+  if (len - kBpChainLds > cap_chain) {   // (the host grows the scratch and asks again)
+    if (tid < kWordsHead) o[tid] = tid == 0 ? len : tid == 4 ? 1 : tid == 5 ? ctl->error : 0;
+    return;
+  }
+  int32_t *o_word = o + kWordsHead, *o_begin = o_word + cap_words, *o_end = o_begin + cap_words;
+  const int m_last = ((nd - 1) / D.prune_interval) * D.prune_interval;
+  const float extra0 = s_extra0;
+  int nw = 0, end_c = 0, begin_c = 0;   // carried over the tiles (uniform): words so far, newest non-silence end, newest word begin
+  float tot = 0.0f, lm = 0.0f;          // (thread 0's)
+  for (int base = 0; base < len; base += kBpThreads) {
+    const int pos = base + tid;
+    auto hop_at = [&](int q) { const int p = len - 1 - q; return p < kBpChainLds ? s_chain[p] : ch[p - kBpChainLds]; };
+    int word = 0, F = 0, endv = 0;
+    float g = 0.0f, ac = 0.0f;
+    const int prev = (pos > 0 && pos < len) ? hop_at(pos - 1) : -1;   // (hop 0 is the root token's (0,0,One) arc, base-inl.h:1193-1198)
+    if (prev >= 0) {
+      const int t = hop_at(pos);
+      bool eps;
+      const float *llrow;
+      const int a = bp_resolve_hop<kBig>(D, c, ctl, tok, tok_lm, foff, nd, m_last, extra0, t, prev, &eps, &llrow);
+      bp_hop_costs<kBig>(D, c, tok_lm, prev, a, eps, llrow, &g, &ac);
+      word = D.g.arc_olabel[a];
+      const int fr = bp_frame_of(foff, nd, t);
+      F = eps ? fr : fr - 1;
+      if (!eps) {
+        const int il = D.g.arc_ilabel[a];
+        const bool sil = sil_bits && il > 0 && il <= n_tid && ((sil_bits[il >> 5] >> (il & 31)) & 1u);
+        endv = sil ? 0 : F + 1;
+      }
+    }
+    const u64 wm = __ballot(word != 0);
+    const int end_i = wave_incl_max(endv), begin_i = wave_incl_max(word != 0 ? F : 0);
+    int end_x = __shfl_up(end_i, 1, 64), begin_x = __shfl_up(begin_i, 1, 64);   // exclusive: the hops before this one
+    if (lane == 0) { end_x = 0; begin_x = 0; }
+    s_g[tid] = g;
+    s_ac[tid] = ac;
+    if (lane == 63) { s_wave[0][wave] = __popcll(wm); s_wave[1][wave] = end_i; s_wave[2][wave] = begin_i; }
+    __syncthreads();
+    int k = nw + lane_rank(wm);
+    end_x = max(end_x, end_c);
+    begin_x = max(begin_x, begin_c);
+#pragma unroll
+    for (int w = 0; w < kBpThreads / 64; ++w) {
+      if (w < wave) { k += s_wave[0][w]; end_x = max(end_x, s_wave[1][w]); begin_x = max(begin_x, s_wave[2][w]); }
+      nw += s_wave[0][w];
+      end_c = max(end_c, s_wave[1][w]);
+      begin_c = max(begin_c, s_wave[2][w]);
+    }
+    if (word != 0) {
+      if (k < cap_words) { o_word[k] = word; o_begin[k] = F; }
+      if (k >= 1 && k - 1 < cap_words) o_end[k - 1] = max(end_x, begin_x);
+    }
+    if (tid == 0) {
+      const int m = min(kBpThreads, len - base);
+      for (int i = 0; i < m; ++i) {
+        lm += s_g[i];
+        tot += s_g[i] + s_ac[i];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (nw >= 1 && nw - 1 < cap_words) o_end[nw - 1] = max(end_c, begin_c);
+    o[0] = len; o[1] = nw; o[2] = __float_as_int(tot); o[3] = __float_as_int(lm);
+    o[4] = 0; o[5] = ctl->error; o[6] = 0; o[7] = 0;
+  }
 }
 
 // =========================================================================================
@@ -5091,6 +5255,14 @@ void launch_best_path(const DecoderDev &D, const int32_t *chans, int n, int use_
   else
     hipLaunchKernelGGL(best_path_kernel<false>, dim3(n), dim3(kBpThreads), 0, s, D, chans, use_final, cap, ilabel, olabel, graph,
                        ac, n_hops, chain);
+}
+int words_chain_lds() { return kBpChainLds; }
+void launch_words(const DecoderDev &D, const int32_t *chans, int n, int use_final, const uint32_t *sil_bits, int n_tid, int cap_words,
+                  int cap_chain, int32_t *chain, int32_t *out, hipStream_t s) {
+  if (D.big)
+    hipLaunchKernelGGL(words_kernel<true>, dim3(n), dim3(kBpThreads), 0, s, D, chans, use_final, sil_bits, n_tid, cap_words, cap_chain, chain, out);
+  else
+    hipLaunchKernelGGL(words_kernel<false>, dim3(n), dim3(kBpThreads), 0, s, D, chans, use_final, sil_bits, n_tid, cap_words, cap_chain, chain, out);
 }
 void launch_endpoint(const DecoderDev &D, const int32_t *chans, int n, const uint32_t *sil_bits, int n_tid, int32_t *out, hipStream_t s) {
   hipLaunchKernelGGL(endpoint_kernel, dim3(n), dim3(kBpThreads), 0, s, D, chans, sil_bits, n_tid, out);

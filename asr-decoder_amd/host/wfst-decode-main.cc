@@ -26,6 +26,11 @@
 //                  GetPartialWords -- the incremental form, whose device work follows the frames since the last commit, not the
 //                  utterance -- and is printed as "KEY@frames n_stable word-ids...": the first n_stable words are final (the partial
 //                  n-best lines of --nbest follow it as they follow the plain partial line)
+//   --word-times [--silence-phones=a:b:c]  batch shape and --single-stream: after an utterance's "KEY word-ids..." line one line
+//                  "KEY#k word begin end" per word -- the frames of GetWords (wfst_decoder_get_words: the word's label-carrying
+//                  arc, and the next word's begin or, with silence phones and --tid2phone=FILE, one past the word's last frame
+//                  that is not silence; end exclusive): the (start, end) per word of the reference's AlignStruct
+//                  (gpu-asr/gpu-worker-pool-itf.h:85-97)
 //   --inflight=K   batch shape only: K batches in flight, each on its own GpuBatchDecoder (own HIP
 //                  stream) driven by its own host thread -- the reference service's model of one
 //                  decoder object per thread (v2-asrbin/v2-asr-service.cc:95-105); the GPU overlaps
@@ -153,7 +158,8 @@ int main(int argc, char **argv) {
     std::string lattice_file, lattice_text;
     long long lattice_links = 1ll << 22;
     int nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
-    bool pull = false, partial_words = false;
+    bool pull = false, partial_words = false, word_times = false;
+    std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
     std::vector<int> devices(1, 0);
@@ -181,6 +187,14 @@ int main(int argc, char **argv) {
       else if (a.compare(0, 12, "--linger-us=") == 0) linger_us = std::max(0, atoi(a.c_str() + 12));
       else if (a == "--pull") pull = true;
       else if (a == "--partial-words") partial_words = true;
+      else if (a == "--word-times") word_times = true;
+      else if (a.compare(0, 17, "--silence-phones=") == 0) {
+        for (size_t p0 = 17; p0 <= a.size();) {
+          const size_t p1 = std::min(a.find(':', p0), a.size());
+          if (p1 > p0) wt_silence.push_back(atoi(a.substr(p0, p1 - p0).c_str()));
+          p0 = p1 + 1;
+        }
+      }
       else if (a.compare(0, 9, "--repeat=") == 0) repeat = std::max(1, atoi(a.c_str() + 9));
       else if (a.compare(0, 7, "--warm=") == 0) warm = std::max(0, atoi(a.c_str() + 7));
       else if (a.compare(0, 9, "--ragged=") == 0) ragged = std::min(100, std::max(1, atoi(a.c_str() + 9)));
@@ -205,14 +219,16 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words]]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
       return 1;
     }
+    if (word_times && n_threads > 0) { std::cerr << "--word-times goes with the batch shape or --single-stream\n"; return 1; }
+    if (!wt_silence.empty() && (!word_times || tid2phone_file.empty())) { std::cerr << "--silence-phones goes with --word-times and --tid2phone=FILE\n"; return 1; }
     LatticeFasterDecoderConfig opt;
     opt.ReadConfigFile(pos[0]);
-    if (endpointing || !tid2phone_file.empty() || print_endpoints) {
+    if (endpointing || print_endpoints || (!tid2phone_file.empty() && wt_silence.empty())) {
       // endpointing (v1-asr/asr-source.h:280-287): --tid2phone and --endpoint.silence-phones, a streaming shape, a search without LMs
       if (tid2phone_file.empty() || ep_opt.silence_phones.empty()) { std::cerr << "endpointing needs --tid2phone=FILE and --endpoint.silence-phones\n"; return 1; }
       if (chunk <= 0 || !(single || n_threads > 0)) { std::cerr << "endpointing goes with --chunk=N and --single-stream or --threads=N\n"; return 1; }
@@ -343,6 +359,9 @@ int main(int argc, char **argv) {
     long long frame_count = 0, repeat_frames = 0, timed_frames = 0;
     double tot_like = 0;
     auto t0 = std::chrono::steady_clock::now();
+    // --word-times: the words and frames of the utterance emit() is called for next (GetWords), or nullptr
+    struct WordTimes { std::vector<int> words; std::vector<std::pair<int, int> > frames; };
+    const WordTimes *emit_times = nullptr;
     auto emit = [&](const Utt &u, Lattice &best, bool ok) {
       std::vector<int> words, phones;
       float tot = 0, lm = 0;
@@ -354,6 +373,11 @@ int main(int argc, char **argv) {
       out << u.key;
       for (int w : words) out << ' ' << w;
       out << '\n';
+      if (emit_times) {
+        if (emit_times->words != words) throw std::runtime_error("GetWords and GetBestPath disagree on the words of " + u.key);
+        for (size_t k = 0; k < words.size(); ++k)
+          out << u.key << '#' << (k + 1) << ' ' << words[k] << ' ' << emit_times->frames[k].first << ' ' << emit_times->frames[k].second << '\n';
+      }
       std::cerr << "LOG " << u.key << " tot_score " << tot << " lm_score " << lm << " over " << u.frames << " frames.\n";
       tot_like += -tot;
       frame_count += u.frames;
@@ -534,6 +558,7 @@ int main(int argc, char **argv) {
       std::unique_ptr<GpuLatticeDecoder> decode_p(biglm ? new OnlineLatticeDecoderMempoolBiglm(&fst, opt, lm1p, lm2p, &limits)
                                                         : new GpuLatticeDecoder(&fst, opt, &limits));
       GpuLatticeDecoder &decode = *decode_p;
+      if (word_times) decode.SetSilencePhones(wt_silence);
       for (const Utt &u : utts) {
         if (endpointing) {
           bool ok = false;
@@ -584,7 +609,13 @@ int main(int argc, char **argv) {
         decode.FinalizeDecoding();
         Lattice best;
         bool ok = decode.GetBestPath(&best);
+        WordTimes wt;
+        if (word_times && ok) {
+          decode.GetWords(&wt.words, &wt.frames, nullptr, nullptr);
+          emit_times = &wt;
+        }
         emit(u, best, ok);
+        emit_times = nullptr;
         if (want_lattice) {
           Lattice lat;
           bool lok = determinize ? (second ? decode.GetLattice(&lat, slm1p, slm2p) : decode.GetLattice(&lat)) : decode.GetRawLattice(&lat);
@@ -603,6 +634,8 @@ int main(int argc, char **argv) {
         std::vector<Lattice> best, lats;
         std::vector<bool> ok, lat_ok;
         std::vector<std::vector<Lattice> > nbest;
+        std::vector<std::vector<int> > wt_words;                      // --word-times
+        std::vector<std::vector<std::pair<int, int> > > wt_frames;
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -621,6 +654,7 @@ int main(int argc, char **argv) {
           std::unique_ptr<GpuBatchDecoder> decode_p(biglm ? new GpuBatchDecoder(wf, opt, lm1, lm2, batch, &limits)
                                                           : new GpuBatchDecoder(wf, opt, batch, &limits));  // its own stream
           GpuBatchDecoder &decode = *decode_p;
+          if (word_times) decode.SetSilencePhones(wt_silence);
           for (;;) {
             // one device: the next batch nobody has taken; several: batch b belongs to device b mod n_dev (its workers share them)
             const size_t b = n_dev == 1 ? next.fetch_add(1) : (size_t)di + (size_t)n_dev * next_of_dev[(size_t)di].fetch_add(1);
@@ -642,6 +676,7 @@ int main(int argc, char **argv) {
             decode.FinalizeDecoding(ch);
             if (want_lattice && determinize && !second) decode.PrefetchLattices();   // the determinizer runs beside the best paths
             decode.GetBestPaths(ch, &o.best, &o.ok);
+            if (word_times) decode.GetWords(ch, &o.wt_words, &o.wt_frames, nullptr, nullptr);
             if (want_lattice && determinize) {
               o.lats.assign(n, Lattice());
               o.lat_ok.assign(n, false);
@@ -673,7 +708,16 @@ int main(int argc, char **argv) {
         const size_t b0 = b * (size_t)batch;
         BatchOut &o = outs[b];
         const int n = (int)o.best.size();
-        for (int i = 0; i < n; ++i) emit(utts[b0 + i], o.best[i], o.ok[i]);
+        for (int i = 0; i < n; ++i) {
+          WordTimes wt;
+          if (word_times && o.ok[i]) {
+            wt.words = o.wt_words[i];
+            wt.frames = o.wt_frames[i];
+            emit_times = &wt;
+          }
+          emit(utts[b0 + i], o.best[i], o.ok[i]);
+          emit_times = nullptr;
+        }
         for (int i = 0; i < n && want_lattice; ++i) emit_lattice(utts[b0 + i], o.lats[i], o.lat_ok[i]);
         for (int i = 0; i < n && nbest > 0; ++i) emit_nbest(utts[b0 + i], o.nbest[i]);
       }

@@ -452,6 +452,14 @@ class GpuLatticeDecoder : public DecoderItf {
   // words than the decoder's max_frames (the call is retried once with the size it asks for; that limit no size satisfies).  Over a pool, the
   // requests of many threads go to the device as one list per batcher pass, and the batcher goes on feeding the device meanwhile.
   bool GetPartialWords(std::vector<int> *words, int *n_stable = nullptr);
+  // The best path as words with times, mid-utterance or after FinalizeDecoding, any decoder kind (wfst_decoder_get_words: one
+  // launch, no hop list) -- OnebestLatticeToString's words, tot_score and lm_score (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:
+  // 107-121) and the (start, end) of every word that AlignStruct carries (gpu-asr/gpu-worker-pool-itf.h:85-97), in frames, end
+  // exclusive: (*frames)[k].first is the frame of the arc that carries word k's label, .second the next word's begin -- or, after
+  // SetSilencePhones, one past the word's last frame that is not silence.  false: no path (no frame decoded, or no token).  Over a
+  // pool the same result is derived on the host from the channel's pooled GetBestPath (no silence list there).
+  bool GetWords(std::vector<int> *words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs = true);
+  void SetSilencePhones(const std::vector<int> &phones);   // needs the graph's SetTid2Phone; empty: none
 
  private:
   void Pull(AmInterface *decodable);
@@ -529,6 +537,11 @@ class GpuBatchDecoder {
   void GetPartialWords(const std::vector<int> &channels, std::vector<std::vector<int> > *words, std::vector<int> *n_stable = nullptr,
                        std::vector<int> *stable_frame = nullptr);
   bool GetPartialWords(int channel, std::vector<int> *words, int *n_stable = nullptr);
+  // GetWords (see GpuLatticeDecoder) of many channels (none listed: all) in one device call; (*ok)[i]: the channel has a path
+  void GetWords(const std::vector<int> &channels, std::vector<std::vector<int> > *words,
+                std::vector<std::vector<std::pair<int, int> > > *frames, std::vector<float> *tot, std::vector<float> *lm,
+                std::vector<bool> *ok = nullptr, bool use_final_probs = true);
+  void SetSilencePhones(const std::vector<int> &phones);
   wfst_decoder *Handle() { return _dec; }
 
  private:

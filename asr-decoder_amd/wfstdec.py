@@ -38,6 +38,8 @@ SYMBOLS = [
     "wfst_endpoint_config_default", "wfst_graph_set_tid2phone", "wfst_decoder_set_endpoint_config", "wfst_decoder_endpoint_detected",
     "wfst_endpoint_rules",
     "wfst_decoder_partial_enqueue", "wfst_decoder_partial_ready", "wfst_decoder_partial_fetch", "wfst_decoder_get_partial",
+    "wfst_decoder_set_silence_phones", "wfst_decoder_words_enqueue", "wfst_decoder_words_ready", "wfst_decoder_words_fetch",
+    "wfst_decoder_get_words",
 ]
 
 
@@ -756,6 +758,38 @@ class BatchDecoder:
         stable_frame int32[n]: the frame of the commit token, 0 if none yet)."""
         self.partial_enqueue(channels, cap_words)
         return self.partial_fetch()
+
+    def set_silence_phones(self, phones):
+        """The silence phones that word end times skip (wfst_decoder_set_silence_phones); an empty list clears them."""
+        a = np.ascontiguousarray(phones, dtype=np.int32).reshape(-1)
+        _check(lib().wfst_decoder_set_silence_phones(self.h, _i32(a) if a.size else None, int(a.size)))
+
+    def words_enqueue(self, channels=None, use_final_probs=True, cap_words=256):
+        """First half of words(): the work goes on the results stream behind the listed channels' own; returns at once."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        _check(lib().wfst_decoder_words_enqueue(self.h, _i32(ch), int(ch.shape[0]), int(bool(use_final_probs)), int(cap_words)))
+        self._words_req = (int(ch.shape[0]), int(cap_words))
+
+    def words_ready(self):
+        rc = lib().wfst_decoder_words_ready(self.h)
+        if rc < 0:
+            _check(rc)
+        return bool(rc)
+
+    def words_fetch(self):
+        n, cap = self._words_req
+        words, begin, end = np.zeros((n, cap), np.int32), np.zeros((n, cap), np.int32), np.zeros((n, cap), np.int32)
+        nw, nh = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        tot, lm = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        _check(lib().wfst_decoder_words_fetch(self.h, _i32(words), _i32(begin), _i32(end), _i32(nw), _i32(nh), _f32(tot), _f32(lm)))
+        return [(words[i, : nw[i]].copy(), begin[i, : nw[i]].copy(), end[i, : nw[i]].copy(), tot[i], lm[i], int(nh[i])) for i in range(n)]
+
+    def words(self, channels=None, use_final_probs=True, cap_words=256):
+        """The best path of the listed channels (all if None) as words with times, in one launch (wfst_decoder_get_words): per
+        channel (words int32[k], begin int32[k], end int32[k] -- frames, end exclusive --, tot_score float32, lm_score float32,
+        n_hops).  More than cap_words words: WfstError (WFST_E_CAPACITY)."""
+        self.words_enqueue(channels, use_final_probs, cap_words)
+        return self.words_fetch()
 
     def frontier(self, channel, cap=1 << 20):
         st = np.zeros(cap, np.int32)

@@ -632,6 +632,48 @@ int wfst_decoder_partial_fetch(wfst_decoder *d, int32_t *words /* [n][cap_words]
 int wfst_decoder_get_partial(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t cap_words, int32_t *words,
                              int32_t *n_words, int32_t *n_stable, int32_t *stable_frame);
 
+/* ---- an utterance's result in one launch: words, word times and scores ----------------------------------------------------
+ * What the reference's services deliver per utterance, without the hop list: OnebestLatticeToString's word string, tot_score and
+ * lm_score (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:107-121) and the (start, end) time of every word that the GPU service's
+ * BestPathAndAlignCallback(const std::string &, AlignStruct &, bool, bool) hands over (AlignStruct =
+ * vector<pair<string, pair<float, float>>>, gpu-asr/gpu-worker-pool-itf.h:85-97) -- times here are frames; the caller multiplies
+ * by its frame shift.  Any decoder kind, biglm included; mid-utterance or after FinalizeDecoding.
+ *
+ * Let h_0 .. h_{H-1} be the hops wfst_decoder_get_best_path(channel, use_final_probs) would return now, F(j) the number of hops
+ * i < j with ilabel_i != 0 (the frame hop j consumes if it is emitting) and E = F(H).  For listed channel i:
+ *   n_hops[i] = H (0: the reference's "no path" -- n_words[i] = 0, both scores 0);
+ *   words[i * cap_words .. + n_words[i])  the non-zero olabels in hop order; word k sits at hop j_k;
+ *   begin_frame[.. k] = F(j_k);
+ *   end_frame[.. k]   (exclusive) with L_k = begin_frame of word k + 1, or E for the last word:
+ *                     without a silence list L_k; with one, 1 + the largest F(i) over the emitting hops i in [j_k, j_{k+1})
+ *                     ([j_k, H) for the last word) whose phone tid2phone[ilabel_i] is not a silence phone, and begin_frame[k] if
+ *                     there is none;
+ *   tot_score[i], lm_score[i]  bit for bit what wfst_lattice_to_vector_batch returns for those hops (float sums of
+ *                     graph + acoustic and of graph, in hop order).
+ * Where an HCLG places a word's olabel relative to the word's phones is a property of the graph, so begin_frame is the frame of
+ * the label-carrying arc, not of the word's first phone.
+ *
+ * Errors and state follow wfst_decoder_get_best_path and its halves: the same use_final_probs rule after FinalizeDecoding
+ * (WFST_E_STATE), a device error of another channel's utterance does not fail the request, one words request may be outstanding
+ * per decoder (a second _enqueue: WFST_E_STATE) beside an outstanding best-path or partial request, and the listed channels must
+ * not be advanced or initialised in between.  WFST_E_CAPACITY: a channel has more words than cap_words -- n_words[i] is the
+ * needed size, the first cap_words words and times are written, scores and n_hops are valid.  There is no hop capacity: the
+ * library sizes the walk's scratch itself, and when a path outgrows it _fetch grows it and runs the list again.  Any output
+ * pointer may be NULL. */
+int wfst_decoder_words_enqueue(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs, int32_t cap_words);
+int wfst_decoder_words_ready(wfst_decoder *d);
+int wfst_decoder_words_fetch(wfst_decoder *d, int32_t *words /* [n][cap_words] */, int32_t *begin_frame, int32_t *end_frame,
+                             int32_t *n_words, int32_t *n_hops, float *tot_score, float *lm_score);
+int wfst_decoder_get_words(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs, int32_t cap_words,
+                           int32_t *words, int32_t *begin_frame, int32_t *end_frame, int32_t *n_words, int32_t *n_hops,
+                           float *tot_score, float *lm_score);
+
+/* The silence phones that word end times skip (the silence list of the reference's word alignment and of
+ * --endpoint.silence-phones): any decoder kind, biglm included.  The list is checked as wfst_decoder_set_endpoint_config checks
+ * its own (WFST_E_ARG: a phone <= 0 or a duplicate) and needs the graph's tid2phone (WFST_E_STATE without); n == 0 clears it.
+ * wfst_decoder_set_endpoint_config sets this list too.  WFST_E_STATE while a words request is outstanding. */
+int wfst_decoder_set_silence_phones(wfst_decoder *d, const int32_t *phones, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
