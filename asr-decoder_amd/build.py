@@ -9,10 +9,10 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", "wfst_kernels.hip"), os.path.join(HERE, "csrc", "wfst_nbest.hip"),
-        os.path.join(HERE, "csrc", "wfst_determinize.hip"), os.path.join(HERE, "csrc", "wfst_compose.hip"),
-        os.path.join(HERE, "csrc", "wfst_capi.cc"), os.path.join(HERE, "csrc", "wfst_capi_words.cc"),
+        os.path.join(HERE, "csrc", "wfst_determinize.hip"), os.path.join(HERE, "csrc", "wfst_compose.hip"), os.path.join(HERE, "csrc", "wfst_ingest.hip"),
+        os.path.join(HERE, "csrc", "wfst_capi.cc"), os.path.join(HERE, "csrc", "wfst_capi_words.cc"), os.path.join(HERE, "csrc", "wfst_capi_ingest.cc"),
         os.path.join(HERE, "csrc", "wfst_openfst.cc")]
-HDRS = [os.path.join(HERE, "csrc", "wfst_device.h"), os.path.join(HERE, "csrc", "wfst_determinize.h"), os.path.join(HERE, "csrc", "wfst_determinize_wave.h"), os.path.join(HERE, "csrc", "wfst_openfst.h"), os.path.join(HERE, "csrc", "wfst_hip_own.h"), os.path.join(HERE, "csrc", "wfst_capi_words.h"),
+HDRS = [os.path.join(HERE, "csrc", "wfst_device.h"), os.path.join(HERE, "csrc", "wfst_determinize.h"), os.path.join(HERE, "csrc", "wfst_determinize_wave.h"), os.path.join(HERE, "csrc", "wfst_openfst.h"), os.path.join(HERE, "csrc", "wfst_hip_own.h"), os.path.join(HERE, "csrc", "wfst_capi_words.h"), os.path.join(HERE, "csrc", "wfst_capi_ingest.h"), os.path.join(HERE, "csrc", "wfst_ingest.h"),
         os.path.join(HERE, "..", "include", "wfst_decoder.h")]
 LIB = os.path.join(HERE, "lib", "libwfstdec.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -48,8 +48,11 @@ def build_variant(name, defines):
     return out
 
 
-def kernel_resources(extra=()):
-    """What the compiler made of the decode kernels (wfst_kernels.hip, device code only, the library's own flags):
+INGEST_SRC = os.path.join(HERE, "csrc", "wfst_ingest.hip")
+
+
+def kernel_resources(extra=(), source=None):
+    """What the compiler made of the kernels of `source` (default: the decode kernels, wfst_kernels.hip; device code only, the library's own flags):
     {kernel name: {"vgprs", "agprs", "sgprs", "vgpr_spill", "sgpr_spill", "scratch", "occupancy", "lds"}} from
     -Rpass-analysis=kernel-resource-usage; "lds" is the static LDS in bytes.  Template instantiations keep their mangled names,
     plain kernels go by their function name.  (tests/test_kernel_resources.py; `python build.py --resources` prints the lines.)"""
@@ -58,7 +61,7 @@ def kernel_resources(extra=()):
     flags = [f for f in FLAGS if f not in ("-shared", "-fPIC")]
     with tempfile.TemporaryDirectory() as tmp:
         r = subprocess.run([HIPCC] + flags + list(extra) + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                                                           "-o", os.path.join(tmp, "kernels.o"), SRCS[0]],
+                                                           "-o", os.path.join(tmp, "kernels.o"), source or SRCS[0]],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])

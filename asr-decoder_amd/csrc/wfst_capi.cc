@@ -18,6 +18,7 @@
 #include "wfst_device.h"
 #include "wfst_hip_own.h"
 #include "wfst_capi_words.h"
+#include "wfst_capi_ingest.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -274,6 +275,7 @@ struct wfst_decoder {
   int32_t sil_ntid = 0;
   DevBuf<uint32_t> sil_bits;
   WordsState wd;   // wfst_decoder_words_enqueue / _ready / _fetch (wfst_capi_words.cc)
+  IngestState ing; // wfst_decoder_set_score_transform / _advance_chunk / _get_scores (wfst_capi_ingest.cc)
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
   int32_t hist_slab_stride = 0;        // ... of this many floats
@@ -1553,29 +1555,9 @@ int wfst_decoder_advance(wfst_decoder *d, const int32_t *channels, int32_t n, co
   return advance_device(d, channels, n, loglikes, n_frames_ready, stride, max_num_frames);
 }
 
-int wfst_decoder_advance_host(wfst_decoder *d, const int32_t *channels, int32_t n,
-                              const float *const *loglikes_host, const int32_t *n_frames_ready,
-                              int32_t stride, int32_t max_num_frames) {
-  if (!d) return fail(WFST_E_ARG, "NULL decoder");
-  if (!loglikes_host || !n_frames_ready) return fail(WFST_E_ARG, "NULL loglikes / n_frames_ready");
-  HIP_TRY(hipSetDevice(d->device));
-  const int32_t cnt = channels ? n : d->n_channels;
-  if (cnt <= 0 || cnt > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
-  if (d->hist_stride != 0 && d->hist_stride != stride) {
-    for (int c = 0; c < d->n_channels; ++c)
-      if (d->hist_rows[c] > 0) return fail(WFST_E_ARG, "stride changed while channels hold frames");
-  }
-  d->hist_stride = stride;
-  std::vector<const float *> dev_ptrs((size_t)cnt);
-  size_t need_rows = 0;
-  for (int i = 0; i < cnt; ++i) {
-    const int c = channels ? channels[i] : i;
-    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
-    const int32_t have = d->hist_rows[c], want = n_frames_ready[i];
-    if (want < have) return fail(WFST_E_ARG, "NumFramesReady decreased");
-    if (want > have && !loglikes_host[i]) return fail(WFST_E_ARG, "NULL log-likelihood matrix");
-    need_rows = std::max(need_rows, (size_t)want);
-  }
+// The device history of the rows handed over (wfst_decoder_advance_host, wfst_decoder_advance_chunk): room for need_rows rows of `stride`
+// floats per channel; `channels` / cnt: the call's list (its channels follow a moved history through advance_device).
+static int hist_reserve(wfst_decoder *d, const int32_t *channels, int32_t cnt, size_t need_rows, int32_t stride) {
   if (need_rows > d->hist_cap || (d->hist_slab.p && d->hist_slab_stride != stride)) {
     // The histories of all channels are one allocation of uniform pitch.  (A decoder created with a small wfst_limits.max_frames --
     // a caller that sizes its utterances -- gets the whole history at once: regrowing costs an allocation, a device copy and a free
@@ -1612,6 +1594,33 @@ int wfst_decoder_advance_host(wfst_decoder *d, const int32_t *channels, int32_t 
       d->hist_rows_cap[c] = ncap;
     }
   }
+  return WFST_OK;
+}
+
+int wfst_decoder_advance_host(wfst_decoder *d, const int32_t *channels, int32_t n,
+                              const float *const *loglikes_host, const int32_t *n_frames_ready,
+                              int32_t stride, int32_t max_num_frames) {
+  if (!d) return fail(WFST_E_ARG, "NULL decoder");
+  if (!loglikes_host || !n_frames_ready) return fail(WFST_E_ARG, "NULL loglikes / n_frames_ready");
+  HIP_TRY(hipSetDevice(d->device));
+  const int32_t cnt = channels ? n : d->n_channels;
+  if (cnt <= 0 || cnt > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
+  if (d->hist_stride != 0 && d->hist_stride != stride) {
+    for (int c = 0; c < d->n_channels; ++c)
+      if (d->hist_rows[c] > 0) return fail(WFST_E_ARG, "stride changed while channels hold frames");
+  }
+  d->hist_stride = stride;
+  std::vector<const float *> dev_ptrs((size_t)cnt);
+  size_t need_rows = 0;
+  for (int i = 0; i < cnt; ++i) {
+    const int c = channels ? channels[i] : i;
+    if (c < 0 || c >= d->n_channels) return fail(WFST_E_ARG, "channel index out of range");
+    const int32_t have = d->hist_rows[c], want = n_frames_ready[i];
+    if (want < have) return fail(WFST_E_ARG, "NumFramesReady decreased");
+    if (want > have && !loglikes_host[i]) return fail(WFST_E_ARG, "NULL log-likelihood matrix");
+    need_rows = std::max(need_rows, (size_t)want);
+  }
+  { const int rch = hist_reserve(d, channels, cnt, need_rows, stride); if (rch != WFST_OK) return rch; }
   for (int i = 0; i < cnt; ++i) dev_ptrs[i] = d->hist_dev[channels ? channels[i] : i];
   // Upload and decode in slices of kSlice frames: the host copies slice k+1 (pageable memory: the
   // copy call returns when the caller's buffer is consumed) while the GPU decodes slice k, so the
@@ -3430,6 +3439,38 @@ int words_begin(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use
                                     use_final_probs ? nullptr : "You cannot call FinalizeDecoding() and then GetBestPath with use_final_probs == false");
   if (rc != WFST_OK) return rc;
   return results_stream_behind(d, channels, n, st);   // behind these channels' own work only (see mark_ev)
+}
+
+// What wfst_capi_ingest.cc -- the entry points that launch ingest_kernel -- needs of a decoder.
+IngestView ingest_view(wfst_decoder *d) {
+  return IngestView{d->device, d->n_channels, d->D.max_frames, d->graph->max_col, &d->ing, d->stream, d->copy_stream, d->h_state.data(),
+                    d->h_decoded.data(), d->hist_rows.data(), d->hist_dev.data(), d->h_ll_base.data(), d->hist_stride};
+}
+int ingest_reserve(wfst_decoder *d, const int32_t *channels, int32_t cnt, size_t need_rows, int32_t stride) {
+  d->hist_stride = stride;
+  const int rc = hist_reserve(d, channels, cnt, need_rows, stride);
+  if (rc != WFST_OK) return rc;
+  if (!d->copy_stream) HIP_TRY(d->copy_stream.create());
+  return WFST_OK;
+}
+int ingest_behind_channels(wfst_decoder *d, const int32_t *channels, int32_t cnt) {
+  bool waited[wfst_decoder::kMarkRing] = {};
+  for (int i = 0; i < cnt; ++i) {
+    const int k = d->chan_mark[(size_t)channels[i]];
+    if (k >= 0 && !waited[k]) { HIP_TRY(hipStreamWaitEvent(d->copy_stream, d->mark_ev[k], 0)); waited[k] = true; }
+  }
+  return WFST_OK;
+}
+int ingest_advance(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t stride, int32_t max_num_frames) {
+  const int32_t cnt = channels ? n : d->n_channels;
+  std::vector<const float *> dev_ptrs((size_t)cnt);
+  std::vector<int32_t> ready((size_t)cnt);
+  for (int i = 0; i < cnt; ++i) {
+    const int c = channels ? channels[i] : i;
+    dev_ptrs[(size_t)i] = d->hist_dev[c];
+    ready[(size_t)i] = d->hist_rows[c];
+  }
+  return advance_device(d, channels, n, dev_ptrs.data(), ready.data(), stride, max_num_frames);
 }
 }  // namespace wfst
 }  // extern "C++"

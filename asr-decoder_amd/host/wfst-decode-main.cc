@@ -31,6 +31,13 @@
 //                  arc, and the next word's begin or, with silence phones and --tid2phone=FILE, one past the word's last frame
 //                  that is not silence; end exclusive): the (start, end) per word of the reference's AlignStruct
 //                  (gpu-asr/gpu-worker-pool-itf.h:85-97)
+//   --device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]  batch shape only: the matrices
+//                  on disk are the acoustic model's RAW output; N frames at a time every utterance's rows are converted to the
+//                  dtype on the host, put into a staging buffer the device reads, and handed over where they lie
+//                  (GpuBatchDecoder::AdvanceDecodingChunk): the device makes (x - log_prior) * acoustic_scale of them -- the
+//                  reference CLI's --acoustic-scale (default 0.1 there; 1 here) and DecodableMatrixScaledMapped
+//                  (kaldi-nnet3bin/kaldi-hclg-my-decoder.cc:37-41,107), the prior layer of its own network (nnet/nnet-layer.cc:30).
+//                  FILE: binary float32 array, one log prior per column
 //   --inflight=K   batch shape only: K batches in flight, each on its own GpuBatchDecoder (own HIP
 //                  stream) driven by its own host thread -- the reference service's model of one
 //                  decoder object per thread (v2-asrbin/v2-asr-service.cc:95-105); the GPU overlaps
@@ -112,6 +119,28 @@ bool ReadUtt(std::ifstream &in, Utt *u) {
   in.read((char *)u->m.data(), u->m.size() * 4);
   return (bool)in;
 }
+// float32 -> IEEE binary16 / bfloat16 bits, round to nearest even (--score-dtype: what a half-precision model would have written)
+uint16_t ToBf16(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // NaN stays NaN
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+uint16_t ToF16(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+  if (a >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);   // >= 65536 (65520 .. 65536 is rounded below): infinity
+  if (a < 0x33000000u) return (uint16_t)sign;                 // < 2^-25: zero
+  uint32_t mant = (a & 0x7fffffu) | 0x800000u;
+  const int e = (int)(a >> 23) - 127;                         // value = mant * 2^(e - 23)
+  const int shift = e >= -14 ? 13 : 13 + (-14 - e);           // normal: 10 mantissa bits; denormal: fewer
+  const uint32_t q = mant >> shift, rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  uint32_t h = e >= -14 ? (uint32_t)((e + 15) << 10) + (q - 0x400u) : q;
+  if (rem > half || (rem == half && (h & 1u))) ++h;           // (a carry runs into the exponent, up to infinity, as it should)
+  return (uint16_t)(sign | h);
+}
 // DecodableInterface over a host matrix: the shape every reference caller has.
 class HostMatrixDecodable : public MatrixDecodable {
  public:
@@ -165,6 +194,10 @@ int main(int argc, char **argv) {
     std::vector<int> devices(1, 0);
     std::vector<std::string> pos;
     std::string tid2phone_file;
+    bool device_chunks = false, scale_given = false;
+    float acoustic_scale = 1.0f;
+    std::string log_priors_file;
+    int score_dtype = WFST_DTYPE_F32;
     OnlineEndpointConfig ep_opt;
     bool endpointing = false, print_endpoints = false;
     for (int i = 1; i < argc; ++i) {
@@ -186,6 +219,16 @@ int main(int argc, char **argv) {
       else if (a.compare(0, 7, "--pool=") == 0) pool_channels = std::max(0, atoi(a.c_str() + 7));
       else if (a.compare(0, 12, "--linger-us=") == 0) linger_us = std::max(0, atoi(a.c_str() + 12));
       else if (a == "--pull") pull = true;
+      else if (a == "--device-chunks") device_chunks = true;
+      else if (a.compare(0, 17, "--acoustic-scale=") == 0) { acoustic_scale = (float)atof(a.c_str() + 17); scale_given = true; }
+      else if (a.compare(0, 13, "--log-priors=") == 0) log_priors_file = a.substr(13);
+      else if (a.compare(0, 14, "--score-dtype=") == 0) {
+        const std::string v = a.substr(14);
+        if (v == "f32") score_dtype = WFST_DTYPE_F32;
+        else if (v == "f16") score_dtype = WFST_DTYPE_F16;
+        else if (v == "bf16") score_dtype = WFST_DTYPE_BF16;
+        else { std::cerr << "--score-dtype is f32, f16 or bf16\n"; return 1; }
+      }
       else if (a == "--partial-words") partial_words = true;
       else if (a == "--word-times") word_times = true;
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
@@ -221,9 +264,15 @@ int main(int argc, char **argv) {
     if (pos.size() < 3) {
       std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
-                   "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
+                   "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
+                   "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
       return 1;
     }
+    if ((scale_given || !log_priors_file.empty() || score_dtype != WFST_DTYPE_F32) && !device_chunks) {
+      std::cerr << "--acoustic-scale / --log-priors / --score-dtype go with --device-chunks (without it the matrices are finished scores)\n";
+      return 1;
+    }
+    if (device_chunks && (chunk <= 0 || single || n_threads > 0)) { std::cerr << "--device-chunks goes with --chunk=N and the batch shape\n"; return 1; }
     if (word_times && n_threads > 0) { std::cerr << "--word-times goes with the batch shape or --single-stream\n"; return 1; }
     if (!wt_silence.empty() && (!word_times || tid2phone_file.empty())) { std::cerr << "--silence-phones goes with --word-times and --tid2phone=FILE\n"; return 1; }
     LatticeFasterDecoderConfig opt;
@@ -348,6 +397,13 @@ int main(int argc, char **argv) {
 
     std::vector<Utt> utts;
     for (Utt u; ReadUtt(in, &u);) utts.push_back(u);
+    std::vector<float> log_priors;   // --log-priors
+    if (!log_priors_file.empty()) {
+      std::ifstream pf(log_priors_file, std::ios::binary);
+      if (!pf) throw std::runtime_error("cannot open " + log_priors_file);
+      for (float v; pf.read((char *)&v, 4);) log_priors.push_back(v);
+      if (log_priors.empty()) throw std::runtime_error(log_priors_file + ": no log priors");
+    }
     if (ragged > 0)
       for (size_t i = 0; i < utts.size(); ++i) {
         const unsigned h = (unsigned)(i * 2654435761u) >> 8;   // (Knuth's multiplicative hash of the position)
@@ -655,6 +711,11 @@ int main(int argc, char **argv) {
                                                           : new GpuBatchDecoder(wf, opt, batch, &limits));  // its own stream
           GpuBatchDecoder &decode = *decode_p;
           if (word_times) decode.SetSilencePhones(wt_silence);
+          if (device_chunks) decode.SetScoreTransform(acoustic_scale, log_priors);
+          // --device-chunks: a chunk of every channel's rows in the score dtype, page-locked (the device reads it where it lies)
+          const size_t elem = score_dtype == WFST_DTYPE_F32 ? 4 : 2;
+          std::unique_ptr<void, void (*)(void *)> stage(nullptr, wfst_host_free);
+          size_t stage_per = 0;
           for (;;) {
             // one device: the next batch nobody has taken; several: batch b belongs to device b mod n_dev (its workers share them)
             const size_t b = n_dev == 1 ? next.fetch_add(1) : (size_t)di + (size_t)n_dev * next_of_dev[(size_t)di].fetch_add(1);
@@ -672,7 +733,33 @@ int main(int argc, char **argv) {
             }
             BatchOut &o = outs[b];
             decode.InitDecoding(ch);
-            decode.AdvanceDecodingHost(ch, rows, ready, stride);
+            if (device_chunks) {
+              if (!log_priors.empty() && (int)log_priors.size() != stride) throw std::runtime_error("--log-priors: one prior per column of the matrices");
+              if ((size_t)chunk * stride * elem > stage_per) {
+                stage_per = (((size_t)chunk * stride * elem) + 15) & ~(size_t)15;
+                stage.reset(wfst_host_alloc(stage_per * (size_t)batch));
+                if (!stage) throw std::runtime_error("--device-chunks: no page-locked staging buffer");
+              }
+              int longest = 0;
+              for (int i = 0; i < n; ++i) longest = std::max(longest, ready[i]);
+              std::vector<const void *> ptrs(n);
+              std::vector<int> fresh(n);
+              for (int have = 0; have < longest; have += chunk) {
+                for (int i = 0; i < n; ++i) {
+                  fresh[i] = std::max(0, std::min(chunk, ready[i] - have));
+                  char *dst = (char *)stage.get() + stage_per * (size_t)i;
+                  ptrs[i] = fresh[i] ? dst : nullptr;
+                  const float *src = rows[i] + (size_t)have * stride;
+                  const size_t cnt = (size_t)fresh[i] * stride;
+                  if (score_dtype == WFST_DTYPE_F32) memcpy(dst, src, cnt * 4);
+                  else for (size_t e = 0; e < cnt; ++e) ((uint16_t *)dst)[e] = score_dtype == WFST_DTYPE_F16 ? ToF16(src[e]) : ToBf16(src[e]);
+                }
+                decode.AdvanceDecodingChunk(ch, ptrs, fresh, score_dtype, stride, WFST_STREAM_NONE);
+                if (wfst_decoder_sync(decode.Handle()) != WFST_OK) throw std::runtime_error(wfst_last_error());   // (the staging buffer is the next chunk's)
+              }
+            } else {
+              decode.AdvanceDecodingHost(ch, rows, ready, stride);
+            }
             decode.FinalizeDecoding(ch);
             if (want_lattice && determinize && !second) decode.PrefetchLattices();   // the determinizer runs beside the best paths
             decode.GetBestPaths(ch, &o.best, &o.ok);

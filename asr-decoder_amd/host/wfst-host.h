@@ -496,6 +496,15 @@ class GpuBatchDecoder {
                        const std::vector<int> &num_frames_ready, int stride, int max_num_frames = -1);
   void AdvanceDecodingHost(const std::vector<int> &channels, const std::vector<const float *> &host_loglikes,
                            const std::vector<int> &num_frames_ready, int stride, int max_num_frames = -1);
+  // Chunks of the acoustic model's raw output, on the device and in its own precision (wfst_decoder_advance_chunk): entry i appends
+  // num_new_frames[i] rows of n_cols elements of dtype (WFST_DTYPE_*) starting at device_rows[i], row_pitch[i] elements apart (empty:
+  // n_cols), to the channel's utterance as (x - log_priors[j]) * acoustic_scale -- SetScoreTransform, the reference's
+  // --acoustic-scale and prior layer (kaldi-nnet3bin/kaldi-hclg-my-decoder.cc:37-41,107; nnet/nnet-layer.cc:30) -- and decodes.
+  // producer_stream: the hipStream_t whose work writes the rows (nullptr: the default stream; WFST_STREAM_NONE: they are complete).
+  void SetScoreTransform(float acoustic_scale, const std::vector<float> &log_priors = std::vector<float>());
+  void AdvanceDecodingChunk(const std::vector<int> &channels, const std::vector<const void *> &device_rows,
+                            const std::vector<int> &num_new_frames, int dtype, int n_cols, void *producer_stream = nullptr,
+                            const std::vector<int64_t> &row_pitch = std::vector<int64_t>(), int max_num_frames = -1);
   void FinalizeDecoding(const std::vector<int> &channels = std::vector<int>());
   int NumFramesDecoded(int channel) const;
   bool GetBestPath(int channel, Lattice *ofst, bool use_final_probs = true);

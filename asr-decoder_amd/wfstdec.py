@@ -17,6 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libwfstdec%s.so" % (("_" + os.environ["WFST_LIB_VARIANT"]) if os.environ.get("WFST_LIB_VARIANT") else ""))
 
 WFST_OK = 0
+# wfst_decoder_advance_chunk: element types of a chunk, and "no producer stream" (the rows are complete)
+WFST_DTYPE_F32, WFST_DTYPE_F16, WFST_DTYPE_BF16 = 0, 1, 2
+WFST_STREAM_NONE = C.c_void_p(-1).value
 ERR_NAMES = {-1: "WFST_E_ARG", -2: "WFST_E_IO", -3: "WFST_E_DEVICE", -4: "WFST_E_CAPACITY",
              -5: "WFST_E_STATE", -6: "WFST_E_FORMAT"}
 
@@ -40,6 +43,7 @@ SYMBOLS = [
     "wfst_decoder_partial_enqueue", "wfst_decoder_partial_ready", "wfst_decoder_partial_fetch", "wfst_decoder_get_partial",
     "wfst_decoder_set_silence_phones", "wfst_decoder_words_enqueue", "wfst_decoder_words_ready", "wfst_decoder_words_fetch",
     "wfst_decoder_get_words",
+    "wfst_decoder_set_score_transform", "wfst_decoder_advance_chunk", "wfst_decoder_get_scores",
 ]
 
 
@@ -246,6 +250,15 @@ def _f32(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _chunk_dtype(dt):
+    """WFST_DTYPE_* of a torch / numpy dtype (by name: the tensors of advance_chunk are duck-typed)."""
+    name = str(dt).split(".")[-1]
+    try:
+        return {"float32": WFST_DTYPE_F32, "float16": WFST_DTYPE_F16, "half": WFST_DTYPE_F16, "bfloat16": WFST_DTYPE_BF16}[name]
+    except KeyError:
+        raise ValueError("chunks must be float32, float16 or bfloat16, not %s" % (dt,))
+
+
 def device_count():
     return int(lib().wfst_device_count())
 
@@ -349,6 +362,7 @@ class BatchDecoder:
                                                old_lm.h if old_lm is not None else None, new_lm.h if new_lm is not None else None,
                                                C.c_void_p(stream) if stream else None, C.byref(h)))
         self.h = h
+        self._score_cols = 0   # columns of a row of the library-held history (scores())
 
     def free(self):
         if self.h:
@@ -383,7 +397,62 @@ class BatchDecoder:
         assert all(m.shape[1] == stride for m in mats)
         ptrs = (C.c_void_p * cnt)(*[m.ctypes.data for m in mats])
         nr = np.ascontiguousarray(n_frames_ready, dtype=np.int32)
+        self._score_cols = stride
         _check(lib().wfst_decoder_advance_host(self.h, _i32(ch), n, ptrs, _i32(nr), stride, int(max_num_frames)))
+
+    def set_score_transform(self, acoustic_scale=1.0, log_priors=None):
+        """What advance_chunk makes of a raw value x in column j: (float32(x) - log_priors[j]) * acoustic_scale
+        (wfst_decoder_set_score_transform).  Not while an utterance holds ingested frames."""
+        pri = None if log_priors is None else np.ascontiguousarray(log_priors, dtype=np.float32).reshape(-1)
+        _check(lib().wfst_decoder_set_score_transform(self.h, C.c_float(acoustic_scale), _f32(pri), 0 if pri is None else int(pri.shape[0])))
+
+    def advance_chunk(self, chunks, channels=None, max_num_frames=-1, stream="current"):
+        """Hands the NEW rows of each listed channel over where the acoustic model left them (wfst_decoder_advance_chunk).
+        chunks: per listed channel a 2-D device tensor [new frames][n_cols] -- anything with data_ptr(), shape, stride() and
+        dtype; float32, float16 or bfloat16, the last dimension contiguous, one dtype and width for all -- or None (no rows).
+        stream: "current" = torch's current stream, whose enqueued work writes the rows; a raw hipStream_t (int); None = the
+        rows are complete and kept by the caller until sync() or a getter (WFST_STREAM_NONE)."""
+        ch, n = self._chan(channels)
+        cnt = n if ch is not None else self.n
+        chunks = list(chunks)
+        assert len(chunks) == cnt
+        dtype = cols = None
+        ptrs, nf, pitch = (C.c_void_p * cnt)(), np.zeros(cnt, np.int32), np.zeros(cnt, np.int64)
+        for i, t in enumerate(chunks):
+            if t is None:
+                continue
+            if len(t.shape) != 2:
+                raise ValueError("chunk %d is not 2-D" % i)
+            dt = _chunk_dtype(t.dtype)
+            if dtype is None:
+                dtype, cols = dt, int(t.shape[1])
+            if dt != dtype or int(t.shape[1]) != cols:
+                raise ValueError("chunks differ in dtype or width")
+            if int(t.shape[0]) == 0:
+                continue
+            st = t.stride()
+            if cols > 1 and int(st[1]) != 1:
+                raise ValueError("the last dimension of chunk %d is not contiguous" % i)
+            ptrs[i] = int(t.data_ptr())
+            nf[i] = int(t.shape[0])
+            pitch[i] = int(st[0]) if int(t.shape[0]) > 1 else max(int(st[0]), cols)
+        if dtype is None:
+            raise ValueError("no chunk to take the dtype and width from")
+        pitch[nf == 0] = cols
+        if stream == "current":
+            import torch
+            stream = int(torch.cuda.current_stream().cuda_stream)
+        elif stream is None:
+            stream = WFST_STREAM_NONE
+        self._score_cols = cols
+        _check(lib().wfst_decoder_advance_chunk(self.h, _i32(ch), n, ptrs, _i32(nf), pitch.ctypes.data_as(C.POINTER(C.c_int64)), dtype, cols,
+                                                C.c_void_p(int(stream)), int(max_num_frames)))
+
+    def scores(self, channel, first_frame, n_frames):
+        """Rows of the channel's library-held score history as float32 [n_frames][n_cols] (wfst_decoder_get_scores); for tests."""
+        out = np.empty((int(n_frames), self._score_cols), np.float32)
+        _check(lib().wfst_decoder_get_scores(self.h, int(channel), int(first_frame), int(n_frames), _f32(out)))
+        return out
 
     def finalize(self, channels=None):
         ch, n = self._chan(channels)

@@ -674,6 +674,62 @@ int wfst_decoder_get_words(wfst_decoder *d, const int32_t *channels, int32_t n, 
  * wfst_decoder_set_endpoint_config sets this list too.  WFST_E_STATE while a words request is outstanding. */
 int wfst_decoder_set_silence_phones(wfst_decoder *d, const int32_t *phones, int32_t n);
 
+/* ---- acoustic-model chunks ingested on the device: f16 / bf16 / f32 rows, acoustic scale, log priors ---------------------------
+ * What the reference's decodable does between the network and the search: the CLI's --acoustic-scale (default 0.1) and
+ * DecodableMatrixScaledMapped(trans_model, loglikes, acoustic_scale) (kaldi-nnet3bin/kaldi-hclg-my-decoder.cc:37-41,107); its own
+ * network's decodable returns `_acoustic_scale * output[...]` (nnet/nnet-nnet.h:212-232) behind the prior layer's
+ * AddVecToRows(out, frames, cols, _log_priors, -1.0, 1.0) (nnet/nnet-layer.cc:30, nnet/nnet-nnet.cc:156-164).  An acoustic model on
+ * the same device hands over one chunk of rows per step, in its own precision, and keeps nothing:
+ *
+ *   hist[have + r][j] = (float(x[r][j]) - log_priors[j]) * acoustic_scale
+ *
+ * computed in float32 as written (no FMA), where `have` is the number of frames the channel's history held before the call.
+ * Without priors nothing is subtracted, with acoustic_scale == 1.0f nothing is multiplied (float32 in, neither: a bit copy);
+ * float16 -> float32 and bfloat16 -> float32 are exact, denormals kept.
+ *
+ * wfst_decoder_set_score_transform: the transform of every later chunk (default: scale 1, no priors).  log_priors (host, n_cols
+ * floats) are copied to the device; NULL with n_cols == 0 clears them.  WFST_E_STATE while a channel holds frames of an
+ * unfinished utterance in its history (a transform does not change mid-utterance); WFST_E_ARG: n_cols < 0, priors without
+ * n_cols > 0 or n_cols without priors, a scale that is not finite.
+ *
+ * wfst_decoder_advance_chunk: for listed channel channels[i] (NULL: all), rows[i] is a DEVICE pointer to the first of
+ * n_new_frames[i] NEW rows of n_cols elements of `dtype`, row_pitch[i] elements apart (NULL: n_cols); 0 rows are allowed and
+ * rows[i] may then be NULL.  The rows go into the decoder-owned history wfst_decoder_advance_host fills (same allocation, same
+ * regrowth; wfst_decoder_init resets a channel) with a stride of n_cols rounded up to a multiple of 4, pad columns written as 0;
+ * a channel may be fed by both calls in one utterance only if the strides agree.  Then AdvanceDecoding(max_num_frames) as in
+ * wfst_decoder_advance (0: ingest only).  Returns when everything is ENQUEUED.
+ * Ordering: producer_stream is the hipStream_t whose enqueued work writes the rows (NULL: the legacy default stream).  The library
+ * records an event on it; the ingest runs behind that event on the decoder's upload stream -- not on the decode stream, so the
+ * model's next forward pass never waits for a search -- and both the decode stream and producer_stream wait for the ingest:
+ * whatever the caller enqueues on producer_stream after the call may overwrite the chunk buffers (a caller that reuses them from
+ * elsewhere synchronises itself).  WFST_STREAM_NONE: the rows are complete and the caller keeps them until wfst_decoder_sync or
+ * a getter; no event touches a caller stream.  The chunk buffers are never read again after the ingest: the "rows must stay valid
+ * until the next init" contract of wfst_decoder_advance does not apply.
+ * WFST_E_ARG, before any device work: unknown dtype; n_cols <= 0, not above the graph's largest log-likelihood column, or not
+ * the priors' n_cols; a pitch below n_cols; a negative n_new_frames; a pointer not aligned to its element size; a bad or
+ * duplicate channel list; a NULL row pointer with frames to append; a stride other than that of the frames the histories hold.
+ * WFST_E_STATE: a channel not initialised or already finalized.  WFST_E_CAPACITY, before any work is enqueued:
+ * have + n_new_frames[i] > wfst_limits.max_frames.
+ *
+ * wfst_decoder_get_scores: rows [first_frame, first_frame + n_frames) of the channel's library-held history, n_cols floats each
+ * (the n_cols of the chunk call; the stride of wfst_decoder_advance_host), copied to the host behind the channel's ingests -- for
+ * tests and debugging, like wfst_decoder_get_frontier.  WFST_E_STATE: the channel reads the caller's own matrix
+ * (wfst_decoder_advance); WFST_E_ARG: a range outside the frames held. */
+#define WFST_DTYPE_F32 0
+#define WFST_DTYPE_F16 1   /* IEEE binary16 */
+#define WFST_DTYPE_BF16 2
+#define WFST_STREAM_NONE ((void *)(intptr_t)-1)
+
+int wfst_decoder_set_score_transform(wfst_decoder *d, float acoustic_scale, const float *log_priors /* host, n_cols floats, or NULL */,
+                                     int32_t n_cols);
+int wfst_decoder_advance_chunk(wfst_decoder *d, const int32_t *channels, int32_t n,
+                               const void *const *rows,        /* [n] DEVICE pointer to the first NEW row of entry i */
+                               const int32_t *n_new_frames,    /* [n] rows appended to entry i's utterance (0 allowed, rows[i] may then be NULL) */
+                               const int64_t *row_pitch,       /* [n] elements between rows; NULL: n_cols */
+                               int32_t dtype, int32_t n_cols, void *producer_stream, int32_t max_num_frames);
+int wfst_decoder_get_scores(wfst_decoder *d, int32_t channel, int32_t first_frame, int32_t n_frames,
+                            float *out /* host, [n_frames][n_cols] */);
+
 #ifdef __cplusplus
 }
 #endif
