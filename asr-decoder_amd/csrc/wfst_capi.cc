@@ -19,6 +19,7 @@
 #include "wfst_hip_own.h"
 #include "wfst_capi_words.h"
 #include "wfst_capi_ingest.h"
+#include "wfst_capi_nbwords.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -276,6 +277,7 @@ struct wfst_decoder {
   DevBuf<uint32_t> sil_bits;
   WordsState wd;   // wfst_decoder_words_enqueue / _ready / _fetch (wfst_capi_words.cc)
   IngestState ing; // wfst_decoder_set_score_transform / _advance_chunk / _get_scores (wfst_capi_ingest.cc)
+  NbWordsState nbw; // wfst_decoder_get_nbest_words (wfst_capi_nbwords.cc)
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
   int32_t hist_slab_stride = 0;        // ... of this many floats
@@ -3439,6 +3441,142 @@ int words_begin(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use
                                     use_final_probs ? nullptr : "You cannot call FinalizeDecoding() and then GetBestPath with use_final_probs == false");
   if (rc != WFST_OK) return rc;
   return results_stream_behind(d, channels, n, st);   // behind these channels' own work only (see mark_ev)
+}
+
+// What wfst_capi_nbwords.cc -- wfst_decoder_get_nbest_words, the entry point that launches nbest_words_kernel -- needs of a decoder.
+int nbw_begin(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t n_paths, const wfst_lm *old_lm, const wfst_lm *new_lm,
+              int32_t cap_words, int32_t *slots, NbWordsState **ws, hipStream_t *stream) {
+  if (!d || !channels) return fail(WFST_E_ARG, "NULL decoder / channel list");
+  if ((old_lm == nullptr) != (new_lm == nullptr)) return fail(WFST_E_ARG, "bad argument (both LMs or neither)");
+  if (n_paths < 1 || n_paths > 64) return fail(WFST_E_ARG, "1 <= n <= 64 paths (more: wfst_decoder_get_nbest_paths)");
+  if (cap_words <= 0) return fail(WFST_E_ARG, "cap_words <= 0");
+  if (old_lm && (old_lm->device != d->device || new_lm->device != d->device)) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
+  if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
+  if (!d->D.lattice) return fail(WFST_E_STATE, "GetNbestTxt needs a decoder created with wfst_limits.lattice_links > 0");
+  int rc = check_channel_list(d, channels, n, "GetNbestTxt", nullptr);
+  if (rc != WFST_OK) return rc;
+  HIP_TRY(hipSetDevice(d->device));
+  rc = ensure_det_workspace(d);
+  if (rc != WFST_OK) return rc;
+  rc = finish_prefetch(d);   // (the workspace slots are the prefetch's until it is harvested)
+  if (rc != WFST_OK) return rc;
+  *slots = std::max(1, std::min(d->det_slots, 128));
+  *ws = &d->nbw;
+  *stream = d->stream;
+  return WFST_OK;
+}
+int nbw_channel_state(const wfst_decoder *d, int32_t channel) { return d->h_state[(size_t)channel]; }
+int nbw_det_slots(wfst_decoder *d, int32_t *slots, int64_t *bytes_per_slot) {
+  if (!d) return fail(WFST_E_ARG, "NULL decoder");
+  if (!d->D.lattice) return fail(WFST_E_STATE, "GetLattice needs a decoder created with wfst_limits.lattice_links > 0");
+  HIP_TRY(hipSetDevice(d->device));
+  const int rc = ensure_det_workspace(d);
+  if (rc != WFST_OK) return rc;
+  if (slots) *slots = d->det_slots;
+  if (bytes_per_slot) *bytes_per_slot = d->det.words_per_channel * 4 + (int64_t)d->det.out_cap * (int64_t)(sizeof(int4) + sizeof(float2));
+  return WFST_OK;
+}
+
+int nbw_round(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_final_probs, const wfst_lm *old_lm, const wfst_lm *new_lm,
+              int32_t n_paths, std::vector<int32_t> *status, NbPathsDev *Pout) {
+  const int32_t cnt = (int32_t)list.size();
+  status->assign((size_t)cnt, WFST_OK);
+  std::vector<int32_t> live;
+  for (int c : list)
+    if (d->h_state[(size_t)c] == 1) live.push_back(c);
+  // GetLattice: list[i]'s determinized lattice into workspace slot i -- unless the slots hold these very lattices already (finalized
+  // channels: a prefetch harvested just before, or the last batched call).  Nothing is fetched into the host caches here, so what
+  // they hold of these channels (det_cache / det_live_nd, resc_cache, nbp_cache) stays what it was: the host copies do not depend
+  // on the slots.
+  std::vector<int32_t> dres;
+  if (live.empty() && slots_hold(d, list)) {
+    dres = d->post_dev_dres;
+  } else {
+    const int32_t *dev;
+    int32_t dcnt;
+    int rc;
+    if (!live.empty()) {
+      rc = stage_channels(d, live.data(), (int32_t)live.size(), &dev, &dcnt);
+      if (rc != WFST_OK) return rc;
+      launch_lattice_emit(d->D, dev, dcnt, use_final_probs ? 1 : 0, d->stream);
+    }
+    rc = stage_channels(d, list.data(), cnt, &dev, &dcnt);   // (in stream order behind the emit launch that reads the live list)
+    if (rc != WFST_OK) return rc;
+    d->post_dev_list.clear();   // (the slots are about to hold other lattices than the last batched call's)
+    launch_determinize(d->D, d->det, dev, cnt, d->stream);
+    HIP_TRY(hipGetLastError());
+    dres.resize((size_t)cnt * 4);
+    HIP_TRY(hipMemcpyAsync(dres.data(), d->det.result, dres.size() * 4, hipMemcpyDeviceToHost, d->stream));
+    rc = read_ctl(d);  // synchronises the stream
+    if (rc != WFST_OK) return rc;
+    bool all_held = live.empty();
+    for (int i = 0; i < cnt; ++i) {
+      const int32_t e = d->p_ctl.p[list[(size_t)i]].error;
+      if (e) (*status)[(size_t)i] = fail_ctl_error(list[(size_t)i], e);   // a device error of THIS channel's utterance
+      if (e || dres[(size_t)4 * i + 2]) all_held = false;
+    }
+    if (all_held) hold_slots(d, list, dres);
+  }
+  for (int i = 0; i < cnt; ++i)
+    if ((*status)[(size_t)i] == WFST_OK && dres[(size_t)4 * i + 2]) (*status)[(size_t)i] = det_error(d, list[(size_t)i], dres[(size_t)4 * i + 2]);
+  std::vector<int32_t> cres;
+  if (old_lm) {
+    const bool det_held = slots_hold(d, list);   // (and their composition under these very LMs?)
+    if (det_held && d->post_dev_o == old_lm && d->post_dev_n == new_lm && d->post_dev_cres.size() == (size_t)cnt * 4) {
+      cres = d->post_dev_cres;
+    } else {
+      cres.resize((size_t)cnt * 4);
+      const int rc = compose_slots(d, old_lm, new_lm, cnt, cres.data());
+      if (rc != WFST_OK) return rc;
+      bool ok = true;
+      for (int i = 0; i < cnt; ++i)
+        if (cres[(size_t)4 * i + 2] != 0) {
+          ok = false;
+          if ((*status)[(size_t)i] == WFST_OK)
+            (*status)[(size_t)i] = fail(WFST_E_CAPACITY, "channel " + std::to_string(list[(size_t)i]) + ": the composed lattice outgrew the composition workspace (" +
+                                                             std::to_string(d->cmp.pair_cap) + " states / " + std::to_string(d->cmp.arc_cap) + " arcs)");
+        }
+      if (det_held && ok) { d->post_dev_cres = cres; d->post_dev_o = old_lm; d->post_dev_n = new_lm; }
+    }
+  }
+  const std::vector<int32_t> &lres = old_lm ? cres : dres;
+  NbPathsDev P = {};
+  P.a = old_lm ? d->cmp.out_a : d->det.out_a;
+  P.w = old_lm ? d->cmp.out_w : d->det.out_w;
+  P.res = old_lm ? d->cmp.result : d->det.result;
+  P.fin = old_lm ? d->cmp.out_fin : nullptr;
+  P.in_stride = old_lm ? d->cmp.arc_cap : d->det.out_cap;
+  P.fin_stride = old_lm ? d->cmp.pair_cap : 0;
+  // NShortestPath's workspace: the largest lattice of the round times the round, within the batch's bounds (a lattice beyond
+  // them reports a capacity of its own: nbest_paths_kernel checks its workspace per slot)
+  int32_t ns_max = 1, na_max = 1;
+  for (int i = 0; i < cnt; ++i) {
+    if ((*status)[(size_t)i] != WFST_OK) continue;
+    if ((int64_t)lres[(size_t)4 * i + 1] > P.in_stride) {
+      (*status)[(size_t)i] = fail(WFST_E_CAPACITY, "channel " + std::to_string(list[(size_t)i]) + ": more arcs than the lattice's slot holds");
+      continue;
+    }
+    ns_max = std::max(ns_max, lres[(size_t)4 * i]);
+    na_max = std::max(na_max, lres[(size_t)4 * i + 1]);
+  }
+  const NbestBounds &b = kNbestBatch;
+  P.n = n_paths;
+  P.ws_ints = nbest_ws_ints(ns_max, na_max);
+  P.list_cap = std::min<int64_t>((int64_t)ns_max * n_paths + 1, b.list_cap);
+  P.out_cap = (int32_t)std::min<int64_t>((int64_t)n_paths * ns_max, b.out_cap);
+  auto grow = [&](auto &buf, int64_t need) -> bool { return (int64_t)buf.n >= need || buf.alloc((size_t)need) == hipSuccess; };
+  if (!grow(d->np_ws, P.ws_ints * cnt) || !grow(d->np_lists, P.list_cap * cnt) || !grow(d->np_arcs, (int64_t)P.out_cap * cnt) ||
+      !grow(d->np_off, (int64_t)(n_paths + 1) * cnt) || !grow(d->np_tot, (int64_t)n_paths * cnt) || !grow(d->np_out, 4ll * cnt)) {
+    (void)hipGetLastError();
+    return fail(WFST_E_CAPACITY, "n-best: no device memory for the path workspace of " + std::to_string(cnt) + " lattice(s), " +
+                                     std::to_string(n_paths) + " paths each: " + b.fallback);
+  }
+  P.ws = d->np_ws.p; P.lists = d->np_lists.p;
+  P.out = d->np_out.p; P.out_off = d->np_off.p; P.out_tot = d->np_tot.p; P.out_arcs = d->np_arcs.p;
+  launch_nbest_paths(P, cnt, d->stream, ns_max <= b.small_states ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  *Pout = P;
+  return WFST_OK;
 }
 
 // What wfst_capi_ingest.cc -- the entry points that launch ingest_kernel -- needs of a decoder.

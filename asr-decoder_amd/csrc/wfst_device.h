@@ -448,6 +448,10 @@ struct NbPathsDev {
   int32_t out_cap;
 };
 void launch_nbest_paths(const NbPathsDev &P, int n_slots, hipStream_t s, int small = 0);   // small: one wave per lattice (lattices of a few hundred states, short lists)
+// the text of the paths a launch_nbest_paths over n_slots lattices left in P's buffers (nbest_words_kernel): packed = [n_slots][4] the
+// slots' result words (P.out), then per (slot, path) kNbWordsHead ints {n_words, tot bits, lm bits, path cost bits} + cap_words words
+constexpr int32_t kNbWordsHead = 4;
+void launch_nbest_words(const NbPathsDev &P, int n_slots, int cap_words, int32_t *packed, hipStream_t s);
 
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as

@@ -578,6 +578,68 @@ __global__ __launch_bounds__(kNpThreads) void nbest_paths_kernel(NbPathsDev P) {
   }
 }
 
+// ---- nbest_words_kernel: the paths nbest_paths_kernel left in its workspace as TEXT -----------------------------------------
+// OnebestLatticeToString per path (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:107-121 = LatticeToVector, newfst/lattice-functions.cc:
+// 179-217): the non-zero olabels of the path's arcs in order, tot += graph + acoustic and lm += graph in arc order.  Grid (lattice
+// slot, path), one wave per path: the path's arc indices in tiles of 64 (coalesced), the arcs they name gathered, the words compacted
+// by a ballot and a prefix rank with the running count carried across tiles, the two sums kept arc by arc (every lane adds the
+// tile's costs in the same order, read lane by lane; no tree reduction: the sums must round as the host's loop does).
+// packed: [n_slots][4] the slots' result words {paths found, arcs on them, status, -}, then per (slot, path) kNbWordsHead ints
+// {n_words (-1: an index outside the lattice), tot bits, lm bits, path cost bits} and cap_words words.
+__global__ __launch_bounds__(64) void nbest_words_kernel(NbPathsDev P, int cap_words, int32_t *packed) {
+  const int slot = blockIdx.x, path = blockIdx.y, lane = threadIdx.x;
+  const int n_slots = gridDim.x;
+  const int32_t *out = P.out + 4 * (size_t)slot;
+  int32_t *rec = packed + 4 * (size_t)n_slots + ((size_t)slot * P.n + path) * ((size_t)kNbWordsHead + cap_words);
+  if (path == 0 && lane < 4) packed[4 * (size_t)slot + lane] = out[lane];
+  const int found = out[2] == 0 ? out[0] : 0;
+  const int32_t *off = P.out_off + (size_t)slot * (P.n + 1);
+  const int total = min(out[1], P.out_cap);
+  int b = 0, e = 0;
+  if (path < found) { b = off[path]; e = off[path + 1]; }
+  const bool bad_range = b < 0 || e < b || e > total;
+  if (path >= found || bad_range) {
+    if (lane < kNbWordsHead) rec[lane] = (lane == 0 && path < found) ? -1 : 0;
+    return;
+  }
+  const int na = (int)min((int64_t)P.res[4 * (size_t)slot + 1], P.in_stride);
+  const int32_t *arcs = P.out_arcs + (size_t)slot * P.out_cap;
+  const int4 *A = P.a + (size_t)slot * P.in_stride;
+  const float2 *W = P.w + (size_t)slot * P.in_stride;
+  int nw = 0;
+  bool bad = false;
+  float tot = 0.0f, lm = 0.0f;
+  for (int base = b; base < e; base += 64) {
+    const int k = base + lane;
+    const int arc = k < e ? arcs[k] : -1;
+    const bool ok = k < e && arc >= 0 && arc < na;
+    if (k < e && !ok) bad = true;
+    const int word = ok ? A[arc].z : 0;
+    const float2 w = ok ? W[arc] : make_float2(0.0f, 0.0f);
+    const u64 m = __ballot(word != 0);
+    const int at = nw + __popcll(m & ((1ull << lane) - 1ull));
+    if (word != 0 && at < cap_words) rec[kNbWordsHead + at] = word;
+    nw += __popcll(m);
+    const int cnt = min(64, e - base);
+    for (int j = 0; j < cnt; ++j) {
+      const float g = __shfl(w.x, j, 64), a = __shfl(w.y, j, 64);
+      lm += g;
+      tot += g + a;
+    }
+  }
+  bad = __ballot(bad) != 0;
+  if (lane == 0) {
+    rec[0] = bad ? -1 : nw;
+    rec[1] = __float_as_int(tot);
+    rec[2] = __float_as_int(lm);
+    rec[3] = __float_as_int(P.out_tot[(size_t)slot * P.n + path]);
+  }
+}
+
+void launch_nbest_words(const NbPathsDev &P, int n_slots, int cap_words, int32_t *packed, hipStream_t s) {
+  hipLaunchKernelGGL(nbest_words_kernel, dim3(n_slots, P.n), dim3(64), 0, s, P, cap_words, packed);
+}
+
 void launch_nbest_paths(const NbPathsDev &P, int n_slots, hipStream_t s, int small) {
   if (small) hipLaunchKernelGGL(nbest_paths_kernel<64>, dim3(n_slots), dim3(64), 0, s, P);
   else hipLaunchKernelGGL(nbest_paths_kernel<1024>, dim3(n_slots), dim3(1024), 0, s, P);

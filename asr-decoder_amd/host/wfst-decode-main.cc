@@ -26,6 +26,10 @@
 //                  GetPartialWords -- the incremental form, whose device work follows the frames since the last commit, not the
 //                  utterance -- and is printed as "KEY@frames n_stable word-ids...": the first n_stable words are final (the partial
 //                  n-best lines of --nbest follow it as they follow the plain partial line)
+//   --partial-nbest=K  with --chunk=N, in every shape (--single-stream, --threads=N [--pool=M], the batch shape): after every chunk
+//                  but the last, per stream, the service's per-chunk GetNbestTxt (GetNbestWords: wfst_decoder_get_nbest_words, one
+//                  list call for the streams that ask together) as "KEY@frames nbest k: word-ids... tot=.. lm=.." per path, over the
+//                  second-pass lattice with --second-lm-old/--second-lm-new; a stream's own failure: "KEY@frames nbest status=code"
 //   --word-times [--silence-phones=a:b:c]  batch shape and --single-stream: after an utterance's "KEY word-ids..." line one line
 //                  "KEY#k word begin end" per word -- the frames of GetWords (wfst_decoder_get_words: the word's label-carrying
 //                  arc, and the next word's begin or, with silence phones and --tid2phone=FILE, one past the word's last frame
@@ -186,7 +190,7 @@ int main(int argc, char **argv) {
     bool single = false, determinize = false;
     std::string lattice_file, lattice_text;
     long long lattice_links = 1ll << 22;
-    int nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
+    int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
     bool pull = false, partial_words = false, word_times = false;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
@@ -230,6 +234,7 @@ int main(int argc, char **argv) {
         else { std::cerr << "--score-dtype is f32, f16 or bf16\n"; return 1; }
       }
       else if (a == "--partial-words") partial_words = true;
+      else if (a.compare(0, 16, "--partial-nbest=") == 0) partial_nbest = atoi(a.c_str() + 16);
       else if (a == "--word-times") word_times = true;
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
@@ -262,7 +267,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -287,6 +292,10 @@ int main(int argc, char **argv) {
     }
     if (partial_words && (!(single || n_threads > 0) || chunk <= 0 || endpointing || !lm_old_file.empty())) {
       std::cerr << "--partial-words goes with --chunk=N and --single-stream or --threads=N (no endpointing, no --lm-old/--lm-new)\n";
+      return 1;
+    }
+    if (partial_nbest != 0 && (partial_nbest < 1 || partial_nbest > 64 || chunk <= 0 || endpointing || device_chunks || !lm_old_file.empty())) {
+      std::cerr << "--partial-nbest=K (1..64) goes with --chunk=N (no endpointing, no --device-chunks, no --lm-old/--lm-new)\n";
       return 1;
     }
     if (single && devices.size() > 1) { std::cerr << "--devices lists several devices: batch shape only\n"; return 1; }
@@ -329,7 +338,7 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0;
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0;
     auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths) {
       for (size_t k = 0; k < paths.size(); ++k) {
         std::vector<int> words, phones;
@@ -373,6 +382,21 @@ int main(int argc, char **argv) {
     const bool exact_nbest = !nbest_lattice_file.empty() || second || nbest > 16;
     wfst_limits limits = {0, 0, 0, 0, 0};  // zeros = the library defaults
     limits.lattice_links = want_lattice ? lattice_links : 0;
+    // --partial-nbest: "key@frames nbest k: w1 w2 ... tot=.. lm=.." per path, or "key@frames nbest status=code" for a channel's own failure
+    auto nbest_lines = [](const std::string &key, int frames, int status, const std::vector<std::vector<int> > &w, const std::vector<float> &t,
+                          const std::vector<float> &l) {
+      std::string o;
+      const std::string head = key + "@" + std::to_string(frames) + " nbest ";
+      if (status != WFST_OK) o += head + "status=" + std::to_string(status) + "\n";
+      for (size_t k = 0; k < w.size(); ++k) {
+        o += head + std::to_string(k + 1) + ":";
+        for (int x : w[k]) o += " " + std::to_string(x);
+        char buf[64];
+        snprintf(buf, sizeof(buf), " tot=%.9g lm=%.9g\n", (double)t[k], (double)l[k]);
+        o += buf;
+      }
+      return o;
+    };
     // (--max-frames / --max-tokens / --arena-tokens: wfst_limits as the caller sizes them; 0 = the library's defaults)
     limits.max_frames = max_frames;
     limits.max_tokens_per_frame = (int32_t)max_tokens_per_frame;
@@ -558,6 +582,13 @@ int main(int argc, char **argv) {
                     o += "\n";
                   }
                 }
+                if (partial_nbest > 0) {   // (over the pool: one list call per batcher pass for all the threads that ask the same)
+                  std::vector<std::vector<int> > w;
+                  std::vector<float> t, l;
+                  int st = WFST_OK;
+                  dp->GetNbestWords(&w, &t, &l, partial_nbest, false, slm1p, slm2p, &st);
+                  if (first_pass) res[ui].partials += nbest_lines(u.key, decode.NumFramesDecoded(), st, w, t, l);
+                }
               }
             } else {
               decode.AdvanceDecoding(am);
@@ -658,6 +689,13 @@ int main(int argc, char **argv) {
                 out << "\n";
               }
             }
+            if (partial_nbest > 0) {
+              std::vector<std::vector<int> > pw;
+              std::vector<float> pt, pl;
+              int st = WFST_OK;
+              decode.GetNbestWords(&pw, &pt, &pl, partial_nbest, false, slm1p, slm2p, &st);
+              out << nbest_lines(u.key, decode.NumFramesDecoded(), st, pw, pt, pl);
+            }
           }
         } else {
           decode.AdvanceDecoding(&decodable);
@@ -692,6 +730,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<Lattice> > nbest;
         std::vector<std::vector<int> > wt_words;                      // --word-times
         std::vector<std::vector<std::pair<int, int> > > wt_frames;
+        std::string partials;                                         // --partial-nbest
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -757,6 +796,25 @@ int main(int argc, char **argv) {
                 decode.AdvanceDecodingChunk(ch, ptrs, fresh, score_dtype, stride, WFST_STREAM_NONE);
                 if (wfst_decoder_sync(decode.Handle()) != WFST_OK) throw std::runtime_error(wfst_last_error());   // (the staging buffer is the next chunk's)
               }
+            } else if (partial_nbest > 0) {
+              // the streaming shape over the batch: every channel's next chunk, then ONE n-best text call for the channels still running
+              int longest = 0;
+              for (int i = 0; i < n; ++i) longest = std::max(longest, ready[i]);
+              std::vector<int> upto(n);
+              for (int have = chunk;; have += chunk) {
+                for (int i = 0; i < n; ++i) upto[i] = std::min(ready[i], have);
+                decode.AdvanceDecodingHost(ch, rows, upto, stride);
+                if (have >= longest) break;
+                std::vector<int> live;
+                for (int i = 0; i < n; ++i)
+                  if (have < ready[i]) live.push_back(i);
+                std::vector<std::vector<std::vector<int> > > w;
+                std::vector<std::vector<float> > t, l;
+                std::vector<int> st;
+                decode.GetNbestWords(live, partial_nbest, slm1, slm2, false, &w, &t, &l, &st);
+                for (size_t q = 0; q < live.size(); ++q)
+                  o.partials += nbest_lines(utts[b0 + (size_t)live[q]].key, decode.NumFramesDecoded(live[q]), st[q], w[q], t[q], l[q]);
+              }
             } else {
               decode.AdvanceDecodingHost(ch, rows, ready, stride);
             }
@@ -795,6 +853,7 @@ int main(int argc, char **argv) {
         const size_t b0 = b * (size_t)batch;
         BatchOut &o = outs[b];
         const int n = (int)o.best.size();
+        out << o.partials;
         for (int i = 0; i < n; ++i) {
           WordTimes wt;
           if (word_times && o.ok[i]) {

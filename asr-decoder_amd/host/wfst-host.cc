@@ -11,6 +11,11 @@
 #include <map>
 #include <iostream>
 #include <sstream>
+#include <tuple>
+
+// wfst_decoder_get_nbest_words is referenced weakly: this file is also linked against doubles of the C ABI that end at the calls
+// it made before (the pool's and the partial words' sanitizer harnesses); there the n-best text reports itself missing.
+#pragma weak wfst_decoder_get_nbest_words
 
 namespace datemoon {
 
@@ -535,7 +540,7 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
       if (call(&c, 1) != WFST_OK) r->error = std::make_exception_ptr(std::runtime_error(std::string(what) + ": " + wfst_last_error()));
     }
   };
-  double ms[kKinds] = {0, 0, 0, 0, 0, 0, 0};
+  double ms[kKinds] = {0, 0, 0, 0, 0, 0, 0, 0};
   // a kind's requesters go on as soon as that kind is served: the threads whose chunks have just been enqueued pull their next
   // chunks while the batcher fetches other channels' best paths (which waits for the device)
   auto clocked = [&](int kind, auto &&f) {
@@ -574,6 +579,7 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
     ms[kPartial] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   clocked(kEndpoint, [&] { ExecuteEndpoint(by_kind[kEndpoint]); });
+  clocked(kNbestWords, [&] { ExecuteNbestWords(by_kind[kNbestWords]); });
   clocked(kCall, [&] {
     for (Request *r : by_kind[kCall]) {
       try {
@@ -588,6 +594,7 @@ void GpuChannelPool::Execute(std::vector<Request *> &batch) {
     for (int k = 0; k <= kCall; ++k) _stats.ms_by_kind[k] += ms[k];
     _stats.ms_endpoint += ms[kEndpoint];
     _stats.ms_partial += ms[kPartial];
+    _stats.ms_nbest_words += ms[kNbestWords];
   }
   if (!_trace_file.empty() && !_trace.empty())
     for (int k = 0; k < kKinds; ++k) _trace.back().ms[k] = ms[k];
@@ -1615,6 +1622,124 @@ bool GpuBatchDecoder::GetBestPath(int channel, Lattice *ofst, bool use_final_pro
   GetBestPaths(std::vector<int>(1, channel), &l, &ok, use_final_probs);
   *ofst = l[0];
   return ok[0];
+}
+
+// ---- the n-best text of channel lists (wfst_decoder_get_nbest_words) ------------------------------------------------------------
+// One C-ABI call for `ch`; words / tot / lm [i][k] of listed channel i's path k, status[i] its own code.  A path with more words
+// than the first capacity: once more with the size the call reports.  Returns the call's own code.
+static int NbestWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, int n, bool use_final_probs, const wfst_lm *l1, const wfst_lm *l2,
+                          std::vector<std::vector<std::vector<int> > > *words, std::vector<std::vector<float> > *tot,
+                          std::vector<std::vector<float> > *lm, std::vector<int> *status) {
+  if (!wfst_decoder_get_nbest_words) throw std::runtime_error("GetNbestWords: this build's device library has no wfst_decoder_get_nbest_words");
+  const size_t cnt = ch.size(), np = (size_t)std::max(n, 1);
+  int32_t cap = 64;
+  for (int32_t c : ch) cap = std::max(cap, wfst_decoder_num_frames_decoded(dec, c) / 4 + 64);
+  std::vector<int32_t> st(cnt), got(cnt), nw(cnt * np);
+  std::vector<float> t(cnt * np), l(cnt * np);
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    std::vector<int32_t> w(cnt * np * (size_t)cap);
+    const int rc = wfst_decoder_get_nbest_words(dec, ch.data(), (int32_t)cnt, n, use_final_probs ? 1 : 0, l1, l2, cap, st.data(), got.data(), nw.data(),
+                                                w.data(), t.data(), l.data(), nullptr);
+    if (rc != WFST_OK) return rc;
+    const int32_t longest = nw.empty() ? 0 : *std::max_element(nw.begin(), nw.end());
+    if (longest > cap && attempt == 0) { cap = longest; continue; }
+    words->assign(cnt, std::vector<std::vector<int> >());
+    tot->assign(cnt, std::vector<float>());
+    lm->assign(cnt, std::vector<float>());
+    for (size_t i = 0; i < cnt; ++i)
+      for (int32_t k = 0; k < got[i]; ++k) {
+        const int32_t *p = w.data() + (i * np + (size_t)k) * (size_t)cap;
+        (*words)[i].push_back(std::vector<int>(p, p + std::min(nw[i * np + (size_t)k], cap)));
+        (*tot)[i].push_back(t[i * np + (size_t)k]);
+        (*lm)[i].push_back(l[i * np + (size_t)k]);
+      }
+    break;
+  }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+// GetNbestWords of every waiting channel: the requests grouped by what they ask -- (n, use_final_probs, LM pair): a service has
+// one -- and one wfst_decoder_get_nbest_words per group; a list the library refuses is retried request by request
+void GpuChannelPool::ExecuteNbestWords(std::vector<Request *> &requests) {
+  typedef std::tuple<int, bool, const wfst_lm *, const wfst_lm *> Key;
+  std::map<Key, std::vector<Request *> > groups;
+  for (Request *r : requests) groups[Key(r->nb_n, r->use_final_probs, r->nb_old, r->nb_new)].push_back(r);
+  for (auto &gr : groups) {
+    auto call = [&](const std::vector<Request *> &rs) {
+      std::vector<int32_t> ch;
+      for (Request *r : rs) ch.push_back(r->channel);
+      std::vector<std::vector<std::vector<int> > > w;
+      std::vector<std::vector<float> > t, l;
+      std::vector<int> st;
+      const int rc = NbestWordsCall(_dec, ch, std::get<0>(gr.first), std::get<1>(gr.first), std::get<2>(gr.first), std::get<3>(gr.first), &w, &t, &l, &st);
+      if (rc == WFST_OK)
+        for (size_t i = 0; i < rs.size(); ++i) { rs[i]->nb_words.swap(w[i]); rs[i]->nb_tot.swap(t[i]); rs[i]->nb_lm.swap(l[i]); rs[i]->nb_status = st[i]; }
+      std::lock_guard<std::mutex> lk(_mu);
+      _stats.nbest_words_calls += 1;
+      _stats.nbest_words_requests += (long long)rs.size();
+      return rc;
+    };
+    try {
+      if (call(gr.second) == WFST_OK) continue;
+      for (Request *r : gr.second)
+        if (gr.second.size() == 1 || call(std::vector<Request *>(1, r)) != WFST_OK)
+          r->error = std::make_exception_ptr(std::runtime_error(std::string("GetNbestWords: ") + wfst_last_error()));
+    } catch (...) {
+      for (Request *r : gr.second) r->error = std::current_exception();
+    }
+  }
+}
+
+bool GpuLatticeDecoder::GetNbestWords(std::vector<std::vector<int> > *words, std::vector<float> *tot, std::vector<float> *lm, int n,
+                                      bool use_final_probs, ArpaLm *oldlm, ArpaLm *newlm, int *status) {
+  const wfst_lm *l1 = oldlm ? oldlm->Handle() : nullptr, *l2 = newlm ? newlm->Handle() : nullptr;
+  std::vector<std::vector<int> > w;
+  std::vector<float> t, l;
+  int st = WFST_OK;
+  if (_pool) {
+    GpuChannelPool::Request q;
+    q.kind = GpuChannelPool::kNbestWords;
+    q.channel = _chan;
+    q.nb_n = n;
+    q.use_final_probs = use_final_probs;
+    q.nb_old = l1;
+    q.nb_new = l2;
+    _pool->Submit(&q);
+    _decoded = q.decoded;
+    w.swap(q.nb_words); t.swap(q.nb_tot); l.swap(q.nb_lm);
+    st = q.nb_status;
+  } else {
+    std::vector<std::vector<std::vector<int> > > ww;
+    std::vector<std::vector<float> > tt, ll;
+    std::vector<int> ss;
+    if (NbestWordsCall(_dec, std::vector<int32_t>(1, 0), n, use_final_probs, l1, l2, &ww, &tt, &ll, &ss) != WFST_OK) Fatal("GetNbestWords");
+    w.swap(ww[0]); t.swap(tt[0]); l.swap(ll[0]);
+    st = ss[0];
+  }
+  if (status) *status = st;
+  else if (st != WFST_OK && !(st == WFST_E_CAPACITY && !w.empty())) throw std::runtime_error(std::string("GetNbestWords: ") + wfst_last_error());
+  if (words) words->swap(w);
+  if (tot) tot->swap(t);
+  if (lm) lm->swap(l);
+  return words ? !words->empty() : !w.empty();
+}
+
+void GpuBatchDecoder::GetNbestWords(const std::vector<int> &channels, int n, ArpaLm *oldlm, ArpaLm *newlm, bool use_final_probs,
+                                    std::vector<std::vector<std::vector<int> > > *words, std::vector<std::vector<float> > *tot,
+                                    std::vector<std::vector<float> > *lm, std::vector<int> *status) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<std::vector<std::vector<int> > > w;
+  std::vector<std::vector<float> > t, l;
+  std::vector<int> st;
+  if (NbestWordsCall(_dec, ch, n, use_final_probs, oldlm ? oldlm->Handle() : nullptr, newlm ? newlm->Handle() : nullptr, &w, &t, &l, &st) != WFST_OK)
+    Fatal("GetNbestWords");
+  if (words) words->swap(w);
+  if (tot) tot->swap(t);
+  if (lm) lm->swap(l);
+  if (status) *status = st;
 }
 
 }  // namespace datemoon

@@ -288,6 +288,9 @@ class GpuChannelPool {
     long long partial_calls;      // wfst_decoder_partial_enqueue calls issued ...
     long long partial_requests;   // ... for this many GetPartialWords requests
     double ms_partial;            // batcher time in them (enqueueing and fetching; the device works beside the batcher)
+    long long nbest_words_calls;      // wfst_decoder_get_nbest_words calls issued ...
+    long long nbest_words_requests;   // ... for this many GetNbestWords requests
+    double ms_nbest_words;            // batcher time in them (synchronous)
     long long partial_max_per_pass;   // the most of those LIST calls one batcher pass issued (one).  Not counted here or in partial_calls: the
                                       // synchronous request-by-request calls after a refused list or a capacity too small, which hold the batcher
   };
@@ -298,7 +301,7 @@ class GpuChannelPool {
   friend class GpuLatticeDecoder;
   GpuChannelPool(const GpuChannelPool &);
   GpuChannelPool &operator=(const GpuChannelPool &);
-  enum Kind { kInit = 0, kAdvance, kFinalize, kBestPath, kCall, kEndpoint, kPartial, kKinds };
+  enum Kind { kInit = 0, kAdvance, kFinalize, kBestPath, kCall, kEndpoint, kPartial, kNbestWords, kKinds };
   struct Request {
     Kind kind;
     int channel;
@@ -315,6 +318,11 @@ class GpuChannelPool {
     // kPartial: the words of the partial best path, the first n_stable of them final
     std::vector<int32_t> words;
     int n_stable = 0;
+    // kNbestWords: asked with (nb_n paths, use_final_probs, the LM pair or none); the channel's status and its paths' text
+    int nb_n = 0, nb_status = 0;
+    const wfst_lm *nb_old = nullptr, *nb_new = nullptr;
+    std::vector<std::vector<int> > nb_words;
+    std::vector<float> nb_tot, nb_lm;
     // outcome
     int decoded;                  // NumFramesDecoded of the channel after the request
     std::exception_ptr error;
@@ -348,6 +356,8 @@ class GpuChannelPool {
   bool PollPartials(bool block);
   void ExecutePartial(std::vector<Request *> &rs);    // synchronous, request by request (a refused list, a capacity too small)
   std::vector<Request *> _pt_wait, _pt_flight;   // (the batcher thread's own)
+  // GetNbestWords of every waiting channel: one wfst_decoder_get_nbest_words per distinct (n, use_final_probs, LM pair); synchronous
+  void ExecuteNbestWords(std::vector<Request *> &rs);
   int _pt_cap = 0;
   // The decoder objects' row buffers as slots of ONE page-locked allocation, equally spaced: rows of consecutive channels that cover
   // the same frames then go to the device as one 2-D copy (wfst_decoder_advance_host).  Allocated by the first object that asks, every
@@ -460,6 +470,13 @@ class GpuLatticeDecoder : public DecoderItf {
   // pool the same result is derived on the host from the channel's pooled GetBestPath (no silence list there).
   bool GetWords(std::vector<int> *words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs = true);
   void SetSilencePhones(const std::vector<int> &phones);   // needs the graph's SetTid2Phone; empty: none
+  // The service's per-chunk GetNbestTxt (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:139-150), mid-utterance or after
+  // FinalizeDecoding: the words, tot_score and lm_score of the n (<= 64) cheapest paths of GetLattice's lattice (with LMs: of its
+  // second pass), the text made on the device (wfst_decoder_get_nbest_words).  false: no path.  The channel's own failure (a lattice
+  // beyond the batch's bounds ...) throws, or with `status` given is returned there (WFST_OK otherwise).  Over a pool, the requests
+  // of many threads go to the device as one list per batcher pass and distinct (n, use_final_probs, LM pair).
+  bool GetNbestWords(std::vector<std::vector<int> > *words, std::vector<float> *tot, std::vector<float> *lm, int n, bool use_final_probs = true,
+                     ArpaLm *oldlm = nullptr, ArpaLm *newlm = nullptr, int *status = nullptr);
 
  private:
   void Pull(AmInterface *decodable);
@@ -551,6 +568,11 @@ class GpuBatchDecoder {
                 std::vector<std::vector<std::pair<int, int> > > *frames, std::vector<float> *tot, std::vector<float> *lm,
                 std::vector<bool> *ok = nullptr, bool use_final_probs = true);
   void SetSilencePhones(const std::vector<int> &phones);
+  // GetNbestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
+  // (*words)[i][k], (*tot)[i][k], (*lm)[i][k] of listed channel i's path k; (*status)[i]: WFST_OK or the channel's own error code
+  void GetNbestWords(const std::vector<int> &channels, int n, ArpaLm *oldlm, ArpaLm *newlm, bool use_final_probs,
+                     std::vector<std::vector<std::vector<int> > > *words, std::vector<std::vector<float> > *tot,
+                     std::vector<std::vector<float> > *lm, std::vector<int> *status = nullptr);
   wfst_decoder *Handle() { return _dec; }
 
  private:

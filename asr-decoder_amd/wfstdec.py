@@ -44,6 +44,7 @@ SYMBOLS = [
     "wfst_decoder_set_silence_phones", "wfst_decoder_words_enqueue", "wfst_decoder_words_ready", "wfst_decoder_words_fetch",
     "wfst_decoder_get_words",
     "wfst_decoder_set_score_transform", "wfst_decoder_advance_chunk", "wfst_decoder_get_scores",
+    "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
 ]
 
 
@@ -731,6 +732,30 @@ class BatchDecoder:
         K = npth.value
         return [dict(olabel=ol[off[i]:off[i + 1]].copy(), graph=gr[off[i]:off[i + 1]].copy(), acoustic=ac[off[i]:off[i + 1]].copy(),
                      tot=float(tot[i])) for i in range(K)]
+
+    def determinizer_slots(self):
+        """(lattices one determinize launch takes, bytes of one workspace slot) (wfst_decoder_get_determinizer_slots)."""
+        s, b = C.c_int32(0), C.c_int64(0)
+        _check(lib().wfst_decoder_get_determinizer_slots(self.h, C.byref(s), C.byref(b)))
+        return s.value, b.value
+
+    def nbest_words(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256):
+        """GetNbestTxt of a LIST of channels (None: all), live and finalized ones mixed, in one launch per stage
+        (wfst_decoder_get_nbest_words): per channel (status, [dict(words, tot, lm, path_tot)]), cheapest path first -- what
+        nbest_paths(c, n_paths, ...) + wfst_lattice_to_vector give, the text made on the device.  status: WFST_OK or the channel's own
+        error code; with WFST_E_CAPACITY for words (more than cap_words on a path) the dicts carry n_words, the needed size."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
+        cnt, n = len(ch), int(n_paths)
+        status, got = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32)
+        nw = np.zeros((cnt, max(n, 1)), np.int32)
+        words = np.zeros((cnt, max(n, 1), max(int(cap_words), 1)), np.int32)
+        tot, lm, ptot = (np.zeros((cnt, max(n, 1)), np.float32) for _ in range(3))
+        _check(lib().wfst_decoder_get_nbest_words(self.h, _i32(ch), cnt, n, int(bool(use_final_probs)),
+                                                  old_lm.h if old_lm is not None else None, new_lm.h if new_lm is not None else None,
+                                                  int(cap_words), _i32(status), _i32(got), _i32(nw), _i32(words), _f32(tot), _f32(lm), _f32(ptot)))
+        return [(int(status[i]), [dict(words=words[i, k, : min(int(nw[i, k]), int(cap_words))].copy(), n_words=int(nw[i, k]), tot=np.float32(tot[i, k]),
+                                       lm=np.float32(lm[i, k]), path_tot=np.float32(ptot[i, k])) for k in range(int(got[i]))])
+                for i in range(cnt)]
 
     def raw_lattices(self, channels=None, use_final_probs=True, threads=0):
         """GetRawLattice of many finalized channels.  The first call fetches the pruned lattices of all

@@ -480,6 +480,42 @@ int wfst_decoder_rescore_lattices(wfst_decoder *d, const int32_t *channels, int3
 int wfst_decoder_nbest_paths_batch(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t n_paths, int32_t use_final_probs,
                                    const wfst_lm *old_lm, const wfst_lm *new_lm);
 
+/* ---- n-best TEXT of a channel list, mid-utterance included -----------------------------------------------------------------
+ * The service's per-chunk GetNbestTxt (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:139-150, called with end_of_utterance = false
+ * from v2-asr/v2-asr-task.h:298-319): GetLattice (raw lattice, DeterminizeLatticeWrapper, under --use-second ComposeLattice x 2),
+ * NShortestPath, then OnebestLatticeToString per path -- for a LIST of channels, live (initialised, not finalized) and finalized
+ * ones mixed, in one launch per stage: the live channels' lattices emitted, all determinized, composed with the LM pair if one is
+ * given, their n cheapest paths found, and the paths turned into text on the device (nbest_words_kernel), so that words and three
+ * floats per path cross the link instead of every arc of every path.
+ *
+ * For listed channel i and path k, with P = what wfst_decoder_get_nbest_paths(channels[i], n_paths, use_final_probs, old_lm, new_lm,
+ * ...) returns at this moment: got_paths[i] = P's *n_paths; path_tot[i][k] = P's path_tot[k], bit for bit; words[i][k][..] = the
+ * non-zero a_olabel of path k in order, n_words[i][k] of them; tot_score / lm_score[i][k] = bit for bit what wfst_lattice_to_vector
+ * returns for path k's arcs (float sums in arc order).  A finalized channel with use_final_probs == 0 has no lattice (got_paths 0,
+ * status WFST_OK, as GetRawLattice has it); so has a channel with no frame decoded.  Entries of paths k >= got_paths[i] are zero.
+ *
+ * A failure of ONE channel does not fail the list: the call returns WFST_OK and status[i] carries the channel's own error code with
+ * got_paths[i] = 0 (wfst_last_error() then holds the message of the last such channel, although the call succeeded) -- a lattice beyond the determinizer's, the composition's or the n-best search's batch limits (WFST_E_CAPACITY),
+ * a device error of that channel's utterance.  More words on a path than cap_words: status[i] = WFST_E_CAPACITY, n_words[i][k] is
+ * the needed size and the first cap_words words are written (got_paths[i] stays).
+ * The call itself fails, before any device work, with WFST_E_ARG (n_paths outside 1..64, one LM without the other, an LM on
+ * another device, a bad or duplicate list, cap_words <= 0) or WFST_E_STATE (a decoder without lattice_links, a listed channel never
+ * initialised).  Any output pointer may be NULL.  Lists longer than the determinizer's workspace slots are taken in rounds.
+ * What the per-channel getters and the prefetch keep for the same channels is untouched: they answer afterwards what they would
+ * have answered without this call.
+ * Synchronous, and deliberately without enqueue / ready / fetch halves: the stages exchange their sizes through the host (the
+ * determinizer's result words size the composition's and the search's workspaces), and unpicking that is a change of its own. */
+int wfst_decoder_get_nbest_words(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t n_paths /* 1..64 */,
+                                 int32_t use_final_probs, const wfst_lm *old_lm, const wfst_lm *new_lm, int32_t cap_words,
+                                 int32_t *status /* [n] */, int32_t *got_paths /* [n] */, int32_t *n_words /* [n][n_paths] */,
+                                 int32_t *words /* [n][n_paths][cap_words] */, float *tot_score, float *lm_score /* [n][n_paths] */,
+                                 float *path_tot /* [n][n_paths] */);
+
+/* How many lattices ONE launch of the determinizer (and of the stages behind it) takes -- the workspace slots that
+ * wfst_limits.det_workspace_bytes buys, at most one per channel -- and the bytes one slot takes; a longer list goes in rounds.
+ * Allocates the workspace if no call has yet.  Either output may be NULL.  WFST_E_STATE: a decoder without lattice_links. */
+int wfst_decoder_get_determinizer_slots(wfst_decoder *d, int32_t *slots, int64_t *bytes_per_slot);
+
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
  * ConvertNbestToVector, then LatticeToVector per path) of channels of a lattice-mode decoder, finalized
