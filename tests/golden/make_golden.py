@@ -35,7 +35,19 @@ def graph_bytes(g, tmp="/tmp/_golden_graph.bin"):
         return np.frombuffer(f.read(), dtype=np.uint8).copy(), tmp
 
 
-def run_cases(ref, name, g, tid2pdf, utts, cfgs, modes):
+def savez_smallest(path, **arrays):
+    """np.savez_compressed at zlib's highest level (np.load reads it like any other .npz)"""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            z.writestr(k + ".npy", buf.getvalue())
+
+
+def run_cases(ref, name, g, tid2pdf, utts, cfgs, modes, save=np.savez_compressed):
     gb, path = graph_bytes(g)
     h = ref.load_graph(path)
     # an empty tid2pdf means "no map": LogLikelihood(f, ilabel) reads column ilabel
@@ -69,7 +81,7 @@ def run_cases(ref, name, g, tid2pdf, utts, cfgs, modes):
                 k += 1
     ref.free_graph(h)
     out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    save(os.path.join(OUT, name + ".npz"), **out)
     print("wrote %s.npz: %d cases" % (name, k))
 
 
@@ -293,17 +305,8 @@ def biglm_goldens(ref):
     print("wrote biglm_hclg600.npz: %d cases" % k)
 
 
-def main():
-    pyoracle.build_ref()
-    ref = pyoracle.RefDecoder()
-    if "--biglm-only" in sys.argv:
-        return biglm_goldens(ref)
-    if "--openfst-only" in sys.argv:
-        return openfst_goldens(ref)
-    if "--lattice-only" in sys.argv:
-        return lattice_goldens(ref)
-
-    # 1. small hclg-like graph, several configurations (beam-only, max/min-active binding)
+def hclg600_inputs():
+    """(graph, tid2pdf, utterances, configurations, modes) of hclg600.npz"""
     n_tid, n_pdf, T = 600, 300, 40
     g = synth.make_hclg_like(600, seed=11, n_tid=n_tid, n_words=500)
     m = synth.default_tid2pdf(n_tid)
@@ -321,7 +324,33 @@ def main():
         dict(chunk=7, finalize=False),
         dict(chunk=0, finalize=False, use_final_probs=False),
     ]
+    return g, m, utts, cfgs, modes
+
+
+def neg_goldens(ref):
+    """hclg600's graph and configurations with its three utterances shifted by +4: every path cost is negative from the first
+    frame on (pseudo-log-likelihoods after prior division), the regime no other vector here is in.  (Shifted mantissas deflate a
+    little worse; at the highest level the file stays below hclg600.npz.)"""
+    g, m, utts, cfgs, modes = hclg600_inputs()
+    run_cases(ref, "neg_hclg600", g, m, [(x + np.float32(4.0)).astype(np.float32) for x in utts], cfgs, modes, save=savez_smallest)
+
+
+def main():
+    pyoracle.build_ref()
+    ref = pyoracle.RefDecoder()
+    if "--biglm-only" in sys.argv:
+        return biglm_goldens(ref)
+    if "--openfst-only" in sys.argv:
+        return openfst_goldens(ref)
+    if "--lattice-only" in sys.argv:
+        return lattice_goldens(ref)
+    if "--neg-only" in sys.argv:
+        return neg_goldens(ref)
+
+    # 1. small hclg-like graph, several configurations (beam-only, max/min-active binding)
+    g, m, utts, cfgs, modes = hclg600_inputs()
     run_cases(ref, "hclg600", g, m, utts, cfgs, modes)
+    neg_goldens(ref)
 
     # 2. traceback quirk: two parallel arcs 0->1 (SURVEY.md section 7, "Traceback quirk");
     #    with lattice_beam 8 the reference returns the higher-index arc (word 22).

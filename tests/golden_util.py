@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-GOLDEN_NAMES = ["hclg600", "quirk_parallel_arcs", "eps_chains", "no_final", "dead_end"]
+GOLDEN_NAMES = ["hclg600", "quirk_parallel_arcs", "eps_chains", "no_final", "dead_end", "neg_hclg600"]
 
 
 class Golden:

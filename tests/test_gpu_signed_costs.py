@@ -1,0 +1,781 @@
+"""-m gpu: every decoder path on NEGATIVE and ZERO-CROSSING path costs.
+
+Every device kernel orders float costs through one mapping to an orderable uint32 (f2o / o2f in csrc/wfst_kernels.hip, nb_f2o in
+csrc/wfst_nbest.hip) which has one branch per sign of the float; the radix select of GetCutoff starts from the bits the frame's
+lowest and highest key share, which is none when a frame's costs straddle zero.  The rest of the suite decodes log-likelihoods
+around -2 over graphs with weights >= 0: path costs are positive there from the second frame on, so only one branch ever runs.
+The workloads here (tests/signed_util.py) are that recipe shifted upwards: `crossing` (the best cost of a frame changes sign five
+or six times an utterance, frames over max_active straddle zero), `negative` (costs negative throughout and falling) and `zero`,
+the unshifted positive control.  test_the_data_does_what_it_claims proves that from the oracle's trace.
+
+Bar: as everywhere in this suite, bit for bit against the C oracle (itself pinned to the compiled reference on these very
+workloads by tests/test_oracle_vs_reference.py) -- in its order-free mode where max_active / min_active or a per-frame limit bind
+(DESIGN.md section 4).  No tolerances except where an existing comparison this module borrows has one.
+
+If f2o's negative branch were the positive one (keys of negative floats ordered backwards): the atomic minima of ChanCtl::bound /
+best_next and of the insert table would keep the COSTLIEST of two negative arrivals, so from the first frame with a negative cost
+on G.assert_same_as_oracle fails in test_best_path_decoders[negative-*] and [crossing-*] (transition-ids / costs), the frontier
+costs in test_per_frame_best_cost_and_frontier, nodes() in test_raw_lattice -- while every [zero-*] case, like the rest of the
+suite, still passes."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import pyoracle
+import signed_util as S
+from golden_util import bits
+from test_gpu_biglm import gold  # noqa: F401  (the module-scoped fixture over tests/golden/biglm_hclg600.npz)
+
+pytestmark = pytest.mark.gpu
+
+LIM = dict(max_frames=512, max_tokens_per_frame=32768, arena_tokens=1 << 22)
+LAT = dict(max_frames=512, max_tokens_per_frame=32768, arena_tokens=1 << 21, lattice_links=1 << 22)
+SHIFT_NAMES = ["zero", "crossing", "negative"]
+# the 400-frame utterance of the token-collection case: the oracle creates 346 491 tokens on it (beam-only, `negative`)
+GC_FRAMES, GC_SEED, GC_TOKENS_CREATED = 400, 31, 346491
+
+
+def _binds(cd):
+    return not (cd["max_active"] >= 100000 and cd["min_active"] == 0)
+
+
+class World:
+    """The graph on the device and in the oracle, the shifted utterances, and the oracle's results (each computed once)."""
+
+    def __init__(self, synth, oracle, d):
+        import gpu_util as G
+
+        self.G, self.W, self.oracle, self.synth, self.dir = G, G.wfstdec, oracle, synth, d
+        self.g, self.m, self.mats = S.workloads(synth)
+        self.path = str(d / "g.bin")
+        self.g.write(self.path)
+        self.graph = self.W.Graph.load(self.path)
+        self.graph.set_tid2pdf(self.m)
+        self.graph.set_tid2phone(np.arange(S.GRAPH["n_tid"] + 1, dtype=np.int32))
+        self.h = oracle.load_graph(self.path)
+        self.cache = {}
+        self.figures = []
+
+    def close(self):
+        self.graph.free()
+        self.oracle.free_graph(self.h)
+
+    def _of(self, cd, f):
+        try:
+            self.oracle.set_order_free(_binds(cd))
+            return f()
+        finally:
+            self.oracle.set_order_free(False)
+
+    def decode(self, x, cd, key, **kw):
+        """oracle.decode in the mode the device is held to (order-free where the limits bind), kept under `key`"""
+        k = ("d", key, tuple(sorted(cd.items())), tuple(sorted(kw.items())))
+        if k not in self.cache:
+            self.cache[k] = self._of(cd, lambda: self.oracle.decode(self.h, pyoracle.Config(**cd), x, self.m, **kw))
+        return self.cache[k]
+
+    def lattice(self, x, cd, key, **kw):
+        k = ("l", key, tuple(sorted(cd.items())), tuple(sorted(kw.items())))
+        if k not in self.cache:
+            try:
+                self.oracle.set_order_free(True)
+                self.cache[k] = pyoracle.oracle_raw_lattice(self.oracle, self.h, pyoracle.Config(**cd), x, self.m, **kw)
+            finally:
+                self.oracle.set_order_free(False)
+        return self.cache[k]
+
+
+@pytest.fixture(scope="module")
+def world(synth, oracle, tmp_path_factory):
+    w = World(synth, oracle, tmp_path_factory.mktemp("signed"))
+    yield w
+    for line in w.figures:   # (what the summary of a change to these kernels quotes: run with -s)
+        print(line)
+    w.close()
+
+
+def _check(G, r, o, what):
+    """bit for bit; on an exact cost tie on the oracle's best path (capped by test_the_data_does_what_it_claims) the total only"""
+    if o.extra.get("ties", 0):
+        assert bool(r.ok) == bool(o.ok) and abs(r.tot_score - o.tot_score) <= 1e-4 * max(1.0, abs(o.tot_score)), what
+        return
+    G.assert_same_as_oracle(r, o, what)
+
+
+# ---- the data ---------------------------------------------------------------------------------------------------------------------
+def test_the_data_does_what_it_claims(world):
+    tied = triples = 0
+    for name in SHIFT_NAMES:
+        for ci, cd in enumerate(S.CFGS):
+            for ui, x in enumerate(world.mats[name]):
+                t = world.oracle.decode(world.h, pyoracle.Config(**cd), x, world.m, trace=True)
+                what = "%s cfg %d utt %d" % (name, ci, ui)
+                assert t.ok, what
+                if name == "crossing":
+                    assert S.sign_changes(t.frame_best) >= 3, what + ": the best cost does not cross zero three times"
+                    if _binds(cd):
+                        assert S.straddling_frames(t.frame_ntoks, t.frame_best, cd) >= 3, what + ": no select over a range that straddles zero"
+                if name == "negative":
+                    assert (t.frame_best[1:] < 0).all() and t.tot_score < -100.0, what
+                if name == "zero":
+                    assert (t.frame_best[1:] > 0).all(), what + ": the control is not positive"
+                triples += 1
+                tied += int(world.decode(x, cd, (name, ui)).extra["ties"] > 0)
+    assert triples == 18 and 10 * tied <= triples, "%d of %d (utterance, config, shift) triples with an exact cost tie on the best path" % (tied, triples)
+
+
+# ---- 1. best-path decoders --------------------------------------------------------------------------------------------------------
+# kind -> (config, the oracle's config, BatchDecoder limits, graph options, column padding, the path flags it must report)
+KINDS = {
+    "default": (S.BEAM_ONLY, None, LIM, None, 0, dict(staged=1, two_launch=1, degcode=1, ll_row=1, best_exp=1)),
+    # max_active / min_active bind: the select of the fused frame boundary on two-launch frames, of the closure launch on every
+    # gc_stride-th frame (three launches) ...
+    "binding": (S.BINDING, None, LIM, None, 0, dict(staged=1, two_launch=1, best_exp=1)),
+    # ... and a decoder whose arena leaves no room for a stride: three launches on every frame
+    "three_launch": (S.BINDING, None, dict(LIM, arena_tokens=1 << 16), None, 0, dict(staged=1, two_launch=0, gc_stride=1)),
+    "soft_limit": (S.BEAM_ONLY, dict(S.BEAM_ONLY, max_active=256), dict(LIM, max_tokens_per_frame=256), None, 0, dict(soft_limit=1)),
+    "plain_closure": (S.BEAM_ONLY, None, LIM, dict(fuse_closures=0), 0, dict(staged=0, best_exp=0, degcode=0)),
+    "big_arena": (S.BEAM_ONLY, None, dict(LIM, arena_tokens=(1 << 22) + 4096), None, 0, dict(staged=1, degcode=0)),
+    "gather": (S.BEAM_ONLY, None, LIM, None, 1, dict(staged=1, ll_row=0)),
+}
+
+
+def _stream(dec, dev, T, stride, chunk, each=None):
+    dec.init()
+    ptrs = [t.data_ptr() for t in dev]
+    for r in ([max(T)] if chunk <= 0 else list(range(chunk, max(T), chunk)) + [max(T)]):
+        dec.advance(ptrs, [min(r, t) for t in T], stride)
+        if each is not None:
+            each(r)
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+@pytest.mark.parametrize("shift", SHIFT_NAMES)
+def test_best_path_decoders(world, shift, kind):
+    G, W = world.G, world.W
+    cd, ocd, lim, gopt, pad, flags = KINDS[kind]
+    ocd = ocd or cd
+    mats = world.mats[shift]
+    fed = [np.ascontiguousarray(np.pad(x, ((0, 0), (0, pad)))) for x in mats] if pad else mats
+    T = [int(x.shape[0]) for x in mats]
+    stride = int(fed[0].shape[1])
+    graph = world.graph
+    if gopt:
+        graph = W.Graph.load(world.path, options=W.GraphOptions(**gopt))
+        graph.set_tid2pdf(world.m)
+    dev = G.upload(fed)
+    dec = W.BatchDecoder(graph, G.gpu_config(cd), len(mats), **lim)
+    try:
+        want = [world.decode(x, ocd, (shift, ui)) for ui, x in enumerate(mats)]
+        # one call
+        _stream(dec, dev, T, stride, 0)
+        dec.finalize()
+        pf = dec.path_flags()
+        assert {k: pf[k] for k in flags} == flags, "%s: path flags %s" % (kind, pf)
+        if kind == "binding":
+            assert 1 < pf["gc_stride"] < min(T), pf   # (both kinds of frame ran)
+        for ui, d in enumerate(dec.best_paths()):
+            assert want[ui].ok
+            _check(G, G.GpuResult(d), want[ui], "%s %s utt %d, one call" % (shift, kind, ui))
+        if kind == "soft_limit":
+            assert all(dec.degraded_frames(c) > 0 for c in range(len(mats))), "the per-frame limit never bound"
+        else:
+            assert all(dec.degraded_frames(c) == 0 for c in range(len(mats)))
+
+        # chunks of 7, the partial best path after every chunk against the oracle's prefix decode
+        def partial(r):
+            for ui, d in enumerate(dec.best_paths(use_final_probs=False)):
+                k = min(r, T[ui])
+                po = world.decode(mats[ui][:k], ocd, (shift, ui, k), chunk=7, finalize=False, use_final_probs=False)
+                _check(G, G.GpuResult(d), po, "%s %s utt %d, partial at %d" % (shift, kind, ui, k))
+
+        _stream(dec, dev, T, stride, 7, partial)
+        dec.finalize()
+        for ui, d in enumerate(dec.best_paths()):
+            _check(G, G.GpuResult(d), want[ui], "%s %s utt %d, chunks of 7" % (shift, kind, ui))
+
+        # frame by frame: the frontier sizes reached, and the frames on which the select runs over costs of both signs
+        limit = min(ocd["max_active"], lim["max_tokens_per_frame"])
+        peak = strad = 0
+
+        def frame(r):
+            nonlocal peak, strad
+            for c in range(len(mats)):
+                if r <= T[c]:
+                    _, co = dec.frontier(c)
+                    peak = max(peak, len(co))
+                    strad += int(len(co) > limit and co.min() < 0 < co.max())
+
+        _stream(dec, dev, T, stride, 1, frame)
+        dec.finalize()
+        world.figures.append("figures: %-13s %-8s peak frontier %5d tokens, select over a zero-straddling range on %3d frames (3 utterances)" % (kind, shift, peak, strad))
+        if _binds(ocd):
+            assert peak > limit, "the limit never bound"
+            if shift == "crossing":
+                assert strad >= 3, "no select ran over a range that straddles zero"
+            if shift == "zero":
+                assert strad == 0
+    finally:
+        dec.free()
+        if gopt:
+            graph.free()
+
+
+@pytest.mark.parametrize("shift", SHIFT_NAMES)
+def test_per_frame_best_cost_and_frontier(world, shift):
+    """As tests/test_gpu_parity.py::test_per_frame_best_cost_and_token_subset: every 5 frames the device's frontier is a subset of
+    the reference's token list, each cost equal bit for bit (the sign bit included), the best cost the same."""
+    G = world.G
+    x = world.mats[shift][0]
+    T = int(x.shape[0])
+    dec = world.W.BatchDecoder(world.graph, G.gpu_config(S.BEAM_ONLY), 1, **LIM)
+    dev = G.upload([x])
+    dec.init()
+    signs = set()
+    try:
+        for f in range(0, T + 1, 5):
+            if f:
+                dec.advance([dev[0].data_ptr()], [f], x.shape[1])
+            st, co = dec.frontier(0)
+            o = world.oracle.decode(world.h, pyoracle.Config(**S.BEAM_ONLY), x[: max(f, 1)], world.m, dump_frame=f, dump_cap=1 << 20)
+            ost, oco, on = o.dump
+            assert on == len(ost) and 0 < len(st) <= on and len(set(st.tolist())) == len(st), "frame %d" % f
+            ref = dict(zip(ost.tolist(), bits(oco).tolist()))
+            for a, b in zip(st.tolist(), bits(co).tolist()):
+                assert ref.get(a) == b, "frame %d state %d" % (f, a)
+            assert bits([co.min()]) == bits([oco.min()]), "frame %d best cost" % f
+            signs |= {bool(co.min() < 0)} if f else set()
+    finally:
+        dec.free()
+    assert signs == {"zero": {False}, "crossing": {False, True}, "negative": {True}}[shift]
+
+
+def test_token_collection_on_falling_costs(world):
+    """A 400-frame `negative` utterance (the total falls to about -800) in an arena of an eighth of the tokens it creates:
+    gc_pass runs, several times, and nothing shows in the result."""
+    G = world.G
+    x = S.shifted(world.synth.make_loglikes(world.g, GC_FRAMES, S.N_PDF, world.m, seed=GC_SEED)[0], S.SHIFTS["negative"])
+    o = world.decode(x, S.BEAM_ONLY, "gc")
+    assert o.ok and o.tot_score < -400.0 and o.extra["ties"] == 0
+    assert abs(o.extra["tokens_created"] - GC_TOKENS_CREATED) <= GC_TOKENS_CREATED // 50   # (the arena below is an eighth of this)
+    dec = world.W.BatchDecoder(world.graph, G.gpu_config(S.BEAM_ONLY), 1, max_frames=512, max_tokens_per_frame=4096,
+                               arena_tokens=GC_TOKENS_CREATED // 8)
+    try:
+        r = G.decode_batch(world.graph, S.BEAM_ONLY, [x], chunk=64, dec=dec)[0]
+        G.assert_same_as_oracle(r, o, "400 frames")
+        assert r.stats["collections"] > 0 and dec.degraded_frames(0) == 0, r.stats
+        world.figures.append("figures: token collection, negative: %d collections, widest frame %d tokens" % (r.stats["collections"], r.stats["peak_tokens"]))
+    finally:
+        dec.free()
+
+
+# ---- 2. lattice mode --------------------------------------------------------------------------------------------------------------
+def _same_lattice(d, O, what):
+    from test_gpu_lattice import as_raw, nodes
+
+    assert (d is not None) == bool(O.ok), what
+    L = as_raw(d)
+    assert np.array_equal(nodes(L), nodes(O)), what + " states"
+    assert np.array_equal(L.labelled_arcs(), O.labelled_arcs()), what + " arcs"
+    return L
+
+
+@pytest.mark.parametrize("dbg", [0, 0x800, 0x1000])
+@pytest.mark.parametrize("ci", [0, 1])
+@pytest.mark.parametrize("shift", ["crossing", "negative"])
+def test_raw_lattice(world, shift, ci, dbg):
+    """GetRawLattice state by state and arc by arc: mid-utterance at frame 25 (the back-pruning passes of frames 10 and 20 have
+    run: their extra costs are differences of costs of either sign) and after FinalizeDecoding; with the raw back-pruning pass for
+    every channel (debug 0x800) and with the iterated closure pass (0x1000)."""
+    G = world.G
+    cd = dict(S.CFGS[ci], prune_interval=10)
+    mats = world.mats[shift]
+    T = [int(x.shape[0]) for x in mats]
+    dec = world.W.BatchDecoder(world.graph, G.gpu_config(cd), len(mats), options=world.W.Options(debug=dbg) if dbg else None, **LAT)
+    dev = G.upload(mats)
+    ptrs = [t.data_ptr() for t in dev]
+    try:
+        dec.init()
+        dec.advance(ptrs, [25] * len(mats), S.N_PDF)
+        for ui, x in enumerate(mats):
+            O = world.lattice(x[:25], cd, (shift, ui, 25), finalize=False, use_final_probs=False)
+            _same_lattice(dec.raw_lattice(ui, False), O, "%s cfg %d debug %#x utt %d at frame 25" % (shift, ci, dbg, ui))
+        dec.advance(ptrs, T, S.N_PDF)
+        dec.finalize()
+        best = dec.best_paths()
+        for ui, x in enumerate(mats):
+            what = "%s cfg %d debug %#x utt %d" % (shift, ci, dbg, ui)
+            L = _same_lattice(dec.raw_lattice(ui), world.lattice(x, cd, (shift, ui)), what)
+            assert np.all(L.a_dst > L.a_src) and (L.st_cost < 0).any(), what
+            _check(G, G.GpuResult(best[ui]), world.decode(x, cd, (shift, ui)), what + " best path of the lattice decoder")
+    finally:
+        dec.free()
+
+
+def _same_nbest_paths(got, want, what):
+    """the same paths, every arc bit for bit, in the same order; paths whose totals agree to 1e-5 may swap places"""
+    assert len(got) == len(want) >= 1, "%s: %d paths, the restatement has %d" % (what, len(got), len(want))
+    key = lambda p: (tuple(p["olabel"].tolist()), tuple(bits(p["graph"]).tolist()), tuple(bits(p["acoustic"]).tolist()))
+    i = 0
+    while i < len(got):
+        j = i
+        while j + 1 < len(got) and abs(got[j + 1]["tot"] - got[i]["tot"]) <= 1e-5 * max(1.0, abs(got[i]["tot"])):
+            j += 1
+        assert sorted(key(p) for p in got[i: j + 1]) == sorted(key(p) for p in want[i: j + 1]), "%s: paths %d..%d differ" % (what, i, j)
+        i = j + 1
+    for p, q in zip(got, want):
+        assert abs(p["tot"] - q["tot"]) <= 2e-5 * max(1.0, abs(q["tot"])), what
+
+
+@pytest.mark.parametrize("shift", ["crossing", "negative"])
+def test_lattice_getters(world, shift, tmp_path):
+    """GetLattice (against the host build of the determinizer and, where it is built, the compiled reference), the n-best text,
+    GetNbest as paths and the second LM pass, on lattices whose arc and path costs have both signs."""
+    from test_compose_lattice import _same as same_multiset
+    from test_gpu_determinize import _check_against, _ref_or_none, as_det
+    from test_gpu_fuzz import py_nbest
+    from test_gpu_lattice import as_raw
+
+    G, W = world.G, world.W
+    lmsynth = importlib.import_module("asr-decoder_amd.lmsynth")
+    V = S.GRAPH["n_words"]
+    p1, p2 = str(tmp_path / "a.bin"), str(tmp_path / "b.bin")
+    lmsynth.make_lm(V, 2, 80, 5, 0, 0, seed=260).to_fsa().write(p1)      # (the pair of tests/test_compose_lattice.py over this vocabulary)
+    lmsynth.make_lm(V, 3, 120, 8, 500, 5, seed=270).to_fsa().write(p2)
+    L1, L2 = W.Lm.load(p1, -1.0), W.Lm.load(p2, 1.0)
+    o1, o2 = pyoracle.Lm(world.oracle, p1, -1.0), pyoracle.Lm(world.oracle, p2, 1.0)
+    lib, ref = pyoracle.build_det_host(), _ref_or_none()
+    cd = dict(S.BEAM_ONLY, prune_interval=10)
+    mats = world.mats[shift]
+    dec = W.BatchDecoder(world.graph, G.gpu_config(cd), len(mats), **LAT)
+    dev = G.upload(mats)
+    try:
+        dec.init()
+        dec.advance([t.data_ptr() for t in dev], [int(x.shape[0]) for x in mats], S.N_PDF)
+        dec.finalize()
+        nb = dec.nbest(4)
+        best = dec.best_paths()
+        for c in reversed(range(len(mats))):
+            what = "%s utt %d" % (shift, c)
+            raw = dec.raw_lattice(c)
+            _same_lattice(raw, world.lattice(mats[c], cd, (shift, c)), what)
+            D = _check_against(G, dec, c, raw, lib, ref, tmp_path, what)
+            # n-best text against the exhaustive Python k-best over the raw lattice
+            ext = py_nbest(as_raw(raw), 4 + 24)
+            assert len(nb[c]) == len(ext[:4]) >= 1, what
+            for k, (a, b) in enumerate(zip(nb[c], ext)):
+                assert abs(a["tot_score"] - b[1]) <= 1e-4 * max(1.0, abs(b[1])), "%s rank %d cost" % (what, k)
+                hits = [e for e in ext if np.array_equal(e[0], a["words"]) and abs(e[1] - a["tot_score"]) <= 1e-4 * max(1.0, abs(e[1]))]
+                assert hits, "%s: path %d is not a path of the lattice at that cost" % (what, k)
+                assert any(abs(e[2] - a["lm_score"]) <= 1e-3 * max(1.0, abs(e[2])) for e in hits), "%s rank %d lm score" % (what, k)
+            assert len({tuple(p["words"].tolist()) for p in nb[c]}) == len(nb[c]), what + " duplicate word sequences"
+            assert np.array_equal(nb[c][0]["words"], best[c]["words"]), what + " 1-best of the n-best"
+            # GetNbest as paths against NShortestPath restated, on the determinized lattice
+            _same_nbest_paths(dec.nbest_paths(c, 5), pyoracle.nshortest_paths(D, 5), what + " n-best paths")
+            # the second LM pass against ComposeLattice restated
+            got = dec.rescored_lattice(c, L1, L2)
+            assert got is not None, what
+            C2 = pyoracle.compose_lattice(pyoracle.compose_lattice(D, o1), o2)
+            same_multiset(as_det(got), C2, what + " rescored lattice")
+            tots = C2.a_graph + C2.a_ac
+            assert (tots < 0).any() and (tots > 0).any(), what + ": arc costs of one sign only"
+    finally:
+        dec.free()
+        for x in (L1, L2, o1, o2):
+            x.free()
+
+
+@pytest.mark.parametrize("shift", ["crossing", "negative"])
+def test_nbest_words_of_a_live_and_two_finalized_channels(world, shift):
+    """wfst_decoder_get_nbest_words over a list that mixes a live channel (15 frames in) with two finalized ones, against its
+    definition: a second decoder fed identically, asked channel by channel for nbest_paths, each path through LatticeToVector."""
+    from test_gpu_nbest_words import _same, _want
+
+    G, W = world.G, world.W
+    cd = dict(S.BEAM_ONLY, prune_interval=10)
+    mats = world.mats[shift]
+    T = [int(mats[0].shape[0]), 15, int(mats[2].shape[0])]
+    dev = G.upload(mats)
+    A, B = (W.BatchDecoder(world.graph, G.gpu_config(cd), len(mats), **LAT) for _ in range(2))
+    try:
+        for d in (A, B):
+            d.init()
+            d.advance([t.data_ptr() for t in dev], T, S.N_PDF)
+            d.finalize(channels=[0, 2])
+        order = [1, 2, 0]
+        for n in (1, 5):
+            got = A.nbest_words(n, channels=order, use_final_probs=True)
+            for i, c in enumerate(order):
+                want = _want(W, B, c, n, (None, None), True)
+                assert isinstance(want, list) and len(want) >= 1, "%s channel %d: no paths to compare" % (shift, c)
+                _same(got[i], want, "%s channel %d n %d" % (shift, c, n))
+                if shift == "negative":
+                    assert all(p["tot"] < 0 for p in got[i][1])
+    finally:
+        A.free()
+        B.free()
+
+
+# ---- 3. biglm ---------------------------------------------------------------------------------------------------------------------
+def test_biglm_on_negative_costs(gold, oracle):  # noqa: F811
+    """tests/test_gpu_biglm.py::test_ngram_pair_equals_the_fixed_mode_oracle over its golden graph with the scores shifted by +4
+    (LM differences of either sign added to negative path costs): best path for every golden configuration and mode, and the
+    raw lattice of the lattice decoder mid-utterance and after FinalizeDecoding; oracle: fixed DiffArpaLm, order-free."""
+    from test_gpu_biglm import _beam_only, _decode, _same
+
+    G, meta = gold["G"], gold["meta"]
+    utts = [S.shifted(u, S.SHIFTS["negative"]) for u in gold["utts"]]
+    mats = [u[: 40 - 7 * i] for i, u in enumerate(utts)]   # ragged lengths
+    old, new = gold["lms"]["ngram"]
+    h = oracle.load_graph(gold["gpath"])
+    o1 = pyoracle.Lm(oracle, gold["lm_paths"][("ngram", "old")], -1.0)
+    o2 = pyoracle.Lm(oracle, gold["lm_paths"][("ngram", "new")], 1.0)
+    n_ok = n_lat = 0
+    try:
+        oracle.set_order_free(True)
+        for cd in meta["cfgs"]:
+            for md in meta["modes"]:
+                md = dict(md)
+                md.pop("trace", None)
+                res = _decode(G, gold["graph"], cd, mats, old, new, **md)
+                for i, (r, ll) in enumerate(zip(res, mats)):
+                    o = pyoracle.biglm_decode(oracle, h, pyoracle.Config(**cd), o1, o2, ll, gold["m"], fixed=True, **md)
+                    assert o.extra["lm_oob"] == 0 and o.extra["ties"] == 0
+                    _same(r, o, "%s %s utt %d" % (cd, md, i))
+                    assert not o.ok or o.tot_score < 0
+                    n_ok += int(o.ok)
+        for cd in [c for c in meta["cfgs"] if _beam_only(c)] + [dict(beam=13.0, max_active=1000000, min_active=0, lattice_beam=25.0)]:
+            cd = dict(cd, prune_interval=7)
+            dec = G.wfstdec.BatchDecoder(gold["graph"], G.gpu_config(cd), len(mats), old_lm=old, new_lm=new, max_frames=64,
+                                         max_tokens_per_frame=32768, arena_tokens=1 << 20, lattice_links=1 << 21)
+            try:
+                dev = G.upload(mats)
+                ptrs = [t.data_ptr() for t in dev]
+                dec.init()
+                dec.advance(ptrs, [min(20, x.shape[0]) for x in mats], int(mats[0].shape[1]))
+                for i, ll in enumerate(mats):
+                    k = min(20, ll.shape[0])
+                    O = pyoracle.biglm_raw_lattice(oracle, h, pyoracle.Config(**cd), o1, o2, ll[:k], gold["m"], finalize=False, use_final_probs=False, fixed=True)
+                    d = dec.raw_lattice(i, use_final_probs=False)
+                    assert (d is not None) == bool(O.ok)
+                    if d is not None:
+                        _same_lattice(d, O, "%s utt %d at frame %d" % (cd, i, k))
+                        n_lat += 1
+                dec.advance(ptrs, [int(x.shape[0]) for x in mats], int(mats[0].shape[1]))
+                dec.finalize()
+                best = dec.best_paths()
+                for i, ll in enumerate(mats):
+                    o = pyoracle.biglm_decode(oracle, h, pyoracle.Config(**cd), o1, o2, ll, gold["m"], fixed=True)
+                    assert o.extra["ties"] == 0
+                    _same(G.GpuResult(best[i]), o, "%s utt %d lattice decoder" % (cd, i))
+                    O = pyoracle.biglm_raw_lattice(oracle, h, pyoracle.Config(**cd), o1, o2, ll, gold["m"], fixed=True)
+                    d = dec.raw_lattice(i)
+                    assert (d is not None) == bool(O.ok)
+                    if d is not None:
+                        _same_lattice(d, O, "%s utt %d" % (cd, i))
+                        n_lat += 1
+            finally:
+                dec.free()
+    finally:
+        oracle.set_order_free(False)
+        oracle.free_graph(h)
+        o1.free()
+        o2.free()
+    assert n_ok >= 20 and n_lat >= 8, (n_ok, n_lat)
+
+
+# ---- 4. result getters ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lattice", [False, True])
+def test_words_on_crossing_costs(world, lattice):
+    """words, word times, total and LM score in one launch, bit for bit against the host restatement of tests/test_gpu_words.py,
+    mid-utterance and final; and the total is the oracle's (a running float32 sum that changes sign on the way)."""
+    from test_gpu_words import run_workload
+
+    G = world.G
+    cd = dict(S.BEAM_ONLY, prune_interval=10)
+    mats = world.mats["crossing"]
+    dec = world.W.BatchDecoder(world.graph, G.gpu_config(cd), len(mats), **(LAT if lattice else LIM))
+    try:
+        seen = run_workload(G, dec, mats, 10, "crossing")
+        got = dec.words()
+    finally:
+        dec.free()
+    assert all(e[3] > 0 and len(e[0]) > 0 for _, e in seen[-len(mats):])
+    for ui, x in enumerate(mats):
+        o = world.decode(x, cd, ("crossing", ui))
+        assert np.array_equal(got[ui][0], o.words) and bits([got[ui][3], got[ui][4]]).tolist() == bits([o.tot_score, o.lm_score]).tolist(), "utt %d" % ui
+
+
+@pytest.mark.parametrize("lattice", [False, True])
+def test_partial_on_crossing_costs(world, lattice):
+    """partial words after every chunk of 7 equal the oracle's prefix decode; the stable prefix is never retracted and is a prefix
+    of the final words (the commit token is found by walking best-cost backpointers whose costs change sign)."""
+    from test_gpu_partial import stream
+
+    G = world.G
+    cd = dict(S.BEAM_ONLY, prune_interval=10)
+    mats = world.mats["crossing"]
+
+    def check(c, fr, words, ns, sf):
+        po = world.decode(mats[c][:fr], cd, ("crossing", c, fr, "partial"), finalize=False, use_final_probs=False)
+        assert np.array_equal(words, po.words), "channel %d @%d: partial words != the oracle's" % (c, fr)
+        assert sf < max(fr, 1)
+
+    dec = world.W.BatchDecoder(world.graph, G.gpu_config(cd), len(mats), **(LAT if lattice else LIM))
+    try:
+        hist, fin, _ = stream(G, dec, mats, 7, S.N_PDF, check)
+    finally:
+        dec.free()
+    committed = 0
+    for c, x in enumerate(mats):
+        o = world.decode(x, cd, ("crossing", c))
+        hist[c].check_final(o.words, "the oracle's final words")
+        assert np.array_equal(fin[c], o.words)
+        committed += hist[c].calls[-1][2]
+    assert committed > 0, "nothing was ever committed: the safety checks were vacuous"
+
+
+@pytest.mark.parametrize("lattice", [False, True])
+def test_endpoint_on_crossing_costs(world, lattice):
+    """EndpointDetected after every chunk of 10: the relative final cost (a difference of two costs of possibly different sign)
+    bit for bit against the oracle's token dump and the decoder's own frontier, trailing silence against the oracle's path, the
+    rule against the engine of tests/test_endpoint_rules.py."""
+    from test_endpoint_rules import rule_py
+    from test_gpu_endpoint import INF, ep_cfg, trailing_of
+
+    G, W = world.G, world.W
+    cd = dict(S.BEAM_ONLY, prune_interval=10)
+    cfg_o = pyoracle.Config(**cd)
+    mats = world.mats["crossing"]
+    T = [int(x.shape[0]) for x in mats]
+    rng = np.random.default_rng(5)
+    sil = set(int(v) for v in rng.choice(np.arange(1, S.GRAPH["n_tid"] + 1), S.GRAPH["n_tid"] // 2, replace=False))
+    cfg = ep_cfg(W, sil, fs=0.1, rules={1: dict(max_relative_cost=INF)})
+    dec = W.BatchDecoder(world.graph, G.gpu_config(cd), len(mats), **(LAT if lattice else LIM))
+    dev = G.upload(mats)
+    final = world.g.final_state
+    finite = neg_best = 0
+    try:
+        dec.set_endpoint_config(cfg)
+        dec.init()
+        for r in range(10, max(T) + 10, 10):
+            ready = [min(r, t) for t in T]
+            dec.advance([t.data_ptr() for t in dev], ready, S.N_PDF)
+            det, rule, tr, rl = dec.endpoint()
+            for c, x in enumerate(mats):
+                nd = ready[c]
+                o = world.decode(x[:nd], cd, ("crossing", c, nd, "partial"), finalize=False, use_final_probs=False)
+                dmp = world.oracle.decode(world.h, cfg_o, x[:nd], world.m, finalize=False, use_final_probs=False, trace=True, dump_frame=nd, dump_cap=1 << 18)
+                st, co, n = dmp.dump
+                assert n == len(st)
+                fin = co[st == final]
+                rel = np.float32(INF) if len(fin) == 0 else np.float32(np.float32(fin.min()) - np.float32(dmp.frame_best[nd]))
+                what = "channel %d frame %d" % (c, nd)
+                assert bits([rl[c]]) == bits([rel]), what + " relative cost vs oracle"
+                fst, fco = dec.frontier(c)
+                ffin = fco[fst == final]
+                own = np.float32(INF) if len(ffin) == 0 else np.float32(np.float32(ffin.min()) - np.float32(fco.min()))
+                assert bits([rl[c]]) == bits([own]), what + " relative cost vs frontier"
+                assert rule[c] == rule_py(cfg, nd, tr[c], rl[c]) and det[c] == (rule[c] != 0), what
+                if not o.extra["ties"]:
+                    assert tr[c] == trailing_of(o.path_ilabel, sil), what + " trailing silence vs oracle"
+                finite += int(rel != np.float32(INF))
+                neg_best += int(dmp.frame_best[nd] < 0)
+        dec.finalize()
+    finally:
+        dec.free()
+    assert finite >= 3 and neg_best >= 3, (finite, neg_best)
+
+
+# ---- 5. the natural entry ---------------------------------------------------------------------------------------------------------
+def test_f16_chunks_with_priors_on_negative_costs(world):
+    """set_score_transform(0.1, prior) + advance_chunk with float16 raw scores y = f16(x / 0.1 + prior), x the `negative`
+    matrices: scores() is the host transform (float32(y) - prior) * 0.1 bit for bit (positive values, unlike every other ingest
+    test), and the decode equals `advance` on those matrices and the oracle's."""
+    import torch
+
+    G, W = world.G, world.W
+    prior = np.random.RandomState(20).normal(-5.0, 1.5, S.N_PDF).astype(np.float32)
+    raw, host = [], []
+    for x in world.mats["negative"]:
+        y = torch.from_numpy((x / np.float32(0.1) + prior).astype(np.float32)).to(torch.float16)
+        raw.append(y.to("cuda:0"))
+        host.append(((y.float().numpy() - prior) * np.float32(0.1)).astype(np.float32))
+    T = [int(x.shape[0]) for x in host]
+    assert all((h > 0).mean() > 0.8 and np.abs(h - x).max() < 2e-3 for h, x in zip(host, world.mats["negative"]))
+    want = G.decode_batch(world.graph, S.BEAM_ONLY, host, limits=LIM)
+    dec = W.BatchDecoder(world.graph, G.gpu_config(S.BEAM_ONLY), len(raw), **LIM)
+    try:
+        dec.set_score_transform(0.1, prior)
+        dec.init()
+        for r0 in range(0, max(T), 7):
+            dec.advance_chunk([y[r0: r0 + 7] if r0 < t else None for y, t in zip(raw, T)])
+        dec.finalize()
+        got = [G.GpuResult(d) for d in dec.best_paths()]
+        for c in range(len(raw)):
+            assert np.array_equal(bits(dec.scores(c, 0, T[c])), bits(host[c])), "ingested scores of channel %d" % c
+    finally:
+        dec.free()
+    for c, (y, x) in enumerate(zip(got, want)):
+        assert y.ok and x.ok
+        G.assert_same_path(y, x.words, x.tids, x.path_ilabel, x.path_olabel, x.path_graph, x.path_ac, [x.tot_score, x.lm_score], "channel %d against advance" % c)
+        o = world.decode(host[c], S.BEAM_ONLY, ("f16", c))
+        assert o.ok and o.tot_score < -100.0
+        _check(G, y, o, "channel %d against the oracle" % c)
+
+
+# ---- 6. signed graph weights ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("negative_eps", [False, True])
+def test_signed_graph_weights(negative_eps, synth, oracle, tmp_path):
+    """tests/test_gpu_fuzz.py's random graphs with 1.0 taken off every emitting arc weight and log-likelihoods N(mu, 1), mu in
+    {-0.5, 0, +1}: path costs of both signs from graph weights alone.  negative_eps = False: closures must still be fused
+    (staged == 1) wherever random_graph's own weights allow it -- one of the eight graphs has a closure beyond the fusing limits
+    whatever its weights.  negative_eps = True: 1.0 off the final costs and 0.5 off the forward epsilon weights as well;
+    wfst_graph_load must then fall back to unfused rows (staged == 0: a fused closure tests an arrival once, which stands for
+    every hop only if no epsilon weight is negative).  A final cost is an epsilon arc of the flat format, so the negative final
+    costs belong to the second block: with them the first could not stay fused.
+
+    Per case: best path (fused / unfused best-path decoder and the lattice decoder) and raw lattice against the order-free
+    oracle; the reference's own, visiting-order dependent result may differ only on a parallel-arc hop, as in the fuzzer.  (The
+    oracle equals the compiled reference on these graphs in both blocks:
+    tests/test_oracle_vs_reference.py::test_oracle_matches_reference_on_random_graphs_with_signed_weights.)"""
+    import gpu_util as G
+
+    W = G.wfstdec
+    rng = np.random.default_rng(int(os.environ.get("WFST_FUZZ_SEED", "1234")) + 9000 + int(negative_eps))
+    n_cases = n_exact = n_lat = n_neg = n_tied = n_ref_diff = n_fusable = 0
+    for case in range(8):
+        n_states = int(rng.integers(4, 70))
+        n_labels = int(rng.integers(3, 12))
+        g, g0 = S.signed_graph(synth, rng, n_states, n_labels, negative_eps)
+        path = str(tmp_path / ("g%d.bin" % case))
+        g.write(path)
+        graph = W.Graph.load(path)
+        g0.write(path + ".plain")
+        graph0 = W.Graph.load(path + ".plain")
+        probe = W.BatchDecoder(graph0, G.gpu_config(dict(beam=8.0)), 1, max_frames=8, max_tokens_per_frame=256, arena_tokens=4096)
+        fusable = probe.path_flags()["staged"]   # (with random_graph's own weights)
+        probe.free()
+        graph0.free()
+        n_fusable += fusable
+        ho = oracle.load_graph(path)
+        binding = case >= 4
+        cd = dict(beam=float(rng.uniform(3.0, 14.0)), max_active=int(rng.choice([40, 12, 25])) if binding else 1000000,
+                  min_active=int(rng.choice([0, 5, 9])) if binding else 0,
+                  lattice_beam=float(rng.uniform(0.5, 8.0)), prune_interval=int(rng.integers(3, 30)))
+        mu = float(rng.choice([-0.5, 0.0, 1.0]))
+        lens = [int(rng.integers(1, 45)) for _ in range(int(rng.integers(1, 6)))]
+        mats = [rng.normal(mu, 1.0, size=(T, n_labels + 1)).astype(np.float32) for T in lens]
+        dev = G.upload(mats)
+        bp = W.BatchDecoder(graph, G.gpu_config(cd), len(mats), max_frames=64, max_tokens_per_frame=4096, arena_tokens=1 << 16)
+        lat = W.BatchDecoder(graph, G.gpu_config(cd), len(mats), max_frames=64, max_tokens_per_frame=4096, arena_tokens=1 << 16, lattice_links=1 << 18)
+        try:
+            for dec in (bp, lat):
+                _stream(dec, dev, lens, n_labels + 1, 7)
+                dec.finalize()
+            assert bp.path_flags()["staged"] == (0 if negative_eps else fusable), "case %d: %s" % (case, bp.path_flags())
+            assert lat.path_flags()["staged"] == bp.path_flags()["staged"]
+            best, best_lat = bp.best_paths(), lat.best_paths()
+            for i, x in enumerate(mats):
+                what = "negative_eps %d case %d utt %d (states %d, T %d, beam %.2f, mu %.1f)" % (negative_eps, case, i, n_states, lens[i], cd["beam"], mu)
+                ref_mode = oracle.decode(ho, pyoracle.Config(**cd), x, None)
+                try:
+                    oracle.set_order_free(True)
+                    o = oracle.decode(ho, pyoracle.Config(**cd), x, None)
+                    O = pyoracle.oracle_raw_lattice(oracle, ho, pyoracle.Config(**cd), x, None)
+                finally:
+                    oracle.set_order_free(False)
+                assert bool(best[i]["ok"]) == bool(best_lat[i]["ok"]) == bool(o.ok) == bool(ref_mode.ok), what
+                n_cases += 1
+                if o.ok and o.extra["ties"] == 0:
+                    for kind, b in (("best-path", best[i]), ("lattice", best_lat[i])):
+                        G.assert_same_as_oracle(G.GpuResult(b), o, what + " " + kind + " decoder")
+                    n_exact += 1
+                    n_neg += int(o.tot_score < 0)
+                    same_as_ref = np.array_equal(o.tids, ref_mode.tids) and np.array_equal(o.words, ref_mode.words)
+                    n_ref_diff += int(not same_as_ref and not binding)
+                    if not same_as_ref and not binding:  # only where parallel arcs are in play, and never in length
+                        assert ref_mode.extra["quirk_hops"] + o.extra["quirk_hops"] > 0 and len(o.tids) == len(ref_mode.tids), what
+                elif o.ok:
+                    n_tied += 1
+                    assert len(best[i]["tids"]) == len(o.tids) and abs(best[i]["tot_score"] - o.tot_score) <= 1e-4 * max(1.0, abs(o.tot_score)), what
+                d = lat.raw_lattice(i)
+                assert (d is not None) == O.ok, what
+                if d is not None:
+                    _same_lattice(d, O, what)
+                    n_lat += 1
+        finally:
+            bp.free()
+            lat.free()
+            oracle.free_graph(ho)
+            graph.free()
+    if "WFST_FUZZ_SEED" not in os.environ:
+        assert n_cases >= 12 and n_exact >= 8 and n_lat >= 8 and n_neg >= 4, (n_cases, n_exact, n_lat, n_neg)
+        assert n_fusable >= 6, "%d of 8 graphs fusable before their weights changed: the block checks little" % n_fusable
+    assert n_tied <= max(1, n_cases // 10) and n_ref_diff <= max(2, n_cases // 8), (n_tied, n_ref_diff, n_cases)
+
+
+# ---- 7. exact zero ----------------------------------------------------------------------------------------------------------------
+def zero_case(synth):
+    """A 6-state graph with zero-weight arcs and 14 frames whose column 1 is exactly 0.0 (or -0.0) for the first eight: the best
+    token sits on state 1's zero-weight self loop at exactly +0.0 while the other tokens drift away from zero on both sides of
+    their start -- one of them (state 3's loop, +0.3 a frame) undercuts it from frame 8 on, and the best cost is negative."""
+    g = synth.graph_from_arc_lists(
+        6, 0,
+        {
+            0: [(1, 0, 0.0, 1), (2, 7, 0.5, 2)],
+            1: [(1, 0, 0.0, 1), (2, 8, 0.25, 3), (0, 0, 0.0, 4)],
+            2: [(2, 0, 0.3, 2), (3, 9, 0.0, 3)],
+            3: [(3, 0, 0.0, 3), (1, 0, 0.75, 1), (0, 10, 0.5, 5)],
+            4: [(4, 11, 0.0, 4), (2, 0, 0.125, 1)],
+            5: [(2, 0, 0.2, 5), (4, 12, 0.0, 3)],
+        },
+        {3: 0.0, 4: 1.0, 5: 0.25},
+    )
+    ll = np.zeros((14, 5), np.float32)
+    ll[:, 2], ll[:, 3], ll[:, 4] = -1.0, 0.3, -0.6
+    ll[3, 1] = ll[5, 1] = -0.0
+    ll[8:, 1] = -0.4
+    return g, ll
+
+
+def test_exact_zero_costs(synth, oracle, tmp_path):
+    import gpu_util as G
+
+    g, ll = zero_case(synth)
+    path = str(tmp_path / "z.bin")
+    g.write(path)
+    graph = G.wfstdec.Graph.load(path)
+    ho = oracle.load_graph(path)
+    try:
+        wide = dict(beam=13.0, max_active=1000, min_active=0, lattice_beam=8.0, prune_interval=5)
+        t = oracle.decode(ho, pyoracle.Config(**wide), ll, None, trace=True)
+        zeros = [f for f in range(1, len(ll) + 1) if bits([t.frame_best[f]])[0] == 0]
+        assert len(zeros) >= 5 and (t.frame_best[1:] < 0).any(), t.frame_best   # (+0.0, bit for bit, on five frames and more)
+        for cd in (wide, dict(wide, max_active=2), dict(wide, beam=0.5, lattice_beam=0.25)):
+            for T in (len(ll), 1):
+                x = ll[:T]
+                try:
+                    oracle.set_order_free(True)
+                    o = oracle.decode(ho, pyoracle.Config(**cd), x, None)
+                    O = pyoracle.oracle_raw_lattice(oracle, ho, pyoracle.Config(**cd), x, None)
+                finally:
+                    oracle.set_order_free(False)
+                what = "%s T %d" % (cd, T)
+                assert o.ok and o.extra["ties"] == 0, what
+                r = G.decode_batch(graph, cd, [x], trace=True, limits=dict(max_frames=32, max_tokens_per_frame=4096, arena_tokens=1 << 14))[0]
+                G.assert_same_as_oracle(r, o, what)
+                if cd is wide and T > 1:
+                    assert np.array_equal(bits(r.frame_best), bits(t.frame_best)), what + " best cost per frame (the sign of zero included)"
+                dec = G.wfstdec.BatchDecoder(graph, G.gpu_config(cd), 1, max_frames=32, max_tokens_per_frame=4096, arena_tokens=1 << 14, lattice_links=1 << 14)
+                try:
+                    rl = G.decode_batch(graph, cd, [x], dec=dec)[0]
+                    G.assert_same_as_oracle(rl, o, what + " lattice decoder")
+                    _same_lattice(dec.raw_lattice(0), O, what)
+                finally:
+                    dec.free()
+    finally:
+        oracle.free_graph(ho)
+        graph.free()

@@ -84,3 +84,67 @@ def test_oracle_matches_reference_on_random_graphs(block, oracle, refdec, synth,
         refdec.free_graph(hr)
         oracle.free_graph(ho)
     assert n >= 10
+
+
+@pytest.mark.parametrize("ci", range(len(CFGS)))
+@pytest.mark.parametrize("shift", ["crossing", "negative"])
+def test_oracle_matches_reference_on_negative_and_zero_crossing_costs(shift, ci, oracle, refdec, synth, tmp_path):
+    """The workloads of tests/signed_util.py (path costs that change sign from frame to frame, or are negative throughout): the
+    oracle's comparisons, minima and cutoffs run over floats of both signs there, as the reference's do."""
+    import signed_util as S
+
+    g, m, mats = S.workloads(synth)
+    path = str(tmp_path / "g.bin")
+    g.write(path)
+    hr, ho = refdec.load_graph(path), oracle.load_graph(path)
+    cfg = pyoracle.Config(**CFGS[ci])
+    for ll in mats[shift]:
+        for kw in (dict(trace=True), dict(chunk=0), dict(chunk=11, finalize=False),
+                   dict(chunk=0, finalize=False, use_final_probs=False)):
+            r = refdec.decode(hr, cfg, ll, m, **kw)
+            _same(r, oracle.decode(ho, cfg, ll, m, **kw))
+            if "trace" in kw and shift == "crossing" and CFGS[ci]["beam"] >= 10.0:   # (a beam of 4 loses the planted path early)
+                assert S.sign_changes(r.frame_best) >= 3
+            if "trace" in kw and shift == "negative":
+                assert (r.frame_best[1:] < 0).all()
+    refdec.free_graph(hr)
+    oracle.free_graph(ho)
+
+
+@pytest.mark.parametrize("negative_eps", [False, True])
+@pytest.mark.parametrize("block", range(2))
+def test_oracle_matches_reference_on_random_graphs_with_signed_weights(block, negative_eps, oracle, refdec, synth, tmp_path):
+    """test_oracle_matches_reference_on_random_graphs over graphs with negative emitting weights and, negative_eps, negative
+    final costs and epsilon weights as well (signed_util.signed_graph), log-likelihoods N(mu, 1) with mu of either sign."""
+    import signed_util as S
+
+    rng = np.random.default_rng(int(os.environ.get("WFST_FUZZ_SEED", "4321")) + block)
+    n = n_neg = 0
+    for case in range(8):
+        n_states = int(rng.integers(4, 70))
+        n_labels = int(rng.integers(3, 12))
+        g, _ = S.signed_graph(synth, rng, n_states, n_labels, negative_eps)
+        path = str(tmp_path / ("g%d.bin" % case))
+        g.write(path)
+        hr, ho = refdec.load_graph(path), oracle.load_graph(path)
+        cd = dict(beam=float(rng.uniform(3.0, 14.0)), max_active=int(rng.choice([1000000, 40, 12])), min_active=int(rng.choice([0, 5])),
+                  lattice_beam=float(rng.uniform(0.5, 8.0)), prune_interval=int(rng.integers(3, 30)))
+        cfg = pyoracle.Config(**cd)
+        mu = float(rng.choice([-0.5, 0.0, 1.0]))
+        for T in (int(rng.integers(1, 45)), int(rng.integers(1, 45))):
+            x = rng.normal(mu, 1.0, size=(T, n_labels + 1)).astype(np.float32)
+            r = refdec.decode(hr, cfg, x, None, chunk=0)
+            if not r.ok:       # the reference aborts in PruneForwardLinks when every token died; skip those
+                continue
+            _same(r, oracle.decode(ho, cfg, x, None, chunk=0))
+            R = pyoracle.ref_raw_lattice(refdec, hr, cfg, x, None)
+            O = pyoracle.oracle_raw_lattice(oracle, ho, cfg, x, None)
+            assert R.ok == O.ok
+            if R.ok:
+                assert (R.n_states, int(R.st_final.sum())) == (O.n_states, int(O.st_final.sum()))
+                assert np.array_equal(R.arc_multiset(), O.arc_multiset())
+            n += 1
+            n_neg += int(r.tot_score < 0)
+        refdec.free_graph(hr)
+        oracle.free_graph(ho)
+    assert n >= 8 and n_neg >= 3, (n, n_neg)
