@@ -168,6 +168,12 @@ __host__ __device__ inline uint32_t pack_code(uint32_t n_eps, uint32_t n_emit, u
 __host__ __device__ inline uint32_t flags_of(uint32_t next_eps) {
   return (next_eps & kFlagOutEps) | ((next_eps & 0x7FFFFFFFu) ? kFlagEpsTarget : 0u);
 }
+// THE TIE RULE (deviation 3).  Of the arrivals at a token that equal its final cost bit for bit the winner is
+// the least under (emitting arc before epsilon arrival, then row index of the arc -- of a fused or flattened path: of its last arc);
+// rows are in file order (states ascending, a state's arcs as uploaded, epsilon arcs first).  That is the low word of every packed
+// (f2o(cost) << 32 | ...) minimum: kEpsRec / kEpsWon sit above the arc index, the other bits beside it depend on the target state
+// alone.  The best path ends in the cheapest token, then the lowest row, biglm then the lowest pair_keys[] value (bp_frontier).
+// biglm, equal (cost, arc) from several source tokens: the lowest source pair_keys[] value (insert pass 1b, bp_scan_eps_pred).
 constexpr uint32_t kEpsRec = 0x20000000u;          // in a candidate record / token: an epsilon arrival (fused closures)
 constexpr uint32_t kArcMask = ~(kFlagMask | kEpsRec);  // arc (row) indices are < 2^29
 constexpr uint32_t kNoArc = kArcMask;              // "no arc" (root token), flags kept beside it

@@ -1413,6 +1413,67 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
     // (kTwo: the frame's tokens as a raw buffer -- base = the frame's first token, 2 GB of range; dword 3 as for any raw 32-bit buffer)
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t tok_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(tok + base), 0, 0x7FFFFFF0, 0x00020000);
 
+    // pass 1b (biglm): the same packed (cost | arc) value from SEVERAL source tokens -- two tokens of one graph state whose LM
+    // histories cost the same, merged by back-off into one LM pair -- goes to the lowest source pair key (pair_keys[]: the LM states
+    // themselves; pair ids are interned by atomicAdd and token indices are arena order, neither is stable).  The records that hold
+    // a slot's minimum put their source pair key through a second minimum on the slot itself (emptied for it, restored by the
+    // winner), and only that record may claim the slot in pass 2.  An item of more than one sweep (a single bucket beyond
+    // joint_max; no planned item is) keeps the bare claim: one of the tied sources.
+    bool big_win[kInsertUnroll];
+#pragma unroll
+    for (int k = 0; k < kInsertUnroll; ++k) big_win[k] = false;
+    if constexpr (kBig) {
+      if (one_sweep) {   // (uniform)
+        const u64 *pkeys = D.pair_keys + (size_t)c * D.pair_cap;
+        const int32_t *src_lm = D.tok_lm + (size_t)c * D.arena_cap;
+        const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);
+        int bslot[kInsertUnroll];
+        u64 bspk[kInsertUnroll], bpacked[kInsertUnroll];
+#pragma unroll
+        for (int k = 0; k < kInsertUnroll; ++k) {
+          bslot[k] = -1; bspk[k] = 0ull; bpacked[k] = 0ull;
+          if (!(__int_as_float(r[k].y) < cutoff)) continue;
+          const uint32_t h = hash_of(r[k], rl[k]);
+          if (log2sub && (int)((h >> sub_shift) & ((1u << log2sub) - 1u)) != sub) continue;
+          const u64 packed = ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w;
+          uint32_t slot = lds_slot_of(h, log2grp, log2sl);
+          const KeyT key = key_of(r[k], rl[k]);
+          for (int q = 0; q < SL; ++q) {
+            const KeyT kk = keys[slot];
+            if (kk == key) {
+              if (vals[slot] == packed) {
+                const uint32_t src = (uint32_t)r[k].z & idx_mask;
+                const int32_t sp = src < (uint32_t)D.arena_cap ? src_lm[src] : -1;
+                bslot[k] = (int)slot;
+                bpacked[k] = packed;
+                bspk[k] = (sp >= 0 && sp < D.pair_cap) ? ld_agent(&pkeys[sp]) : 0ull;
+              }
+              break;
+            }
+            if (kk == kNoKey) break;
+            slot = (slot + 1) & mask;
+          }
+        }
+        __syncthreads();   // every holder of a minimum knows itself
+#pragma unroll
+        for (int k = 0; k < kInsertUnroll; ++k)
+          if (bslot[k] >= 0) vals[bslot[k]] = kEmptyVal;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kInsertUnroll; ++k)
+          if (bslot[k] >= 0) atomicMin(&vals[bslot[k]], bspk[k]);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kInsertUnroll; ++k)
+          if (bslot[k] >= 0) big_win[k] = vals[bslot[k]] == bspk[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kInsertUnroll; ++k)
+          if (big_win[k]) vals[bslot[k]] = bpacked[k];   // (as pass 1 left it: pass 2 claims it)
+        __syncthreads();
+      }
+    }
+
     // pass 2: the record that won its state writes the token
     // (lattice mode: an item that fits one sweep -- every planned item does -- keeps each live
     // record's {source token, arc, cost} and LDS slot in registers for pass 3)
@@ -1447,7 +1508,8 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
                 // biglm likewise: two tokens of ONE graph state (different LM pairs) whose histories have cost the same take the same
                 // arc into the same LM pair (back-off merges them) at the same cost -- the same packed value twice.  Both "won", the
                 // item wrote one token more than the keys it had counted, over its neighbour's first (found by a fuzz seed, round 6).
-                winner = vals[slot] == packed && (!(kFused || kBig) || atomicCAS(&vals[slot], packed, packed | 0xFFFFFFFFull) == packed);
+                winner = vals[slot] == packed && (!(kBig && one_sweep) || big_win[k]) &&
+                         (!(kFused || kBig) || atomicCAS(&vals[slot], packed, packed | 0xFFFFFFFFull) == packed);
                 in_table = true;
                 break;
               }
@@ -4125,8 +4187,11 @@ __device__ __forceinline__ const int32_t *bp_stage_foff(const DecoderDev &D, int
   return s_foff;
 }
 
-// The frontier reduction: minima over the n tokens from fb on, packed (f2o(cost) << 32 | arena index) so that a tie goes to the
-// lower index; ~0: none.  kWhat says how many are wanted:
+// The frontier reduction: minima over the n tokens from fb on, returned as (f2o(cost) << 32 | arena index); ~0: none.  A tie on
+// the cost goes to the lowest graph row (rows ascend with the states), biglm then to the lowest LM pair key (pair_keys[]: old LM
+// state | new LM state << 32) -- a frame holds one token per (row[, pair]), so the answer names one token whatever order the
+// insert workgroups took their arena slots in (the arena index rides beside the key, it is never compared).  kWhat says how many
+// are wanted:
 //   kFrAll  all: the cheapest token (BestPathEnd(use_final_probs = false));
 //   kFrFin  + fin: the cheapest token on the super-final state (IsFinal, optimize-fst.h:189-192; final weight One);
 //   kFrWf   + wf: biglm -- costs carry the LM's final cost (ComputeFinalCosts, biglm.h:160-215; diff-lm.h:48-53): fin with it, and
@@ -4136,44 +4201,65 @@ __device__ __forceinline__ const int32_t *bp_stage_foff(const DecoderDev &D, int
 enum { kFrAll = 0, kFrFin = 1, kFrWf = 2 };
 struct BpFrontier { u64 all, fin, wf; };
 template <int kWhat>
-struct BpFrontierLds { u64 v[kWhat + 1][kBpThreads / 64]; };
+struct BpFrontierLds { u64 v[kWhat + 1][kBpThreads / 64], pk[kWhat + 1][kBpThreads / 64]; uint32_t idx[kWhat + 1][kBpThreads / 64]; };
 template <int kWhat, class F>
 __device__ __forceinline__ BpFrontier bp_frontier(const DecoderDev &D, int c, const int4 *tok, const int32_t *tok_lm, int fb, int n,
                                                   BpFrontierLds<kWhat> *lds, F &&per_token) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  u64 b[3] = {~0ull, ~0ull, ~0ull};
+  u64 b[3] = {~0ull, ~0ull, ~0ull}, bk[3] = {~0ull, ~0ull, ~0ull};   // (cost << 32 | row), pair key
+  uint32_t bi[3] = {0u, 0u, 0u};                                     // the arena index that goes with them
+  auto take = [&](int j, u64 v, u64 pk, uint32_t idx) {
+    if (v < b[j] || (v == b[j] && pk < bk[j])) { b[j] = v; bk[j] = pk; bi[j] = idx; }
+  };
   for (int i = tid; i < n; i += kBpThreads) {
     const int4 t = tok[fb + i];
-    const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)(fb + i);
-    b[0] = v < b[0] ? v : b[0];
+    const uint32_t idx = (uint32_t)(fb + i);
     if constexpr (kWhat == kFrWf) {
       const u64 pk = D.pair_keys[(size_t)c * D.pair_cap + tok_lm[fb + i]];
+      take(0, ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)t.x, pk, idx);
       const float lm_final = lm_final_cost(D.lm_old, (int)(uint32_t)pk) + lm_final_cost(D.lm_new, (int)(uint32_t)(pk >> 32));
-      const u64 w = ((u64)f2o(__int_as_float(t.y) + lm_final) << 32) | (uint32_t)(fb + i);
-      b[2] = w < b[2] ? w : b[2];
-      if (t.x == D.g.final_state) b[1] = w < b[1] ? w : b[1];
-    } else if constexpr (kWhat == kFrFin) {
-      if (t.x == D.g.final_state) b[1] = v < b[1] ? v : b[1];
+      const u64 w = ((u64)f2o(__int_as_float(t.y) + lm_final) << 32) | (uint32_t)t.x;
+      take(2, w, pk, idx);
+      if (t.x == D.g.final_state) take(1, w, pk, idx);
+    } else {
+      const u64 v = ((u64)f2o(__int_as_float(t.y)) << 32) | (uint32_t)t.x;
+      take(0, v, 0ull, idx);
+      if constexpr (kWhat == kFrFin) {
+        if (t.x == D.g.final_state) take(1, v, 0ull, idx);
+      }
     }
     per_token(t, fb + i);
   }
 #pragma unroll
   for (int j = 0; j <= kWhat; ++j) {
-    b[j] = wave_min_u64(b[j]);
-    if (lane == 0) lds->v[j][wave] = b[j];
+    const u64 vmin = wave_min_u64(b[j]);
+    u64 kmin = 0ull;
+    if constexpr (kWhat == kFrWf) kmin = wave_min_u64(b[j] == vmin ? bk[j] : ~0ull);
+    // the lowest lane that holds the minimum publishes its index (a frame has one token per (row[, pair]), so it is the only one
+    // where there is a token at all; the ballot keeps the answer one lane's whatever the caller's arena holds)
+    const u64 holders = __ballot(b[j] == vmin && (kWhat != kFrWf || bk[j] == kmin));
+    if (lane == (int)__ffsll((unsigned long long)holders) - 1) { lds->v[j][wave] = vmin; lds->pk[j][wave] = kmin; lds->idx[j][wave] = bi[j]; }
   }
   __syncthreads();
+  u64 out[3] = {~0ull, ~0ull, ~0ull};
   if (tid == 0) {
 #pragma unroll
-    for (int j = 0; j <= kWhat; ++j)
-      for (int w = 1; w < kBpThreads / 64; ++w) b[j] = lds->v[j][w] < b[j] ? lds->v[j][w] : b[j];
+    for (int j = 0; j <= kWhat; ++j) {
+      u64 v = lds->v[j][0], k = lds->pk[j][0];
+      uint32_t ix = lds->idx[j][0];
+      for (int w = 1; w < kBpThreads / 64; ++w) {
+        const u64 v2 = lds->v[j][w], k2 = lds->pk[j][w];
+        if (v2 < v || (v2 == v && k2 < k)) { v = v2; k = k2; ix = lds->idx[j][w]; }
+      }
+      out[j] = v == ~0ull ? ~0ull : ((v & 0xFFFFFFFF00000000ull) | ix);
+    }
   }
-  return BpFrontier{b[0], b[1], b[2]};
+  return BpFrontier{out[0], out[1], out[2]};
 }
 
 // A token won by an epsilon arc carries kPrevUnresolved; its predecessor is the token of the arc's source state `need` on its
 // own frame [lo, hi), which the whole workgroup looks for (bp_scan_eps_pred, answer in `found`).  LDS; need < 0: nothing asked.
-struct BpScanReq { int need, lo, hi, found; };
+struct BpScanReq { int need, lo, hi, found; u64 best_pk; };   // best_pk (biglm): the lowest pair key among the tokens that qualify
 
 // The walk's lane-0 step: from token t follow resolved backpointers in one go (a dependent load per hop, nothing else on the
 // chain), handing each visited token to sink(t), until the root (-1 returned), the token `stop` (-1: none) or `bound` tokens
@@ -4192,6 +4278,7 @@ __device__ __forceinline__ int bp_follow(const DecoderDev &D, const int4 *tok, c
       rq->hi = foff[fr + 1];
       rq->need = D.g.arc_src[(uint32_t)T.w & kArcMask] & 0x7FFFFFFF;
       rq->found = -1;
+      rq->best_pk = ~0ull;
       break;
     }
     t = T.z >= 0 ? (int)((uint32_t)T.z & idx_mask) : -1;
@@ -4219,8 +4306,10 @@ __device__ __forceinline__ int bp_arc_lm(const DecoderDev &D, int c, const int32
 // biglm: several tokens may sit on the source state, one per LM state -- the one whose LM state and cost lead to t over the arc.
 template <bool kBig>
 __device__ __forceinline__ void bp_scan_eps_pred(const DecoderDev &D, int c, const int4 *tok, const int32_t *tok_lm, int lo, int hi,
-                                                 int need, int t, int *found) {
+                                                 int need, int t, int *found, u64 *best_pk) {
   const int tid = threadIdx.x;
+  [[maybe_unused]] int my_i = -1;        // biglm: this thread's qualifying token of the lowest pair key
+  [[maybe_unused]] u64 my_pk = ~0ull;
   constexpr int kScanU = 4;   // states of the frame in flight per thread
   for (int i0 = lo + tid; i0 < hi; i0 += kBpThreads * kScanU) {
     int sx[kScanU];
@@ -4247,9 +4336,18 @@ __device__ __forceinline__ void bp_scan_eps_pred(const DecoderDev &D, int c, con
         }
         const float tot = __int_as_float(S.y) + (__int_as_float(D.g.arcs[a].z) + lm_score);
         if (nlm != tok_lm[t] || __float_as_int(tot) != T.y) continue;
+        // several tokens may qualify (LM histories of equal cost that back-off merges): the lowest pair key, as in the insert
+        const u64 pk = D.pair_keys[(size_t)c * D.pair_cap + tok_lm[i]];
+        if (pk < my_pk) { my_pk = pk; my_i = i; }
+      } else {
+        *found = i;
       }
-      *found = i;
     }
+  }
+  if constexpr (kBig) {   // (every thread of the workgroup calls: one barrier)
+    if (my_i >= 0) atomicMin(best_pk, my_pk);
+    __syncthreads();
+    if (my_i >= 0 && my_pk == *best_pk) *found = my_i;
   }
 }
 
@@ -4337,7 +4435,7 @@ __device__ __forceinline__ void bp_walk_chunk(const DecoderDev &D, int c, const 
     }
     __syncthreads();
     if (W->rq.need < 0) break;
-    bp_scan_eps_pred<false>(D, c, tok, nullptr, W->rq.lo, W->rq.hi, W->rq.need, W->cur, &W->rq.found);
+    bp_scan_eps_pred<false>(D, c, tok, nullptr, W->rq.lo, W->rq.hi, W->rq.need, W->cur, &W->rq.found, nullptr);
     __syncthreads();
     if (tid == 0) W->tok[W->k] = W->cur = W->rq.found;
     __syncthreads();
@@ -4395,7 +4493,7 @@ __device__ __forceinline__ void bp_walk(const DecoderDev &D, int c, const int4 *
     __syncthreads();
     if (s_rq->need >= 0) {
       if (dbg) ++w.n_unres;
-      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_rq->lo, s_rq->hi, s_rq->need, *s_t, &s_rq->found);
+      bp_scan_eps_pred<kBig>(D, c, tok, tok_lm, s_rq->lo, s_rq->hi, s_rq->need, *s_t, &s_rq->found, &s_rq->best_pk);
       __syncthreads();
       if (tid == 0) *s_t = s_rq->found;  // -1 (never expected) ends the walk
       if (tid == 0 && dbg) w.scan += wall_clock64() - tw0;
@@ -4856,7 +4954,7 @@ __global__ __launch_bounds__(kBpThreads) void partial_kernel(DecoderDev D, const
   // ---- the walk's end: the previous commit token, found by its state on its frame ----------------------------------------------
   int stop = -1;   // (the root)
   if (cf > 0) {
-    bp_scan_eps_pred<false>(D, c, tok, nullptr, foff[cf], foff[cf + 1], cs, 0, &s_w.rq.found);
+    bp_scan_eps_pred<false>(D, c, tok, nullptr, foff[cf], foff[cf + 1], cs, 0, &s_w.rq.found, nullptr);
     __syncthreads();
     stop = s_w.rq.found;
     if (stop < 0) {   // never expected: the commit token is an ancestor of every living token

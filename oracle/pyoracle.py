@@ -190,6 +190,13 @@ class OracleDecoder(_Base):
         (what the GPU computes) instead of the reference's visiting-order-dependent evolving one."""
         self.lib.oracle_set_order_free(int(bool(on)))
 
+    def set_tie_rule(self, rule):
+        """See oracle/wfst_oracle.c `g_tie_rule`: on an exact cost tie the least arrival under (emitting before epsilon, arc
+        index[, source LM pair key]) keeps the backpointer, and the best path ends in the least token under (cost, graph state[, LM
+        pair key]) -- the rule the GPU path follows (deviation 3) -- instead of the reference's first arrival.
+        2: the same with the HIGHEST source LM pair key (biglm; the other end of the set of optimal predecessors: what a wrong source choice would give)."""
+        self.lib.oracle_set_tie_rule(int(rule))
+
     def decode(self, *a, **kw):
         r = super().decode(*a, **kw)
         e = self._tls.extra

@@ -69,6 +69,8 @@ typedef struct Token {
   int lm_state; /* biglm: LM pair state of the token's key */
   int lat_id;   /* lattice state id during GetRawLattice */
   int tie;      /* audit only: an equal-cost rival arrived after this cost was set */
+  uint64_t win_arc; /* tie mode: the winning arrival's (class << 32 | global arc index); class 0 emitting arc, 1 epsilon arc */
+  uint64_t win_src; /* tie mode, biglm: the LM pair key (old LM state | new LM state << 32) of the winning arrival's source token */
 } Token;
 typedef struct { Token *toks; int must_prune_forward_links, must_prune_tokens; } TokenList;
 
@@ -89,6 +91,17 @@ typedef struct PoolBlock { struct PoolBlock *next; } PoolBlock;
 typedef struct { void *free_head; PoolBlock *blocks; size_t elem_size; } Pool;
 
 static int g_order_free = 0; /* see process_emitting and prune_forward_links */
+/* Tie mode (oracle_set_tie_rule): what the GPU path computes on an exact cost tie, stated without any visiting order.
+ * Of the arrivals at a token whose cost equals the token's final cost, the winner is the least under
+ *   (class: emitting arc before epsilon arc; global arc index = the arc's position in the graph file;
+ *    biglm: LM pair key of the source token, old LM state | new LM state << 32),
+ * and BestPathEnd starts from the least token under (cost [+ final cost], graph state, biglm: the token's own LM pair key).
+ * Default 0 = the reference's behaviour: the first arrival keeps the backpointer, the first token of the list the end.
+ * Costs, token sets, links and lattices are the same in both modes; only backpointers and the end token differ. */
+/* 2: as 1, but among arrivals of equal (cost, class, arc) the HIGHEST source pair key -- the other end of the set of optimal
+ * predecessors: the tests use it to show that the source pair key decides (deviation 3). */
+static int g_tie_rule = 0;
+void oracle_set_tie_rule(int rule) { g_tie_rule = rule; }
 
 /* ---- LM automaton: newlm/arpa2fsa.h:22-247; binary file ArpaLm::Read :355-397 + Fsa::Read arpa2fsa.cc:68-176 ---- */
 typedef struct { int wordid; float weight; int tostateid; } FsaArc;
@@ -341,7 +354,7 @@ static inline Key make_key(int state, int lm_state) { return (Key)(uint32_t)stat
 static Token *new_token(Decoder *d, float tot, float extra, Link *links, Token *next, Token *bp) {
   Token *t = (Token *)pool_new(&d->tok_pool);
   t->tot_cost = tot; t->extra_cost = extra; t->links = links; t->next = next; t->backpointer = bp; t->is_final = 0; t->tie = 0;
-  t->final_cost = 0.0f; t->state = -1; t->lm_state = 0; t->lat_id = -1;
+  t->final_cost = 0.0f; t->state = -1; t->lm_state = 0; t->lat_id = -1; t->win_arc = 0; t->win_src = 0; /* (the root: no arrival takes its place) */
   d->num_toks++; d->cnt_tok_created++; return t;
 }
 static Link *new_link(Decoder *d, Token *nt, int il, int ol, float gc, float ac, Link *next) {
@@ -375,21 +388,33 @@ static void clear_active_tokens(Decoder *d) { /* base-inl.h:69-85 */
 }
 
 /* FindOrAddToken: base-inl.h:88-136 */
-static Elem *find_or_add_token(Decoder *d, Key key, int frame_plus_one, float tot_cost, Token *bp, int *changed) {
+static uint64_t lm_pair_key(const Decoder *d, int lm_state) {
+  if (!d->dlm || lm_state < 0 || lm_state >= d->dlm->n_vec) return 0;
+  return (uint64_t)(uint32_t)d->dlm->vec[lm_state][0] | ((uint64_t)(uint32_t)d->dlm->vec[lm_state][1] << 32);
+}
+/* `arc`: the arc of this arrival (tie mode: its class and index decide an exact cost tie, see g_tie_rule) */
+static Elem *find_or_add_token(Decoder *d, Key key, int frame_plus_one, float tot_cost, Token *bp, int *changed, const Arc *arc) {
   Token **toks = &d->active[frame_plus_one].toks;
+  const uint64_t win_arc = ((uint64_t)(arc->ilabel == 0) << 32) | (uint64_t)(arc - d->g->arcs);
+  const uint64_t win_src = g_tie_rule ? lm_pair_key(d, bp->lm_state) : 0;
   Elem *e = hl_insert(&d->toks, key, NULL);
   if (e->val == NULL) {
     Token *nt = new_token(d, tot_cost, 0.0f, NULL, *toks, bp);
     nt->state = KEY_STATE(key); nt->lm_state = KEY_LM(key);
+    nt->win_arc = win_arc; nt->win_src = win_src;
     *toks = nt; e->val = nt;
     if (changed) *changed = 1;
   } else {
     Token *tok = e->val;
-    if (tok->tot_cost > tot_cost) { tok->tot_cost = tot_cost; tok->backpointer = bp; tok->tie = 0; if (changed) *changed = 1; }
+    if (tok->tot_cost > tot_cost) { tok->tot_cost = tot_cost; tok->backpointer = bp; tok->tie = 0; tok->win_arc = win_arc; tok->win_src = win_src; if (changed) *changed = 1; }
     else {
       /* audit only: an equal cost through ANOTHER predecessor is a real tie (first arrival wins here, lowest
        * arc index on the GPU); the same predecessor arriving again is the closure re-processing a token */
       if (tok->tot_cost == tot_cost && tok->backpointer != bp) tok->tie = 1;
+      /* tie mode: the smaller arrival takes the backpointer; the cost did not move, so nothing is requeued */
+      if (g_tie_rule && tok->tot_cost == tot_cost && (win_arc < tok->win_arc || (win_arc == tok->win_arc && (g_tie_rule == 2 ? win_src > tok->win_src : win_src < tok->win_src)))) {
+        tok->backpointer = bp; tok->win_arc = win_arc; tok->win_src = win_src;
+      }
       if (changed) *changed = 0;
     }
   }
@@ -497,7 +522,7 @@ static void process_nonemitting(Decoder *d, float cutoff) {
         float tot_cost = cur_cost + graph_cost;
         if (tot_cost < cutoff) {
           int changed = 0;
-          Elem *nt = find_or_add_token(d, make_key(arc->to, next_lm), frame, tot_cost, tok, &changed);
+          Elem *nt = find_or_add_token(d, make_key(arc->to, next_lm), frame, tot_cost, tok, &changed, arc);
           tok->links = new_link(d, nt->val, 0, arc->olabel, graph_cost, 0, tok->links);
           if (changed && g->si[arc->to].niepsilons != 0) queue_push(d, nt);
         }
@@ -579,7 +604,7 @@ static float process_emitting(Decoder *d) {
           float tot_cost = cur_cost + ac_cost + graph_cost;
           if (tot_cost >= next_cutoff) continue;
           else if (tot_cost + adaptive_beam < next_cutoff) next_cutoff = tot_cost + adaptive_beam;
-          Elem *nt = find_or_add_token(d, make_key(arc->to, next_lm), frame + 1, tot_cost, tok, NULL);
+          Elem *nt = find_or_add_token(d, make_key(arc->to, next_lm), frame + 1, tot_cost, tok, NULL, arc);
           tok->links = new_link(d, nt->val, arc->ilabel, arc->olabel, graph_cost, ac_cost, tok->links);
         }
       }
@@ -854,11 +879,14 @@ static int decode_impl(void *gp, const Config *rc, DiffLm *dlm, const float *log
       float cost = tok->tot_cost;
       if (use_final_probs && any_final) { if (!tok->is_final) cost = FLOAT_INF; else cost += tok->final_cost; }
       if (cost < best_cost) { best_cost = cost; best_tok = tok; }
+      else if (g_tie_rule && best_tok && cost == best_cost && cost != FLOAT_INF &&   /* the end-token rule of g_tie_rule */
+               ((uint32_t)tok->state < (uint32_t)best_tok->state ||
+                (tok->state == best_tok->state && lm_pair_key(d, tok->lm_state) < lm_pair_key(d, best_tok->lm_state)))) best_tok = tok;
     }
     if (best_tok) {
       /* GetBestPath + TraceBackBestPath: base-inl.h:1071-1094,1160-1200.  Hops come out last
        * to first; the lattice is walked start->final by LatticeToVector, i.e. reversed. */
-      int cap = 1024, n = 0;
+      int cap = 1024, n = 0, cyclic = 0;
       int *hi = (int *)malloc(cap * sizeof(int)), *ho = (int *)malloc(cap * sizeof(int));
       float *hg = (float *)malloc(cap * sizeof(float)), *ha = (float *)malloc(cap * sizeof(float));
       for (Token *tok = best_tok; tok;) {
@@ -874,6 +902,7 @@ static int decode_impl(void *gp, const Config *rc, DiffLm *dlm, const float *log
         if (n == cap) { cap *= 2; hi = (int *)realloc(hi, cap * sizeof(int)); ho = (int *)realloc(ho, cap * sizeof(int)); hg = (float *)realloc(hg, cap * sizeof(float)); ha = (float *)realloc(ha, cap * sizeof(float)); }
         hi[n] = il; ho[n] = ol; hg[n] = gc; ha[n] = ac; ++n;
         tok = tok->backpointer;
+        if ((int64_t)n > d->cnt_tok_created + 1) { cyclic = 1; break; } /* tie mode over a zero-cost epsilon cycle: backpointers may close a loop */
       }
       /* LatticeToVector: newfst/lattice-functions.cc:179-217 */
       float tot = 0, lm = 0; int nw = 0, nt = 0;
@@ -886,7 +915,8 @@ static int decode_impl(void *gp, const Config *rc, DiffLm *dlm, const float *log
       }
       *n_path = n; *n_words = nw; *n_tids = nt; *tot_score = tot; *lm_score = lm;
       free(hi); free(ho); free(hg); free(ha);
-      ok = 1;
+      ok = !cyclic; /* (a cyclic chain is no path: the decode fails) */
+      if (cyclic) { *n_path = 0; *n_words = 0; *n_tids = 0; }
     }
   }
   if (extra) { extra[0] = d->cnt_N; extra[1] = d->cnt_E; extra[2] = d->cnt_Z; extra[3] = d->cnt_tok_created; extra[4] = d->cnt_link_created; extra[5] = tie_hops; extra[6] = quirk_hops;
