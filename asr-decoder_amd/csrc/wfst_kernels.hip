@@ -1200,6 +1200,14 @@ constexpr int kInsertThreads = 512;
 #define WFST_INSERT_UNROLL 3
 #endif
 constexpr int kInsertUnroll = WFST_INSERT_UNROLL;   // (1536 records in one sweep: wfst_options.joint_max's default; a fourth record per thread cost five VGPRs at the 80-register limit)
+// a thread's kInsertUnroll table slots (pass 1 -> pass 2) or token positions within the item (claims -> stores), 16 bits apiece:
+// the register budget has no room for one each (a table is at most 2^15 slots: 12 bytes a slot, 160 KB of LDS)
+constexpr uint32_t kNoSlot = 0xFFFFu;
+constexpr int kInsertPk = (kInsertUnroll + 1) / 2;
+__device__ __forceinline__ void put16(uint32_t *p, int k, uint32_t v) {
+  p[k >> 1] = (k & 1) ? (p[k >> 1] & 0xFFFFu) | (v << 16) : (p[k >> 1] & 0xFFFF0000u) | v;
+}
+__device__ __forceinline__ uint32_t get16(const uint32_t *p, int k) { return (k & 1) ? p[k >> 1] >> 16 : p[k >> 1] & 0xFFFFu; }
 
 // insert_kernel: a fixed grid of workgroups pulls the planned items (first gridDim.x statically,
 // then by ticket); 512 threads, dynamic LDS = lds_slots * 12 bytes (16 in lattice mode).
@@ -1365,7 +1373,13 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
     // pass 1: insert-or-min.  Candidates that lost against the final cutoff are dropped here: the
     // reference keeps those order-dependent extras (base-inl.h:330) but never expands them.
     // (an item that fits one sweep -- every planned item does -- keeps its records in registers for pass 2)
+    // (... and, beside each record, the slot it ended on: pass 2 goes straight back to it.  kNoSlot: the record is not in the
+    // table -- at or above the final cutoff, another sub-pass's, a +inf filler)
     const bool one_sweep = n <= kInsertThreads * kInsertUnroll;
+    const bool carry = one_sweep && SL <= 0x8000;   // (uniform)
+    uint32_t cs[kInsertPk];
+#pragma unroll
+    for (int j = 0; j < kInsertPk; ++j) cs[j] = ~0u;
     for (int i0 = 0; i0 < n; i0 += kInsertThreads * kInsertUnroll) {
       if (i0 > 0) {
 #pragma unroll
@@ -1388,8 +1402,10 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
           if (kk == key) { found = true; break; }
           slot = (slot + 1) & mask;
         }
-        if (found) atomicMin(&vals[slot], ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w);
-        else atomicOr(&ctl->error, kErrTableFull);
+        if (found) {
+          atomicMin(&vals[slot], ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w);
+          put16(cs, k, slot & 0xFFFFu);   // (read under `carry` only)
+        } else atomicOr(&ctl->error, kErrTableFull);
       }
     }
     __syncthreads();
@@ -1413,6 +1429,27 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
     // (kTwo: the frame's tokens as a raw buffer -- base = the frame's first token, 2 GB of range; dword 3 as for any raw 32-bit buffer)
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t tok_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(tok + base), 0, 0x7FFFFFF0, 0x00020000);
 
+    // the slot of record k's state (-1: the record is not in the table): the one pass 1 left beside it, or -- an item of more
+    // than one sweep, whose records come from HBM again -- found by hashing it and walking the probe chain once more
+    auto slot_of = [&](int k) -> int {
+      if (carry) {
+        const uint32_t s = get16(cs, k);
+        return s == kNoSlot ? -1 : (int)s;
+      }
+      if (!(__int_as_float(r[k].y) < cutoff)) return -1;
+      const uint32_t h = hash_of(r[k], rl[k]);
+      if (log2sub && (int)((h >> sub_shift) & ((1u << log2sub) - 1u)) != sub) return -1;
+      uint32_t slot = lds_slot_of(h, log2grp, log2sl);
+      const KeyT key = key_of(r[k], rl[k]);
+      for (int q = 0; q < SL; ++q) {
+        const KeyT kk = keys[slot];
+        if (kk == key) return (int)slot;
+        if (kk == kNoKey) break;
+        slot = (slot + 1) & mask;
+      }
+      return -1;
+    };
+
     // pass 1b (biglm): the same packed (cost | arc) value from SEVERAL source tokens -- two tokens of one graph state whose LM
     // histories cost the same, merged by back-off into one LM pair -- goes to the lowest source pair key (pair_keys[]: the LM states
     // themselves; pair ids are interned by atomicAdd and token indices are arena order, neither is stable).  The records that hold
@@ -1428,30 +1465,18 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
         const int32_t *src_lm = D.tok_lm + (size_t)c * D.arena_cap;
         const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);
         int bslot[kInsertUnroll];
-        u64 bspk[kInsertUnroll], bpacked[kInsertUnroll];
+        u64 bspk[kInsertUnroll];
 #pragma unroll
         for (int k = 0; k < kInsertUnroll; ++k) {
-          bslot[k] = -1; bspk[k] = 0ull; bpacked[k] = 0ull;
-          if (!(__int_as_float(r[k].y) < cutoff)) continue;
-          const uint32_t h = hash_of(r[k], rl[k]);
-          if (log2sub && (int)((h >> sub_shift) & ((1u << log2sub) - 1u)) != sub) continue;
+          bslot[k] = -1; bspk[k] = 0ull;
+          const int slot = slot_of(k);
+          if (slot < 0) continue;
           const u64 packed = ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w;
-          uint32_t slot = lds_slot_of(h, log2grp, log2sl);
-          const KeyT key = key_of(r[k], rl[k]);
-          for (int q = 0; q < SL; ++q) {
-            const KeyT kk = keys[slot];
-            if (kk == key) {
-              if (vals[slot] == packed) {
-                const uint32_t src = (uint32_t)r[k].z & idx_mask;
-                const int32_t sp = src < (uint32_t)D.arena_cap ? src_lm[src] : -1;
-                bslot[k] = (int)slot;
-                bpacked[k] = packed;
-                bspk[k] = (sp >= 0 && sp < D.pair_cap) ? ld_agent(&pkeys[sp]) : 0ull;
-              }
-              break;
-            }
-            if (kk == kNoKey) break;
-            slot = (slot + 1) & mask;
+          if (vals[slot] == packed) {
+            const uint32_t src = (uint32_t)r[k].z & idx_mask;
+            const int32_t sp = src < (uint32_t)D.arena_cap ? src_lm[src] : -1;
+            bslot[k] = slot;
+            bspk[k] = (sp >= 0 && sp < D.pair_cap) ? ld_agent(&pkeys[sp]) : 0ull;
           }
         }
         __syncthreads();   // every holder of a minimum knows itself
@@ -1469,79 +1494,73 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < kInsertUnroll; ++k)
-          if (big_win[k]) vals[bslot[k]] = bpacked[k];   // (as pass 1 left it: pass 2 claims it)
+          if (big_win[k]) vals[bslot[k]] = ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w;   // (as pass 1 left it: pass 2 claims it)
         __syncthreads();
       }
     }
 
     // pass 2: the record that won its state writes the token
-    // (lattice mode: an item that fits one sweep -- every planned item does -- keeps each live
-    // record's {source token, arc, cost} and LDS slot in registers for pass 3)
-    int lk_src[kInsertUnroll], lk_arc[kInsertUnroll], lk_cost[kInsertUnroll], lk_slot[kInsertUnroll];
-#pragma unroll
-    for (int k = 0; k < kInsertUnroll; ++k) lk_slot[k] = -1;
+    // (lattice mode: an item that fits one sweep -- every planned item does -- still has its records and their slots in
+    // registers in pass 3)
     for (int i0 = 0; i0 < n; i0 += kInsertThreads * kInsertUnroll) {
       if (!one_sweep) {
 #pragma unroll
         for (int k = 0; k < kInsertUnroll; ++k) r[k] = load_rec(i0 + k * kInsertThreads + tid, &rl[k]);
       }
+      // the claims of all the thread's records first -- which of them write a token, and where within the item (wp[]; kNoSlot: no
+      // token) --, then the stores: the claims' LDS round trips run back to back, no token store's address arithmetic between them
+      uint32_t wp[kInsertPk];
+#pragma unroll
+      for (int j = 0; j < kInsertPk; ++j) wp[j] = ~0u;
 #pragma unroll
       for (int k = 0; k < kInsertUnroll; ++k) {
         bool winner = false;
-        u64 packed = 0;
-        uint32_t wslot = 0;
-        bool in_table = false;
-        if (__int_as_float(r[k].y) < cutoff) {
-          const uint32_t h = hash_of(r[k], rl[k]);
-          if (!log2sub || (int)((h >> sub_shift) & ((1u << log2sub) - 1u)) == sub) {
-            packed = ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w;
-            uint32_t slot = lds_slot_of(h, log2grp, log2sl);
-            const KeyT key = key_of(r[k], rl[k]);
-            for (int q = 0; q < SL; ++q) {
-              const KeyT kk = keys[slot];
-              if (kk == key) {
-                // the record holding the state's minimum writes the token.  With fused closures two
-                // candidates at one state can yield the SAME epsilon arrival (same last arc, costs equal
-                // after rounding): the first to swap the slot's value away is the one
-                // (the claimed value keeps the cost: lattice mode reads it back for the links, pass 3; its low word, arc bits and flags
-                // all ones, is no record's -- row indices stay below kNoArc)
-                // biglm likewise: two tokens of ONE graph state (different LM pairs) whose histories have cost the same take the same
-                // arc into the same LM pair (back-off merges them) at the same cost -- the same packed value twice.  Both "won", the
-                // item wrote one token more than the keys it had counted, over its neighbour's first (found by a fuzz seed, round 6).
-                winner = vals[slot] == packed && (!(kBig && one_sweep) || big_win[k]) &&
-                         (!(kFused || kBig) || atomicCAS(&vals[slot], packed, packed | 0xFFFFFFFFull) == packed);
-                in_table = true;
-                break;
-              }
-              if (kk == kNoKey) break;
-              slot = (slot + 1) & mask;
-            }
-            wslot = slot;
-          }
-        }
-        if (kLat && in_table && !(kFused && ((uint32_t)r[k].w & kEpsRec))) {   // (a fused epsilon arrival is no link: epsilon_links)
-          lk_src[k] = r[k].z; lk_arc[k] = (int)((uint32_t)r[k].w & kArcMask); lk_cost[k] = r[k].y; lk_slot[k] = (int)wslot;
+        const int slot = slot_of(k);
+        if (slot >= 0) {
+          const u64 packed = ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w;
+          // the record holding the state's minimum writes the token.  With fused closures two
+          // candidates at one state can yield the SAME epsilon arrival (same last arc, costs equal
+          // after rounding): the first to swap the slot's value away is the one
+          // (the claimed value keeps the cost: lattice mode reads it back for the links, pass 3; its low word, arc bits and flags
+          // all ones, is no record's -- row indices stay below kNoArc)
+          // biglm likewise: two tokens of ONE graph state (different LM pairs) whose histories have cost the same take the same
+          // arc into the same LM pair (back-off merges them) at the same cost -- the same packed value twice.  Both "won", the
+          // item wrote one token more than the keys it had counted, over its neighbour's first (found by a fuzz seed, round 6).
+          winner = vals[slot] == packed && (!(kBig && one_sweep) || big_win[k]) &&
+                   (!(kFused || kBig) || atomicCAS(&vals[slot], packed, packed | 0xFFFFFFFFull) == packed);
         }
         const u64 wm = __ballot(winner);
         if (!wm) continue;
         int wb = 0;
         if (lane == 0) wb = atomicAdd(&s_wpos, __popcll(wm));
         wb = __builtin_amdgcn_readfirstlane(wb);
+        if (winner) {
+          put16(wp, k, (uint32_t)(wb + lane_rank(wm)));
+          if (kLat) tidx[slot] = wb + lane_rank(wm);   // (within the item: pass 3 adds the item's first token)
+        }
+      }
+      // the stores: every winner's token at the item's first + its position, and what goes with a token
+#pragma unroll
+      for (int k = 0; k < kInsertUnroll; ++k) {
+        const uint32_t pos = get16(wp, k);
+        const bool winner = pos != kNoSlot;
+        const u64 wm = __ballot(winner);
+        if (!wm) continue;
+        const u64 packed = ((u64)f2o(__int_as_float(r[k].y)) << 32) | (uint32_t)r[k].w;
         int idx = 0;
         const uint32_t flags = (uint32_t)r[k].w & kFlagMask;
         if (winner) {
-          idx = base + gpos + wb + lane_rank(wm);
+          idx = base + gpos + (int)pos;
           // {state, cost, source token, arc | flags}.  Two-launch decoders, on the frames whose GetCutoff may have to look at the
           // tokens (risky): WRITE-THROUGH (sc1) -- the workgroup that closes the frame reads the frame's costs in this same launch
           if (kTwo && risky) {   // (uniform)
             typedef int v4i_t __attribute__((ext_vector_type(4)));
             const v4i_t v = {r[k].x, r[k].y, r[k].z, r[k].w};
-            __builtin_amdgcn_raw_buffer_store_b128(v, tok_rsrc, (gpos + wb + lane_rank(wm)) * 16, 0, 16);   // (aux 16 = sc1)
+            __builtin_amdgcn_raw_buffer_store_b128(v, tok_rsrc, (gpos + (int)pos) * 16, 0, 16);   // (aux 16 = sc1)
           } else {
             tok[idx] = r[k];
           }
           if constexpr (kBig) D.tok_lm[(size_t)c * D.arena_cap + idx] = rl[k];
-          if (kLat) tidx[wslot] = idx;
           // (kTwo: the best token's graph ROW rides in the low word -- all the next frame's seed needs, DecoderDev::best_row)
           if (!(kTwo && D.best_exp)) {   // (best_exp: the expansion has found the best token already)
             const u64 b = (packed & 0xFFFFFFFF00000000ull) | (uint32_t)(kTwo ? r[k].x : idx);
@@ -1639,8 +1658,12 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
         // frame of a heavy channel at beam 15, serialised in L2 -- and on the control line every other atomic of the frame uses):
         // links per thread -> prefix over the workgroup -> the item's block
         int cnt = 0;
+        int lk_slot[kInsertUnroll];
 #pragma unroll
-        for (int k = 0; k < kInsertUnroll; ++k) cnt += lk_slot[k] >= 0;
+        for (int k = 0; k < kInsertUnroll; ++k) {
+          lk_slot[k] = (kFused && ((uint32_t)r[k].w & kEpsRec)) ? -1 : slot_of(k);   // (a fused epsilon arrival is no link: epsilon_links)
+          cnt += lk_slot[k] >= 0;
+        }
         int incl = cnt;
         incl = wave_incl_scan(incl);
         if (lane == 63) ish.lw[wave] = incl;
@@ -1659,8 +1682,8 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
         for (int k = 0; k < kInsertUnroll; ++k) {
           if (lk_slot[k] < 0) continue;
           // (link_delta: link cost - cost of the token that won the state, the table's minimum)
-          const int lw = D.link_delta ? __float_as_int(__int_as_float(lk_cost[k]) - o2f((uint32_t)(vals[lk_slot[k]] >> 32))) : lk_cost[k];
-          if ((int64_t)lp < D.link_cap) links[lp] = make_int4(lk_src[k], tidx[lk_slot[k]], lk_arc[k], lw);
+          const int lw = D.link_delta ? __float_as_int(__int_as_float(r[k].y) - o2f((uint32_t)(vals[lk_slot[k]] >> 32))) : r[k].y;
+          if ((int64_t)lp < D.link_cap) links[lp] = make_int4(r[k].z, base + gpos + tidx[lk_slot[k]], (int)((uint32_t)r[k].w & kArcMask), lw);
           else atomicOr(&ctl->error, kErrLinksFull);
           ++lp;
         }
@@ -1680,7 +1703,7 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
               const KeyT key = key_of(r, rlm);
               for (int q = 0; q < SL; ++q) {
                 const KeyT kk = keys[slot];
-                if (kk == key) { live = true; dst = tidx[slot]; dcost = o2f((uint32_t)(vals[slot] >> 32)); break; }
+                if (kk == key) { live = true; dst = base + gpos + tidx[slot]; dcost = o2f((uint32_t)(vals[slot] >> 32)); break; }
                 if (kk == kNoKey) break;
                 slot = (slot + 1) & mask;
               }
