@@ -1231,8 +1231,9 @@ void wfst_decoder_free(wfst_decoder *d) {
           fprintf(stderr, "[wfst dbg] %-18s n=%llu mean=%.2f us max=%.2f us\n", names[k], t[3 * k + 2],
                   0.01 * t[3 * k] / t[3 * k + 2], 0.01 * t[3 * k + 1]);
       {
-        const char *more[] = {"insert:head (launch/ticket -> item known)", "insert:countdown+ticket", "insert:frame boundary"};
-        for (int k = 22; k < 25; ++k)
+        const char *more[] = {"insert:head (launch/ticket -> item known)", "insert:countdown+ticket", "insert:frame boundary",
+                              "insert:count-out atomic, issue -> answer (part of countdown+ticket)"};
+        for (int k = 22; k < 26; ++k)
           if (t[3 * k + 2]) fprintf(stderr, "[wfst dbg] %-18s n=%llu mean=%.2f us max=%.2f us\n", more[k - 22], t[3 * k + 2], 0.01 * t[3 * k] / t[3 * k + 2], 0.01 * t[3 * k + 1]);
       }
       if (t[62] && (d->D.dbg & 128))

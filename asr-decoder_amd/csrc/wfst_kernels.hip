@@ -1369,6 +1369,15 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
     if (tid == 0) { s_nstates = 0; s_wpos = 0; s_ok = 1; }
     __syncthreads();
     if (tid == 0) dbg_phase(D, 6, tq);
+#ifndef WFST_RECORDS_AT_FIRST_USE   // (A/B builds: the compiler places the wait for the records)
+    // (the records are waited for HERE, where every path passes and pass 1 needs them at once -- not at their first use inside
+    // pass 1's loop, which an item without records skips: as far as the compiler could tell they were then still in flight in
+    // pass 2, and every token store sat between two full drains of the wave's memory queue)
+    if constexpr (kTwo) {
+#pragma unroll
+      for (int k = 0; k < kInsertUnroll; ++k) asm volatile("" ::"v"(r[k].x), "v"(r[k].y), "v"(r[k].z), "v"(r[k].w));
+    }
+#endif
 
     // pass 1: insert-or-min.  Candidates that lost against the final cutoff are dropped here: the
     // reference keeps those order-dependent extras (base-inl.h:330) but never expands them.
@@ -1506,6 +1515,15 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
       if (!one_sweep) {
 #pragma unroll
         for (int k = 0; k < kInsertUnroll; ++k) r[k] = load_rec(i0 + k * kInsertThreads + tid, &rl[k]);
+#ifndef WFST_RECORDS_AT_FIRST_USE   // (A/B builds: the compiler places the wait for the records)
+        // (the reloaded records are waited for HERE, on the path that reloads them: a record whose claim is skipped is otherwise
+        // still in flight, as far as the compiler can tell, where the paths meet again -- and every token store of a one-sweep
+        // item, which reloads nothing, then sits between two full drains of the wave's memory queue)
+        if constexpr (kTwo) {
+#pragma unroll
+          for (int k = 0; k < kInsertUnroll; ++k) asm volatile("" ::"v"(r[k].x), "v"(r[k].y), "v"(r[k].z), "v"(r[k].w));
+        }
+#endif
       }
       // the claims of all the thread's records first -- which of them write a token, and where within the item (wp[]; kNoSlot: no
       // token) --, then the stores: the claims' LDS round trips run back to back, no token store's address arithmetic between them
@@ -1750,8 +1768,11 @@ __device__ __forceinline__ void insert_body(const DecoderDev &D, int group, int 
       // that item counts itself out) and the frame's error bit (set, where it is, by this same lane on this same word) -- so
       // with the best token known since the expansion (best_exp) nothing this workgroup sent has to be waited for, and nothing
       // is loaded behind the countdown.  Without best_exp the best token travels by atomicMin from here: drained first.
+      unsigned long long ta = tq;   // (phase timers, slot 25: from the end of the tail, where the atomic is issued, to its answer)
       if (own_best) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const u64 old = atomicAdd(reinterpret_cast<u64 *>(&ctl->new_count), 0xFFFFFFFF00000000ull);
+      u64 old = atomicAdd(reinterpret_cast<u64 *>(&ctl->new_count), 0xFFFFFFFF00000000ull);
+      asm volatile("" : "+v"(old));   // (the answer has ARRIVED here: slot 25 ends on it, not on whatever uses it first)
+      dbg_phase(D, 25, ta);
       last = ((old >> 32) & 0xFFFFull) == 1;
       if (last) {
         bsh.h_nf = (int)(uint32_t)old;
