@@ -19,6 +19,7 @@
 #include "wfst_hip_own.h"
 #include "wfst_capi_words.h"
 #include "wfst_capi_ingest.h"
+#include "wfst_capi_liveprune.h"
 #include "wfst_capi_nbwords.h"
 #include "wfst_openfst.h"
 
@@ -278,6 +279,7 @@ struct wfst_decoder {
   WordsState wd;   // wfst_decoder_words_enqueue / _ready / _fetch (wfst_capi_words.cc)
   IngestState ing; // wfst_decoder_set_score_transform / _advance_chunk / _get_scores (wfst_capi_ingest.cc)
   NbWordsState nbw; // wfst_decoder_get_nbest_words (wfst_capi_nbwords.cc)
+  LivePruneState lpr; // wfst_decoder_set_live_lattice_prune (wfst_capi_liveprune.cc): the scratch behind D.snap_extra
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
   int32_t hist_slab_stride = 0;        // ... of this many floats
@@ -3578,6 +3580,18 @@ int nbw_round(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fin
   HIP_TRY(hipGetLastError());
   *Pout = P;
   return WFST_OK;
+}
+
+// What wfst_capi_liveprune.cc -- wfst_decoder_set_live_lattice_prune / _get_live_lattice_prune -- needs of a decoder.
+LivePruneView live_prune_view(wfst_decoder *d) {
+  return LivePruneView{d->device, d->D.lattice, d->n_channels, d->D.arena_cap, &d->lpr, &d->D.live_prune, &d->D.snap_extra};
+}
+void live_prune_drop_live(wfst_decoder *d) {
+  for (int c = 0; c < d->n_channels; ++c) {
+    if (d->h_state[(size_t)c] != 1) continue;
+    if (!d->det_live_nd.empty()) d->det_live_nd[(size_t)c] = -1;
+    if (!d->resc_cache.empty()) { d->resc_cache[(size_t)c].key.valid = false; d->nbp_cache[(size_t)c].key.valid = false; }
+  }
 }
 
 // What wfst_capi_ingest.cc -- the entry points that launch ingest_kernel -- needs of a decoder.

@@ -384,6 +384,11 @@ struct DecoderDev {
   int32_t *tok_lm;
   int32_t *bucket_lm;
   unsigned long long *eps_keys;
+  // pruned live lattices (wfst_decoder_set_live_lattice_prune): live_prune != 0 -- launch_lattice_emit serves a live channel from its
+  // SNAPSHOT, FinalizeDecoding's pruning priced into snap_extra[c][arena_cap] ({orderable extra, cost bits}, as extra[]) by
+  // lattice_snapshot_kernel with the channel left as it is; nullptr until the mode is first set
+  uint2 *snap_extra;
+  int32_t live_prune;
   unsigned long long *dbg_t;  // [64] phase timers (WFST_DBG & 32): sums, maxima, counts
   int32_t dbg;  // WFST_DBG ablation bits (timing experiments only; results are wrong when set)
 };

@@ -2860,18 +2860,34 @@ __device__ __forceinline__ int block_exscan(int v, ScanShared &ps, int *total) {
   return base + incl - v;
 }
 
+// link_extra (base-inl.h:524-526, 782-784) of a link whose destination holds {orderable extra eo, cost bits}: extra of the destination +
+// (link cost - cost of the destination); w = the link's 4th word (link_delta: that difference itself); +inf for a dead destination.
+// The ONE statement of it: the walk prices with it and lattice_emit_kernel tells a snapshot's dead links with it.
+__device__ __forceinline__ float link_extra_of(int32_t link_delta, uint32_t eo, uint32_t cost_bits, int32_t w) {
+  if (eo >= f2o(__builtin_huge_valf())) return __builtin_huge_valf();
+  return o2f(eo) + (link_delta ? __int_as_float(w) : __int_as_float(w) - __uint_as_float(cost_bits));
+}
+
 // kFinal: FinalizeDecoding.  Returns with extras valid for every frame, dead tokens and links gone, and
 // ctl->pruned_upto = n_decoded.
 // raw_done (running passes only): the frames never priced before, [pruned_upto, n_decoded), have been priced by the launches of
 // lattice_prune_raw_* (several workgroups per channel and frame, below): the walk starts at frame pruned_upto - 1.
-template <bool kFinal>
-__device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShared &ps, bool raw_done = false) {
+// kSnap (with kFinal; DecoderDev::live_prune): the SNAPSHOT of a live channel -- the same walk, priced into the channel's scratch extras
+// (DecoderDev::snap_extra) with nothing of the channel written: no link is marked (lattice_emit_kernel tells a dead link from the scratch
+// extras by link_extra_of, the walk's own expression), extra[], pruned_upto, lat_stats and the timers stay as they are.  The walk never
+// reads an extra it has not written in the same pass (kFinal prices every frame; the previous pass's extras only feed the running
+// passes' stopping rule), and the links an earlier pass marked stay skipped, as the finalized twin skips them.
+// snap_use_final == 0 (kSnap only): every token of the newest frame is final at cost 0 -- ComputeFinalCosts' answer when no token
+// of the frame is final in the graph.
+template <bool kFinal, bool kSnap = false>
+__device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShared &ps, bool raw_done = false, int snap_use_final = 1) {
+  static_assert(kFinal || !kSnap, "a snapshot is a FinalizeDecoding walk");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   ChanCtl *ctl = D.ctl + c;
   const int nd = ctl->n_decoded;
   int4 *tok = D.tok + (size_t)c * D.arena_cap;
   int4 *links = D.links + (size_t)c * D.link_cap;
-  uint2 *extra = D.extra + (size_t)c * D.arena_cap;
+  uint2 *extra = (kSnap ? D.snap_extra : D.extra) + (size_t)c * D.arena_cap;
   int32_t *remap = D.remap + (size_t)c * D.arena_cap;   // previous extras while walking, new indices while compacting
   int32_t *foff = D.frame_off + (size_t)c * (D.max_frames + 2);
   int32_t *loff = D.link_off + (size_t)c * (D.max_frames + 3);
@@ -2907,7 +2923,7 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
       for (int u = 0; u < kPU; ++u) {
         if (L[u].x < 0) continue;
         const uint32_t eo = (uint32_t)e[u];
-        const float le = eo >= kInfO ? kInf : o2f(eo) + (D.link_delta ? __int_as_float(L[u].w) : __int_as_float(L[u].w) - __int_as_float((int)(e[u] >> 32)));
+        const float le = link_extra_of(D.link_delta, eo, (uint32_t)(e[u] >> 32), L[u].w);
         f(i0 + u * kBT + tid, L[u], le);
       }
     }
@@ -2930,7 +2946,7 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
       if (!ch) break;
     }
     for_links(e0, e1, [&](int i, const int4 &, float le) {
-      if (!(le <= lb)) links[i].x = -1;
+      if (!kSnap && !(le <= lb)) links[i].x = -1;
     });
     __syncthreads();
   };
@@ -2952,6 +2968,7 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
       const int4 t = tok[i];
       const u64 v = (u64)f2o(__int_as_float(t.y));
       b_all = v < b_all ? v : b_all;
+      if (kSnap && !snap_use_final) continue;
       if (D.big) {
         const u64 w = (u64)f2o(__int_as_float(t.y) + lm_final(i));
         b_fin = w < b_fin ? w : b_fin;                      // best_cost_with_final: over all tokens
@@ -2964,7 +2981,8 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
     __syncthreads();
     for (int w = 0; w < kBT / 64; ++w) { b_all = ps.red[0][w] < b_all ? ps.red[0][w] : b_all; b_fin = ps.red[1][w] < b_fin ? ps.red[1][w] : b_fin; }
     any_final = b_fin != ~0ull;
-    if (D.big) {   // the final-cost set is non-empty iff some token is final in the graph
+    if (kSnap && !snap_use_final) any_final = false;
+    else if (D.big) {   // the final-cost set is non-empty iff some token is final in the graph
       if (tid == 0) ps.cnt = 0;
       __syncthreads();
       if (any_fin) ps.cnt = 1;
@@ -3021,10 +3039,10 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
     __syncthreads();
   }
   for (int k = k_first; k >= 0; --k) {
-    if (tid == 0 && (D.dbg & 32)) { const unsigned long long now = wall_clock64(); atomicAdd(&D.dbg_t[(k + 1 < n_prev) ? 41 : 40], now - tw); tw = now; }
+    if (!kSnap && tid == 0 && (D.dbg & 32)) { const unsigned long long now = wall_clock64(); atomicAdd(&D.dbg_t[(k + 1 < n_prev) ? 41 : 40], now - tw); tw = now; }
     const int fk = foff[k], fk1 = foff[k + 1], fk2 = foff[k + 2];
     const int nk = fk1 - fk, n1 = fk2 - fk1;
-    const bool had_old = k < n_prev;
+    const bool had_old = !kSnap && k < n_prev;   // (a snapshot reads no extras but its own)
     if (!kFinal && had_old && !moved) break;
     k_lo = k;
     st_links += (u64)(lmid[k + 1] - loff[k + 1]) + 2ull * (u64)(loff[k + 1] - lmid[k]);   // (an epsilon link: priced, then confirmed)
@@ -3127,7 +3145,7 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
         uint2 en;
         if (wide) { en.x = E0x[X.y - fk]; en.y = (xmode || en.x >= kInfO) ? 0u : (uint32_t)tok[X.y].y; }
         else en = E0[X.y - fk];
-        return en.x >= kInfO ? kInf : o2f(en.x) + (D.link_delta ? __int_as_float(X.w) : __int_as_float(X.w) - __uint_as_float(en.y));
+        return link_extra_of(D.link_delta, en.x, en.y, X.w);
       };
       auto min0 = [&](int i, uint32_t o) -> uint32_t { return wide ? atomicMin(&E0x[i], o) : atomicMin(&E0[i].x, o); };
       // emitting links frame k -> k+1
@@ -3157,8 +3175,8 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
         for (int u = 0; u < kPU; ++u) {
           if (ML[u].x < 0) continue;
           const uint32_t eo = (uint32_t)en[u];
-          float le = eo >= kInfO ? kInf : o2f(eo) + (D.link_delta ? __int_as_float(ML[u].w) : __int_as_float(ML[u].w) - __int_as_float((int)(en[u] >> 32)));
-          if (!(le <= lb)) { links[i0 + u * kBT + tid].x = -1; continue; }
+          float le = link_extra_of(D.link_delta, eo, (uint32_t)(en[u] >> 32), ML[u].w);
+          if (!(le <= lb)) { if (!kSnap) links[i0 + u * kBT + tid].x = -1; continue; }
           if (le < 0.0f) le = 0.0f;
           min0(ML[u].x - fk, f2o(le));
         }
@@ -3196,7 +3214,8 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
           if (!ps.flag[fl]) break;
         }
         // the dead ones are marked
-        if (eps_in_regs) {
+        if (kSnap) {   // (a snapshot marks no link)
+        } else if (eps_in_regs) {
 #pragma unroll
           for (int u = 0; u < kPU; ++u) {
             if (EL[u].x < 0) continue;
@@ -3258,12 +3277,12 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
       __syncthreads();   // (the next frame rewrites the other end of the buffer and the flags)
       have = (wide && !xmode) ? -1 : k;   // (a wide frame leaves extras only: its predecessor reads the pairs from HBM; xmode: extras are all it needs)
       hb = cur_end;
-      if (tid == 0 && (D.dbg & 32)) atomicAdd(&D.dbg_t[42], 1ull);
+      if (!kSnap && tid == 0 && (D.dbg & 32)) atomicAdd(&D.dbg_t[42], 1ull);
       continue;
     }
     // ---- the frame in HBM (more tokens than the LDS buffers take) ----
     have = -1;
-    if (tid == 0 && (D.dbg & 32)) atomicAdd(&D.dbg_t[43], 1ull);
+    if (!kSnap && tid == 0 && (D.dbg & 32)) atomicAdd(&D.dbg_t[43], 1ull);
     for (int i0 = fk; i0 < fk1; i0 += kBT * kPU) {
       int cy[kPU];
       uint32_t ox[kPU];
@@ -3284,7 +3303,7 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
     __syncthreads();
     // emitting links frame k -> k+1
     for_links(loff[k + 1], lmid[k + 1], [&](int i, const int4 &L, float le) {
-      if (!(le <= lb)) { links[i].x = -1; return; }
+      if (!(le <= lb)) { if (!kSnap) links[i].x = -1; return; }
       if (le < 0.0f) le = 0.0f;
       atomicMin(&extra[L.x].x, f2o(le));
     });
@@ -3307,6 +3326,7 @@ __device__ __forceinline__ void prune_pass(const DecoderDev &D, int c, PruneShar
   }
   __syncthreads();
 
+  if (kSnap) return;   // the channel's counters, timers and pruned_upto are the running passes'
   if (tid == 0) { D.lat_stats[(size_t)c * 4 + 1] += st_links; D.lat_stats[(size_t)c * 4 + 2] += st_toks; }
   if (tid == 0 && (D.dbg & 32)) {
     const unsigned long long now = wall_clock64();
@@ -5079,6 +5099,10 @@ static_assert(16 + kEmitSlabs + 2 <= kPrRawCount, "prune_par: lattice_emit's sla
 //   lattice_emit_tokens_kernel   the slabs' bases from their counts; the living tokens of slab g written to lat_toks[base + rank]
 // (the channel's counters sit in its parameter block, DecoderDev::prune_par[16..]: slab counts, link counter, error; reset by
 // lattice_emit_reset_kernel).
+// the channel is served from its snapshot (mode 1, the scratch is there, a live channel without an error)
+__device__ __forceinline__ bool live_prune_on(const DecoderDev &D, const ChanCtl *ctl) {
+  return D.live_prune != 0 && D.snap_extra != nullptr && ctl->finalized == 0 && ctl->error == 0;
+}
 struct EmitBounds {
   int foff[kEmitFrames + 2], lseg[2 * (kEmitFrames + 2)];   // lseg[2 f] = link_off[f], [2 f + 1] = link_mid[f]
 };
@@ -5109,10 +5133,14 @@ __global__ __launch_bounds__(kBT) void lattice_emit_kernel(DecoderDev D, const i
   // tokens.  Frames the back-pruning has priced (below pruned_upto) hold their dead as holes: extra = +inf -- except frame 0 before
   // FinalizeDecoding, whose dead tokens the reference keeps (link-less: PruneActiveTokens never calls PruneTokensForFrame(0),
   // base-inl.h:471-476).
-  const uint2 *extra = D.extra + (size_t)c * D.arena_cap;
+  // A SNAPSHOT (live_prune_on: lattice_snapshot_kernel has priced the channel into its scratch extras): the lattice the channel would
+  // hold after FinalizeDecoding at this frame -- every frame is priced, a token is dead iff its scratch extra is +inf (frame 0's
+  // included), a link iff an earlier pass marked it or its link_extra, from the scratch extras, is above lattice_beam.
+  const bool snap = live_prune_on(D, ctl);
+  const uint2 *extra = (snap ? D.snap_extra : D.extra) + (size_t)c * D.arena_cap;
   const uint32_t kInfO = f2o(__builtin_huge_valf());
-  const int pruned_upto = ctl->pruned_upto;
-  const bool finalized = ctl->finalized != 0;
+  const int pruned_upto = snap ? nd + 1 : ctl->pruned_upto;
+  const bool finalized = snap || ctl->finalized != 0;
   __shared__ EmitBounds sb;
   __shared__ ScanShared ps;
   const bool in_lds = nd + 2 <= kEmitFrames + 2;
@@ -5164,6 +5192,14 @@ __global__ __launch_bounds__(kBT) void lattice_emit_kernel(DecoderDev D, const i
       for (int u = 0; u < kEmitU; ++u) {
         const int i = i0 + u * kBT + tid;
         L[u] = i < hi ? links[i] : make_int4(-1, 0, 0, 0);
+      }
+      if (snap) {   // the links FinalizeDecoding's pruning would mark
+        uint2 en[kEmitU];
+#pragma unroll
+        for (int u = 0; u < kEmitU; ++u) en[u] = L[u].x >= 0 ? extra[L[u].y] : make_uint2(0u, 0u);
+#pragma unroll
+        for (int u = 0; u < kEmitU; ++u)
+          if (L[u].x >= 0 && !(link_extra_of(D.link_delta, en[u].x, en[u].y, L[u].w) <= D.lattice_beam)) L[u].x = -1;
       }
       int4 A[kEmitU];
       int il[kEmitU], ol[kEmitU];
@@ -5282,6 +5318,16 @@ __global__ __launch_bounds__(kBT) void lattice_finalize_kernel(DecoderDev D, con
   __shared__ PruneShared ps;
   const int c = chans ? chans[blockIdx.x] : blockIdx.x;
   prune_pass<true>(D, c, ps);
+}
+
+// The snapshot lattice of the listed LIVE channels (wfst_decoder_set_live_lattice_prune): FinalizeDecoding's pruning priced into the
+// scratch extras, the channel untouched (prune_pass<true, true>); lattice_emit_kernel, next on the stream, reads them.  Finalized
+// channels and channels with an error are left alone.
+__global__ __launch_bounds__(kBT) void lattice_snapshot_kernel(DecoderDev D, const int32_t *chans, int use_final) {
+  __shared__ PruneShared ps;
+  const int c = chans ? chans[blockIdx.x] : blockIdx.x;
+  if (!live_prune_on(D, D.ctl + c)) return;
+  prune_pass<true, true>(D, c, ps, false, use_final);
 }
 
 // =========================================================================================
@@ -5418,6 +5464,7 @@ void launch_lattice_prune(const DecoderDev &D, const int32_t *chans, int n, hipS
   launch_lattice_emit(D, chans, n, 1, s);
 }
 void launch_lattice_emit(const DecoderDev &D, const int32_t *chans, int n, int use_final, hipStream_t s) {
+  if (D.live_prune && D.snap_extra) hipLaunchKernelGGL(lattice_snapshot_kernel, dim3(n), dim3(kBT), 0, s, D, chans, use_final);
   hipLaunchKernelGGL(lattice_emit_reset_kernel, dim3((n * 16 + 255) / 256), dim3(256), 0, s, D, chans, n);
   hipLaunchKernelGGL(lattice_emit_kernel, dim3(n, kEmitSlabs), dim3(kBT), 0, s, D, chans, use_final);
   hipLaunchKernelGGL(lattice_emit_tokens_kernel, dim3(n, kEmitSlabs), dim3(kBT), 0, s, D, chans, use_final);

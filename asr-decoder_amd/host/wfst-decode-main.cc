@@ -30,6 +30,10 @@
 //                  but the last, per stream, the service's per-chunk GetNbestTxt (GetNbestWords: wfst_decoder_get_nbest_words, one
 //                  list call for the streams that ask together) as "KEY@frames nbest k: word-ids... tot=.. lm=.." per path, over the
 //                  second-pass lattice with --second-lm-old/--second-lm-new; a stream's own failure: "KEY@frames nbest status=code"
+//   --live-lattice-prune  with --chunk=N --partial-nbest=K, in every shape: the per-chunk n-best comes from the PRUNED live lattice
+//                  (SetLiveLatticePrune: the lattice the stream would hold if the utterance ended at this frame -- FinalizeDecoding's
+//                  pruning on a snapshot, the stream decodes on untouched) instead of from everything alive, which at service sizes
+//                  is mostly beyond the determinizer's bounds; the line format is the same
 //   --word-times [--silence-phones=a:b:c]  batch shape and --single-stream: after an utterance's "KEY word-ids..." line one line
 //                  "KEY#k word begin end" per word -- the frames of GetWords (wfst_decoder_get_words: the word's label-carrying
 //                  arc, and the next word's begin or, with silence phones and --tid2phone=FILE, one past the word's last frame
@@ -191,7 +195,7 @@ int main(int argc, char **argv) {
     std::string lattice_file, lattice_text;
     long long lattice_links = 1ll << 22;
     int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
-    bool pull = false, partial_words = false, word_times = false;
+    bool pull = false, partial_words = false, word_times = false, live_prune = false;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
@@ -235,6 +239,7 @@ int main(int argc, char **argv) {
       }
       else if (a == "--partial-words") partial_words = true;
       else if (a.compare(0, 16, "--partial-nbest=") == 0) partial_nbest = atoi(a.c_str() + 16);
+      else if (a == "--live-lattice-prune") live_prune = true;
       else if (a == "--word-times") word_times = true;
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
@@ -267,7 +272,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -280,6 +285,7 @@ int main(int argc, char **argv) {
     if (device_chunks && (chunk <= 0 || single || n_threads > 0)) { std::cerr << "--device-chunks goes with --chunk=N and the batch shape\n"; return 1; }
     if (word_times && n_threads > 0) { std::cerr << "--word-times goes with the batch shape or --single-stream\n"; return 1; }
     if (!wt_silence.empty() && (!word_times || tid2phone_file.empty())) { std::cerr << "--silence-phones goes with --word-times and --tid2phone=FILE\n"; return 1; }
+    if (live_prune && partial_nbest == 0) { std::cerr << "--live-lattice-prune goes with --chunk=N --partial-nbest=K\n"; return 1; }
     LatticeFasterDecoderConfig opt;
     opt.ReadConfigFile(pos[0]);
     if (endpointing || print_endpoints || (!tid2phone_file.empty() && wt_silence.empty())) {
@@ -533,6 +539,7 @@ int main(int argc, char **argv) {
                                                      : biglm ? new OnlineLatticeDecoderMempoolBiglm(&fst, opt, lm1p, lm2p, &limits)
                                                              : new GpuLatticeDecoder(&fst, opt, &limits));
           DecoderItf &decode = *dp;   // (the reference's interface is all the loop below uses, results aside)
+          if (live_prune) dp->SetLiveLatticePrune(true);   // (over a pool: the shared decoder's, set by every thread before any of them decodes)
           dp->ReserveRows(max_utt_frames, pull && !tid2pdf.empty() ? (int)tid2pdf.size() - 1 : max_utt_cols - 1);
           // every thread has its decoder before the first utterance starts (the service creates them at start-up)
           ready_threads.fetch_add(1);
@@ -646,6 +653,7 @@ int main(int argc, char **argv) {
                                                         : new GpuLatticeDecoder(&fst, opt, &limits));
       GpuLatticeDecoder &decode = *decode_p;
       if (word_times) decode.SetSilencePhones(wt_silence);
+      if (live_prune) decode.SetLiveLatticePrune(true);
       for (const Utt &u : utts) {
         if (endpointing) {
           bool ok = false;
@@ -750,6 +758,7 @@ int main(int argc, char **argv) {
                                                           : new GpuBatchDecoder(wf, opt, batch, &limits));  // its own stream
           GpuBatchDecoder &decode = *decode_p;
           if (word_times) decode.SetSilencePhones(wt_silence);
+          if (live_prune) decode.SetLiveLatticePrune(true);
           if (device_chunks) decode.SetScoreTransform(acoustic_scale, log_priors);
           // --device-chunks: a chunk of every channel's rows in the score dtype, page-locked (the device reads it where it lies)
           const size_t elem = score_dtype == WFST_DTYPE_F32 ? 4 : 2;

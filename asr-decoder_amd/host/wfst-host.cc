@@ -16,6 +16,9 @@
 // wfst_decoder_get_nbest_words is referenced weakly: this file is also linked against doubles of the C ABI that end at the calls
 // it made before (the pool's and the partial words' sanitizer harnesses); there the n-best text reports itself missing.
 #pragma weak wfst_decoder_get_nbest_words
+// ... and so are the pruned live lattices' two calls: SetLiveLatticePrune reports itself missing there
+#pragma weak wfst_decoder_set_live_lattice_prune
+#pragma weak wfst_decoder_get_live_lattice_prune
 
 namespace datemoon {
 
@@ -1741,5 +1744,16 @@ void GpuBatchDecoder::GetNbestWords(const std::vector<int> &channels, int n, Arp
   if (lm) lm->swap(l);
   if (status) *status = st;
 }
+
+// ---- pruned live lattices (wfst_decoder_set_live_lattice_prune) ------------------------------------------------------------------
+static void LiveLatticePruneCall(wfst_decoder *dec, bool on) {
+  if (!wfst_decoder_set_live_lattice_prune) throw std::runtime_error("SetLiveLatticePrune: this build's device library has no wfst_decoder_set_live_lattice_prune");
+  if (wfst_decoder_set_live_lattice_prune(dec, on ? 1 : 0) != WFST_OK) Fatal("SetLiveLatticePrune");
+}
+void GpuChannelPool::SetLiveLatticePrune(bool on) { LiveLatticePruneCall(_dec, on); }
+void GpuLatticeDecoder::SetLiveLatticePrune(bool on) {
+  OnDevice([&] { LiveLatticePruneCall(_dec, on); });
+}
+void GpuBatchDecoder::SetLiveLatticePrune(bool on) { LiveLatticePruneCall(_dec, on); }
 
 }  // namespace datemoon

@@ -295,6 +295,11 @@ class GpuChannelPool {
                                       // synchronous request-by-request calls after a refused list or a capacity too small, which hold the batcher
   };
   Stats GetStats();
+  // Pruned live lattices (wfst_decoder_set_live_lattice_prune): the live getters of every channel of the pool's decoder -- GetRawLattice,
+  // GetLattice, GetNbest, GetNbestWords, GetNbestShortlist before FinalizeDecoding -- serve the lattice the channel would hold if the
+  // utterance ended at this frame (FinalizeDecoding's pruning on a snapshot; the channel decodes on untouched).  The setting is the
+  // device decoder's: call it before worker threads lease channels.
+  void SetLiveLatticePrune(bool on);
   wfst_decoder *Handle() { return _dec; }
 
  private:
@@ -477,6 +482,9 @@ class GpuLatticeDecoder : public DecoderItf {
   // of many threads go to the device as one list per batcher pass and distinct (n, use_final_probs, LM pair).
   bool GetNbestWords(std::vector<std::vector<int> > *words, std::vector<float> *tot, std::vector<float> *lm, int n, bool use_final_probs = true,
                      ArpaLm *oldlm = nullptr, ArpaLm *newlm = nullptr, int *status = nullptr);
+  // Pruned live lattices (see GpuChannelPool::SetLiveLatticePrune) for this object's device decoder: the private one, or -- over a
+  // pool, and so under ShareDevice -- the shared decoder of every object on it (set it before the other threads decode).
+  void SetLiveLatticePrune(bool on);
 
  private:
   void Pull(AmInterface *decodable);
@@ -573,6 +581,7 @@ class GpuBatchDecoder {
   void GetNbestWords(const std::vector<int> &channels, int n, ArpaLm *oldlm, ArpaLm *newlm, bool use_final_probs,
                      std::vector<std::vector<std::vector<int> > > *words, std::vector<std::vector<float> > *tot,
                      std::vector<std::vector<float> > *lm, std::vector<int> *status = nullptr);
+  void SetLiveLatticePrune(bool on);   // pruned live lattices for every channel (see GpuChannelPool::SetLiveLatticePrune)
   wfst_decoder *Handle() { return _dec; }
 
  private:

@@ -45,6 +45,7 @@ SYMBOLS = [
     "wfst_decoder_get_words",
     "wfst_decoder_set_score_transform", "wfst_decoder_advance_chunk", "wfst_decoder_get_scores",
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
+    "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
 ]
 
 
@@ -738,6 +739,18 @@ class BatchDecoder:
         s, b = C.c_int32(0), C.c_int64(0)
         _check(lib().wfst_decoder_get_determinizer_slots(self.h, C.byref(s), C.byref(b)))
         return s.value, b.value
+
+    def set_live_lattice_prune(self, on):
+        """on: the live getters (raw_lattice, determinized_lattice, rescored_lattice, nbest_paths, nbest_words, nbest on a channel
+        that is not finalized) serve the lattice the channel would hold if the utterance ended at this frame -- FinalizeDecoding's
+        pruning on a snapshot, the channel itself untouched -- instead of everything alive (wfst_decoder_set_live_lattice_prune)."""
+        _check(lib().wfst_decoder_set_live_lattice_prune(self.h, 1 if on else 0))
+
+    def live_lattice_prune(self):
+        """(mode, bytes of the snapshot scratch) (wfst_decoder_get_live_lattice_prune)."""
+        m, b = C.c_int32(0), C.c_int64(0)
+        _check(lib().wfst_decoder_get_live_lattice_prune(self.h, C.byref(m), C.byref(b)))
+        return m.value, b.value
 
     def nbest_words(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256):
         """GetNbestTxt of a LIST of channels (None: all), live and finalized ones mixed, in one launch per stage

@@ -516,6 +516,32 @@ int wfst_decoder_get_nbest_words(wfst_decoder *d, const int32_t *channels, int32
  * Allocates the workspace if no call has yet.  Either output may be NULL.  WFST_E_STATE: a decoder without lattice_links. */
 int wfst_decoder_get_determinizer_slots(wfst_decoder *d, int32_t *slots, int64_t *bytes_per_slot);
 
+/* ---- pruned live lattices: FinalizeDecoding's pruning on a snapshot ------------------------------------------------------------
+ * A live raw lattice is the history as the last PruneActiveTokens pass left it plus up to prune_interval frames of unpruned tokens,
+ * of which a percent or two survive any lattice-beam pruning: at the headline configuration it is mostly beyond the determinizer's
+ * bounds (wfst_limits.det_raw_states / det_raw_arcs).  mode 1 makes every getter that emits a LIVE channel's lattice --
+ * wfst_decoder_get_raw_lattice, _get_determinized_lattice, _get_rescored_lattice, _get_nbest_paths, _get_nbest_words, _get_nbest --
+ * work from the SNAPSHOT lattice S(channel, use_final_probs) instead:
+ *   use_final_probs != 0: exactly the raw lattice a twin channel fed the same frames holds after wfst_decoder_finalize -- the pruning
+ *     of FinalizeDecoding (PruneForwardLinksFinal + PruneForwardLinks + PruneTokensForFrame, my-decoder/online-decoder-base-inl.h:725-847):
+ *     the same states (frame, graph state, final flag, forward cost bits), the same arcs (labels and both costs bit for bit), the same
+ *     numbering rules;
+ *   use_final_probs == 0: the same computation with every token of the newest frame final at cost 0 (what ComputeFinalCosts yields
+ *     when no token of that frame is final in the graph); st_final is set on every surviving token of the newest frame.
+ * The channel is NOT changed by it: the pruning is priced into scratch of its own and decoding goes on bit for bit as without the
+ * query.  Finalized channels are served exactly as with mode 0 (the default: everything alive, as before).
+ * The one thing that differs from the reference: its GetLattice(..., false) (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:50-89)
+ * determinizes the UNPRUNED live lattice; mode 1 determinizes S.
+ * The scratch (8 bytes per arena entry of every channel) is allocated when mode 1 is first set and freed with the decoder; if it
+ * cannot be allocated the setter returns the error (WFST_E_CAPACITY / WFST_E_DEVICE) and the mode stays 0.  Changing the mode drops
+ * what the decoder keeps of live channels' lattices, so that no getter answers from the other mode's lattice; what it keeps of
+ * finalized channels stays.  The setting is the decoder's: set it before other threads use the decoder.
+ * WFST_E_STATE: a decoder without lattice_links.  WFST_E_ARG: a mode outside {0, 1}, a NULL decoder.
+ * 0 (default): live getters serve everything alive, as today.  1: they serve S(c, use_final_probs). */
+int wfst_decoder_set_live_lattice_prune(wfst_decoder *d, int32_t mode);
+/* Either output may be NULL; scratch_bytes is 0 until mode 1 has been set once. */
+int wfst_decoder_get_live_lattice_prune(wfst_decoder *d, int32_t *mode, int64_t *scratch_bytes);
+
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
  * ConvertNbestToVector, then LatticeToVector per path) of channels of a lattice-mode decoder, finalized
