@@ -21,6 +21,7 @@
 #include "wfst_capi_ingest.h"
 #include "wfst_capi_liveprune.h"
 #include "wfst_capi_nbwords.h"
+#include "wfst_capi_align.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -279,6 +280,7 @@ struct wfst_decoder {
   WordsState wd;   // wfst_decoder_words_enqueue / _ready / _fetch (wfst_capi_words.cc)
   IngestState ing; // wfst_decoder_set_score_transform / _advance_chunk / _get_scores (wfst_capi_ingest.cc)
   NbWordsState nbw; // wfst_decoder_get_nbest_words (wfst_capi_nbwords.cc)
+  AlignState aln;  // wfst_decoder_align_words (wfst_capi_align.cc)
   LivePruneState lpr; // wfst_decoder_set_live_lattice_prune (wfst_capi_liveprune.cc): the scratch behind D.snap_extra
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
@@ -3579,6 +3581,44 @@ int nbw_round(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fin
   launch_nbest_paths(P, cnt, d->stream, ns_max <= b.small_states ? 1 : 0);
   HIP_TRY(hipGetLastError());
   *Pout = P;
+  return WFST_OK;
+}
+
+// What wfst_capi_align.cc -- wfst_decoder_align_words, the entry point that launches align_index_kernel / align_kernel -- needs of a decoder.
+int align_begin(wfst_decoder *d, const int32_t *channels, int32_t n, AlignView *v) {
+  if (!d || !channels) return fail(WFST_E_ARG, "NULL decoder / channel list");
+  if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
+  if (!d->D.lattice) return fail(WFST_E_STATE, "AlignWords needs a decoder created with wfst_limits.lattice_links > 0");
+  const int rc = check_channel_list(d, channels, n, "AlignWords", nullptr);
+  if (rc != WFST_OK) return rc;
+  *v = AlignView{d->device, &d->D, &d->aln, d->sil_set ? d->sil_bits.p : nullptr, d->sil_ntid, d->stream};
+  return WFST_OK;
+}
+int align_channel_state(const wfst_decoder *d, int32_t channel) { return d->h_state[(size_t)channel]; }
+int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_final_probs, std::vector<int32_t> *sizes) {
+  HIP_TRY(hipSetDevice(d->device));
+  int rc = finish_prefetch(d);
+  if (rc != WFST_OK) return rc;
+  std::vector<int32_t> live;
+  for (int c : list)
+    if (d->h_state[(size_t)c] == 1) live.push_back(c);
+  // Nothing is fetched into the host caches here (lat_cache_*, det_cache, resc_cache, nbp_cache stay what they were), and the
+  // determinizer's slots are not touched: a live channel's lists on the device are emitted anew by every getter that reads them.
+  if (!live.empty()) {
+    const int32_t *dev;
+    int32_t dcnt;
+    rc = stage_channels(d, live.data(), (int32_t)live.size(), &dev, &dcnt);
+    if (rc != WFST_OK) return rc;
+    launch_lattice_emit(d->D, dev, dcnt, use_final_probs ? 1 : 0, d->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  rc = read_ctl(d);  // synchronises the stream
+  if (rc != WFST_OK) return rc;
+  sizes->resize(list.size() * 4);
+  for (size_t i = 0; i < list.size(); ++i) {
+    const ChanCtl &cc = d->p_ctl.p[list[i]];
+    (*sizes)[4 * i] = cc.lat_toks; (*sizes)[4 * i + 1] = cc.lat_arcs; (*sizes)[4 * i + 2] = cc.n_decoded; (*sizes)[4 * i + 3] = cc.error;
+  }
   return WFST_OK;
 }
 

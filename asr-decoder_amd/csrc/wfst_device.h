@@ -464,6 +464,42 @@ void launch_nbest_paths(const NbPathsDev &P, int n_slots, hipStream_t s, int sma
 constexpr int32_t kNbWordsHead = 4;
 void launch_nbest_words(const NbPathsDev &P, int n_slots, int cap_words, int32_t *packed, hipStream_t s);
 
+// ---- lattice-constrained word alignment (wfst_align.hip) -------------------------------------------------------------
+// The cheapest path of a channel's raw lattice (lat_toks[] / lat_arcs[] as lattice_emit_kernel left them) that spells a given word
+// sequence, for n_seqs sequences per listed channel (slot = position in the list).  align_index_kernel builds a slot's
+// by-destination in-arc index once; align_kernel runs one (slot, sequence) pair per workgroup over it.
+//   idx[slot][idx_ints]  recA int4[na_cap] {source state | is_eps << 31, olabel, graph bits, acoustic bits}, recB int4[na_cap]
+//                        {graph state of the source token, ilabel, source frame, 0} (what the tie rule and the word times need),
+//                        head[8] {status (kAln*), states, arcs, frames decoded, ...}, off[ns_cap + 1], cur[ns_cap],
+//                        fbeg / fend / feps[fr_cap] (first state, one past the last state, "has epsilon arcs" of a frame)
+//   cells[]              the pairs' tables d[state][len + 1] (orderable float bits, kAlnUnreached: no path), pair p at cell_off[p]
+//                        (< 0: the pair is not run: seq_len -1, or a table beyond the caller's max_cells)
+//   path[p][ns_cap]      the in-arc records of the traced path, last arc first
+//   out[p]               kAlignHead ints {found, arcs on the path, tot bits, lm bits, error (kAln*), 0, 0, 0}, begin[cap_words],
+//                        end[cap_words]
+constexpr int32_t kAlignHead = 8;
+constexpr uint32_t kAlnUnreached = 0xFFFFFFFFu;
+constexpr int32_t kAlnNoLattice = 1, kAlnTooLarge = 2, kAlnChannelError = 3, kAlnCycle = 4, kAlnInternal = 5;
+struct AlignDev {
+  int32_t *idx;
+  int64_t idx_ints;
+  int32_t ns_cap, na_cap, fr_cap;
+  const int32_t *seq_words;   // [cnt][n_seqs][cap_words]
+  const int32_t *seq_len;     // [cnt][n_seqs]
+  const int64_t *cell_off;    // [cnt][n_seqs]
+  uint32_t *cells;
+  int32_t *path;
+  int32_t n_seqs, cap_words;
+  const uint32_t *sil_bits;   // the silence bitmap over transition-ids 1..n_tid, or nullptr
+  int32_t n_tid;
+  int32_t *out;
+};
+inline int64_t align_idx_ints(int64_t ns_cap, int64_t na_cap, int64_t fr_cap) {
+  return (8 * na_cap + 8 + (ns_cap + 1) + ns_cap + 3 * fr_cap + 3) & ~(int64_t)3;
+}
+void launch_align_index(const DecoderDev &D, const AlignDev &A, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+void launch_align(const DecoderDev &D, const AlignDev &A, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

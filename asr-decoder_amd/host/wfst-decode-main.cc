@@ -39,6 +39,12 @@
 //                  arc, and the next word's begin or, with silence phones and --tid2phone=FILE, one past the word's last frame
 //                  that is not silence; end exclusive): the (start, end) per word of the reference's AlignStruct
 //                  (gpu-asr/gpu-worker-pool-itf.h:85-97)
+//   --nbest-word-times  with --nbest=N and/or --partial-nbest=K, batch shape and --single-stream: after every path's line one line
+//                  "KEY-k#j word begin end" per word ("KEY@frames nbest k#j word begin end" behind a --partial-nbest line) -- the
+//                  path's words aligned on the utterance's RAW lattice (AlignWords: wfst_decoder_align_words), frames as --word-times
+//                  has them; a path whose words the raw lattice does not hold prints "... notfound"
+//   --align-words=FILE  batch shape and --single-stream: FILE holds lines "KEY w1 w2 ..." (several per KEY, at most 64); after the
+//                  utterance's lines, per sequence "KEY align q found=0|1 arcs=N tot=.. lm=.." and "KEY align q#j word begin end"
 //   --device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]  batch shape only: the matrices
 //                  on disk are the acoustic model's RAW output; N frames at a time every utterance's rows are converted to the
 //                  dtype on the host, put into a staging buffer the device reads, and handed over where they lie
@@ -105,6 +111,9 @@
 #include <iostream>
 #include <memory>
 #include <mutex>
+
+#include <map>
+#include <sstream>
 
 #include "wfst-host.h"
 
@@ -195,7 +204,8 @@ int main(int argc, char **argv) {
     std::string lattice_file, lattice_text;
     long long lattice_links = 1ll << 22;
     int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
-    bool pull = false, partial_words = false, word_times = false, live_prune = false;
+    bool pull = false, partial_words = false, word_times = false, live_prune = false, nbest_times = false;
+    std::string align_file;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
@@ -241,6 +251,8 @@ int main(int argc, char **argv) {
       else if (a.compare(0, 16, "--partial-nbest=") == 0) partial_nbest = atoi(a.c_str() + 16);
       else if (a == "--live-lattice-prune") live_prune = true;
       else if (a == "--word-times") word_times = true;
+      else if (a == "--nbest-word-times") nbest_times = true;
+      else if (a.compare(0, 14, "--align-words=") == 0) align_file = a.substr(14);
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
           const size_t p1 = std::min(a.find(':', p0), a.size());
@@ -272,7 +284,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -285,6 +297,24 @@ int main(int argc, char **argv) {
     if (device_chunks && (chunk <= 0 || single || n_threads > 0)) { std::cerr << "--device-chunks goes with --chunk=N and the batch shape\n"; return 1; }
     if (word_times && n_threads > 0) { std::cerr << "--word-times goes with the batch shape or --single-stream\n"; return 1; }
     if (!wt_silence.empty() && (!word_times || tid2phone_file.empty())) { std::cerr << "--silence-phones goes with --word-times and --tid2phone=FILE\n"; return 1; }
+    if (nbest_times && ((nbest == 0 && partial_nbest == 0) || n_threads > 0)) { std::cerr << "--nbest-word-times goes with --nbest=N or --partial-nbest=K, in the batch shape or --single-stream\n"; return 1; }
+    if (!align_file.empty() && n_threads > 0) { std::cerr << "--align-words goes with the batch shape or --single-stream\n"; return 1; }
+    // --align-words: the sequences to align, by utterance key
+    std::map<std::string, std::vector<std::vector<int> > > align_seqs;
+    if (!align_file.empty()) {
+      std::ifstream af(align_file.c_str());
+      if (!af) { std::cerr << "cannot read " << align_file << "\n"; return 1; }
+      std::string line;
+      while (std::getline(af, line)) {
+        std::istringstream ls(line);
+        std::string key;
+        if (!(ls >> key)) continue;
+        std::vector<int> w;
+        for (int x; ls >> x;) w.push_back(x);
+        align_seqs[key].push_back(w);
+        if (align_seqs[key].size() > 64) { std::cerr << "--align-words: more than 64 sequences for " << key << "\n"; return 1; }
+      }
+    }
     if (live_prune && partial_nbest == 0) { std::cerr << "--live-lattice-prune goes with --chunk=N --partial-nbest=K\n"; return 1; }
     LatticeFasterDecoderConfig opt;
     opt.ReadConfigFile(pos[0]);
@@ -344,8 +374,38 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0;
-    auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths) {
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty();
+    // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
+    auto time_lines = [](const std::string &head, const std::vector<int> &words, const WordAlignment &a) {
+      std::string o;
+      if (!a.found) return head + " notfound\n";
+      for (size_t j = 0; j < words.size(); ++j)
+        o += head + "#" + std::to_string(j + 1) + " " + std::to_string(words[j]) + " " + std::to_string(a.frames[j].first) + " " + std::to_string(a.frames[j].second) + "\n";
+      return o;
+    };
+    // the words of every path of an n-best list (none where LatticeToVector fails: emit_nbest skips such a path)
+    auto path_words = [](std::vector<Lattice> &paths) {
+      std::vector<std::vector<int> > w(paths.size());
+      for (size_t k = 0; k < paths.size(); ++k) {
+        std::vector<int> phones;
+        float tot = 0, lm = 0;
+        if (!LatticeToVector(paths[k], w[k], phones, tot, lm)) w[k].clear();
+      }
+      return w;
+    };
+    // --align-words: the lines of one utterance
+    auto emit_align = [&](const Utt &u, const std::vector<WordAlignment> &al) {
+      auto it = align_seqs.find(u.key);
+      if (it == align_seqs.end()) return;
+      for (size_t q = 0; q < it->second.size() && q < al.size(); ++q) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), " found=%d arcs=%d tot=%.9g lm=%.9g\n", al[q].found ? 1 : 0, al[q].n_arcs, (double)al[q].tot, (double)al[q].lm);
+        const std::string head = u.key + " align " + std::to_string(q + 1);
+        out << head << buf;
+        if (al[q].found) out << time_lines(head, it->second[q], al[q]);
+      }
+    };
+    auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<WordAlignment> *times = nullptr) {
       for (size_t k = 0; k < paths.size(); ++k) {
         std::vector<int> words, phones;
         float tot = 0, lm = 0;
@@ -354,6 +414,7 @@ int main(int argc, char **argv) {
         out << u.key << '-' << (k + 1);
         for (int w : words) out << ' ' << w;
         out << '\n';
+        if (times && k < times->size()) out << time_lines(u.key + "-" + std::to_string(k + 1), words, (*times)[k]);
         std::cerr << "LOG " << u.key << '-' << (k + 1) << " tot_score " << tot << " lm_score " << lm << "\n";
       }
     };
@@ -389,8 +450,8 @@ int main(int argc, char **argv) {
     wfst_limits limits = {0, 0, 0, 0, 0};  // zeros = the library defaults
     limits.lattice_links = want_lattice ? lattice_links : 0;
     // --partial-nbest: "key@frames nbest k: w1 w2 ... tot=.. lm=.." per path, or "key@frames nbest status=code" for a channel's own failure
-    auto nbest_lines = [](const std::string &key, int frames, int status, const std::vector<std::vector<int> > &w, const std::vector<float> &t,
-                          const std::vector<float> &l) {
+    auto nbest_lines = [&](const std::string &key, int frames, int status, const std::vector<std::vector<int> > &w, const std::vector<float> &t,
+                           const std::vector<float> &l, const std::vector<WordAlignment> *times = nullptr) {
       std::string o;
       const std::string head = key + "@" + std::to_string(frames) + " nbest ";
       if (status != WFST_OK) o += head + "status=" + std::to_string(status) + "\n";
@@ -400,6 +461,7 @@ int main(int argc, char **argv) {
         char buf[64];
         snprintf(buf, sizeof(buf), " tot=%.9g lm=%.9g\n", (double)t[k], (double)l[k]);
         o += buf;
+        if (times && k < times->size()) o += time_lines(head + std::to_string(k + 1), w[k], (*times)[k]);
       }
       return o;
     };
@@ -702,7 +764,9 @@ int main(int argc, char **argv) {
               std::vector<float> pt, pl;
               int st = WFST_OK;
               decode.GetNbestWords(&pw, &pt, &pl, partial_nbest, false, slm1p, slm2p, &st);
-              out << nbest_lines(u.key, decode.NumFramesDecoded(), st, pw, pt, pl);
+              std::vector<WordAlignment> al;
+              if (nbest_times && !pw.empty()) decode.GetNbestWordTimes(pw, &al, false);
+              out << nbest_lines(u.key, decode.NumFramesDecoded(), st, pw, pt, pl, nbest_times ? &al : nullptr);
             }
           }
         } else {
@@ -728,7 +792,14 @@ int main(int argc, char **argv) {
           if (!exact_nbest) decode.GetNbestShortlist(paths, nbest);
           else if (second) decode.GetNbest(paths, nbest, slm1p, slm2p);
           else decode.GetNbest(paths, nbest);
-          emit_nbest(u, paths);
+          std::vector<WordAlignment> al;
+          if (nbest_times && !paths.empty()) decode.GetNbestWordTimes(path_words(paths), &al);
+          emit_nbest(u, paths, nbest_times ? &al : nullptr);
+        }
+        if (align_seqs.count(u.key)) {
+          std::vector<WordAlignment> al;
+          decode.GetNbestWordTimes(align_seqs[u.key], &al);
+          emit_align(u, al);
         }
       }
     } else {  // the MI355X shape: `batch` utterances per pass, `inflight` passes at a time
@@ -739,6 +810,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<int> > wt_words;                      // --word-times
         std::vector<std::vector<std::pair<int, int> > > wt_frames;
         std::string partials;                                         // --partial-nbest
+        std::vector<std::vector<WordAlignment> > nb_times, al_times;  // --nbest-word-times, --align-words
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -821,8 +893,12 @@ int main(int argc, char **argv) {
                 std::vector<std::vector<float> > t, l;
                 std::vector<int> st;
                 decode.GetNbestWords(live, partial_nbest, slm1, slm2, false, &w, &t, &l, &st);
+                std::vector<std::vector<WordAlignment> > al;
+                std::vector<int> ast;
+                if (nbest_times && !live.empty()) decode.AlignWords(live, w, false, &al, &ast);   // (one call for the channels still running)
                 for (size_t q = 0; q < live.size(); ++q)
-                  o.partials += nbest_lines(utts[b0 + (size_t)live[q]].key, decode.NumFramesDecoded(live[q]), st[q], w[q], t[q], l[q]);
+                  o.partials += nbest_lines(utts[b0 + (size_t)live[q]].key, decode.NumFramesDecoded(live[q]), st[q], w[q], t[q], l[q],
+                                            nbest_times && ast[q] == WFST_OK ? &al[q] : nullptr);
               }
             } else {
               decode.AdvanceDecodingHost(ch, rows, ready, stride);
@@ -846,6 +922,19 @@ int main(int argc, char **argv) {
                 else if (second) decode.GetNbest(i, o.nbest[i], nbest, slm1, slm2);
                 else decode.GetNbest(i, o.nbest[i], nbest);
               }
+              if (nbest_times) {   // every path of every channel in one call
+                std::vector<std::vector<std::vector<int> > > seqs(n);
+                for (int i = 0; i < n; ++i) seqs[i] = path_words(o.nbest[i]);
+                decode.AlignWords(ch, seqs, true, &o.nb_times);
+              }
+            }
+            if (!align_seqs.empty()) {
+              std::vector<std::vector<std::vector<int> > > seqs(n);
+              for (int i = 0; i < n; ++i) {
+                auto it = align_seqs.find(utts[b0 + i].key);
+                if (it != align_seqs.end()) seqs[i] = it->second;
+              }
+              decode.AlignWords(ch, seqs, true, &o.al_times);
             }
           }
         } catch (const std::exception &e) {
@@ -874,7 +963,8 @@ int main(int argc, char **argv) {
           emit_times = nullptr;
         }
         for (int i = 0; i < n && want_lattice; ++i) emit_lattice(utts[b0 + i], o.lats[i], o.lat_ok[i]);
-        for (int i = 0; i < n && nbest > 0; ++i) emit_nbest(utts[b0 + i], o.nbest[i]);
+        for (int i = 0; i < n && nbest > 0; ++i) emit_nbest(utts[b0 + i], o.nbest[i], nbest_times ? &o.nb_times[i] : nullptr);
+        for (int i = 0; i < n && !o.al_times.empty(); ++i) emit_align(utts[b0 + i], o.al_times[i]);
       }
     }
     double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

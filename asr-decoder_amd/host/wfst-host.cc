@@ -19,6 +19,8 @@
 // ... and so are the pruned live lattices' two calls: SetLiveLatticePrune reports itself missing there
 #pragma weak wfst_decoder_set_live_lattice_prune
 #pragma weak wfst_decoder_get_live_lattice_prune
+// ... and the word alignment's: AlignWords reports itself missing there
+#pragma weak wfst_decoder_align_words
 
 namespace datemoon {
 
@@ -1743,6 +1745,87 @@ void GpuBatchDecoder::GetNbestWords(const std::vector<int> &channels, int n, Arp
   if (tot) tot->swap(t);
   if (lm) lm->swap(l);
   if (status) *status = st;
+}
+
+// ---- word times for any word sequence of the lattice (wfst_decoder_align_words) -----------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i][q] for seqs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.
+static int AlignWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<std::vector<int> > > &seqs,
+                          bool use_final_probs, long long max_cells, std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_align_words) throw std::runtime_error("AlignWords: this build's device library has no wfst_decoder_align_words");
+  if (seqs.size() != ch.size()) throw std::runtime_error("AlignWords: one list of sequences per listed channel");
+  const size_t cnt = ch.size();
+  size_t ns = 1, cap = 1;
+  for (const auto &s : seqs) {
+    ns = std::max(ns, s.size());
+    for (const auto &w : s) cap = std::max(cap, w.size());
+  }
+  std::vector<int32_t> words(cnt * ns * cap, 0), len(cnt * ns, -1), st(cnt), found(cnt * ns), na(cnt * ns), b(cnt * ns * cap), e(cnt * ns * cap);
+  std::vector<float> t(cnt * ns), l(cnt * ns);
+  for (size_t i = 0; i < cnt; ++i)
+    for (size_t q = 0; q < seqs[i].size(); ++q) {
+      len[i * ns + q] = (int32_t)seqs[i][q].size();
+      std::copy(seqs[i][q].begin(), seqs[i][q].end(), words.begin() + (i * ns + q) * cap);
+    }
+  const int rc = wfst_decoder_align_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, (int32_t)cap, words.data(), len.data(),
+                                          max_cells, st.data(), found.data(), na.data(), b.data(), e.data(), t.data(), l.data());
+  if (rc != WFST_OK) return rc;
+  out->assign(cnt, std::vector<WordAlignment>());
+  for (size_t i = 0; i < cnt; ++i) {
+    (*out)[i].resize(seqs[i].size());
+    for (size_t q = 0; q < seqs[i].size(); ++q) {
+      WordAlignment &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.n_arcs = na[p]; a.tot = t[p]; a.lm = l[p];
+      for (size_t k = 0; k < seqs[i][q].size(); ++k) a.frames.push_back(std::make_pair(b[p * cap + k], e[p * cap + k]));
+    }
+  }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::AlignWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
+                                 std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status, long long max_cells) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<std::vector<WordAlignment> > o;
+  std::vector<int> st;
+  if (AlignWordsCall(_dec, ch, seqs, use_final_probs, max_cells, &o, &st) != WFST_OK) Fatal("AlignWords");
+  if (!status)
+    for (int s : st)
+      if (s != WFST_OK) Fatal("AlignWords");
+  if (out) out->swap(o);
+  if (status) *status = st;
+}
+
+void GpuLatticeDecoder::GetNbestWordTimes(const std::vector<std::vector<int> > &nbest, std::vector<WordAlignment> *out, bool use_final_probs) {
+  std::vector<std::vector<WordAlignment> > o;
+  if (!nbest.empty()) {
+    std::vector<int> st;
+    int rc = WFST_OK;
+    std::string msg;
+    // (the C-ABI calls of one decoder are not re-entrant: over a pool this runs in the batcher thread, like GetNbest)
+    OnDevice([&] {
+      rc = AlignWordsCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<std::vector<int> > >(1, nbest), use_final_probs, 0, &o, &st);
+      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+    });
+    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("AlignWords: " + msg);
+  }
+  if (out) {
+    out->clear();
+    if (!o.empty()) out->swap(o[0]);
+  }
+}
+
+bool GpuLatticeDecoder::AlignWords(const std::vector<int> &words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs) {
+  std::vector<WordAlignment> a;
+  GetNbestWordTimes(std::vector<std::vector<int> >(1, words), &a, use_final_probs);
+  if (frames) frames->swap(a[0].frames);
+  if (tot) *tot = a[0].tot;
+  if (lm) *lm = a[0].lm;
+  return a[0].found;
 }
 
 // ---- pruned live lattices (wfst_decoder_set_live_lattice_prune) ------------------------------------------------------------------

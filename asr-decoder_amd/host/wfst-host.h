@@ -402,6 +402,16 @@ class GpuChannelPool {
 // one piece from a MatrixDecodable) and shipped to the GPU; the search runs there.
 // Fatal conditions throw std::runtime_error (the reference's LOG_ERR does, util/log-message.cc:
 // 122-145); soft ones print a warning and return false, as in the reference.
+// One word sequence aligned on a channel's raw lattice (wfst_decoder_align_words): the cheapest path that spells it.  frames[k] =
+// (begin, end) of word k in frames, end exclusive, by GetWords' definition with the aligned path's arcs as the hops; tot / lm =
+// LatticeToVector's two scores of that path; found = false (and everything else empty / zero): the sequence is not in the lattice.
+struct WordAlignment {
+  bool found = false;
+  int n_arcs = 0;
+  float tot = 0.0f, lm = 0.0f;
+  std::vector<std::pair<int, int> > frames;
+};
+
 class GpuLatticeDecoder : public DecoderItf {
  public:
   GpuLatticeDecoder(Fst *graph, const LatticeFasterDecoderConfig &config, const wfst_limits *limits = nullptr);
@@ -482,6 +492,14 @@ class GpuLatticeDecoder : public DecoderItf {
   // of many threads go to the device as one list per batcher pass and distinct (n, use_final_probs, LM pair).
   bool GetNbestWords(std::vector<std::vector<int> > *words, std::vector<float> *tot, std::vector<float> *lm, int n, bool use_final_probs = true,
                      ArpaLm *oldlm = nullptr, ArpaLm *newlm = nullptr, int *status = nullptr);
+  // Word times for any word sequence of the lattice -- an n-best path, the rescored 1-best a --use-second service returns
+  // (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:122-130), an outside transcript: the cheapest path of the channel's RAW lattice
+  // that spells `words` (wfst_decoder_align_words), mid-utterance or after FinalizeDecoding; (*frames)[k] as GetWords has them
+  // (SetSilencePhones included), *tot / *lm that path's scores.  false: the sequence is not in the lattice (or there is none).  The
+  // channel's own failure throws.  Over a pool the call runs in the batcher thread, like GetNbest.
+  bool AlignWords(const std::vector<int> &words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs = true);
+  // ... of every path GetNbestWords returned, in one device call: (*out)[k] for nbest[k]
+  void GetNbestWordTimes(const std::vector<std::vector<int> > &nbest, std::vector<WordAlignment> *out, bool use_final_probs = true);
   // Pruned live lattices (see GpuChannelPool::SetLiveLatticePrune) for this object's device decoder: the private one, or -- over a
   // pool, and so under ShareDevice -- the shared decoder of every object on it (set it before the other threads decode).
   void SetLiveLatticePrune(bool on);
@@ -581,6 +599,11 @@ class GpuBatchDecoder {
   void GetNbestWords(const std::vector<int> &channels, int n, ArpaLm *oldlm, ArpaLm *newlm, bool use_final_probs,
                      std::vector<std::vector<std::vector<int> > > *words, std::vector<std::vector<float> > *tot,
                      std::vector<std::vector<float> > *lm, std::vector<int> *status = nullptr);
+  // AlignWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
+  // seqs[i] = the word sequences for listed channel i (at most 64), (*out)[i][q] the answer for seqs[i][q]; (*status)[i]: WFST_OK or
+  // the channel's own error code (nothing of it is found then; without `status` it throws).  max_cells: see wfst_decoder_align_words.
+  void AlignWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
+                  std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status = nullptr, long long max_cells = 0);
   void SetLiveLatticePrune(bool on);   // pruned live lattices for every channel (see GpuChannelPool::SetLiveLatticePrune)
   wfst_decoder *Handle() { return _dec; }
 

@@ -46,6 +46,7 @@ SYMBOLS = [
     "wfst_decoder_set_score_transform", "wfst_decoder_advance_chunk", "wfst_decoder_get_scores",
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
+    "wfst_decoder_align_words",
 ]
 
 
@@ -769,6 +770,50 @@ class BatchDecoder:
         return [(int(status[i]), [dict(words=words[i, k, : min(int(nw[i, k]), int(cap_words))].copy(), n_words=int(nw[i, k]), tot=np.float32(tot[i, k]),
                                        lm=np.float32(lm[i, k]), path_tot=np.float32(ptot[i, k])) for k in range(int(got[i]))])
                 for i in range(cnt)]
+
+    def align_words(self, seqs, channels=None, use_final_probs=True, max_cells=0):
+        """Lattice-constrained word alignment of a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_align_words): seqs[i] = the word sequences to align on channels[i] (each a sequence of word ids > 0, possibly
+        empty; None: skipped).  Per channel a list with one dict per sequence: found, begin / end (int32 arrays, frames, end
+        exclusive), tot, lm (float32: the aligned path's LatticeToVector scores), n_arcs, and status -- WFST_OK or the CHANNEL's
+        own error code (then nothing of it is found)."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
+        cnt = len(ch)
+        if len(seqs) != cnt:
+            raise ValueError("one list of sequences per listed channel")
+        ns = max([len(s) for s in seqs] + [1])
+        cap = max([len(w) for s in seqs for w in s if w is not None] + [1])
+        words = np.zeros((cnt, ns, cap), np.int32)
+        lens = np.full((cnt, ns), -1, np.int32)
+        for i, s in enumerate(seqs):
+            for q, w in enumerate(s):
+                if w is not None:
+                    lens[i, q] = len(w)
+                    words[i, q, :len(w)] = np.asarray(w, np.int32)
+        status = np.zeros(cnt, np.int32)
+        found, na = np.zeros((cnt, ns), np.int32), np.zeros((cnt, ns), np.int32)
+        begin, end = np.zeros((cnt, ns, cap), np.int32), np.zeros((cnt, ns, cap), np.int32)
+        tot, lm = np.zeros((cnt, ns), np.float32), np.zeros((cnt, ns), np.float32)
+        _check(lib().wfst_decoder_align_words(self.h, _i32(ch), cnt, int(bool(use_final_probs)), ns, cap, _i32(words), _i32(lens),
+                                              C.c_int64(int(max_cells)), _i32(status), _i32(found), _i32(na), _i32(begin), _i32(end),
+                                              _f32(tot), _f32(lm)))
+        return [[dict(found=bool(found[i, q]), begin=begin[i, q, :max(int(lens[i, q]), 0)].copy(), end=end[i, q, :max(int(lens[i, q]), 0)].copy(),
+                      tot=np.float32(tot[i, q]), lm=np.float32(lm[i, q]), n_arcs=int(na[i, q]), status=int(status[i]))
+                 for q in range(len(seqs[i]))] for i in range(cnt)]
+
+    def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):
+        """nbest_words(...) with word times: every path's words aligned on its channel's raw lattice (align_words); the dicts of
+        nbest_words gain found, begin, end, n_arcs and align_tot / align_lm (the aligned path's own scores: the determinizer
+        re-associates the sums, so they may differ from tot / lm in the last bits)."""
+        res = self.nbest_words(n_paths, channels, old_lm, new_lm, use_final_probs, cap_words)
+        ch = list(range(self.n)) if channels is None else [int(c) for c in channels]
+        seqs = [[p["words"] if p["n_words"] <= int(cap_words) else None for p in paths] for _, paths in res]
+        al = self.align_words(seqs, ch, use_final_probs, max_cells)
+        for (_, paths), a in zip(res, al):
+            for p, x in zip(paths, a):
+                p.update(found=x["found"], begin=x["begin"], end=x["end"], n_arcs=x["n_arcs"], align_tot=x["tot"], align_lm=x["lm"],
+                         align_status=x["status"])
+        return res
 
     def raw_lattices(self, channels=None, use_final_probs=True, threads=0):
         """GetRawLattice of many finalized channels.  The first call fetches the pruned lattices of all

@@ -542,6 +542,55 @@ int wfst_decoder_set_live_lattice_prune(wfst_decoder *d, int32_t mode);
 /* Either output may be NULL; scratch_bytes is 0 until mode 1 has been set once. */
 int wfst_decoder_get_live_lattice_prune(wfst_decoder *d, int32_t *mode, int64_t *scratch_bytes);
 
+/* ---- lattice-constrained word alignment: word times for any n-best path ---------------------------------------------------------
+ * The services hand a client (start, end) per word for the first-pass best path only (AlignStruct, gpu-asr/gpu-worker-pool-itf.h:85-97:
+ * wfst_decoder_get_words here).  The determinizer drops the input labels (OutputNoolabel), so the paths of GetNbestTxt
+ * (kaldi-nnet3/kaldi-online-nnet3-my-decoder.cc:139-150) and the rescored 1-best a --use-second deployment returns (:122-130) are
+ * words and costs without times.  This call puts them back: given a word sequence, the cheapest path of the channel's RAW lattice
+ * that spells it, with that path's word times and scores -- for a list of channels, live and finalized ones mixed, n_seqs sequences
+ * per channel, one launch per stage (the live channels' lattices emitted, the in-arc index of every lattice built once, one
+ * dynamic program per (channel, sequence): align_index_kernel / align_kernel).
+ *
+ * The lattice R = what wfst_decoder_get_raw_lattice(channel, use_final_probs) returns at this moment (wfst_decoder_set_live_lattice_prune,
+ * the use_final_probs rule after FinalizeDecoding and "no lattice" honoured): every arc goes to a higher state id, state 0 is the
+ * start, final states are flagged and carry no weight.
+ * The recurrence, for a sequence w[0..L) of word ids > 0: d[0][0] = 0.0f; every arc a = (s -> t, ilabel, olabel, graph, acoustic)
+ * takes (s, k) to (t, k) if olabel == 0 and to (t, k + 1) if k < L and olabel == w[k] -- no other transition -- with
+ *   d[t][k'] = min(d[t][k'], d[s][k] + (graph + acoustic)),
+ * all in float32, graph + acoustic rounded first and then added (LatticeToVector's tot += graph + acoustic); a total of zero is +0,
+ * and a total that is not finite is no path.  The answer ends in the final state e with the least d[e][L]; found = 0 if no final
+ * state has one.  The path is recovered backwards: at (t, k') an in-arc with d[s][k] + (graph + acoustic) == d[t][k'].
+ * The tie rule does not depend on the numbering of states or arcs: among several such in-arcs the least wins under (emitting before
+ * epsilon, graph state of the source token, ilabel, olabel, bits of graph, bits of acoustic -- the float's 32 bits as an unsigned
+ * number); among several best final states the least graph state.  On biglm lattices two tokens of a frame may share a graph
+ * state: a tie that survives the rule is unspecified there.
+ *
+ * Per listed channel i and sequence q (seq_len[i][q] words at seq_words[i][q][..]; -1: skipped, all outputs zero): found[i][q];
+ * n_arcs[i][q] arcs on the path; tot_score = d[e][L]; lm_score = the float32 sum of graph along the path in arc order; per word k
+ * begin_frame[i][q][k] = the frame of the source state of the arc that carries the word, and end_frame[i][q][k] (exclusive) by
+ * wfst_decoder_get_words' own definition with the aligned path's arcs as its hops: the next word's begin, the end state's frame for the
+ * last word; with a silence list (wfst_decoder_set_silence_phones) one past the last non-silence emitting arc of the word's span,
+ * begin_frame[i][q][k] if there is none.  The empty sequence (seq_len 0) is found where a path without words is.
+ *
+ * A failure of ONE channel goes into status[i] with found[i][..] = 0 and the call still returns WFST_OK: a sequence whose table of
+ * states x (seq_len + 1) cells is beyond max_cells (WFST_E_CAPACITY), a device error of that channel's utterance.  max_cells = 0 is
+ * the default, 65 536 states (the determinizer's own default bound) x 65: a table takes 4 bytes per cell and 4 bytes per state of path
+ * scratch, 16.5 MiB per sequence at that bound; the index takes 32 bytes per arc and 8 per state of a listed lattice.  The workspace is
+ * sized from the emitted lattices and the sequences, allocated by the first call, kept with the decoder; lists whose tables pass
+ * 256 MiB together are taken in rounds.
+ * The call itself fails, before any device work, with WFST_E_ARG (n_seqs outside 1..64, cap_words <= 0, a seq_len above cap_words, a
+ * word id <= 0 inside a sequence, a bad or duplicate channel list, NULL sequences) or WFST_E_STATE (a decoder without lattice_links, a
+ * listed channel never initialised).  Any output pointer may be NULL.  The decoder's state is only read: decoding goes on bit for bit
+ * as without the call, and what the other getters keep for the same channels answers afterwards what it would have answered.
+ * Synchronous, as wfst_decoder_get_nbest_words is and for the same reason: the lattices' sizes pass through the host. */
+int wfst_decoder_align_words(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                             int32_t n_seqs /* per channel, 1..64 */, int32_t cap_words,
+                             const int32_t *seq_words /* [n][n_seqs][cap_words] */, const int32_t *seq_len /* [n][n_seqs], -1 = skip */,
+                             int64_t max_cells /* states x (len + 1) per sequence; 0 = default */,
+                             int32_t *status /* [n] */, int32_t *found, int32_t *n_arcs /* [n][n_seqs] */,
+                             int32_t *begin_frame, int32_t *end_frame /* [n][n_seqs][cap_words] */,
+                             float *tot_score, float *lm_score /* [n][n_seqs] */);
+
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
  * ConvertNbestToVector, then LatticeToVector per path) of channels of a lattice-mode decoder, finalized
