@@ -500,6 +500,34 @@ inline int64_t align_idx_ints(int64_t ns_cap, int64_t na_cap, int64_t fr_cap) {
 void launch_align_index(const DecoderDev &D, const AlignDev &A, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 void launch_align(const DecoderDev &D, const AlignDev &A, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- lattice edit distance (wfst_nearest.hip) ---------------------------------------------------------------------------
+// The path of a channel's raw lattice nearest a reference word sequence: least (word errors, cost), for n_refs references per listed
+// channel, over the in-arc index align_index_kernel built (AlignDev::idx; the other fields of the AlignDev are not read).
+//   cells[]              the pairs' tables v[state][len + 1]: errors << 32 | orderable float bits of the cost, kNrUnreached: no path;
+//                        pair p at cell_off[p] (< 0: the pair is not run: ref_len -1, or a table beyond the caller's max_cells)
+//   path[p][path_cap]    the traceback's steps, last first: kind << 30 | in-arc record (kind 3, the deletion step: no arc);
+//                        path_cap >= ns_cap + cap_words
+//   out[p]               kNearestHead ints {found, arcs on the path, tot bits, lm bits, error (kAln*), n_err, n_cor, n_sub, n_ins,
+//                        n_del, n_hyp, 0}, hyp_words[cap_hyp], begin[cap_hyp], end[cap_hyp], ref_hyp[cap_words]
+constexpr int32_t kNearestHead = 12;
+constexpr unsigned long long kNrUnreached = ~0ull;
+struct NearestDev {
+  const int4 *lat_toks;       // DecoderDev::lat_toks, lat_tok_cap entries per channel
+  int64_t lat_tok_cap;
+  const int32_t *ref_words;   // [cnt][n_refs][cap_words]
+  const int32_t *ref_len;     // [cnt][n_refs]
+  const int64_t *cell_off;    // [cnt][n_refs], in cells
+  unsigned long long *cells;
+  int32_t *path;
+  int32_t path_cap;
+  int32_t n_refs, cap_words, cap_hyp;
+  const uint32_t *sil_bits;   // the silence bitmap over transition-ids 1..n_tid, or nullptr
+  int32_t n_tid;
+  int32_t *out;
+};
+constexpr int64_t nearest_out_ints(int64_t cap_words, int64_t cap_hyp) { return kNearestHead + 3 * cap_hyp + cap_words; }
+void launch_nearest(const AlignDev &A, const NearestDev &N, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

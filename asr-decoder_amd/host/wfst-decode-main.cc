@@ -45,6 +45,13 @@
 //                  has them; a path whose words the raw lattice does not hold prints "... notfound"
 //   --align-words=FILE  batch shape and --single-stream: FILE holds lines "KEY w1 w2 ..." (several per KEY, at most 64); after the
 //                  utterance's lines, per sequence "KEY align q found=0|1 arcs=N tot=.. lm=.." and "KEY align q#j word begin end"
+//   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
+//                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
+//                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
+//                  and "KEY nearest q#j word begin end" per word of that path ("KEY nearest q notfound": no lattice); behind the
+//                  last utterance one line "nearest %WER p [ errors / reference words, I ins, D del, S sub ]" over all of them --
+//                  with correct transcripts the lattices' oracle error, in the form kaldi-bin/bin/nbest-compute-wer.cc:166-167
+//                  prints the 1-best's
 //   --device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]  batch shape only: the matrices
 //                  on disk are the acoustic model's RAW output; N frames at a time every utterance's rows are converted to the
 //                  dtype on the host, put into a staging buffer the device reads, and handed over where they lie
@@ -205,7 +212,7 @@ int main(int argc, char **argv) {
     long long lattice_links = 1ll << 22;
     int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
     bool pull = false, partial_words = false, word_times = false, live_prune = false, nbest_times = false;
-    std::string align_file;
+    std::string align_file, nearest_file;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
@@ -253,6 +260,7 @@ int main(int argc, char **argv) {
       else if (a == "--word-times") word_times = true;
       else if (a == "--nbest-word-times") nbest_times = true;
       else if (a.compare(0, 14, "--align-words=") == 0) align_file = a.substr(14);
+      else if (a.compare(0, 16, "--nearest-words=") == 0) nearest_file = a.substr(16);
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
           const size_t p1 = std::min(a.find(':', p0), a.size());
@@ -284,7 +292,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -299,11 +307,15 @@ int main(int argc, char **argv) {
     if (!wt_silence.empty() && (!word_times || tid2phone_file.empty())) { std::cerr << "--silence-phones goes with --word-times and --tid2phone=FILE\n"; return 1; }
     if (nbest_times && ((nbest == 0 && partial_nbest == 0) || n_threads > 0)) { std::cerr << "--nbest-word-times goes with --nbest=N or --partial-nbest=K, in the batch shape or --single-stream\n"; return 1; }
     if (!align_file.empty() && n_threads > 0) { std::cerr << "--align-words goes with the batch shape or --single-stream\n"; return 1; }
-    // --align-words: the sequences to align, by utterance key
-    std::map<std::string, std::vector<std::vector<int> > > align_seqs;
-    if (!align_file.empty()) {
-      std::ifstream af(align_file.c_str());
-      if (!af) { std::cerr << "cannot read " << align_file << "\n"; return 1; }
+    if (!nearest_file.empty() && n_threads > 0) { std::cerr << "--nearest-words goes with the batch shape or --single-stream\n"; return 1; }
+    // --align-words / --nearest-words: the sequences to align and the references, by utterance key
+    std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs;
+    for (int which = 0; which < 2; ++which) {
+      const std::string &file = which ? nearest_file : align_file, flag = which ? "--nearest-words" : "--align-words";
+      std::map<std::string, std::vector<std::vector<int> > > &into = which ? nearest_refs : align_seqs;
+      if (file.empty()) continue;
+      std::ifstream af(file.c_str());
+      if (!af) { std::cerr << "cannot read " << file << "\n"; return 1; }
       std::string line;
       while (std::getline(af, line)) {
         std::istringstream ls(line);
@@ -311,8 +323,8 @@ int main(int argc, char **argv) {
         if (!(ls >> key)) continue;
         std::vector<int> w;
         for (int x; ls >> x;) w.push_back(x);
-        align_seqs[key].push_back(w);
-        if (align_seqs[key].size() > 64) { std::cerr << "--align-words: more than 64 sequences for " << key << "\n"; return 1; }
+        into[key].push_back(w);
+        if (into[key].size() > 64) { std::cerr << flag << ": more than 64 sequences for " << key << "\n"; return 1; }
       }
     }
     if (live_prune && partial_nbest == 0) { std::cerr << "--live-lattice-prune goes with --chunk=N --partial-nbest=K\n"; return 1; }
@@ -374,7 +386,7 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty();
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty();
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
     auto time_lines = [](const std::string &head, const std::vector<int> &words, const WordAlignment &a) {
       std::string o;
@@ -403,6 +415,24 @@ int main(int argc, char **argv) {
         const std::string head = u.key + " align " + std::to_string(q + 1);
         out << head << buf;
         if (al[q].found) out << time_lines(head, it->second[q], al[q]);
+      }
+    };
+    // --nearest-words: the lines of one utterance, and the sums of the closing line
+    long long nr_err = 0, nr_words = 0, nr_ins = 0, nr_del = 0, nr_sub = 0;
+    auto emit_nearest = [&](const Utt &u, const std::vector<NearestPath> &np) {
+      auto it = nearest_refs.find(u.key);
+      if (it == nearest_refs.end()) return;
+      for (size_t q = 0; q < it->second.size() && q < np.size(); ++q) {
+        const NearestPath &a = np[q];
+        const std::string head = u.key + " nearest " + std::to_string(q + 1);
+        if (!a.found) { out << head << " notfound\n"; continue; }
+        char buf[160];
+        snprintf(buf, sizeof(buf), " err=%d cor=%d sub=%d ins=%d del=%d arcs=%d tot=%.9g lm=%.9g\n", a.errors, a.cor, a.sub, a.ins, a.del, a.n_arcs,
+                 (double)a.tot, (double)a.lm);
+        out << head << buf;
+        for (size_t j = 0; j < a.words.size(); ++j)
+          out << head << "#" << (j + 1) << " " << a.words[j] << " " << a.frames[j].first << " " << a.frames[j].second << "\n";
+        nr_err += a.errors; nr_words += (long long)it->second[q].size(); nr_ins += a.ins; nr_del += a.del; nr_sub += a.sub;
       }
     };
     auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<WordAlignment> *times = nullptr) {
@@ -801,6 +831,11 @@ int main(int argc, char **argv) {
           decode.GetNbestWordTimes(align_seqs[u.key], &al);
           emit_align(u, al);
         }
+        if (nearest_refs.count(u.key)) {
+          std::vector<NearestPath> np;
+          decode.NearestWords(nearest_refs[u.key], &np);
+          emit_nearest(u, np);
+        }
       }
     } else {  // the MI355X shape: `batch` utterances per pass, `inflight` passes at a time
       struct BatchOut {
@@ -811,6 +846,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<std::pair<int, int> > > wt_frames;
         std::string partials;                                         // --partial-nbest
         std::vector<std::vector<WordAlignment> > nb_times, al_times;  // --nbest-word-times, --align-words
+        std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -936,6 +972,14 @@ int main(int argc, char **argv) {
               }
               decode.AlignWords(ch, seqs, true, &o.al_times);
             }
+            if (!nearest_refs.empty()) {   // every reference of every channel in one call
+              std::vector<std::vector<std::vector<int> > > refs(n);
+              for (int i = 0; i < n; ++i) {
+                auto it = nearest_refs.find(utts[b0 + i].key);
+                if (it != nearest_refs.end()) refs[i] = it->second;
+              }
+              decode.NearestWords(ch, refs, true, &o.nearest);
+            }
           }
         } catch (const std::exception &e) {
           errors[(size_t)k] = e.what();
@@ -965,7 +1009,14 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && want_lattice; ++i) emit_lattice(utts[b0 + i], o.lats[i], o.lat_ok[i]);
         for (int i = 0; i < n && nbest > 0; ++i) emit_nbest(utts[b0 + i], o.nbest[i], nbest_times ? &o.nb_times[i] : nullptr);
         for (int i = 0; i < n && !o.al_times.empty(); ++i) emit_align(utts[b0 + i], o.al_times[i]);
+        for (int i = 0; i < n && !o.nearest.empty(); ++i) emit_nearest(utts[b0 + i], o.nearest[i]);
       }
+    }
+    if (!nearest_refs.empty()) {   // errors over reference words, as nbest-compute-wer prints them
+      char buf[160];
+      snprintf(buf, sizeof(buf), "nearest %%WER %.2f [ %lld / %lld, %lld ins, %lld del, %lld sub ]\n", nr_words ? 100.0 * (double)nr_err / (double)nr_words : 0.0,
+               nr_err, nr_words, nr_ins, nr_del, nr_sub);
+      out << buf;
     }
     double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (timed_frames) {   // (--warm: the clock started behind the warm-up passes)

@@ -21,6 +21,8 @@
 #pragma weak wfst_decoder_get_live_lattice_prune
 // ... and the word alignment's: AlignWords reports itself missing there
 #pragma weak wfst_decoder_align_words
+// ... and the lattice edit distance's: NearestWords reports itself missing there
+#pragma weak wfst_decoder_nearest_words
 
 namespace datemoon {
 
@@ -1826,6 +1828,93 @@ bool GpuLatticeDecoder::AlignWords(const std::vector<int> &words, std::vector<st
   if (tot) *tot = a[0].tot;
   if (lm) *lm = a[0].lm;
   return a[0].found;
+}
+
+// ---- the lattice path nearest a transcript (wfst_decoder_nearest_words) ---------------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i][q] for refs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.  A path with
+// more words than the first call made room for is asked for again with n_hyp's room.
+static int NearestWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<std::vector<int> > > &refs,
+                            bool use_final_probs, long long max_cells, std::vector<std::vector<NearestPath> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_nearest_words) throw std::runtime_error("NearestWords: this build's device library has no wfst_decoder_nearest_words");
+  if (refs.size() != ch.size()) throw std::runtime_error("NearestWords: one list of references per listed channel");
+  const size_t cnt = ch.size();
+  size_t ns = 1, cap = 1;
+  for (const auto &s : refs) {
+    ns = std::max(ns, s.size());
+    for (const auto &w : s) cap = std::max(cap, w.size());
+  }
+  const size_t np = cnt * ns;
+  std::vector<int32_t> words(np * cap, 0), len(np, -1), st(cnt), found(np), ne(np), nc(np), nsub(np), ni(np), ndel(np), na(np), nh(np), rh(np * cap);
+  std::vector<int32_t> hyp, b, e;
+  std::vector<float> t(np), l(np);
+  for (size_t i = 0; i < cnt; ++i)
+    for (size_t q = 0; q < refs[i].size(); ++q) {
+      len[i * ns + q] = (int32_t)refs[i][q].size();
+      std::copy(refs[i][q].begin(), refs[i][q].end(), words.begin() + (i * ns + q) * cap);
+    }
+  size_t hcap = cap + 16;
+  for (int pass = 0;; ++pass) {
+    hyp.assign(np * hcap, 0); b.assign(np * hcap, 0); e.assign(np * hcap, 0);
+    const int rc = wfst_decoder_nearest_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, (int32_t)cap, words.data(), len.data(),
+                                              (int32_t)hcap, max_cells, st.data(), found.data(), ne.data(), nc.data(), nsub.data(), ni.data(),
+                                              ndel.data(), na.data(), nh.data(), hyp.data(), b.data(), e.data(), rh.data(), t.data(), l.data());
+    if (rc != WFST_OK) return rc;
+    const size_t most = (size_t)*std::max_element(nh.begin(), nh.end());
+    if (most <= hcap || pass) break;
+    hcap = most;
+  }
+  out->assign(cnt, std::vector<NearestPath>());
+  for (size_t i = 0; i < cnt; ++i) {
+    (*out)[i].resize(refs[i].size());
+    for (size_t q = 0; q < refs[i].size(); ++q) {
+      NearestPath &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.errors = ne[p]; a.cor = nc[p]; a.sub = nsub[p]; a.ins = ni[p]; a.del = ndel[p]; a.n_arcs = na[p]; a.tot = t[p]; a.lm = l[p];
+      for (size_t j = 0; j < std::min((size_t)nh[p], hcap); ++j) {
+        a.words.push_back(hyp[p * hcap + j]);
+        a.frames.push_back(std::make_pair(b[p * hcap + j], e[p * hcap + j]));
+      }
+      a.ref_hyp.assign(rh.begin() + p * cap, rh.begin() + p * cap + refs[i][q].size());
+    }
+  }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::NearestWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &refs, bool use_final_probs,
+                                   std::vector<std::vector<NearestPath> > *out, std::vector<int> *status, long long max_cells) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<std::vector<NearestPath> > o;
+  std::vector<int> st;
+  if (NearestWordsCall(_dec, ch, refs, use_final_probs, max_cells, &o, &st) != WFST_OK) Fatal("NearestWords");
+  if (!status)
+    for (int s : st)
+      if (s != WFST_OK) Fatal("NearestWords");
+  if (out) out->swap(o);
+  if (status) *status = st;
+}
+
+void GpuLatticeDecoder::NearestWords(const std::vector<std::vector<int> > &refs, std::vector<NearestPath> *out, bool use_final_probs) {
+  std::vector<std::vector<NearestPath> > o;
+  if (!refs.empty()) {
+    std::vector<int> st;
+    int rc = WFST_OK;
+    std::string msg;
+    // (the C-ABI calls of one decoder are not re-entrant: over a pool this runs in the batcher thread, like AlignWords)
+    OnDevice([&] {
+      rc = NearestWordsCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<std::vector<int> > >(1, refs), use_final_probs, 0, &o, &st);
+      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+    });
+    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("NearestWords: " + msg);
+  }
+  if (out) {
+    out->clear();
+    if (!o.empty()) out->swap(o[0]);
+  }
 }
 
 // ---- pruned live lattices (wfst_decoder_set_live_lattice_prune) ------------------------------------------------------------------

@@ -412,6 +412,19 @@ struct WordAlignment {
   std::vector<std::pair<int, int> > frames;
 };
 
+// The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
+// cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
+// them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
+// LatticeToVector's two scores of the path.  found = false (everything else empty / zero): the channel has no lattice, or no final
+// state of it is reached.
+struct NearestPath {
+  bool found = false;
+  int errors = 0, cor = 0, sub = 0, ins = 0, del = 0, n_arcs = 0;
+  float tot = 0.0f, lm = 0.0f;
+  std::vector<int> words, ref_hyp;
+  std::vector<std::pair<int, int> > frames;
+};
+
 class GpuLatticeDecoder : public DecoderItf {
  public:
   GpuLatticeDecoder(Fst *graph, const LatticeFasterDecoderConfig &config, const wfst_limits *limits = nullptr);
@@ -500,6 +513,11 @@ class GpuLatticeDecoder : public DecoderItf {
   bool AlignWords(const std::vector<int> &words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs = true);
   // ... of every path GetNbestWords returned, in one device call: (*out)[k] for nbest[k]
   void GetNbestWordTimes(const std::vector<std::vector<int> > &nbest, std::vector<WordAlignment> *out, bool use_final_probs = true);
+  // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
+  // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
+  // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
+  // 1-best's).  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void NearestWords(const std::vector<std::vector<int> > &refs, std::vector<NearestPath> *out, bool use_final_probs = true);
   // Pruned live lattices (see GpuChannelPool::SetLiveLatticePrune) for this object's device decoder: the private one, or -- over a
   // pool, and so under ShareDevice -- the shared decoder of every object on it (set it before the other threads decode).
   void SetLiveLatticePrune(bool on);
@@ -604,6 +622,11 @@ class GpuBatchDecoder {
   // the channel's own error code (nothing of it is found then; without `status` it throws).  max_cells: see wfst_decoder_align_words.
   void AlignWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
                   std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status = nullptr, long long max_cells = 0);
+  // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
+  // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
+  // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.
+  void NearestWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &refs, bool use_final_probs,
+                    std::vector<std::vector<NearestPath> > *out, std::vector<int> *status = nullptr, long long max_cells = 0);
   void SetLiveLatticePrune(bool on);   // pruned live lattices for every channel (see GpuChannelPool::SetLiveLatticePrune)
   wfst_decoder *Handle() { return _dec; }
 

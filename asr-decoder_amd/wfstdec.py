@@ -46,7 +46,7 @@ SYMBOLS = [
     "wfst_decoder_set_score_transform", "wfst_decoder_advance_chunk", "wfst_decoder_get_scores",
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
-    "wfst_decoder_align_words",
+    "wfst_decoder_align_words", "wfst_decoder_nearest_words",
 ]
 
 
@@ -800,6 +800,54 @@ class BatchDecoder:
         return [[dict(found=bool(found[i, q]), begin=begin[i, q, :max(int(lens[i, q]), 0)].copy(), end=end[i, q, :max(int(lens[i, q]), 0)].copy(),
                       tot=np.float32(tot[i, q]), lm=np.float32(lm[i, q]), n_arcs=int(na[i, q]), status=int(status[i]))
                  for q in range(len(seqs[i]))] for i in range(cnt)]
+
+    def nearest_words(self, refs, channels=None, use_final_probs=True, max_cells=0, cap_hyp=0):
+        """Lattice edit distance of a LIST of channels (None: all), live and finalized ones mixed (wfst_decoder_nearest_words):
+        refs[i] = the reference word sequences for channels[i] (each a sequence of word ids > 0, possibly empty; None: skipped).  Per
+        channel a list with one dict per reference -- the lattice path nearest it: found, n_err, n_cor, n_sub, n_ins, n_del, n_arcs,
+        n_hyp, hyp_words, begin / end (int32 arrays per hypothesis word, frames, end exclusive; min(n_hyp, cap_hyp) entries),
+        ref_hyp (per reference word the hypothesis word's index, -1: deleted), tot, lm (float32) and status -- WFST_OK or the
+        CHANNEL's own error code.  cap_hyp = 0: room for every path -- the call is made again, with n_hyp's room, if a path
+        has more words than the first guess (the longest reference + 16) holds; a cap_hyp of the caller's is taken as it is."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
+        cnt = len(ch)
+        if len(refs) != cnt:
+            raise ValueError("one list of references per listed channel")
+        ns = max([len(s) for s in refs] + [1])
+        cap = max([len(w) for s in refs for w in s if w is not None] + [1])
+        words = np.zeros((cnt, ns, cap), np.int32)
+        lens = np.full((cnt, ns), -1, np.int32)
+        for i, s in enumerate(refs):
+            for q, w in enumerate(s):
+                if w is not None:
+                    lens[i, q] = len(w)
+                    words[i, q, :len(w)] = np.asarray(w, np.int32)
+        hcap = int(cap_hyp) if cap_hyp else cap + 16
+        while True:
+            status = np.zeros(cnt, np.int32)
+            z = lambda: np.zeros((cnt, ns), np.int32)
+            found, ne, nc, nsub, ni, ndel, na, nh = z(), z(), z(), z(), z(), z(), z(), z()
+            hyp, begin, end = (np.zeros((cnt, ns, hcap), np.int32) for _ in range(3))
+            rh = np.zeros((cnt, ns, cap), np.int32)
+            tot, lm = np.zeros((cnt, ns), np.float32), np.zeros((cnt, ns), np.float32)
+            _check(lib().wfst_decoder_nearest_words(self.h, _i32(ch), cnt, int(bool(use_final_probs)), ns, cap, _i32(words), _i32(lens), hcap,
+                                                    C.c_int64(int(max_cells)), _i32(status), _i32(found), _i32(ne), _i32(nc), _i32(nsub),
+                                                    _i32(ni), _i32(ndel), _i32(na), _i32(nh), _i32(hyp), _i32(begin), _i32(end), _i32(rh),
+                                                    _f32(tot), _f32(lm)))
+            if cap_hyp or int(nh.max()) <= hcap:
+                break
+            hcap = int(nh.max())   # (a path with more words than the guess: once more, with room for it)
+        out = []
+        for i in range(cnt):
+            row = []
+            for q in range(len(refs[i])):
+                m, ln = min(int(nh[i, q]), hcap), max(int(lens[i, q]), 0)
+                row.append(dict(found=bool(found[i, q]), n_err=int(ne[i, q]), n_cor=int(nc[i, q]), n_sub=int(nsub[i, q]), n_ins=int(ni[i, q]),
+                                n_del=int(ndel[i, q]), n_arcs=int(na[i, q]), n_hyp=int(nh[i, q]), hyp_words=hyp[i, q, :m].copy(),
+                                begin=begin[i, q, :m].copy(), end=end[i, q, :m].copy(), ref_hyp=rh[i, q, :ln].copy(),
+                                tot=np.float32(tot[i, q]), lm=np.float32(lm[i, q]), status=int(status[i])))
+            out.append(row)
+        return out
 
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):
         """nbest_words(...) with word times: every path's words aligned on its channel's raw lattice (align_words); the dicts of

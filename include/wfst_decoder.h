@@ -591,6 +591,66 @@ int wfst_decoder_align_words(wfst_decoder *d, const int32_t *channels, int32_t n
                              int32_t *begin_frame, int32_t *end_frame /* [n][n_seqs][cap_words] */,
                              float *tot_score, float *lm_score /* [n][n_seqs] */);
 
+/* ---- lattice edit distance: the lattice path nearest a transcript ----------------------------------------------------------------
+ * wfst_decoder_align_words is all or nothing: for a transcript that is nearly in the lattice (a human transcript with one wrong word, a
+ * caption file, another system's hypothesis) it answers found = 0.  This call answers with the path of the channel's RAW lattice
+ * nearest a reference word sequence: the least word edit distance between any lattice path and the reference -- the lattice's oracle
+ * error, Kaldi's lattice-oracle figure beside the 1-best WER that kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts, the measure of what
+ * lattice_beam, prune_interval, the live-prune mode or a degraded frame leave in a lattice -- and, among the paths at that distance, the
+ * cheapest, with its edit operations and (begin, end) per word: lightly supervised alignment.  For a list of channels, live and
+ * finalized ones mixed, n_refs references per channel, one launch per stage (the live channels' lattices emitted, align_index_kernel,
+ * one dynamic program per (channel, reference): nearest_kernel).
+ *
+ * The lattice R = what wfst_decoder_get_raw_lattice(channel, use_final_probs) returns at this moment (wfst_decoder_set_live_lattice_prune,
+ * the use_final_probs rule after FinalizeDecoding and "no lattice" honoured exactly as wfst_decoder_align_words states them): every arc
+ * goes to a higher state id, state 0 is the start, final states are flagged and carry no weight.
+ * The cells, for a reference r[0..L) of word ids > 0: v[s][k] = (e, d), int errors and a float32 cost, ordered lexicographically (e
+ * first, then d as floats); a cell not reached is greater than every other.  v[0][0] = (0, +0.0f).  With c(a) = graph + acoustic,
+ * rounded first, and d' = (d + c(a)) + 0.0f -- a d' that is not finite is no transition (wfst_decoder_align_words' rules) -- the
+ * transitions are, and there are no others:
+ *   free                  (s, k) -> (t, k)     over an arc a with olabel == 0:           (e, d')
+ *   match / substitution  (s, k) -> (t, k + 1) over an arc a with olabel != 0, k < L:    (e + (olabel != r[k]), d')
+ *   insertion             (s, k) -> (t, k)     over an arc a with olabel != 0:           (e + 1, d')   (a lattice word the reference lacks)
+ *   deletion              (s, k) -> (s, k + 1) with k < L:                               (e + 1, d)    (a reference word no arc carries)
+ * and v[t][k'] is the minimum over all arrivals.  The kinds go by OLABEL, not by ilabel: a word may sit on an epsilon arc.  Float
+ * addition is monotone, so v[t][k'] is the minimum over the paths p from (0, 0) of (Levenshtein(words(p), r[0..k')), the sequential
+ * float32 sum of c along p).  The answer ends in the final state e with the least v[e][L], the least graph state among equals;
+ * found = 0 only if no final state is reached at all.
+ * The traceback runs backwards from (e, L) to (0, 0) by exact equality of both halves of the cell.  Among several qualifying
+ * predecessors the least key wins; the key's first part is the kind order -- 0: match / substitution, from (s, k - 1); 1: free arc,
+ * from (s, k); 2: insertion, from (s, k); 3: the deletion step, from (t, k - 1) -- and for the arc kinds wfst_decoder_align_words' tuple
+ * follows: ilabel == 0 last, graph state of the source token, ilabel, olabel, bits of graph, bits of acoustic.  Nothing depends on the
+ * numbering of states or arcs.  On biglm lattices two tokens of a frame may share a graph state: a tie that survives the rule is
+ * unspecified there.
+ *
+ * Per listed channel i and reference q (ref_len[i][q] words at ref_words[i][q][..]; -1: skipped, all outputs zero): found; n_err = e;
+ * n_cor, n_sub, n_ins, n_del counted along the traceback (sub + ins + del == n_err, cor + sub + del == L, cor + sub + ins == n_hyp);
+ * n_arcs; n_hyp and hyp_words[i][q][..], the non-zero olabels of the path in order; begin_frame / end_frame[i][q][j] per HYPOTHESIS word
+ * by wfst_decoder_align_words' own definition over the path's arcs (the list of wfst_decoder_set_silence_phones included);
+ * ref_hyp[i][q][k], for reference word k the index of the hypothesis word it was matched or substituted with, -1 if it was deleted --
+ * strictly increasing over its non-negative entries: how a caller reads the transcript's own word times; tot_score = d; lm_score =
+ * the float32 sum of graph along the path in arc order.
+ *
+ * A failure of ONE channel goes into status[i] and the call still returns WFST_OK: a reference whose table of states x (ref_len + 1)
+ * cells is beyond max_cells (WFST_E_CAPACITY, found[i][..] = 0), a device error of that channel's utterance (likewise), or a path with
+ * n_hyp > cap_hyp (WFST_E_CAPACITY: n_hyp is the room needed, the first cap_hyp words and times are written as
+ * wfst_decoder_get_nbest_words does, and everything else of the channel's answers stands).  max_cells = 0 is
+ * wfst_decoder_align_words' default bound, 65 536 states x 65 cells.  A cell is 8 bytes here (errors in the high word, the cost's
+ * orderable float bits in the low word: one unsigned 64-bit minimum): 32.5 MiB of table per reference at that bound.  The workspace is
+ * the decoder's, shared with wfst_decoder_align_words and grown on demand; lists whose tables pass 256 MiB together are taken in rounds.
+ * The call itself fails, before any device work, with WFST_E_ARG (n_refs outside 1..64, cap_words or cap_hyp <= 0, a ref_len above
+ * cap_words, a word id <= 0 inside a reference, a bad or duplicate channel list, NULL references) or WFST_E_STATE (a decoder without
+ * lattice_links, a listed channel never initialised).  Any output pointer may be NULL.  The decoder's state is only read: decoding goes
+ * on bit for bit as without the call.  Synchronous, as wfst_decoder_align_words is and for the same reason. */
+int wfst_decoder_nearest_words(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                               int32_t n_refs /* per channel, 1..64 */, int32_t cap_words,
+                               const int32_t *ref_words /* [n][n_refs][cap_words] */, const int32_t *ref_len /* [n][n_refs], -1 = skip */,
+                               int32_t cap_hyp, int64_t max_cells /* states x (len + 1) per reference; 0 = default */,
+                               int32_t *status /* [n] */, int32_t *found, int32_t *n_err, int32_t *n_cor, int32_t *n_sub, int32_t *n_ins,
+                               int32_t *n_del, int32_t *n_arcs, int32_t *n_hyp /* [n][n_refs] */,
+                               int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame /* [n][n_refs][cap_hyp] */,
+                               int32_t *ref_hyp /* [n][n_refs][cap_words] */, float *tot_score, float *lm_score /* [n][n_refs] */);
+
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
  * ConvertNbestToVector, then LatticeToVector per path) of channels of a lattice-mode decoder, finalized
