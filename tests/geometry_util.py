@@ -1,0 +1,472 @@
+"""Graphs aimed at the constants the expansion kernels are cut along (plain numpy, no GPU): slots per pass of the staged
+expansion (1408 in row form, 1536 in gather form), a pseudo-arc pair cut by the end of a pass, the three leaf-path branches,
+the degree-code field widths (n_eps <= 3, n_emit <= 15, n_pseudo <= 31), the fusing caps (48 paths, 8 hops), the seed tile's
+stride of 256 arcs, tile cuts at 128 and 256 tokens (frontiers of a given size), compacting tiles, and the row form's limits (stride % 4 == 0, stride <= 3072).
+
+Every builder sits on synth.graph_from_arc_lists, is deterministic from its seed, draws its weights as tests/test_gpu_fuzz.py
+does (epsilon weights > 0: a negative one makes a graph unfusable for another reason) and returns (graph, facts): the facts
+are RECOMPUTED from the finished arrays (shape_facts), never copied from the builder's parameters.
+
+Every leaf gets a self-loop and two or three emitting arcs back into the graph, so utterances survive; a few states away
+from the closure structures are final (graph_from_arc_lists gives each an epsilon arc to the super-final state: a closure
+path of its own, which counts against the 48)."""
+import zlib
+
+import numpy as np
+
+PATH_CAP, DEPTH_CAP = 48, 8            # wfst_capi.cc: a closure of more paths or hops leaves the whole graph unfused
+SLOTS_ROW, SLOTS_GATHER = 1408, 1536   # wfst_kernels.hip: row slots of a tile staged per pass
+CODE_EPS, CODE_EMIT, CODE_PSEUDO = 3, 15, 31   # wfst_device.h pack_code: the largest counts a degree code holds
+N_WORDS = 30                           # word labels stay below this (the LM pairs of the biglm leg know 30 words)
+
+
+# ---- shape facts, from the arrays ----------------------------------------------------------------------------------------------
+def shape_facts(g):
+    """Per state of the flat graph `g`: n_eps, n_emit, the closure's path count and depth and the multiset of its paths' hop
+    counts -- breadth first exactly as wfst_capi.cc counts them (the state's own epsilon arcs, then those of every path's end
+    state in list order; counting stops at 4 * PATH_CAP paths or 4 * DEPTH_CAP hops) -- and pseudo arcs (the sum over the
+    state's emitting arcs of their targets' closure paths).  fusable: what the loader decides from the same numbers."""
+    off = g.row_offsets()
+    n = g.n_states
+    n_eps = g.state_info["niepsilons"].astype(np.int64)
+    n_emit = g.state_info["num_arcs"].astype(np.int64) - n_eps
+    to, w, il = g.arcs["to"], g.arcs["w"], g.arcs["ilabel"]
+    assert all((il[off[s]:off[s] + n_eps[s]] == 0).all() and (il[off[s] + n_eps[s]:off[s + 1]] != 0).all() for s in range(n))
+    paths = np.zeros(n, np.int64)
+    depth = np.zeros(n, np.int64)
+    hops = {}
+    for s in np.nonzero(n_eps)[0]:
+        lst = []   # (target, depth)
+        k = -1
+        while k < len(lst) and len(lst) < 4 * PATH_CAP:
+            u, d = (int(s), 1) if k < 0 else (lst[k][0], lst[k][1] + 1)
+            if d <= 4 * DEPTH_CAP:
+                for i in range(int(n_eps[u])):
+                    lst.append((int(to[off[u] + i]), d))
+            k += 1
+        paths[s] = len(lst)
+        depth[s] = max(d for _, d in lst)
+        hops[int(s)] = sorted(d for _, d in lst)
+    n_pseudo = np.zeros(n, np.int64)
+    for s in range(n):
+        n_pseudo[s] = paths[to[off[s] + n_eps[s]:off[s + 1]]].sum()
+    eps_w = w[il == 0]
+    fusable = bool((paths <= PATH_CAP).all() and (depth <= DEPTH_CAP).all() and (eps_w >= 0).all())
+    return dict(n_eps=n_eps, n_emit=n_emit, paths=paths, depth=depth, hops=hops, n_pseudo=n_pseudo, fusable=fusable,
+                n_states=n, n_arcs=g.n_arcs, max_label=int(il.max()), min_label=int(il[il > 0].min()),
+                row_slots=int(n + g.n_arcs + 2 * n_pseudo.sum()) if fusable else int(n + g.n_arcs))
+
+
+def code_known(f, s):
+    """Does state s travel with a degree code (wfst_device.h pack_code)?  (3, 15, 31) itself reads as unknown."""
+    e, m, p = int(f["n_eps"][s]), int(f["n_emit"][s]), int(f["n_pseudo"][s])
+    return e <= CODE_EPS and m <= CODE_EMIT and p <= CODE_PSEUDO and (e, m, p) != (CODE_EPS, CODE_EMIT, CODE_PSEUDO)
+
+
+# ---- the builder ---------------------------------------------------------------------------------------------------------------
+class _Net:
+    def __init__(self, synth, seed, n_cols):
+        self.synth, self.rng, self.n_cols = synth, np.random.default_rng(seed), int(n_cols)
+        self.arcs, self.finals = [], {}
+        self.leafy = []      # states that get the leaf treatment in finish()
+        self.pool = []       # states the leaves' arcs may enter
+
+    def state(self, leafy=True, pool=True):
+        s = len(self.arcs)
+        self.arcs.append([])
+        if leafy:
+            self.leafy.append(s)
+        if pool:
+            self.pool.append(s)
+        return s
+
+    def label(self):
+        return int(self.rng.integers(1, self.n_cols))
+
+    def word(self, p):
+        return int(self.rng.integers(1, N_WORDS)) if self.rng.random() < p else 0
+
+    def emit(self, s, to, lab=None, w=None):
+        self.arcs[s].append((self.label() if lab is None else int(lab), self.word(0.4), float(self.rng.uniform(0.0, 3.0)) if w is None else float(w), to))
+
+    def eps(self, s, to):
+        self.arcs[s].append((0, self.word(0.5), float(self.rng.uniform(0.01, 2.5)), to))
+
+    def closure(self, root, paths, depth):
+        """Epsilon arcs below `root` so that its closure has exactly `paths` paths, the deepest of `depth` hops: a chain of `depth`
+        states (paths of 1 .. depth hops) and paths - depth further end states hung in turn below the root and the chain's first two
+        states (paths of 1, 2 and 3 hops).  Every state of it is a leaf of the graph's emitting structure."""
+        assert paths >= depth >= 1
+        chain = [root]
+        for _ in range(depth):
+            d = self.state()
+            self.eps(chain[-1], d)
+            chain.append(d)
+        hang = chain[:min(3, depth)]
+        for k in range(paths - depth):
+            self.eps(hang[k % len(hang)], self.state())
+        return chain
+
+    def finish(self, start, n_final=3):
+        # a few final states of their own, entered like any other state of the pool
+        for _ in range(n_final):
+            self.finals[self.state()] = float(self.rng.uniform(0.0, 2.0))
+        pool = np.asarray(self.pool)
+        for s in self.leafy:
+            self.emit(s, s, w=float(self.rng.uniform(0.05, 0.8)))   # self loop
+            for t in self.rng.choice(pool, size=int(self.rng.integers(2, 4)), replace=False):
+                self.emit(s, int(t))
+        g = self.synth.graph_from_arc_lists(len(self.arcs), start, dict(enumerate(self.arcs)), self.finals)
+        return g, shape_facts(g)
+
+
+def _hub(net, E, P, paths, depth, labels=None):
+    """The start state: E emitting arcs to E distinct states, P of them (evenly spread) with a closure of `paths` paths."""
+    hub = net.state(leafy=False)
+    assert hub == 0
+    roots = []
+    with_closure = set(np.linspace(0, E - 1, P).astype(int).tolist()) if P else set()
+    assert len(with_closure) == P
+    for k in range(E):
+        t = net.state()
+        net.emit(hub, t, lab=None if labels is None else labels[k % len(labels)])
+        if k in with_closure:
+            net.closure(t, paths, depth)
+            roots.append(t)
+    return hub, roots
+
+
+def _hub_facts(g, f):
+    off = g.row_offsets()
+    s = g.start
+    tg = g.arcs["to"][off[s] + f["n_eps"][s]:off[s + 1]]
+    f.update(hub=s, E=int(f["n_emit"][s]), hub_eps=int(f["n_eps"][s]), hub_targets_distinct=len(set(tg.tolist())) == len(tg),
+             hub_pseudo=int(f["n_pseudo"][s]), hub_slots=int(f["n_emit"][s] + 2 * f["n_pseudo"][s]))
+    return f
+
+
+def hub(synth, E, P=0, paths=2, depth=2, n_cols=64, seed=1, labels=None):
+    """Start state = a hub of E emitting arcs to E distinct states, P of which have a closure (paths, depth): exactly P * paths
+    pseudo arcs.  The start token is frame 0's only (and best) token: a one-token tile of E + 2 * n_pseudo slots, a seed tile over E arcs."""
+    net = _Net(synth, seed, n_cols)
+    _hub(net, E, P, paths, depth, labels)
+    g, f = net.finish(0)
+    return g, _hub_facts(g, f)
+
+
+def cut_pair(synth, E=1401, P=70, seed=2):
+    """A hub with E odd and two-path closures below P of its targets (2 * P pseudo arcs): pair i starts on slot E + 2 i, so
+    with E = 1401 pair 3 starts on slot 1407 (the last of a row-form pass of 1408) and pair 67 on slot 1535 (gather form, 1536).
+    The even twin E = 1400 has no cut pair."""
+    g, f = hub(synth, E, P, paths=2, depth=2, seed=seed)
+    for form, S in (("row", SLOTS_ROW), ("gather", SLOTS_GATHER)):
+        i2 = S - 1 - f["E"]
+        f["cut_" + form] = i2 // 2 if (i2 >= 0 and i2 % 2 == 0 and i2 // 2 < f["hub_pseudo"]) else None
+    return g, f
+
+
+def closure_limits(synth, paths, depth, seed=3):
+    """A hub of 16 whose arc 5 enters a state with a closure of exactly `paths` paths, the deepest of `depth` hops."""
+    net = _Net(synth, seed, 64)
+    _, roots = _hub(net, 16, 1, paths, depth)
+    g, f = net.finish(0, n_final=2)
+    f = _hub_facts(g, f)
+    r = roots[0]
+    f.update(root=r, root_paths=int(f["paths"][r]), root_depth=int(f["depth"][r]), root_hops=f["hops"][r])
+    return g, f
+
+
+def code_edges(synth, seed=4):
+    """One fan state (the start) whose arcs enter, in the same frame, states on both sides of every degree-code field: n_eps 3 / 4,
+    n_emit 15 / 16, n_pseudo 31 / 32 (each of the second kind exceeds that field alone), (3, 15, 31) itself, states far beyond
+    each field, a state without arcs and one with epsilon arcs only.  facts["special"]: name -> state."""
+    net = _Net(synth, seed, 64)
+    fan = net.state(leafy=False)
+    plain = [net.state() for _ in range(48)]
+    sp = {}
+
+    def special(name, n_eps, n_emit, n_pseudo):
+        s = net.state(leafy=False, pool=True)
+        sp[name] = s
+        net.emit(fan, s)
+        for _ in range(n_eps):
+            net.eps(s, net.state())
+        left = n_emit
+        if n_pseudo:
+            r = net.state()
+            net.closure(r, n_pseudo, min(2, n_pseudo))
+            net.emit(s, r)
+            left -= 1
+        if left > 0 and not n_eps:   # (a self-loop on a state with epsilon arcs would carry pseudo arcs of its own)
+            net.emit(s, s, w=float(net.rng.uniform(0.05, 0.8)))
+            left -= 1
+        for k in range(left):
+            net.emit(s, plain[(s + k) % len(plain)])
+        return s
+
+    special("eps3", 3, 4, 0)
+    special("eps4", 4, 4, 0)
+    special("emit15", 0, 15, 0)
+    special("emit16", 0, 16, 0)
+    special("pseudo31", 0, 3, 31)
+    special("pseudo32", 0, 3, 32)
+    special("all_max", 3, 15, 31)     # the code that reads as unknown
+    special("below_max", 3, 15, 30)   # the largest code there is
+    special("eps7", 7, 2, 0)
+    special("emit40", 0, 40, 0)
+    special("pseudo41", 0, 2, 41)
+    special("no_arcs", 0, 0, 0)
+    special("eps_only", 2, 0, 0)
+    for p in plain[:6]:
+        net.emit(fan, p)
+    g, f = net.finish(0)
+    f["special"] = sp
+    return g, _hub_facts(g, f)
+
+
+def frontier_of(synth, N, plateau=0, seed=5):
+    """The start state fans out to N - 1 distinct states with self-loops and arcs among themselves (nothing leads back to the start);
+    three of them are final, so from frame 1 on the super-final state holds a token too: with a beam that prunes nothing the frontier
+    of every frame f >= 1 is exactly N tokens.
+    plateau = M: M of the fan states are entered by the start's arcs alone, all with one label and weight, and loop with one label and
+    weight: their tokens cost the same, bit for bit, in every frame.  A max_active that falls inside the plateau leaves all M live (the
+    cutoff is the max_active-th cheapest cost, and `cost <= cutoff` holds for every one of them) in tiles sized for max_active."""
+    net = _Net(synth, seed, 64)
+    start = net.state(leafy=False, pool=False)
+    wp, ws = float(net.rng.uniform(1.0, 2.0)), float(net.rng.uniform(0.3, 0.6))
+    flat = []
+    for k in range(N - 1):
+        if k % 8 != 7 and len(flat) < plateau:      # (spread through the state numbering)
+            s = net.state(leafy=False, pool=False)
+            flat.append(s)
+            net.emit(start, s, lab=3, w=wp)
+        else:
+            s = net.state()
+            net.emit(start, s)
+    assert len(flat) == plateau
+    for s in net.pool[:3]:
+        net.finals[s] = float(net.rng.uniform(0.0, 2.0))
+    pool = np.asarray(net.pool)
+    for s in flat:
+        net.arcs[s].append((5, 0, ws, s))
+        for t in net.rng.choice(pool, size=2, replace=False):
+            net.emit(s, int(t))
+    g, f = net.finish(0, n_final=0)
+    f["plateau"] = flat
+    return g, _hub_facts(g, f)
+
+
+def wide_columns(synth, n_cols, seed=6):
+    """A small hub whose labels include the lowest and the highest column of a matrix of n_cols columns (identity mapping: column =
+    ilabel, so labels 1 and n_cols - 1), on arcs with and without a closure behind them."""
+    labels = [n_cols - 1, 1] + [int(x) for x in np.random.default_rng(seed).integers(1, n_cols, size=14)]
+    g, f = hub(synth, 16, 4, paths=3, depth=3, n_cols=n_cols, seed=seed, labels=labels)
+    return g, f
+
+
+# ---- the cases the CPU and the GPU tests share -----------------------------------------------------------------------------------
+BEAM = dict(beam=30.0, max_active=1000000, min_active=0, lattice_beam=8.0)
+BINDING = dict(beam=12.0, max_active=300, min_active=20, lattice_beam=8.0)
+MIN_ACTIVE = dict(beam=8.0, max_active=1000000, min_active=600, lattice_beam=8.0)
+MIN_BINDS = dict(beam=2.0, max_active=1000000, min_active=600, lattice_beam=8.0)     # fewer than 600 tokens within the beam: min_active sets the cutoff
+WIDE = dict(beam=100.0, max_active=1000000, min_active=0, lattice_beam=8.0)            # frontier_of: nothing is pruned
+MAX200 = dict(beam=100.0, max_active=200, min_active=0, lattice_beam=8.0)              # compacting tiles, one round
+MAX600 = dict(beam=100.0, max_active=600, min_active=0, lattice_beam=8.0)              # compacting tiles, a second round (plateau)
+TINY = dict(beam=12.0, max_active=30, min_active=10, lattice_beam=8.0)                 # max_active below the small graphs' frontiers
+# (biglm: the reference's final pruning ranges over non-final tokens too and leaves short utterances without a path at lattice_beam 8)
+BIGLM = dict(BEAM, lattice_beam=40.0)
+BIGLM_WIDE = dict(WIDE, lattice_beam=120.0)
+CFGS = dict(tiny=TINY, min_binds=MIN_BINDS, biglm=BIGLM, biglm_wide=BIGLM_WIDE, beam=BEAM, binding=BINDING, min_active=MIN_ACTIVE, wide=WIDE, max200=MAX200, max600=MAX600)
+LENGTHS = (8, 3, 1)   # one channel ends while the others go on
+
+GRAPHS = {
+    "cut1401": lambda sy: cut_pair(sy, 1401),
+    "cut1400": lambda sy: cut_pair(sy, 1400),
+    "code_edges": lambda sy: code_edges(sy),
+    "closure48x8": lambda sy: closure_limits(sy, 48, 8),
+    "closure49x8": lambda sy: closure_limits(sy, 49, 8),
+    "closure20x9": lambda sy: closure_limits(sy, 20, 9),
+    "frontier127": lambda sy: frontier_of(sy, 127),
+    "frontier128": lambda sy: frontier_of(sy, 128),
+    "frontier129": lambda sy: frontier_of(sy, 129),
+    "frontier255": lambda sy: frontier_of(sy, 255),
+    "frontier256": lambda sy: frontier_of(sy, 256),
+    "frontier257": lambda sy: frontier_of(sy, 257),
+    "frontier1024": lambda sy: frontier_of(sy, 1024),
+    "frontier1025": lambda sy: frontier_of(sy, 1025),
+    "frontier1280": lambda sy: frontier_of(sy, 1280),
+    "frontier1281": lambda sy: frontier_of(sy, 1281),
+    "plateau1025": lambda sy: frontier_of(sy, 1025, plateau=860),
+    "hub16": lambda sy: hub(sy, 16, 4),
+    "hub257": lambda sy: hub(sy, 257, 8),
+    "hub3000": lambda sy: hub(sy, 3000, 40),
+    "wide4": lambda sy: wide_columns(sy, 4),
+    "wide3072": lambda sy: wide_columns(sy, 3072),
+    "wide3076": lambda sy: wide_columns(sy, 3076),
+}
+N_COLS = {"wide4": 4, "wide3072": 3072, "wide3076": 3076}
+COMMON = ("cut1400", "cut1401", "code_edges", "closure48x8", "frontier256", "frontier257")
+# (frontier127 / 128 / 129: a decoder of three channels cuts frontiers of this size into tiles of 128 tokens -- plain_tile_tokens)
+ROW_EXTRA = ("hub3000", "hub257", "wide4", "wide3072", "wide3076", "frontier127", "frontier128", "frontier129", "frontier255", "frontier1024", "frontier1025")
+MANY_CHANNELS = 72   # the tiles256 leg: 72 channels x 1280 tokens > 700 x 128, so its tiles hold 256 tokens
+
+
+def plain_tile_tokens(n, channels, tile_tokens=256, staged=True):
+    """Tokens per (non-compacting) expansion tile of a frame of n tokens in a launch over `channels` channels, as both frame
+    boundaries choose it (wfst_kernels.hip: prep_frame and frame_boundary_fused, `700ll * 256` / `700ll * 128`; tile_tokens =
+    wfst_options.tile_tokens; decoders off the fused rows start from 512).  A restatement: when the kernels' sizing changes, the
+    cases that name a tile size (frontier127..129, the tiles256 leg) assert the size they were built for and fail here first."""
+    t = tile_tokens if staged else 512
+    if n * channels <= 700 * 256:
+        t = 256
+    if n * channels <= 700 * 128:
+        t = 128
+    return min(t, tile_tokens) if staged else t
+
+
+def config_of(name, cfg=None):
+    """The configuration a leg decodes graph `name` with unless it names one: the frontier graphs with the beam that prunes nothing."""
+    return cfg or ("wide" if name.startswith(("frontier", "plateau")) else "beam")
+
+
+def n_cols_of(name):
+    return N_COLS.get(name, 64)
+
+
+def utterances(name, n=3):
+    """n matrices of N(-1.5, 1) log-likelihoods for graph `name`, of 8, 3 and 1 frames."""
+    rng = np.random.default_rng(zlib.crc32(name.encode()))   # (of the name alone: a new graph moves no other graph's utterances)
+    return [rng.normal(-1.5, 1.0, size=(LENGTHS[i % len(LENGTHS)], n_cols_of(name))).astype(np.float32) for i in range(n)]
+
+
+# (leg -> the (graph, configuration) pairs it decodes; tests/test_geometry_graphs.py proves every triple tie-free)
+def leg_cases():
+    legs = {}
+    legs["row"] = [(n, config_of(n)) for n in COMMON + ROW_EXTRA] + [("cut1401", "binding"), ("cut1401", "min_active"), ("code_edges", "binding"),
+                                                                      ("hub3000", "min_active")]
+    for leg in ("gather_stride", "gather_align", "row_to_gather"):
+        legs[leg] = [(n, config_of(n)) for n in COMMON + ROW_EXTRA]
+    for leg in ("header", "plain", "three_launch", "lattice", "lattice_iterated", "small_tiles"):
+        legs[leg] = [(n, config_of(n)) for n in COMMON]
+    # tiles of 256 tokens: frontiers of 5 x 256 and one more, and the cut pair's hub beside 1.5 k other tokens, in 72 channels
+    legs["tiles256"] = [("frontier1280", "wide"), ("frontier1281", "wide"), ("cut1401", "beam")]
+    legs["small_tiles"] = legs["small_tiles"] + [("hub3000", "beam")]
+    legs["unfusable"] = [("closure49x8", "beam"), ("closure20x9", "beam")]
+    legs["compacting"] = [("frontier1025", "max200"), ("hub3000", "max200"), ("plateau1025", "max600"), ("frontier1025", "max600"), ("hub3000", "max600"),
+                          ("hub3000", "min_active"), ("hub3000", "min_binds"), ("cut1401", "min_binds"), ("cut1400", "binding"), ("cut1401", "binding"), ("code_edges", "tiny"), ("closure48x8", "tiny"),
+                          ("frontier256", "max200"), ("frontier257", "max200")]
+    legs["biglm"] = [(n, "biglm_wide" if n.startswith("frontier") else "biglm") for n in COMMON + ("hub257",)]
+    return legs
+
+
+def all_triples():
+    seen = []
+    for leg, cases in leg_cases().items():
+        for c in cases:
+            if c not in seen:
+                seen.append(c)
+    return seen
+
+
+# ---- graphs, utterances and the oracle's results, made once and shared -----------------------------------------------------------
+class World:
+    """Builds each graph once (facts, file, oracle handle), and keeps every order-free oracle result asked for: the CPU test and
+    every leg of the GPU test read the same objects, and nothing here changes after it is made."""
+
+    def __init__(self, synth, oracle, tmp_dir):
+        self.synth, self.oracle, self.dir = synth, oracle, tmp_dir
+        self._g, self._h, self._mats, self._res, self._lm = {}, {}, {}, {}, None
+
+    def graph(self, name):
+        if name not in self._g:
+            g, f = GRAPHS[name](self.synth)
+            p = "%s/%s.bin" % (self.dir, name)
+            g.write(p)
+            self._g[name] = (g, f, p)
+        return self._g[name][:2]
+
+    def path(self, name):
+        self.graph(name)
+        return self._g[name][2]
+
+    def handle(self, name):
+        if name not in self._h:
+            self._h[name] = self.oracle.load_graph(self.path(name))
+        return self._h[name]
+
+    def mats(self, name):
+        if name not in self._mats:
+            self._mats[name] = utterances(name)
+        return self._mats[name]
+
+    def _cached(self, key, make, order_free=True):
+        if key not in self._res:
+            try:
+                self.oracle.set_order_free(order_free)
+                self._res[key] = make()
+            finally:
+                self.oracle.set_order_free(False)
+        return self._res[key]
+
+    def _cfg(self, cfg):
+        import pyoracle
+
+        return pyoracle.Config(**CFGS[cfg])
+
+    def oracle_decode(self, name, cfg, ui, frames=None, partial=False, order_free=True):
+        """partial: the prefix of `frames` frames fed frame by frame, not finalized, without final costs (GetBestPath mid-utterance)"""
+        x = self.mats(name)[ui]
+        x = x if frames is None else x[:frames]
+        kw = dict(chunk=1, finalize=False, use_final_probs=False) if partial else {}
+        return self._cached(("best", name, cfg, ui, frames, partial, order_free),
+                            lambda: self.oracle.decode(self.handle(name), self._cfg(cfg), x, None, **kw), order_free)
+
+    def oracle_trace(self, name, cfg, ui):
+        return self._cached(("trace", name, cfg, ui), lambda: self.oracle.decode(self.handle(name), self._cfg(cfg), self.mats(name)[ui], None, trace=True))
+
+    def oracle_dump(self, name, cfg, ui, frame):
+        """(states, costs, count) of the tokens of `frame` (0: the start token and its closure)"""
+        x = self.mats(name)[ui]
+        return self._cached(("dump", name, cfg, ui, frame),
+                            lambda: self.oracle.decode(self.handle(name), self._cfg(cfg), x[:max(frame, 1)], None, dump_frame=frame, dump_cap=1 << 16).dump)
+
+    def oracle_lattice(self, name, cfg, ui):
+        import pyoracle
+
+        return self._cached(("lattice", name, cfg, ui),
+                            lambda: pyoracle.oracle_raw_lattice(self.oracle, self.handle(name), self._cfg(cfg), self.mats(name)[ui], None))
+
+    def lm_paths(self):
+        """A back-off LM pair over the builders' 30 words, made as tests/test_gpu_biglm.py's fuzzer makes its pairs."""
+        if self._lm is None:
+            import importlib
+
+            lmsynth = importlib.import_module("asr-decoder_amd.lmsynth")
+            old = lmsynth.make_lm(N_WORDS, 2, 12, 3, 0, 0, seed=71)
+            new = lmsynth.make_lm(N_WORDS, 3, 20, 3, 16, 2, seed=72)
+            p1, p2 = self.dir + "/lm_old.bin", self.dir + "/lm_new.bin"
+            old.to_fsa().write(p1)
+            new.to_fsa().write(p2)
+            self._lm = (p1, p2)
+        return self._lm
+
+    def oracle_biglm_trace(self, name, cfg, ui):
+        self.oracle_biglm(name, cfg, ui)   # (loads the LM pair)
+        import pyoracle
+
+        o1, o2 = self._res["olm"]
+        return self._cached(("biglm_trace", name, cfg, ui),
+                            lambda: pyoracle.biglm_decode(self.oracle, self.handle(name), self._cfg(cfg), o1, o2, self.mats(name)[ui], None, fixed=True, trace=True))
+
+    def oracle_biglm(self, name, cfg, ui, frames=None, partial=False):
+        import pyoracle
+
+        if "olm" not in self._res:
+            p1, p2 = self.lm_paths()
+            self._res["olm"] = (pyoracle.Lm(self.oracle, p1, -1.0), pyoracle.Lm(self.oracle, p2, 1.0))
+        o1, o2 = self._res["olm"]
+        x = self.mats(name)[ui]
+        x = x if frames is None else x[:frames]
+        kw = dict(chunk=1, finalize=False, use_final_probs=False) if partial else {}
+        return self._cached(("biglm", name, cfg, ui, frames, partial),
+                            lambda: pyoracle.biglm_decode(self.oracle, self.handle(name), self._cfg(cfg), o1, o2, x, None, fixed=True, **kw))
