@@ -21,6 +21,10 @@ struct AlignState {
   DevBuf<int32_t> idx, path, in, out;
   DevBuf<uint32_t> cells;
   PinBuf<int32_t> pin;
+  // wfst_decoder_word_confidence (wfst_capi_posterior.cc): the posterior workspace of a round's channels and its results' landing place
+  DevBuf<double> post;
+  DevBuf<int2> post_idx;
+  PinBuf<double> post_pin;
 };
 
 // what the entry point sees of a decoder (sil_bits: the silence bitmap over transition-ids 1..sil_ntid, nullptr: none)

@@ -528,6 +528,32 @@ struct NearestDev {
 constexpr int64_t nearest_out_ints(int64_t cap_words, int64_t cap_hyp) { return kNearestHead + 3 * cap_hyp + cap_words; }
 void launch_nearest(const AlignDev &A, const NearestDev &N, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- lattice posteriors and word confidences (wfst_posterior.hip) -----------------------------------------------------
+// The sum-over-paths twin of the alignment: forward and backward costs of a listed channel's raw lattice in the log semiring, in
+// float64, over the in-arc index align_index_kernel built (AlignDev::idx), and the statistic read from them for the sequences
+// align_kernel has just placed in time (AlignDev::out, AlignDev::path).  posterior_kernel runs one workgroup per slot,
+// confidence_kernel one per (slot, sequence) pair.
+//   alpha / beta[slot][ns_cap]  forward / backward cost of a state (+inf: no path from the start / to a final state)
+//   gamma[slot][na_cap]         the posterior of an arc, by in-arc record
+//   done[slot][ns_cap]          the level rounds' flags: 0, or 1 + the round that summed the state
+//   soff[slot][ns_cap]          the by-source table: the out-arcs of state s are sarc[s ? soff[s - 1] : 0 .. soff[s])
+//   sarc[slot][na_cap]          {in-arc record, destination state}, grouped by source state
+//   log_z[slot]                 -beta[0]; chan_err[slot]: 0 or kAlnCycle
+//   out[p][1 + cap_words]       {path_logpost, word_post[cap_words]} of pair p (all zero where align_kernel found nothing)
+struct PostDev {
+  double *alpha, *beta, *gamma;
+  int32_t *done, *soff;
+  int2 *sarc;
+  double *log_z;
+  int32_t *chan_err;
+  double graph_scale, acoustic_scale;
+  double *out;
+};
+// bytes of a slot's share of the posterior workspace
+inline int64_t post_slot_bytes(int64_t ns_cap, int64_t na_cap) { return 24 * ns_cap + 16 * na_cap; }
+void launch_posterior(const DecoderDev &D, const AlignDev &A, const PostDev &P, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+void launch_confidence(const AlignDev &A, const PostDev &P, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

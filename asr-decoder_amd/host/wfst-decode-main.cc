@@ -45,6 +45,11 @@
 //                  has them; a path whose words the raw lattice does not hold prints "... notfound"
 //   --align-words=FILE  batch shape and --single-stream: FILE holds lines "KEY w1 w2 ..." (several per KEY, at most 64); after the
 //                  utterance's lines, per sequence "KEY align q found=0|1 arcs=N tot=.. lm=.." and "KEY align q#j word begin end"
+//   --word-confidence[=GRAPH_SCALE,ACOUSTIC_SCALE]  with --nbest-word-times and/or --align-words=FILE: the confidence of every aligned
+//                  word from the posteriors of the RAW lattice (WordConfidences: wfst_decoder_word_confidence; scales default 1,1) --
+//                  every "...#j word begin end" line gains a fourth column conf (min(1, the posterior mass of the arcs that say the
+//                  word at about that time)), and every path line ("KEY-k ...", "KEY@frames nbest k: ...", "KEY align q ...") of a
+//                  path that was found gains " logpost=.." (the log posterior of the aligned path itself)
 //   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
 //                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
 //                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
@@ -213,6 +218,8 @@ int main(int argc, char **argv) {
     int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
     bool pull = false, partial_words = false, word_times = false, live_prune = false, nbest_times = false;
     std::string align_file, nearest_file;
+    bool word_conf = false;
+    double conf_gs = 1.0, conf_as = 1.0;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
     int max_frames = 0, repeat = 1, share_channels = 0, warm = 0, ragged = 0;
@@ -260,6 +267,16 @@ int main(int argc, char **argv) {
       else if (a == "--word-times") word_times = true;
       else if (a == "--nbest-word-times") nbest_times = true;
       else if (a.compare(0, 14, "--align-words=") == 0) align_file = a.substr(14);
+      else if (a == "--word-confidence") word_conf = true;
+      else if (a.compare(0, 18, "--word-confidence=") == 0) {
+        char *end = nullptr;
+        conf_gs = strtod(a.c_str() + 18, &end);
+        if (end == a.c_str() + 18 || *end != ',') { std::cerr << "--word-confidence=GRAPH_SCALE,ACOUSTIC_SCALE\n"; return 1; }
+        const char *second_at = end + 1;
+        conf_as = strtod(second_at, &end);
+        if (end == second_at || *end != 0) { std::cerr << "--word-confidence=GRAPH_SCALE,ACOUSTIC_SCALE\n"; return 1; }
+        word_conf = true;
+      }
       else if (a.compare(0, 16, "--nearest-words=") == 0) nearest_file = a.substr(16);
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
@@ -292,7 +309,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -307,6 +324,7 @@ int main(int argc, char **argv) {
     if (!wt_silence.empty() && (!word_times || tid2phone_file.empty())) { std::cerr << "--silence-phones goes with --word-times and --tid2phone=FILE\n"; return 1; }
     if (nbest_times && ((nbest == 0 && partial_nbest == 0) || n_threads > 0)) { std::cerr << "--nbest-word-times goes with --nbest=N or --partial-nbest=K, in the batch shape or --single-stream\n"; return 1; }
     if (!align_file.empty() && n_threads > 0) { std::cerr << "--align-words goes with the batch shape or --single-stream\n"; return 1; }
+    if (word_conf && !nbest_times && align_file.empty()) { std::cerr << "--word-confidence goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
     if (!nearest_file.empty() && n_threads > 0) { std::cerr << "--nearest-words goes with the batch shape or --single-stream\n"; return 1; }
     // --align-words / --nearest-words: the sequences to align and the references, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs;
@@ -388,12 +406,49 @@ int main(int argc, char **argv) {
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
     const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty();
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
-    auto time_lines = [](const std::string &head, const std::vector<int> &words, const WordAlignment &a) {
+    // (--word-confidence: a fourth column conf)
+    auto time_lines = [&](const std::string &head, const std::vector<int> &words, const WordConfidence &a) {
       std::string o;
       if (!a.found) return head + " notfound\n";
-      for (size_t j = 0; j < words.size(); ++j)
-        o += head + "#" + std::to_string(j + 1) + " " + std::to_string(words[j]) + " " + std::to_string(a.frames[j].first) + " " + std::to_string(a.frames[j].second) + "\n";
+      for (size_t j = 0; j < words.size(); ++j) {
+        o += head + "#" + std::to_string(j + 1) + " " + std::to_string(words[j]) + " " + std::to_string(a.frames[j].first) + " " + std::to_string(a.frames[j].second);
+        if (word_conf) {
+          char buf[32];
+          snprintf(buf, sizeof(buf), " %.9g", a.conf[j]);
+          o += buf;
+        }
+        o += "\n";
+      }
       return o;
+    };
+    // " logpost=.." of a path line under --word-confidence
+    auto logpost_of = [&](const WordConfidence &a) {
+      if (!word_conf || !a.found) return std::string();
+      char buf[40];
+      snprintf(buf, sizeof(buf), " logpost=%.9g", a.path_logpost);
+      return std::string(buf);
+    };
+    // AlignWords' answers as the lines take them (no confidences)
+    auto lift = [](const std::vector<WordAlignment> &a) {
+      std::vector<WordConfidence> o(a.size());
+      for (size_t i = 0; i < a.size(); ++i) static_cast<WordAlignment &>(o[i]) = a[i];
+      return o;
+    };
+    // the word times of one stream's sequences (GetNbestWordTimes), under --word-confidence with the confidences (WordConfidences)
+    auto stream_times = [&](GpuLatticeDecoder &decode, const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *o, bool use_final_probs) {
+      if (word_conf) { decode.WordConfidences(seqs, o, use_final_probs, conf_gs, conf_as); return; }
+      std::vector<WordAlignment> a;
+      decode.GetNbestWordTimes(seqs, &a, use_final_probs);
+      *o = lift(a);
+    };
+    // ... and of a batch's channels (AlignWords / WordConfidences)
+    auto batch_times = [&](GpuBatchDecoder &decode, const std::vector<int> &ch, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
+                           std::vector<std::vector<WordConfidence> > *o, std::vector<int> *status) {
+      if (word_conf) { decode.WordConfidences(ch, seqs, use_final_probs, conf_gs, conf_as, o, status); return; }
+      std::vector<std::vector<WordAlignment> > a;
+      decode.AlignWords(ch, seqs, use_final_probs, &a, status);
+      o->clear();
+      for (const auto &x : a) o->push_back(lift(x));
     };
     // the words of every path of an n-best list (none where LatticeToVector fails: emit_nbest skips such a path)
     auto path_words = [](std::vector<Lattice> &paths) {
@@ -406,14 +461,14 @@ int main(int argc, char **argv) {
       return w;
     };
     // --align-words: the lines of one utterance
-    auto emit_align = [&](const Utt &u, const std::vector<WordAlignment> &al) {
+    auto emit_align = [&](const Utt &u, const std::vector<WordConfidence> &al) {
       auto it = align_seqs.find(u.key);
       if (it == align_seqs.end()) return;
       for (size_t q = 0; q < it->second.size() && q < al.size(); ++q) {
         char buf[96];
-        snprintf(buf, sizeof(buf), " found=%d arcs=%d tot=%.9g lm=%.9g\n", al[q].found ? 1 : 0, al[q].n_arcs, (double)al[q].tot, (double)al[q].lm);
+        snprintf(buf, sizeof(buf), " found=%d arcs=%d tot=%.9g lm=%.9g", al[q].found ? 1 : 0, al[q].n_arcs, (double)al[q].tot, (double)al[q].lm);
         const std::string head = u.key + " align " + std::to_string(q + 1);
-        out << head << buf;
+        out << head << buf << logpost_of(al[q]) << "\n";
         if (al[q].found) out << time_lines(head, it->second[q], al[q]);
       }
     };
@@ -435,7 +490,7 @@ int main(int argc, char **argv) {
         nr_err += a.errors; nr_words += (long long)it->second[q].size(); nr_ins += a.ins; nr_del += a.del; nr_sub += a.sub;
       }
     };
-    auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<WordAlignment> *times = nullptr) {
+    auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<WordConfidence> *times = nullptr) {
       for (size_t k = 0; k < paths.size(); ++k) {
         std::vector<int> words, phones;
         float tot = 0, lm = 0;
@@ -443,6 +498,7 @@ int main(int argc, char **argv) {
         if (!LatticeToVector(paths[k], words, phones, tot, lm)) continue;
         out << u.key << '-' << (k + 1);
         for (int w : words) out << ' ' << w;
+        if (times && k < times->size()) out << logpost_of((*times)[k]);
         out << '\n';
         if (times && k < times->size()) out << time_lines(u.key + "-" + std::to_string(k + 1), words, (*times)[k]);
         std::cerr << "LOG " << u.key << '-' << (k + 1) << " tot_score " << tot << " lm_score " << lm << "\n";
@@ -481,7 +537,7 @@ int main(int argc, char **argv) {
     limits.lattice_links = want_lattice ? lattice_links : 0;
     // --partial-nbest: "key@frames nbest k: w1 w2 ... tot=.. lm=.." per path, or "key@frames nbest status=code" for a channel's own failure
     auto nbest_lines = [&](const std::string &key, int frames, int status, const std::vector<std::vector<int> > &w, const std::vector<float> &t,
-                           const std::vector<float> &l, const std::vector<WordAlignment> *times = nullptr) {
+                           const std::vector<float> &l, const std::vector<WordConfidence> *times = nullptr) {
       std::string o;
       const std::string head = key + "@" + std::to_string(frames) + " nbest ";
       if (status != WFST_OK) o += head + "status=" + std::to_string(status) + "\n";
@@ -489,8 +545,10 @@ int main(int argc, char **argv) {
         o += head + std::to_string(k + 1) + ":";
         for (int x : w[k]) o += " " + std::to_string(x);
         char buf[64];
-        snprintf(buf, sizeof(buf), " tot=%.9g lm=%.9g\n", (double)t[k], (double)l[k]);
+        snprintf(buf, sizeof(buf), " tot=%.9g lm=%.9g", (double)t[k], (double)l[k]);
         o += buf;
+        if (times && k < times->size()) o += logpost_of((*times)[k]);
+        o += "\n";
         if (times && k < times->size()) o += time_lines(head + std::to_string(k + 1), w[k], (*times)[k]);
       }
       return o;
@@ -794,8 +852,8 @@ int main(int argc, char **argv) {
               std::vector<float> pt, pl;
               int st = WFST_OK;
               decode.GetNbestWords(&pw, &pt, &pl, partial_nbest, false, slm1p, slm2p, &st);
-              std::vector<WordAlignment> al;
-              if (nbest_times && !pw.empty()) decode.GetNbestWordTimes(pw, &al, false);
+              std::vector<WordConfidence> al;
+              if (nbest_times && !pw.empty()) stream_times(decode, pw, &al, false);
               out << nbest_lines(u.key, decode.NumFramesDecoded(), st, pw, pt, pl, nbest_times ? &al : nullptr);
             }
           }
@@ -822,13 +880,13 @@ int main(int argc, char **argv) {
           if (!exact_nbest) decode.GetNbestShortlist(paths, nbest);
           else if (second) decode.GetNbest(paths, nbest, slm1p, slm2p);
           else decode.GetNbest(paths, nbest);
-          std::vector<WordAlignment> al;
-          if (nbest_times && !paths.empty()) decode.GetNbestWordTimes(path_words(paths), &al);
+          std::vector<WordConfidence> al;
+          if (nbest_times && !paths.empty()) stream_times(decode, path_words(paths), &al, true);
           emit_nbest(u, paths, nbest_times ? &al : nullptr);
         }
         if (align_seqs.count(u.key)) {
-          std::vector<WordAlignment> al;
-          decode.GetNbestWordTimes(align_seqs[u.key], &al);
+          std::vector<WordConfidence> al;
+          stream_times(decode, align_seqs[u.key], &al, true);
           emit_align(u, al);
         }
         if (nearest_refs.count(u.key)) {
@@ -845,7 +903,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<int> > wt_words;                      // --word-times
         std::vector<std::vector<std::pair<int, int> > > wt_frames;
         std::string partials;                                         // --partial-nbest
-        std::vector<std::vector<WordAlignment> > nb_times, al_times;  // --nbest-word-times, --align-words
+        std::vector<std::vector<WordConfidence> > nb_times, al_times;  // --nbest-word-times, --align-words
         std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
@@ -929,9 +987,9 @@ int main(int argc, char **argv) {
                 std::vector<std::vector<float> > t, l;
                 std::vector<int> st;
                 decode.GetNbestWords(live, partial_nbest, slm1, slm2, false, &w, &t, &l, &st);
-                std::vector<std::vector<WordAlignment> > al;
+                std::vector<std::vector<WordConfidence> > al;
                 std::vector<int> ast;
-                if (nbest_times && !live.empty()) decode.AlignWords(live, w, false, &al, &ast);   // (one call for the channels still running)
+                if (nbest_times && !live.empty()) batch_times(decode, live, w, false, &al, &ast);   // (one call for the channels still running)
                 for (size_t q = 0; q < live.size(); ++q)
                   o.partials += nbest_lines(utts[b0 + (size_t)live[q]].key, decode.NumFramesDecoded(live[q]), st[q], w[q], t[q], l[q],
                                             nbest_times && ast[q] == WFST_OK ? &al[q] : nullptr);
@@ -961,7 +1019,7 @@ int main(int argc, char **argv) {
               if (nbest_times) {   // every path of every channel in one call
                 std::vector<std::vector<std::vector<int> > > seqs(n);
                 for (int i = 0; i < n; ++i) seqs[i] = path_words(o.nbest[i]);
-                decode.AlignWords(ch, seqs, true, &o.nb_times);
+                batch_times(decode, ch, seqs, true, &o.nb_times, nullptr);
               }
             }
             if (!align_seqs.empty()) {
@@ -970,7 +1028,7 @@ int main(int argc, char **argv) {
                 auto it = align_seqs.find(utts[b0 + i].key);
                 if (it != align_seqs.end()) seqs[i] = it->second;
               }
-              decode.AlignWords(ch, seqs, true, &o.al_times);
+              batch_times(decode, ch, seqs, true, &o.al_times, nullptr);
             }
             if (!nearest_refs.empty()) {   // every reference of every channel in one call
               std::vector<std::vector<std::vector<int> > > refs(n);

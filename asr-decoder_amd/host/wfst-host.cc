@@ -23,6 +23,7 @@
 #pragma weak wfst_decoder_align_words
 // ... and the lattice edit distance's: NearestWords reports itself missing there
 #pragma weak wfst_decoder_nearest_words
+#pragma weak wfst_decoder_word_confidence
 
 namespace datemoon {
 
@@ -1828,6 +1829,89 @@ bool GpuLatticeDecoder::AlignWords(const std::vector<int> &words, std::vector<st
   if (tot) *tot = a[0].tot;
   if (lm) *lm = a[0].lm;
   return a[0].found;
+}
+
+// ---- word confidences from the lattice's posteriors (wfst_decoder_word_confidence) -----------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i][q] for seqs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.
+static int WordConfidencesCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<std::vector<int> > > &seqs,
+                               bool use_final_probs, double graph_scale, double acoustic_scale, long long max_cells,
+                               std::vector<std::vector<WordConfidence> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_word_confidence) throw std::runtime_error("WordConfidences: this build's device library has no wfst_decoder_word_confidence");
+  if (seqs.size() != ch.size()) throw std::runtime_error("WordConfidences: one list of sequences per listed channel");
+  const size_t cnt = ch.size();
+  size_t ns = 1, cap = 1;
+  for (const auto &s : seqs) {
+    ns = std::max(ns, s.size());
+    for (const auto &w : s) cap = std::max(cap, w.size());
+  }
+  std::vector<int32_t> words(cnt * ns * cap, 0), len(cnt * ns, -1), st(cnt), found(cnt * ns), na(cnt * ns), b(cnt * ns * cap), e(cnt * ns * cap);
+  std::vector<float> t(cnt * ns), l(cnt * ns);
+  std::vector<double> lz(cnt), wp(cnt * ns * cap), plp(cnt * ns);
+  for (size_t i = 0; i < cnt; ++i)
+    for (size_t q = 0; q < seqs[i].size(); ++q) {
+      len[i * ns + q] = (int32_t)seqs[i][q].size();
+      std::copy(seqs[i][q].begin(), seqs[i][q].end(), words.begin() + (i * ns + q) * cap);
+    }
+  const int rc = wfst_decoder_word_confidence(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, graph_scale, acoustic_scale, (int32_t)ns,
+                                              (int32_t)cap, words.data(), len.data(), max_cells, st.data(), lz.data(), found.data(), na.data(),
+                                              b.data(), e.data(), wp.data(), plp.data(), t.data(), l.data());
+  if (rc != WFST_OK) return rc;
+  out->assign(cnt, std::vector<WordConfidence>());
+  for (size_t i = 0; i < cnt; ++i) {
+    (*out)[i].resize(seqs[i].size());
+    for (size_t q = 0; q < seqs[i].size(); ++q) {
+      WordConfidence &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.log_z = lz[i];
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.n_arcs = na[p]; a.tot = t[p]; a.lm = l[p]; a.path_logpost = plp[p];
+      for (size_t k = 0; k < seqs[i][q].size(); ++k) {
+        a.frames.push_back(std::make_pair(b[p * cap + k], e[p * cap + k]));
+        a.word_post.push_back(wp[p * cap + k]);
+        a.conf.push_back(std::min(1.0, wp[p * cap + k]));
+      }
+    }
+  }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::WordConfidences(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
+                                      double graph_scale, double acoustic_scale, std::vector<std::vector<WordConfidence> > *out,
+                                      std::vector<int> *status, long long max_cells) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<std::vector<WordConfidence> > o;
+  std::vector<int> st;
+  if (WordConfidencesCall(_dec, ch, seqs, use_final_probs, graph_scale, acoustic_scale, max_cells, &o, &st) != WFST_OK) Fatal("WordConfidences");
+  if (!status)
+    for (int s : st)
+      if (s != WFST_OK) Fatal("WordConfidences");
+  if (out) out->swap(o);
+  if (status) *status = st;
+}
+
+void GpuLatticeDecoder::WordConfidences(const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *out, bool use_final_probs,
+                                        double graph_scale, double acoustic_scale) {
+  std::vector<std::vector<WordConfidence> > o;
+  if (!seqs.empty()) {
+    std::vector<int> st;
+    int rc = WFST_OK;
+    std::string msg;
+    // (the C-ABI calls of one decoder are not re-entrant: over a pool this runs in the batcher thread, like AlignWords)
+    OnDevice([&] {
+      rc = WordConfidencesCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<std::vector<int> > >(1, seqs), use_final_probs,
+                               graph_scale, acoustic_scale, 0, &o, &st);
+      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+    });
+    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("WordConfidences: " + msg);
+  }
+  if (out) {
+    out->clear();
+    if (!o.empty()) out->swap(o[0]);
+  }
 }
 
 // ---- the lattice path nearest a transcript (wfst_decoder_nearest_words) ---------------------------------------------------------------

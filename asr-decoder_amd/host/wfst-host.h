@@ -412,6 +412,16 @@ struct WordAlignment {
   std::vector<std::pair<int, int> > frames;
 };
 
+// A WordAlignment with the confidences of its words (wfst_decoder_word_confidence): word_post[k] = the posterior mass of the lattice's
+// arcs that say word k in the word's cell of the time axis (cells cut at the midpoints of consecutive begin frames; above 1 where
+// paths say a short word twice inside one cell), conf[k] = min(1, word_post[k]); path_logpost = the log posterior of the aligned path
+// itself; log_z = the log of the lattice's total weight.  Arcs cost graph_scale * graph + acoustic_scale * acoustic, in double; the
+// alignment's own fields stay unscaled.  The doubles are reproducible to rounding, not bit for bit.
+struct WordConfidence : WordAlignment {
+  std::vector<double> conf, word_post;
+  double path_logpost = 0.0, log_z = 0.0;
+};
+
 // The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
 // cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
 // them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
@@ -513,6 +523,10 @@ class GpuLatticeDecoder : public DecoderItf {
   bool AlignWords(const std::vector<int> &words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs = true);
   // ... of every path GetNbestWords returned, in one device call: (*out)[k] for nbest[k]
   void GetNbestWordTimes(const std::vector<std::vector<int> > &nbest, std::vector<WordAlignment> *out, bool use_final_probs = true);
+  // ... with the confidence of every word (wfst_decoder_word_confidence), in one device call: (*out)[k] for seqs[k] (at most 64).
+  // The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void WordConfidences(const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *out, bool use_final_probs = true,
+                       double graph_scale = 1.0, double acoustic_scale = 1.0);
   // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
   // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
@@ -622,6 +636,11 @@ class GpuBatchDecoder {
   // the channel's own error code (nothing of it is found then; without `status` it throws).  max_cells: see wfst_decoder_align_words.
   void AlignWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
                   std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status = nullptr, long long max_cells = 0);
+  // WordConfidences (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage;
+  // the arguments and the status rule are AlignWords'
+  void WordConfidences(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
+                       double graph_scale, double acoustic_scale, std::vector<std::vector<WordConfidence> > *out,
+                       std::vector<int> *status = nullptr, long long max_cells = 0);
   // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
   // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.

@@ -46,7 +46,7 @@ SYMBOLS = [
     "wfst_decoder_set_score_transform", "wfst_decoder_advance_chunk", "wfst_decoder_get_scores",
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
-    "wfst_decoder_align_words", "wfst_decoder_nearest_words",
+    "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
 ]
 
 
@@ -849,6 +849,49 @@ class BatchDecoder:
             out.append(row)
         return out
 
+    def word_confidences(self, seqs, channels=None, use_final_probs=True, graph_scale=1.0, acoustic_scale=1.0, max_cells=0):
+        """Word confidences from the posteriors of the raw lattice, for a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_word_confidence): seqs[i] = the word sequences on channels[i], as align_words takes them.  Per channel a list
+        with one dict per sequence: align_words' fields (found, begin, end, tot, lm, n_arcs, status: the aligned path's own, unscaled)
+        plus word_post (float64 per word: the posterior mass of the arcs that say the word in the word's cell of the time axis,
+        unclamped), conf = min(1, word_post), path_logpost (the log posterior of the aligned path) and log_z (the channel's).  The
+        arcs cost graph_scale * graph + acoustic_scale * acoustic, in float64; the sums' order is the device's, so the floats are
+        reproducible to rounding, not bit for bit."""
+        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
+        cnt = len(ch)
+        if len(seqs) != cnt:
+            raise ValueError("one list of sequences per listed channel")
+        ns = max([len(s) for s in seqs] + [1])
+        cap = max([len(w) for s in seqs for w in s if w is not None] + [1])
+        words = np.zeros((cnt, ns, cap), np.int32)
+        lens = np.full((cnt, ns), -1, np.int32)
+        for i, s in enumerate(seqs):
+            for q, w in enumerate(s):
+                if w is not None:
+                    lens[i, q] = len(w)
+                    words[i, q, :len(w)] = np.asarray(w, np.int32)
+        status = np.zeros(cnt, np.int32)
+        found, na = np.zeros((cnt, ns), np.int32), np.zeros((cnt, ns), np.int32)
+        begin, end = np.zeros((cnt, ns, cap), np.int32), np.zeros((cnt, ns, cap), np.int32)
+        tot, lm = np.zeros((cnt, ns), np.float32), np.zeros((cnt, ns), np.float32)
+        log_z, wp, plp = np.zeros(cnt, np.float64), np.zeros((cnt, ns, cap), np.float64), np.zeros((cnt, ns), np.float64)
+        f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        _check(lib().wfst_decoder_word_confidence(self.h, _i32(ch), cnt, int(bool(use_final_probs)), C.c_double(float(graph_scale)),
+                                                  C.c_double(float(acoustic_scale)), ns, cap, _i32(words), _i32(lens),
+                                                  C.c_int64(int(max_cells)), _i32(status), f64(log_z), _i32(found), _i32(na), _i32(begin),
+                                                  _i32(end), f64(wp), f64(plp), _f32(tot), _f32(lm)))
+        out = []
+        for i in range(cnt):
+            row = []
+            for q in range(len(seqs[i])):
+                ln = max(int(lens[i, q]), 0)
+                post = wp[i, q, :ln].copy()
+                row.append(dict(found=bool(found[i, q]), begin=begin[i, q, :ln].copy(), end=end[i, q, :ln].copy(), tot=np.float32(tot[i, q]),
+                                lm=np.float32(lm[i, q]), n_arcs=int(na[i, q]), status=int(status[i]), word_post=post,
+                                conf=np.minimum(1.0, post), path_logpost=float(plp[i, q]), log_z=float(log_z[i])))
+            out.append(row)
+        return out
+
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):
         """nbest_words(...) with word times: every path's words aligned on its channel's raw lattice (align_words); the dicts of
         nbest_words gain found, begin, end, n_arcs and align_tot / align_lm (the aligned path's own scores: the determinizer
@@ -861,6 +904,22 @@ class BatchDecoder:
             for p, x in zip(paths, a):
                 p.update(found=x["found"], begin=x["begin"], end=x["end"], n_arcs=x["n_arcs"], align_tot=x["tot"], align_lm=x["lm"],
                          align_status=x["status"])
+        return res
+
+    def nbest_words_conf(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0,
+                         graph_scale=1.0, acoustic_scale=1.0):
+        """nbest_words_timed(...) with confidences: every path's words aligned on its channel's raw lattice and weighed against the
+        lattice's posteriors (word_confidences); beside nbest_words_timed's keys the dicts carry conf, word_post, path_logpost and
+        log_z."""
+        res = self.nbest_words(n_paths, channels, old_lm, new_lm, use_final_probs, cap_words)
+        ch = list(range(self.n)) if channels is None else [int(c) for c in channels]
+        seqs = [[p["words"] if p["n_words"] <= int(cap_words) else None for p in paths] for _, paths in res]
+        al = self.word_confidences(seqs, ch, use_final_probs, graph_scale, acoustic_scale, max_cells)
+        for (_, paths), a in zip(res, al):
+            for p, x in zip(paths, a):
+                p.update(found=x["found"], begin=x["begin"], end=x["end"], n_arcs=x["n_arcs"], align_tot=x["tot"], align_lm=x["lm"],
+                         align_status=x["status"], conf=x["conf"], word_post=x["word_post"], path_logpost=x["path_logpost"],
+                         log_z=x["log_z"])
         return res
 
     def raw_lattices(self, channels=None, use_final_probs=True, threads=0):

@@ -651,6 +651,62 @@ int wfst_decoder_nearest_words(wfst_decoder *d, const int32_t *channels, int32_t
                                int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame /* [n][n_refs][cap_hyp] */,
                                int32_t *ref_hyp /* [n][n_refs][cap_words] */, float *tot_score, float *lm_score /* [n][n_refs] */);
 
+/* ---- word confidences from lattice posteriors -----------------------------------------------------------------------------------
+ * How sure the decoder is of a word: the posterior mass of the lattice's arcs that say the word at about the time a hypothesis says
+ * it.  The sum-over-paths twin of wfst_decoder_align_words, on the same lattice, for a list of channels, live and finalized ones
+ * mixed, n_seqs sequences per channel, one launch per stage (the live channels' lattices emitted, align_index_kernel, align_kernel,
+ * posterior_kernel, confidence_kernel).
+ *
+ * The lattice R is exactly wfst_decoder_align_words': what wfst_decoder_get_raw_lattice(channel, use_final_probs) returns at this
+ * moment (wfst_decoder_set_live_lattice_prune, the use_final_probs rule after FinalizeDecoding and "no lattice" honoured).  State 0 is
+ * the start, every arc goes to a higher state id, final states are flagged and carry no weight, and a final state may have out-arcs.
+ * All arithmetic is float64.  For the scales graph_scale and acoustic_scale (finite, >= 0) an arc a = (s -> t, graph, acoustic) costs
+ *   c(a) = graph_scale * (double)graph + acoustic_scale * (double)acoustic,
+ * and an arc whose float32 graph + acoustic is not finite is no arc (wfst_decoder_align_words' rule: both calls see the same paths).
+ *   alpha[0] = 0;   alpha[t] = -log sum over the arcs a: s -> t of exp(-(alpha[s] + c(a)))
+ *   beta[s]  = -log([s is final] + sum over the arcs a: s -> t of exp(-(c(a) + beta[t])))
+ *   log_z    = -beta[0]
+ *   gamma(a) = exp(-(alpha[s] + c(a) + beta[t] + log_z))                                  (the posterior of the arc)
+ * Every sum is taken as m - log(sum exp(-(x - m))) with m the least term.  A state without a finite term is +inf, and its arcs have
+ * posterior 0, never NaN.  The ORDER in which a state's arcs are summed is free -- it is the order of the device's arc index, which
+ * the launch that emits the lattice decides -- so the results are reproducible to rounding (a few ulp of the largest |alpha| or |beta|
+ * per level of the lattice), NOT bit for bit.
+ *
+ * Word confidence, for a sequence w[0..L) of word ids > 0, on top of wfst_decoder_align_words' answer for that sequence -- found,
+ * n_arcs, begin_frame, end_frame, tot_score and lm_score are that call's own, unscaled and bit for bit.  With b[k] = begin_frame[k]
+ * (the frame of the source state of the arc that carries word k) the time axis is cut at the midpoints of consecutive begin frames:
+ *   m[0] = 0;   m[k] = (b[k - 1] + b[k] + 1) >> 1 for 1 <= k < L;   m[L] = +inf;   cell k = the frames m[k] <= f < m[k + 1]
+ *   word_post[k] = sum of gamma(a) over the arcs a with olabel(a) == w[k] whose SOURCE state's frame lies in cell k
+ * -- emitting and epsilon arcs alike: a word may sit on an epsilon arc.  It is the expected number of times a path says w[k] at about
+ * the time the hypothesis does: order-free, without a word-boundary lattice, 1 when every path agrees, and above 1 when paths say a
+ * short word twice inside one cell.  The confidence is min(1, word_post[k]); this call returns word_post UNCLAMPED.
+ * path_logpost[i][q] = -log_z - sum of c(a) along the aligned path, in arc order: the log posterior of that one path (<= 0), a lower
+ * bound of the hypothesis' sentence posterior.  log_z[i] is per channel.  found = 0: word_post and path_logpost are zero.  The empty sequence
+ * is found where the alignment finds it and has no words.
+ * Limitation: a word's arc sits where the graph put its olabel, so the cells follow label positions, not acoustic word boundaries.
+ * Not computed here: a hypothesis' full sentence posterior (a log-semiring table of states x (L + 1)), per-frame transition-id
+ * posteriors (lattice-to-post), minimum Bayes risk / confusion networks.
+ *
+ * A failure of ONE channel goes into status[i] with all of that channel's outputs zero, and the call still returns WFST_OK: a
+ * sequence whose alignment table of states x (seq_len + 1) cells is beyond max_cells (WFST_E_CAPACITY; 0 = wfst_decoder_align_words'
+ * default), a device error of that channel's utterance.  Beside the alignment's workspace (shared with wfst_decoder_align_words, rounds
+ * included) the posteriors take 24 bytes per state and 16 per arc of a listed lattice: alpha, beta, the level flags, gamma and a
+ * by-source arc table.
+ * The call itself fails, before any device work, with WFST_E_ARG (a scale that is negative or not finite, and everything
+ * wfst_decoder_align_words names) or WFST_E_STATE (as there).  Any output pointer may be NULL.  The decoder's state is only read:
+ * decoding goes on bit for bit as without the call, and the other getters answer afterwards what they would have answered.
+ * Synchronous, as wfst_decoder_align_words is and for the same reason. */
+int wfst_decoder_word_confidence(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                                 double graph_scale, double acoustic_scale,
+                                 int32_t n_seqs /* per channel, 1..64 */, int32_t cap_words,
+                                 const int32_t *seq_words /* [n][n_seqs][cap_words] */, const int32_t *seq_len /* [n][n_seqs], -1 = skip */,
+                                 int64_t max_cells /* states x (len + 1) per sequence; 0 = default */,
+                                 int32_t *status /* [n] */, double *log_z /* [n] */,
+                                 int32_t *found, int32_t *n_arcs /* [n][n_seqs] */,
+                                 int32_t *begin_frame, int32_t *end_frame /* [n][n_seqs][cap_words] */,
+                                 double *word_post /* [n][n_seqs][cap_words] */, double *path_logpost /* [n][n_seqs] */,
+                                 float *tot_score, float *lm_score /* [n][n_seqs] */);
+
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
  * ConvertNbestToVector, then LatticeToVector per path) of channels of a lattice-mode decoder, finalized
