@@ -242,6 +242,7 @@ def test_gpu_nbest_equals_reference_pipeline_on_its_own_lattice(lattice_beam, re
     """Bigger lattices, n = 10: the device n-best against the reference's DeterminizeLatticeWrapper
     + NShortestPath + LatticeToVector run (oracle/_ref) on the very lattice the device returns."""
     import gpu_util as G
+    from nbest_util import kbest_distinct, same_nbest
 
     g = synth.make_hclg_like(20000, seed=7, n_tid=2000, n_words=3000)
     m = synth.default_tid2pdf(2000)
@@ -264,6 +265,8 @@ def test_gpu_nbest_equals_reference_pipeline_on_its_own_lattice(lattice_beam, re
         ref = pyoracle.ref_nbest_from_lattice_file(refdec, p, 0, 10)
         assert ref is not None
         _same_nbest(got[i], ref[0], "utt %d lattice_beam %g" % (i, lattice_beam))
+        # and bit for bit what the kernel's own definition gives on this lattice (tests/nbest_util.py)
+        same_nbest(got[i], kbest_distinct(as_raw(dec.raw_lattice(i)), 10), "utt %d lattice_beam %g" % (i, lattice_beam))
     dec.free()
     graph.free()
 

@@ -335,6 +335,7 @@ def test_lattice_getters(world, shift, tmp_path):
     GetNbest as paths and the second LM pass, on lattices whose arc and path costs have both signs."""
     from test_compose_lattice import _same as same_multiset
     from test_gpu_determinize import _check_against, _ref_or_none, as_det
+    from nbest_util import kbest_distinct, kbest_paths_dp, same_nbest, same_paths
     from test_gpu_fuzz import py_nbest
     from test_gpu_lattice import as_raw
 
@@ -372,8 +373,10 @@ def test_lattice_getters(world, shift, tmp_path):
                 assert any(abs(e[2] - a["lm_score"]) <= 1e-3 * max(1.0, abs(e[2])) for e in hits), "%s rank %d lm score" % (what, k)
             assert len({tuple(p["words"].tolist()) for p in nb[c]}) == len(nb[c]), what + " duplicate word sequences"
             assert np.array_equal(nb[c][0]["words"], best[c]["words"]), what + " 1-best of the n-best"
+            same_nbest(nb[c], kbest_distinct(as_raw(raw), 4), what + " against the kernel's own definition")   # (bit for bit)
             # GetNbest as paths against NShortestPath restated, on the determinized lattice
             _same_nbest_paths(dec.nbest_paths(c, 5), pyoracle.nshortest_paths(D, 5), what + " n-best paths")
+            same_paths(dec.nbest_paths(c, 5), kbest_paths_dp(dec.determinized_lattice(c), 5), what + " n-best paths against the kernel's own definition")
             # the second LM pass against ComposeLattice restated
             got = dec.rescored_lattice(c, L1, L2)
             assert got is not None, what

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from nbest_util import kbest_paths_dp, same_paths
 from test_compose_lattice import _as_dict, _setup
 
 shard = importlib.import_module("asr-decoder_amd.shard")
@@ -115,16 +116,19 @@ def test_device_nbest_paths_equal_the_reference(oracle, refdec, synth, tmp_path)
             p = str(tmp_path / "raw.lat")
             with open(p, "wb") as f:
                 f.write(shard.lattice_to_bytes(raw))
+            det = dec.determinized_lattice(c)   # (in the device's arc order: the restatement's answer is exact, ties included)
             for n in (1, 5, 40, 700, 4096):   # (4096: the sort buffer's limit -- candidate lists merged in chunks)
                 ref = pyoracle.ref_nbest_paths_from_lattice_file(refdec, p, 0, n)
                 assert ref is not None
                 got = dec.nbest_paths(c, n)
                 _same_paths(got, ref, "seed %d utt %d n %d" % (seed, c, n))
+                same_paths(got, kbest_paths_dp(det, n), "seed %d utt %d n %d, the kernel's own definition" % (seed, c, n))
                 most = max(most, len(got))
             for n in (3, 60):
                 ref = pyoracle.ref_nbest_paths_from_lattice_file(refdec, p, 0, n, r1, r2)
                 assert ref is not None
                 _same_paths(dec.nbest_paths(c, n, L1, L2), ref, "seed %d utt %d n %d second pass" % (seed, c, n))
+                same_paths(dec.nbest_paths(c, n, L1, L2), kbest_paths_dp(dec.rescored_lattice(c, L1, L2), n), "seed %d utt %d n %d second pass, the kernel's own definition" % (seed, c, n))
             # the short list on the raw lattice agrees on the word sequences
             short = dec.nbest(5)[c]
             long_ = dec.nbest_paths(c, 5)
