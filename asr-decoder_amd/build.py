@@ -12,7 +12,7 @@ SRCS = [os.path.join(HERE, "csrc", "wfst_kernels.hip"), os.path.join(HERE, "csrc
         os.path.join(HERE, "csrc", "wfst_determinize.hip"), os.path.join(HERE, "csrc", "wfst_compose.hip"), os.path.join(HERE, "csrc", "wfst_ingest.hip"),
         os.path.join(HERE, "csrc", "wfst_capi.cc"), os.path.join(HERE, "csrc", "wfst_capi_words.cc"), os.path.join(HERE, "csrc", "wfst_capi_ingest.cc"),
         os.path.join(HERE, "csrc", "wfst_capi_nbwords.cc"), os.path.join(HERE, "csrc", "wfst_capi_liveprune.cc"),
-        os.path.join(HERE, "csrc", "wfst_align.hip"), os.path.join(HERE, "csrc", "wfst_capi_align.cc"),
+        os.path.join(HERE, "csrc", "wfst_align.hip"), os.path.join(HERE, "csrc", "wfst_capi_align.cc"), os.path.join(HERE, "csrc", "wfst_capi_wordquery.cc"),
         os.path.join(HERE, "csrc", "wfst_nearest.hip"), os.path.join(HERE, "csrc", "wfst_capi_nearest.cc"),
         os.path.join(HERE, "csrc", "wfst_posterior.hip"), os.path.join(HERE, "csrc", "wfst_capi_posterior.cc"),
         os.path.join(HERE, "csrc", "wfst_openfst.cc")]

@@ -1750,27 +1750,81 @@ void GpuBatchDecoder::GetNbestWords(const std::vector<int> &channels, int n, Arp
   if (status) *status = st;
 }
 
+// ---- the word queries of a raw lattice: what AlignWords, WordConfidences and NearestWords do alike ------------------------------------
+namespace {
+typedef std::vector<std::vector<std::vector<int> > > SeqLists;   // [listed channel][sequence][word]
+
+// seqs[i][q] as the C ABI takes them: words[cnt][ns][cap] (padded with 0) and len[cnt][ns] (-1: the channel has no such sequence)
+struct PackedSeqs {
+  size_t cnt, ns = 1, cap = 1, np;
+  std::vector<int32_t> words, len;
+  explicit PackedSeqs(const SeqLists &seqs) : cnt(seqs.size()) {
+    for (const auto &s : seqs) {
+      ns = std::max(ns, s.size());
+      for (const auto &w : s) cap = std::max(cap, w.size());
+    }
+    np = cnt * ns;
+    words.assign(np * cap, 0);
+    len.assign(np, -1);
+    for (size_t i = 0; i < cnt; ++i)
+      for (size_t q = 0; q < seqs[i].size(); ++q) {
+        len[i * ns + q] = (int32_t)seqs[i][q].size();
+        std::copy(seqs[i][q].begin(), seqs[i][q].end(), words.begin() + (i * ns + q) * cap);
+      }
+  }
+};
+
+// GpuBatchDecoder's wrapper: call(ch, &out, &status) is one C-ABI call for the listed channels (none listed: all n_channels)
+template <class T, class Call>
+void BatchWordQuery(const char *what, const std::vector<int> &channels, int n_channels, std::vector<std::vector<T> > *out,
+                    std::vector<int> *status, Call call) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < n_channels; ++c) ch.push_back(c);
+  std::vector<std::vector<T> > o;
+  std::vector<int> st;
+  if (call(ch, &o, &st) != WFST_OK) Fatal(what);
+  if (!status)
+    for (int s : st)
+      if (s != WFST_OK) Fatal(what);
+  if (out) out->swap(o);
+  if (status) *status = st;
+}
+
+// GpuLatticeDecoder's wrapper: call(ch, seqs, &out, &status) for the one channel, inside on_device (OnDevice: the C-ABI calls of one
+// decoder are not re-entrant, over a pool this runs in the batcher thread, like GetNbest)
+template <class T, class Run, class Call>
+void StreamWordQuery(const char *what, int chan, const std::vector<std::vector<int> > &seqs, std::vector<T> *out, Run on_device, Call call) {
+  std::vector<std::vector<T> > o;
+  if (!seqs.empty()) {
+    std::vector<int> st;
+    int rc = WFST_OK;
+    std::string msg;
+    on_device([&] {
+      rc = call(std::vector<int32_t>(1, chan), SeqLists(1, seqs), &o, &st);
+      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+    });
+    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error(std::string(what) + ": " + msg);
+  }
+  if (out) {
+    out->clear();
+    if (!o.empty()) out->swap(o[0]);
+  }
+}
+}  // namespace
+
 // ---- word times for any word sequence of the lattice (wfst_decoder_align_words) -----------------------------------------------------
 // One C-ABI call for `ch`: (*out)[i][q] for seqs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.
-static int AlignWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<std::vector<int> > > &seqs,
-                          bool use_final_probs, long long max_cells, std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status) {
+static int AlignWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const SeqLists &seqs, bool use_final_probs, long long max_cells,
+                          std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status) {
   if (!wfst_decoder_align_words) throw std::runtime_error("AlignWords: this build's device library has no wfst_decoder_align_words");
   if (seqs.size() != ch.size()) throw std::runtime_error("AlignWords: one list of sequences per listed channel");
-  const size_t cnt = ch.size();
-  size_t ns = 1, cap = 1;
-  for (const auto &s : seqs) {
-    ns = std::max(ns, s.size());
-    for (const auto &w : s) cap = std::max(cap, w.size());
-  }
-  std::vector<int32_t> words(cnt * ns * cap, 0), len(cnt * ns, -1), st(cnt), found(cnt * ns), na(cnt * ns), b(cnt * ns * cap), e(cnt * ns * cap);
-  std::vector<float> t(cnt * ns), l(cnt * ns);
-  for (size_t i = 0; i < cnt; ++i)
-    for (size_t q = 0; q < seqs[i].size(); ++q) {
-      len[i * ns + q] = (int32_t)seqs[i][q].size();
-      std::copy(seqs[i][q].begin(), seqs[i][q].end(), words.begin() + (i * ns + q) * cap);
-    }
-  const int rc = wfst_decoder_align_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, (int32_t)cap, words.data(), len.data(),
-                                          max_cells, st.data(), found.data(), na.data(), b.data(), e.data(), t.data(), l.data());
+  const PackedSeqs in(seqs);
+  const size_t cnt = in.cnt, ns = in.ns, cap = in.cap, np = in.np;
+  std::vector<int32_t> st(cnt), found(np), na(np), b(np * cap), e(np * cap);
+  std::vector<float> t(np), l(np);
+  const int rc = wfst_decoder_align_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, (int32_t)cap, in.words.data(),
+                                          in.len.data(), max_cells, st.data(), found.data(), na.data(), b.data(), e.data(), t.data(), l.data());
   if (rc != WFST_OK) return rc;
   out->assign(cnt, std::vector<WordAlignment>());
   for (size_t i = 0; i < cnt; ++i) {
@@ -1790,36 +1844,16 @@ static int AlignWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, con
 
 void GpuBatchDecoder::AlignWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
                                  std::vector<std::vector<WordAlignment> > *out, std::vector<int> *status, long long max_cells) {
-  std::vector<int32_t> ch(channels.begin(), channels.end());
-  if (ch.empty())
-    for (int c = 0; c < _n; ++c) ch.push_back(c);
-  std::vector<std::vector<WordAlignment> > o;
-  std::vector<int> st;
-  if (AlignWordsCall(_dec, ch, seqs, use_final_probs, max_cells, &o, &st) != WFST_OK) Fatal("AlignWords");
-  if (!status)
-    for (int s : st)
-      if (s != WFST_OK) Fatal("AlignWords");
-  if (out) out->swap(o);
-  if (status) *status = st;
+  BatchWordQuery("AlignWords", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return AlignWordsCall(_dec, ch, seqs, use_final_probs, max_cells, o, st);
+  });
 }
 
 void GpuLatticeDecoder::GetNbestWordTimes(const std::vector<std::vector<int> > &nbest, std::vector<WordAlignment> *out, bool use_final_probs) {
-  std::vector<std::vector<WordAlignment> > o;
-  if (!nbest.empty()) {
-    std::vector<int> st;
-    int rc = WFST_OK;
-    std::string msg;
-    // (the C-ABI calls of one decoder are not re-entrant: over a pool this runs in the batcher thread, like GetNbest)
-    OnDevice([&] {
-      rc = AlignWordsCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<std::vector<int> > >(1, nbest), use_final_probs, 0, &o, &st);
-      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
-    });
-    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("AlignWords: " + msg);
-  }
-  if (out) {
-    out->clear();
-    if (!o.empty()) out->swap(o[0]);
-  }
+  StreamWordQuery("AlignWords", _chan, nbest, out, [&](auto &&f) { OnDevice(f); },
+                  [&](const auto &ch, const SeqLists &seqs, auto *o, auto *st) {
+                    return AlignWordsCall(_dec, ch, seqs, use_final_probs, 0, o, st);
+                  });
 }
 
 bool GpuLatticeDecoder::AlignWords(const std::vector<int> &words, std::vector<std::pair<int, int> > *frames, float *tot, float *lm, bool use_final_probs) {
@@ -1833,27 +1867,17 @@ bool GpuLatticeDecoder::AlignWords(const std::vector<int> &words, std::vector<st
 
 // ---- word confidences from the lattice's posteriors (wfst_decoder_word_confidence) -----------------------------------------------------
 // One C-ABI call for `ch`: (*out)[i][q] for seqs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.
-static int WordConfidencesCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<std::vector<int> > > &seqs,
-                               bool use_final_probs, double graph_scale, double acoustic_scale, long long max_cells,
-                               std::vector<std::vector<WordConfidence> > *out, std::vector<int> *status) {
+static int WordConfidencesCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const SeqLists &seqs, bool use_final_probs, double graph_scale,
+                               double acoustic_scale, long long max_cells, std::vector<std::vector<WordConfidence> > *out, std::vector<int> *status) {
   if (!wfst_decoder_word_confidence) throw std::runtime_error("WordConfidences: this build's device library has no wfst_decoder_word_confidence");
   if (seqs.size() != ch.size()) throw std::runtime_error("WordConfidences: one list of sequences per listed channel");
-  const size_t cnt = ch.size();
-  size_t ns = 1, cap = 1;
-  for (const auto &s : seqs) {
-    ns = std::max(ns, s.size());
-    for (const auto &w : s) cap = std::max(cap, w.size());
-  }
-  std::vector<int32_t> words(cnt * ns * cap, 0), len(cnt * ns, -1), st(cnt), found(cnt * ns), na(cnt * ns), b(cnt * ns * cap), e(cnt * ns * cap);
-  std::vector<float> t(cnt * ns), l(cnt * ns);
-  std::vector<double> lz(cnt), wp(cnt * ns * cap), plp(cnt * ns);
-  for (size_t i = 0; i < cnt; ++i)
-    for (size_t q = 0; q < seqs[i].size(); ++q) {
-      len[i * ns + q] = (int32_t)seqs[i][q].size();
-      std::copy(seqs[i][q].begin(), seqs[i][q].end(), words.begin() + (i * ns + q) * cap);
-    }
+  const PackedSeqs in(seqs);
+  const size_t cnt = in.cnt, ns = in.ns, cap = in.cap, np = in.np;
+  std::vector<int32_t> st(cnt), found(np), na(np), b(np * cap), e(np * cap);
+  std::vector<float> t(np), l(np);
+  std::vector<double> lz(cnt), wp(np * cap), plp(np);
   const int rc = wfst_decoder_word_confidence(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, graph_scale, acoustic_scale, (int32_t)ns,
-                                              (int32_t)cap, words.data(), len.data(), max_cells, st.data(), lz.data(), found.data(), na.data(),
+                                              (int32_t)cap, in.words.data(), in.len.data(), max_cells, st.data(), lz.data(), found.data(), na.data(),
                                               b.data(), e.data(), wp.data(), plp.data(), t.data(), l.data());
   if (rc != WFST_OK) return rc;
   out->assign(cnt, std::vector<WordConfidence>());
@@ -1880,66 +1904,35 @@ static int WordConfidencesCall(wfst_decoder *dec, const std::vector<int32_t> &ch
 void GpuBatchDecoder::WordConfidences(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
                                       double graph_scale, double acoustic_scale, std::vector<std::vector<WordConfidence> > *out,
                                       std::vector<int> *status, long long max_cells) {
-  std::vector<int32_t> ch(channels.begin(), channels.end());
-  if (ch.empty())
-    for (int c = 0; c < _n; ++c) ch.push_back(c);
-  std::vector<std::vector<WordConfidence> > o;
-  std::vector<int> st;
-  if (WordConfidencesCall(_dec, ch, seqs, use_final_probs, graph_scale, acoustic_scale, max_cells, &o, &st) != WFST_OK) Fatal("WordConfidences");
-  if (!status)
-    for (int s : st)
-      if (s != WFST_OK) Fatal("WordConfidences");
-  if (out) out->swap(o);
-  if (status) *status = st;
+  BatchWordQuery("WordConfidences", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return WordConfidencesCall(_dec, ch, seqs, use_final_probs, graph_scale, acoustic_scale, max_cells, o, st);
+  });
 }
 
 void GpuLatticeDecoder::WordConfidences(const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *out, bool use_final_probs,
                                         double graph_scale, double acoustic_scale) {
-  std::vector<std::vector<WordConfidence> > o;
-  if (!seqs.empty()) {
-    std::vector<int> st;
-    int rc = WFST_OK;
-    std::string msg;
-    // (the C-ABI calls of one decoder are not re-entrant: over a pool this runs in the batcher thread, like AlignWords)
-    OnDevice([&] {
-      rc = WordConfidencesCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<std::vector<int> > >(1, seqs), use_final_probs,
-                               graph_scale, acoustic_scale, 0, &o, &st);
-      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
-    });
-    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("WordConfidences: " + msg);
-  }
-  if (out) {
-    out->clear();
-    if (!o.empty()) out->swap(o[0]);
-  }
+  StreamWordQuery("WordConfidences", _chan, seqs, out, [&](auto &&f) { OnDevice(f); },
+                  [&](const auto &ch, const SeqLists &s, auto *o, auto *st) {
+                    return WordConfidencesCall(_dec, ch, s, use_final_probs, graph_scale, acoustic_scale, 0, o, st);
+                  });
 }
 
 // ---- the lattice path nearest a transcript (wfst_decoder_nearest_words) ---------------------------------------------------------------
 // One C-ABI call for `ch`: (*out)[i][q] for refs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.  A path with
 // more words than the first call made room for is asked for again with n_hyp's room.
-static int NearestWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<std::vector<int> > > &refs,
-                            bool use_final_probs, long long max_cells, std::vector<std::vector<NearestPath> > *out, std::vector<int> *status) {
+static int NearestWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const SeqLists &refs, bool use_final_probs, long long max_cells,
+                            std::vector<std::vector<NearestPath> > *out, std::vector<int> *status) {
   if (!wfst_decoder_nearest_words) throw std::runtime_error("NearestWords: this build's device library has no wfst_decoder_nearest_words");
   if (refs.size() != ch.size()) throw std::runtime_error("NearestWords: one list of references per listed channel");
-  const size_t cnt = ch.size();
-  size_t ns = 1, cap = 1;
-  for (const auto &s : refs) {
-    ns = std::max(ns, s.size());
-    for (const auto &w : s) cap = std::max(cap, w.size());
-  }
-  const size_t np = cnt * ns;
-  std::vector<int32_t> words(np * cap, 0), len(np, -1), st(cnt), found(np), ne(np), nc(np), nsub(np), ni(np), ndel(np), na(np), nh(np), rh(np * cap);
+  const PackedSeqs in(refs);
+  const size_t cnt = in.cnt, ns = in.ns, cap = in.cap, np = in.np;
+  std::vector<int32_t> st(cnt), found(np), ne(np), nc(np), nsub(np), ni(np), ndel(np), na(np), nh(np), rh(np * cap);
   std::vector<int32_t> hyp, b, e;
   std::vector<float> t(np), l(np);
-  for (size_t i = 0; i < cnt; ++i)
-    for (size_t q = 0; q < refs[i].size(); ++q) {
-      len[i * ns + q] = (int32_t)refs[i][q].size();
-      std::copy(refs[i][q].begin(), refs[i][q].end(), words.begin() + (i * ns + q) * cap);
-    }
   size_t hcap = cap + 16;
   for (int pass = 0;; ++pass) {
     hyp.assign(np * hcap, 0); b.assign(np * hcap, 0); e.assign(np * hcap, 0);
-    const int rc = wfst_decoder_nearest_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, (int32_t)cap, words.data(), len.data(),
+    const int rc = wfst_decoder_nearest_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, (int32_t)cap, in.words.data(), in.len.data(),
                                               (int32_t)hcap, max_cells, st.data(), found.data(), ne.data(), nc.data(), nsub.data(), ni.data(),
                                               ndel.data(), na.data(), nh.data(), hyp.data(), b.data(), e.data(), rh.data(), t.data(), l.data());
     if (rc != WFST_OK) return rc;
@@ -1969,36 +1962,16 @@ static int NearestWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, c
 
 void GpuBatchDecoder::NearestWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &refs, bool use_final_probs,
                                    std::vector<std::vector<NearestPath> > *out, std::vector<int> *status, long long max_cells) {
-  std::vector<int32_t> ch(channels.begin(), channels.end());
-  if (ch.empty())
-    for (int c = 0; c < _n; ++c) ch.push_back(c);
-  std::vector<std::vector<NearestPath> > o;
-  std::vector<int> st;
-  if (NearestWordsCall(_dec, ch, refs, use_final_probs, max_cells, &o, &st) != WFST_OK) Fatal("NearestWords");
-  if (!status)
-    for (int s : st)
-      if (s != WFST_OK) Fatal("NearestWords");
-  if (out) out->swap(o);
-  if (status) *status = st;
+  BatchWordQuery("NearestWords", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return NearestWordsCall(_dec, ch, refs, use_final_probs, max_cells, o, st);
+  });
 }
 
 void GpuLatticeDecoder::NearestWords(const std::vector<std::vector<int> > &refs, std::vector<NearestPath> *out, bool use_final_probs) {
-  std::vector<std::vector<NearestPath> > o;
-  if (!refs.empty()) {
-    std::vector<int> st;
-    int rc = WFST_OK;
-    std::string msg;
-    // (the C-ABI calls of one decoder are not re-entrant: over a pool this runs in the batcher thread, like AlignWords)
-    OnDevice([&] {
-      rc = NearestWordsCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<std::vector<int> > >(1, refs), use_final_probs, 0, &o, &st);
-      if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
-    });
-    if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("NearestWords: " + msg);
-  }
-  if (out) {
-    out->clear();
-    if (!o.empty()) out->swap(o[0]);
-  }
+  StreamWordQuery("NearestWords", _chan, refs, out, [&](auto &&f) { OnDevice(f); },
+                  [&](const auto &ch, const SeqLists &r, auto *o, auto *st) {
+                    return NearestWordsCall(_dec, ch, r, use_final_probs, 0, o, st);
+                  });
 }
 
 // ---- pruned live lattices (wfst_decoder_set_live_lattice_prune) ------------------------------------------------------------------

@@ -771,16 +771,14 @@ class BatchDecoder:
                                        lm=np.float32(lm[i, k]), path_tot=np.float32(ptot[i, k])) for k in range(int(got[i]))])
                 for i in range(cnt)]
 
-    def align_words(self, seqs, channels=None, use_final_probs=True, max_cells=0):
-        """Lattice-constrained word alignment of a LIST of channels (None: all), live and finalized ones mixed
-        (wfst_decoder_align_words): seqs[i] = the word sequences to align on channels[i] (each a sequence of word ids > 0, possibly
-        empty; None: skipped).  Per channel a list with one dict per sequence: found, begin / end (int32 arrays, frames, end
-        exclusive), tot, lm (float32: the aligned path's LatticeToVector scores), n_arcs, and status -- WFST_OK or the CHANNEL's
-        own error code (then nothing of it is found)."""
+    def _pack_seqs(self, seqs, channels, what):
+        """The inputs of a word query (align_words, nearest_words, word_confidences): (ch, cnt, ns, cap, words, lens) -- the channel
+        list (None: all), its length, the most sequences of a channel and the most words of a sequence (at least 1), words[cnt][ns][cap]
+        padded with 0 and lens[cnt][ns] (-1: None, or no such sequence).  what: "sequences" / "references", for the error."""
         ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
         cnt = len(ch)
         if len(seqs) != cnt:
-            raise ValueError("one list of sequences per listed channel")
+            raise ValueError("one list of %s per listed channel" % what)
         ns = max([len(s) for s in seqs] + [1])
         cap = max([len(w) for s in seqs for w in s if w is not None] + [1])
         words = np.zeros((cnt, ns, cap), np.int32)
@@ -790,10 +788,23 @@ class BatchDecoder:
                 if w is not None:
                     lens[i, q] = len(w)
                     words[i, q, :len(w)] = np.asarray(w, np.int32)
-        status = np.zeros(cnt, np.int32)
-        found, na = np.zeros((cnt, ns), np.int32), np.zeros((cnt, ns), np.int32)
-        begin, end = np.zeros((cnt, ns, cap), np.int32), np.zeros((cnt, ns, cap), np.int32)
-        tot, lm = np.zeros((cnt, ns), np.float32), np.zeros((cnt, ns), np.float32)
+        return ch, cnt, ns, cap, words, lens
+
+    @staticmethod
+    def _word_results(cnt, ns, width):
+        """The result arrays the word queries share: status[cnt], found, n_arcs [cnt][ns], begin, end [cnt][ns][width], tot, lm."""
+        pair = lambda t: np.zeros((cnt, ns), t)
+        return (np.zeros(cnt, np.int32), pair(np.int32), pair(np.int32), np.zeros((cnt, ns, width), np.int32), np.zeros((cnt, ns, width), np.int32),
+                pair(np.float32), pair(np.float32))
+
+    def align_words(self, seqs, channels=None, use_final_probs=True, max_cells=0):
+        """Lattice-constrained word alignment of a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_align_words): seqs[i] = the word sequences to align on channels[i] (each a sequence of word ids > 0, possibly
+        empty; None: skipped).  Per channel a list with one dict per sequence: found, begin / end (int32 arrays, frames, end
+        exclusive), tot, lm (float32: the aligned path's LatticeToVector scores), n_arcs, and status -- WFST_OK or the CHANNEL's
+        own error code (then nothing of it is found)."""
+        ch, cnt, ns, cap, words, lens = self._pack_seqs(seqs, channels, "sequences")
+        status, found, na, begin, end, tot, lm = self._word_results(cnt, ns, cap)
         _check(lib().wfst_decoder_align_words(self.h, _i32(ch), cnt, int(bool(use_final_probs)), ns, cap, _i32(words), _i32(lens),
                                               C.c_int64(int(max_cells)), _i32(status), _i32(found), _i32(na), _i32(begin), _i32(end),
                                               _f32(tot), _f32(lm)))
@@ -809,27 +820,12 @@ class BatchDecoder:
         ref_hyp (per reference word the hypothesis word's index, -1: deleted), tot, lm (float32) and status -- WFST_OK or the
         CHANNEL's own error code.  cap_hyp = 0: room for every path -- the call is made again, with n_hyp's room, if a path
         has more words than the first guess (the longest reference + 16) holds; a cap_hyp of the caller's is taken as it is."""
-        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
-        cnt = len(ch)
-        if len(refs) != cnt:
-            raise ValueError("one list of references per listed channel")
-        ns = max([len(s) for s in refs] + [1])
-        cap = max([len(w) for s in refs for w in s if w is not None] + [1])
-        words = np.zeros((cnt, ns, cap), np.int32)
-        lens = np.full((cnt, ns), -1, np.int32)
-        for i, s in enumerate(refs):
-            for q, w in enumerate(s):
-                if w is not None:
-                    lens[i, q] = len(w)
-                    words[i, q, :len(w)] = np.asarray(w, np.int32)
+        ch, cnt, ns, cap, words, lens = self._pack_seqs(refs, channels, "references")
         hcap = int(cap_hyp) if cap_hyp else cap + 16
         while True:
-            status = np.zeros(cnt, np.int32)
-            z = lambda: np.zeros((cnt, ns), np.int32)
-            found, ne, nc, nsub, ni, ndel, na, nh = z(), z(), z(), z(), z(), z(), z(), z()
-            hyp, begin, end = (np.zeros((cnt, ns, hcap), np.int32) for _ in range(3))
-            rh = np.zeros((cnt, ns, cap), np.int32)
-            tot, lm = np.zeros((cnt, ns), np.float32), np.zeros((cnt, ns), np.float32)
+            status, found, na, begin, end, tot, lm = self._word_results(cnt, ns, hcap)
+            ne, nc, nsub, ni, ndel, nh = (np.zeros((cnt, ns), np.int32) for _ in range(6))
+            hyp, rh = np.zeros((cnt, ns, hcap), np.int32), np.zeros((cnt, ns, cap), np.int32)
             _check(lib().wfst_decoder_nearest_words(self.h, _i32(ch), cnt, int(bool(use_final_probs)), ns, cap, _i32(words), _i32(lens), hcap,
                                                     C.c_int64(int(max_cells)), _i32(status), _i32(found), _i32(ne), _i32(nc), _i32(nsub),
                                                     _i32(ni), _i32(ndel), _i32(na), _i32(nh), _i32(hyp), _i32(begin), _i32(end), _i32(rh),
@@ -857,23 +853,8 @@ class BatchDecoder:
         unclamped), conf = min(1, word_post), path_logpost (the log posterior of the aligned path) and log_z (the channel's).  The
         arcs cost graph_scale * graph + acoustic_scale * acoustic, in float64; the sums' order is the device's, so the floats are
         reproducible to rounding, not bit for bit."""
-        ch = np.arange(self.n, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32)
-        cnt = len(ch)
-        if len(seqs) != cnt:
-            raise ValueError("one list of sequences per listed channel")
-        ns = max([len(s) for s in seqs] + [1])
-        cap = max([len(w) for s in seqs for w in s if w is not None] + [1])
-        words = np.zeros((cnt, ns, cap), np.int32)
-        lens = np.full((cnt, ns), -1, np.int32)
-        for i, s in enumerate(seqs):
-            for q, w in enumerate(s):
-                if w is not None:
-                    lens[i, q] = len(w)
-                    words[i, q, :len(w)] = np.asarray(w, np.int32)
-        status = np.zeros(cnt, np.int32)
-        found, na = np.zeros((cnt, ns), np.int32), np.zeros((cnt, ns), np.int32)
-        begin, end = np.zeros((cnt, ns, cap), np.int32), np.zeros((cnt, ns, cap), np.int32)
-        tot, lm = np.zeros((cnt, ns), np.float32), np.zeros((cnt, ns), np.float32)
+        ch, cnt, ns, cap, words, lens = self._pack_seqs(seqs, channels, "sequences")
+        status, found, na, begin, end, tot, lm = self._word_results(cnt, ns, cap)
         log_z, wp, plp = np.zeros(cnt, np.float64), np.zeros((cnt, ns, cap), np.float64), np.zeros((cnt, ns), np.float64)
         f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         _check(lib().wfst_decoder_word_confidence(self.h, _i32(ch), cnt, int(bool(use_final_probs)), C.c_double(float(graph_scale)),
