@@ -25,7 +25,8 @@ struct AlignState {
   DevBuf<int32_t> idx, path, in, out;
   DevBuf<uint32_t> cells;
   PinBuf<int32_t> pin;
-  // wfst_decoder_word_confidence (wfst_capi_posterior.cc): the posterior workspace of a round's channels and its results' landing place
+  // wfst_decoder_word_confidence and wfst_decoder_sequence_posterior (wfst_capi_posterior.h: post_workspace): the posterior workspace of
+  // a round's channels and its results' landing place
   DevBuf<double> post;
   DevBuf<int2> post_idx;
   PinBuf<double> post_pin;
@@ -51,7 +52,8 @@ int align_channel_state(const wfst_decoder *d, int32_t channel);
 int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_final_probs, std::vector<int32_t> *sizes);
 
 // ---- the round driver of the word queries (wfst_capi_wordquery.cc) ----------------------------------------------------------
-// wfst_decoder_align_words, wfst_decoder_nearest_words and wfst_decoder_word_confidence ask the listed channels' raw lattices about
+// wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence and wfst_decoder_sequence_posterior ask the
+// listed channels' raw lattices about
 // n_seqs word sequences each: one table of states x (words + 1) cells per (channel, sequence) pair over the in-arc index
 // align_index_kernel builds.  word_query_run is the sequence they share; a WordQuery is what differs.
 
@@ -118,6 +120,7 @@ struct WordQuery {
   const char *item, *abbr;         // what a sequence is called: "sequence" / "seq" (n_seqs, seq_len)
   const char *caps = "cap_words";  // the capacities that must be positive, and the least of those beyond cap_words
   int32_t cap_extra = 1;
+  int32_t min_len = 0;             // the fewest words of a sequence that is asked for (a phrase has one at least)
   const char *arg_error = nullptr; // the entry point's check of arguments of its own, reported behind "NULL decoder / channel list"
   int64_t default_cells, round_cells;   // max_cells = 0; the cells of one round's tables
   int32_t cell_words = 1;          // 32-bit words of a cell (AlignState::cells counts words)

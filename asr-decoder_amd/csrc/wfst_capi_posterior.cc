@@ -30,33 +30,12 @@ struct ConfidenceQuery : WordQuery {
   }
   int launch(WordRound &R) override {
     const AlignView &V = *R.V;
-    AlignState &S = *V.as;
     const AlignDev A = R.align_dev();
-    const size_t cnt = R.cnt, nsc = (size_t)A.ns_cap, nac = (size_t)A.na_cap;
-    // the posterior workspace: alpha, beta [cnt][ns_cap], gamma [cnt][na_cap], then what comes back: log_z [cnt], the pairs' results;
-    // sarc [cnt][na_cap], then done and soff [cnt][ns_cap] as int2 halves
-    const size_t res_at = cnt * (2 * nsc + nac), res_n = cnt + R.pairs * dper, post_n = res_at + res_n;
-    const size_t pidx_n = cnt * nac + cnt * nsc;
-    if (S.post.n < post_n || S.post_idx.n < pidx_n) {
-      ALIGN_TRY(hipStreamSynchronize(V.stream));
-      if (align_grow(S.post, post_n) != hipSuccess || align_grow(S.post_idx, pidx_n) != hipSuccess) {
-        (void)hipGetLastError();
-        return word_query_no_memory(*this, R);
-      }
-    }
-    ALIGN_TRY(S.post_pin.reserve(res_n));
-    PostDev P = {};
-    P.alpha = S.post.p;
-    P.beta = P.alpha + cnt * nsc;
-    P.gamma = P.beta + cnt * nsc;
-    P.log_z = S.post.p + res_at;
-    P.out = P.log_z + cnt;
-    P.sarc = S.post_idx.p;
-    P.done = reinterpret_cast<int32_t *>(S.post_idx.p + cnt * nac);
-    P.soff = P.done + cnt * nsc;
-    P.chan_err = S.out.p + R.pairs * pair_ints;
-    P.graph_scale = graph_scale;
-    P.acoustic_scale = acoustic_scale;
+    const size_t cnt = R.cnt, res_n = cnt + R.pairs * dper;
+    // what comes back: log_z [cnt], the pairs' results
+    PostDev P;
+    const int rc = post_workspace(*this, R, R.pairs * dper, graph_scale, acoustic_scale, &P);
+    if (rc != WFST_OK) return rc;
     launch_align_index(*V.D, A, R.chan, (int)cnt, V.stream);
     ALIGN_TRY(hipGetLastError());
     launch_align(*V.D, A, R.chan, (int)cnt, V.stream);
@@ -66,7 +45,7 @@ struct ConfidenceQuery : WordQuery {
     launch_confidence(A, P, (int)cnt, V.stream);
     ALIGN_TRY(hipGetLastError());
     // log_z and the pairs' doubles land behind the packed results
-    R.more_dst = S.post_pin.p; R.more_src = P.log_z; R.more_bytes = res_n * 8;
+    R.more_dst = V.as->post_pin.p; R.more_src = P.log_z; R.more_bytes = res_n * 8;
     return WFST_OK;
   }
   int unpack(const WordRound &R, size_t j, size_t o, int32_t) override {

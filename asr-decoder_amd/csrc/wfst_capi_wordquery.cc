@@ -1,4 +1,5 @@
-// word_query_run: what wfst_decoder_align_words, wfst_decoder_nearest_words and wfst_decoder_word_confidence do alike -- see
+// word_query_run: what wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence and
+// wfst_decoder_sequence_posterior do alike -- see
 // wfst_capi_align.h.  It launches nothing: the entry points' own units do, in their launch() hooks.
 #include "wfst_capi_align.h"
 
@@ -25,6 +26,7 @@ int word_query_run(WordQuery &q, wfst_decoder *d, const int32_t *channels, int32
   const size_t ns = (size_t)n_seqs, cap = (size_t)cap_words;
   for (size_t p = 0; p < (size_t)n * ns; ++p) {
     if (seq_len[p] > cap_words) return capi_fail(WFST_E_ARG, "a " + abbr + "_len above cap_words");
+    if (seq_len[p] >= 0 && seq_len[p] < q.min_len) return capi_fail(WFST_E_ARG, "a " + abbr + "_len below " + std::to_string(q.min_len));
     for (int k = 0; k < seq_len[p]; ++k)
       if (seq_words[p * cap + (size_t)k] <= 0) return capi_fail(WFST_E_ARG, "a word id <= 0 inside a " + item);
   }

@@ -554,6 +554,28 @@ inline int64_t post_slot_bytes(int64_t ns_cap, int64_t na_cap) { return 24 * ns_
 void launch_posterior(const DecoderDev &D, const AlignDev &A, const PostDev &P, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 void launch_confidence(const AlignDev &A, const PostDev &P, int cnt, hipStream_t s);
 
+// ---- sentence and phrase posteriors (wfst_seqpost.hip) -----------------------------------------------------------------
+// The log-semiring twin of align_kernel's table: the weight of ALL paths that spell a word sequence (mode 0), or that say a phrase
+// somewhere (mode 1), over the in-arc index (AlignDev::idx) and posterior_kernel's alpha, beta and log_z (PostDev).  seqpost_kernel
+// runs one workgroup per (slot, sequence) pair.  Of the AlignDev it reads idx, seq_words, seq_len, cell_off, n_seqs, cap_words and
+//   cells[]              the pairs' tables of float64 cells, pair p at cell_off[p] (in cells; < 0: not run): S[state][len + 1] in
+//                        mode 0, P[state][len] in mode 1
+//   path[p][ns_cap]      the level of a state inside its frame (0, or 1 + the round that sums its row)
+//   out[p]               kSeqPostHead ints {found, state frames of the lattice (frames decoded + 1), 0, 0, error (kAln*), 0, 0, 0}
+// and of the PostDev alpha, beta, log_z, chan_err and the scales.
+//   out[p]               seq_logpost of pair p (0 where nothing is found)
+//   hit[p][cap_frames]   mode 1: hit_mass, written where the lattice's state frames fit cap_frames; nullptr: not asked for
+constexpr int32_t kSeqPostHead = 8;
+struct SeqPostDev {
+  const int4 *lat_toks;       // DecoderDev::lat_toks, lat_tok_cap entries per channel
+  int64_t lat_tok_cap;
+  int32_t mode;               // 0 sentence, 1 phrase
+  int32_t cap_frames;
+  double *out;
+  double *hit;
+};
+void launch_seqpost(const AlignDev &A, const PostDev &P, const SeqPostDev &Q, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

@@ -26,21 +26,13 @@
 
 #include "wfst_align_index.h"   // AlnIndex / aln_carve
 #include "wfst_device.h"
+#include "wfst_post_math.h"     // post_inf / post_finite / post_cost
 
 namespace wfst {
 namespace {
 
 constexpr int kPostThreads = 1024;
 constexpr int kConfWords = 4096;   // sequences up to this many words keep their cut points and sums in LDS
-
-__device__ __forceinline__ double post_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
-__device__ __forceinline__ bool post_finite(double x) { return x - x == 0.0; }
-// c(a), false where the arc is no arc
-__device__ __forceinline__ bool post_cost(const PostDev &P, const int4 &R, double *c) {
-  const float g = __int_as_float(R.z), a = __int_as_float(R.w), v = g + a;
-  *c = P.graph_scale * (double)g + P.acoustic_scale * (double)a;
-  return v - v == 0.0f;
-}
 
 // alpha of state t from the finished values of its sources
 __device__ double post_forward(const PostDev &P, const AlnIndex &X, const double *alpha, int t) {

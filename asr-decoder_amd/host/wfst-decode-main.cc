@@ -50,6 +50,14 @@
 //                  every "...#j word begin end" line gains a fourth column conf (min(1, the posterior mass of the arcs that say the
 //                  word at about that time)), and every path line ("KEY-k ...", "KEY@frames nbest k: ...", "KEY align q ...") of a
 //                  path that was found gains " logpost=.." (the log posterior of the aligned path itself)
+//   --sentence-posterior  with --nbest-word-times and/or --align-words=FILE: every path line of a path that was found gains
+//                  " sentpost=..", the log posterior of the path's WORD SEQUENCE over all paths of the RAW lattice that spell it
+//                  (SequencePosteriors: wfst_decoder_sequence_posterior), where logpost is one path's; the scales are
+//                  --word-confidence=GS,AS's when given, else 1,1
+//   --phrase-posterior=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being phrases of at least one
+//                  word; after the utterance's lines, per phrase "KEY phrase q found=0|1 count=.. conf=.. peak=FRAME": the expected
+//                  number of times a path of the RAW lattice says the phrase, min(1, count), and the lowest frame with the most of
+//                  that mass (the begin frame of the phrase's last word; -1: not found); scales as --sentence-posterior
 //   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
 //                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
 //                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
@@ -137,6 +145,12 @@ struct Utt {
   int frames, cols;
   std::vector<float> m;
 };
+// an aligned sequence as the lines take it: the alignment, under --word-confidence the confidences, under --sentence-posterior the
+// posterior of the whole word sequence
+struct TimedSeq : WordConfidence {
+  bool sent_found = false;
+  double sentpost = 0.0;
+};
 bool ReadUtt(std::ifstream &in, Utt *u) {
   int32_t kl;
   if (!in.read((char *)&kl, 4)) return false;
@@ -217,8 +231,8 @@ int main(int argc, char **argv) {
     long long lattice_links = 1ll << 22;
     int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
     bool pull = false, partial_words = false, word_times = false, live_prune = false, nbest_times = false;
-    std::string align_file, nearest_file;
-    bool word_conf = false;
+    std::string align_file, nearest_file, phrase_file;
+    bool word_conf = false, sent_post = false;
     double conf_gs = 1.0, conf_as = 1.0;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
@@ -278,6 +292,8 @@ int main(int argc, char **argv) {
         word_conf = true;
       }
       else if (a.compare(0, 16, "--nearest-words=") == 0) nearest_file = a.substr(16);
+      else if (a == "--sentence-posterior") sent_post = true;
+      else if (a.compare(0, 19, "--phrase-posterior=") == 0) phrase_file = a.substr(19);
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
           const size_t p1 = std::min(a.find(':', p0), a.size());
@@ -309,7 +325,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -326,11 +342,14 @@ int main(int argc, char **argv) {
     if (!align_file.empty() && n_threads > 0) { std::cerr << "--align-words goes with the batch shape or --single-stream\n"; return 1; }
     if (word_conf && !nbest_times && align_file.empty()) { std::cerr << "--word-confidence goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
     if (!nearest_file.empty() && n_threads > 0) { std::cerr << "--nearest-words goes with the batch shape or --single-stream\n"; return 1; }
-    // --align-words / --nearest-words: the sequences to align and the references, by utterance key
-    std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs;
-    for (int which = 0; which < 2; ++which) {
-      const std::string &file = which ? nearest_file : align_file, flag = which ? "--nearest-words" : "--align-words";
-      std::map<std::string, std::vector<std::vector<int> > > &into = which ? nearest_refs : align_seqs;
+    if (sent_post && !nbest_times && align_file.empty()) { std::cerr << "--sentence-posterior goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
+    if (!phrase_file.empty() && n_threads > 0) { std::cerr << "--phrase-posterior goes with the batch shape or --single-stream\n"; return 1; }
+    // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
+    std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
+    for (int which = 0; which < 3; ++which) {
+      const std::string &file = which == 2 ? phrase_file : which ? nearest_file : align_file;
+      const std::string flag = which == 2 ? "--phrase-posterior" : which ? "--nearest-words" : "--align-words";
+      std::map<std::string, std::vector<std::vector<int> > > &into = which == 2 ? phrases : which ? nearest_refs : align_seqs;
       if (file.empty()) continue;
       std::ifstream af(file.c_str());
       if (!af) { std::cerr << "cannot read " << file << "\n"; return 1; }
@@ -341,6 +360,7 @@ int main(int argc, char **argv) {
         if (!(ls >> key)) continue;
         std::vector<int> w;
         for (int x; ls >> x;) w.push_back(x);
+        if (which == 2 && w.empty()) { std::cerr << flag << ": a phrase has at least one word (" << key << ")\n"; return 1; }
         into[key].push_back(w);
         if (into[key].size() > 64) { std::cerr << flag << ": more than 64 sequences for " << key << "\n"; return 1; }
       }
@@ -404,10 +424,10 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty();
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty();
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
     // (--word-confidence: a fourth column conf)
-    auto time_lines = [&](const std::string &head, const std::vector<int> &words, const WordConfidence &a) {
+    auto time_lines = [&](const std::string &head, const std::vector<int> &words, const TimedSeq &a) {
       std::string o;
       if (!a.found) return head + " notfound\n";
       for (size_t j = 0; j < words.size(); ++j) {
@@ -422,33 +442,61 @@ int main(int argc, char **argv) {
       return o;
     };
     // " logpost=.." of a path line under --word-confidence
-    auto logpost_of = [&](const WordConfidence &a) {
-      if (!word_conf || !a.found) return std::string();
+    // (--sentence-posterior: and " sentpost=..", the log posterior of the path's word sequence over all paths that spell it)
+    auto logpost_of = [&](const TimedSeq &a) {
+      std::string o;
       char buf[40];
-      snprintf(buf, sizeof(buf), " logpost=%.9g", a.path_logpost);
-      return std::string(buf);
-    };
-    // AlignWords' answers as the lines take them (no confidences)
-    auto lift = [](const std::vector<WordAlignment> &a) {
-      std::vector<WordConfidence> o(a.size());
-      for (size_t i = 0; i < a.size(); ++i) static_cast<WordAlignment &>(o[i]) = a[i];
+      if (word_conf && a.found) {
+        snprintf(buf, sizeof(buf), " logpost=%.9g", a.path_logpost);
+        o += buf;
+      }
+      if (sent_post && a.found && a.sent_found) {
+        snprintf(buf, sizeof(buf), " sentpost=%.9g", a.sentpost);
+        o += buf;
+      }
       return o;
     };
-    // the word times of one stream's sequences (GetNbestWordTimes), under --word-confidence with the confidences (WordConfidences)
-    auto stream_times = [&](GpuLatticeDecoder &decode, const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *o, bool use_final_probs) {
-      if (word_conf) { decode.WordConfidences(seqs, o, use_final_probs, conf_gs, conf_as); return; }
+    // AlignWords' / WordConfidences' answers as the lines take them, with the sentence posteriors where there are any
+    auto lift = [](const auto &a, const std::vector<SequencePosterior> &sp) {
+      std::vector<TimedSeq> o(a.size());
+      for (size_t i = 0; i < a.size(); ++i) {
+        static_cast<typename std::decay<decltype(a[i])>::type &>(o[i]) = a[i];
+        if (i < sp.size()) { o[i].sent_found = sp[i].found; o[i].sentpost = sp[i].logpost; }
+      }
+      return o;
+    };
+    // the word times of one stream's sequences (GetNbestWordTimes), under --word-confidence with the confidences (WordConfidences),
+    // under --sentence-posterior with the sequences' posteriors (SequencePosteriors)
+    auto stream_times = [&](GpuLatticeDecoder &decode, const std::vector<std::vector<int> > &seqs, std::vector<TimedSeq> *o, bool use_final_probs) {
+      std::vector<SequencePosterior> sp;
+      if (sent_post) decode.SequencePosteriors(seqs, &sp, false, use_final_probs, conf_gs, conf_as);
+      if (word_conf) {
+        std::vector<WordConfidence> a;
+        decode.WordConfidences(seqs, &a, use_final_probs, conf_gs, conf_as);
+        *o = lift(a, sp);
+        return;
+      }
       std::vector<WordAlignment> a;
       decode.GetNbestWordTimes(seqs, &a, use_final_probs);
-      *o = lift(a);
+      *o = lift(a, sp);
     };
-    // ... and of a batch's channels (AlignWords / WordConfidences)
+    // ... and of a batch's channels (AlignWords / WordConfidences / SequencePosteriors)
     auto batch_times = [&](GpuBatchDecoder &decode, const std::vector<int> &ch, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
-                           std::vector<std::vector<WordConfidence> > *o, std::vector<int> *status) {
-      if (word_conf) { decode.WordConfidences(ch, seqs, use_final_probs, conf_gs, conf_as, o, status); return; }
+                           std::vector<std::vector<TimedSeq> > *o, std::vector<int> *status) {
+      std::vector<std::vector<SequencePosterior> > sp;
+      std::vector<int> sp_status;   // (a channel's own failure shows in the alignment's status; here its posteriors are left out)
+      if (sent_post) decode.SequencePosteriors(ch, seqs, false, use_final_probs, conf_gs, conf_as, &sp, &sp_status);
+      const std::vector<SequencePosterior> none;
+      o->clear();
+      if (word_conf) {
+        std::vector<std::vector<WordConfidence> > a;
+        decode.WordConfidences(ch, seqs, use_final_probs, conf_gs, conf_as, &a, status);
+        for (size_t i = 0; i < a.size(); ++i) o->push_back(lift(a[i], i < sp.size() ? sp[i] : none));
+        return;
+      }
       std::vector<std::vector<WordAlignment> > a;
       decode.AlignWords(ch, seqs, use_final_probs, &a, status);
-      o->clear();
-      for (const auto &x : a) o->push_back(lift(x));
+      for (size_t i = 0; i < a.size(); ++i) o->push_back(lift(a[i], i < sp.size() ? sp[i] : none));
     };
     // the words of every path of an n-best list (none where LatticeToVector fails: emit_nbest skips such a path)
     auto path_words = [](std::vector<Lattice> &paths) {
@@ -461,7 +509,7 @@ int main(int argc, char **argv) {
       return w;
     };
     // --align-words: the lines of one utterance
-    auto emit_align = [&](const Utt &u, const std::vector<WordConfidence> &al) {
+    auto emit_align = [&](const Utt &u, const std::vector<TimedSeq> &al) {
       auto it = align_seqs.find(u.key);
       if (it == align_seqs.end()) return;
       for (size_t q = 0; q < it->second.size() && q < al.size(); ++q) {
@@ -470,6 +518,16 @@ int main(int argc, char **argv) {
         const std::string head = u.key + " align " + std::to_string(q + 1);
         out << head << buf << logpost_of(al[q]) << "\n";
         if (al[q].found) out << time_lines(head, it->second[q], al[q]);
+      }
+    };
+    // --phrase-posterior: the lines of one utterance
+    auto emit_phrases = [&](const Utt &u, const std::vector<SequencePosterior> &sp) {
+      auto it = phrases.find(u.key);
+      if (it == phrases.end()) return;
+      for (size_t q = 0; q < it->second.size() && q < sp.size(); ++q) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), " found=%d count=%.9g conf=%.9g peak=%d\n", sp[q].found ? 1 : 0, sp[q].count, sp[q].conf, sp[q].peak);
+        out << u.key << " phrase " << (q + 1) << buf;
       }
     };
     // --nearest-words: the lines of one utterance, and the sums of the closing line
@@ -490,7 +548,7 @@ int main(int argc, char **argv) {
         nr_err += a.errors; nr_words += (long long)it->second[q].size(); nr_ins += a.ins; nr_del += a.del; nr_sub += a.sub;
       }
     };
-    auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<WordConfidence> *times = nullptr) {
+    auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<TimedSeq> *times = nullptr) {
       for (size_t k = 0; k < paths.size(); ++k) {
         std::vector<int> words, phones;
         float tot = 0, lm = 0;
@@ -537,7 +595,7 @@ int main(int argc, char **argv) {
     limits.lattice_links = want_lattice ? lattice_links : 0;
     // --partial-nbest: "key@frames nbest k: w1 w2 ... tot=.. lm=.." per path, or "key@frames nbest status=code" for a channel's own failure
     auto nbest_lines = [&](const std::string &key, int frames, int status, const std::vector<std::vector<int> > &w, const std::vector<float> &t,
-                           const std::vector<float> &l, const std::vector<WordConfidence> *times = nullptr) {
+                           const std::vector<float> &l, const std::vector<TimedSeq> *times = nullptr) {
       std::string o;
       const std::string head = key + "@" + std::to_string(frames) + " nbest ";
       if (status != WFST_OK) o += head + "status=" + std::to_string(status) + "\n";
@@ -852,7 +910,7 @@ int main(int argc, char **argv) {
               std::vector<float> pt, pl;
               int st = WFST_OK;
               decode.GetNbestWords(&pw, &pt, &pl, partial_nbest, false, slm1p, slm2p, &st);
-              std::vector<WordConfidence> al;
+              std::vector<TimedSeq> al;
               if (nbest_times && !pw.empty()) stream_times(decode, pw, &al, false);
               out << nbest_lines(u.key, decode.NumFramesDecoded(), st, pw, pt, pl, nbest_times ? &al : nullptr);
             }
@@ -880,14 +938,19 @@ int main(int argc, char **argv) {
           if (!exact_nbest) decode.GetNbestShortlist(paths, nbest);
           else if (second) decode.GetNbest(paths, nbest, slm1p, slm2p);
           else decode.GetNbest(paths, nbest);
-          std::vector<WordConfidence> al;
+          std::vector<TimedSeq> al;
           if (nbest_times && !paths.empty()) stream_times(decode, path_words(paths), &al, true);
           emit_nbest(u, paths, nbest_times ? &al : nullptr);
         }
         if (align_seqs.count(u.key)) {
-          std::vector<WordConfidence> al;
+          std::vector<TimedSeq> al;
           stream_times(decode, align_seqs[u.key], &al, true);
           emit_align(u, al);
+        }
+        if (phrases.count(u.key)) {
+          std::vector<SequencePosterior> sp;
+          decode.SequencePosteriors(phrases[u.key], &sp, true, true, conf_gs, conf_as, true);
+          emit_phrases(u, sp);
         }
         if (nearest_refs.count(u.key)) {
           std::vector<NearestPath> np;
@@ -903,7 +966,8 @@ int main(int argc, char **argv) {
         std::vector<std::vector<int> > wt_words;                      // --word-times
         std::vector<std::vector<std::pair<int, int> > > wt_frames;
         std::string partials;                                         // --partial-nbest
-        std::vector<std::vector<WordConfidence> > nb_times, al_times;  // --nbest-word-times, --align-words
+        std::vector<std::vector<TimedSeq> > nb_times, al_times;  // --nbest-word-times, --align-words
+        std::vector<std::vector<SequencePosterior> > phrase_post;     // --phrase-posterior
         std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
@@ -987,7 +1051,7 @@ int main(int argc, char **argv) {
                 std::vector<std::vector<float> > t, l;
                 std::vector<int> st;
                 decode.GetNbestWords(live, partial_nbest, slm1, slm2, false, &w, &t, &l, &st);
-                std::vector<std::vector<WordConfidence> > al;
+                std::vector<std::vector<TimedSeq> > al;
                 std::vector<int> ast;
                 if (nbest_times && !live.empty()) batch_times(decode, live, w, false, &al, &ast);   // (one call for the channels still running)
                 for (size_t q = 0; q < live.size(); ++q)
@@ -1030,6 +1094,14 @@ int main(int argc, char **argv) {
               }
               batch_times(decode, ch, seqs, true, &o.al_times, nullptr);
             }
+            if (!phrases.empty()) {   // every phrase of every channel in one call
+              std::vector<std::vector<std::vector<int> > > seqs(n);
+              for (int i = 0; i < n; ++i) {
+                auto it = phrases.find(utts[b0 + i].key);
+                if (it != phrases.end()) seqs[i] = it->second;
+              }
+              decode.SequencePosteriors(ch, seqs, true, true, conf_gs, conf_as, &o.phrase_post, nullptr, 0, true);
+            }
             if (!nearest_refs.empty()) {   // every reference of every channel in one call
               std::vector<std::vector<std::vector<int> > > refs(n);
               for (int i = 0; i < n; ++i) {
@@ -1067,6 +1139,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && want_lattice; ++i) emit_lattice(utts[b0 + i], o.lats[i], o.lat_ok[i]);
         for (int i = 0; i < n && nbest > 0; ++i) emit_nbest(utts[b0 + i], o.nbest[i], nbest_times ? &o.nb_times[i] : nullptr);
         for (int i = 0; i < n && !o.al_times.empty(); ++i) emit_align(utts[b0 + i], o.al_times[i]);
+        for (int i = 0; i < n && !o.phrase_post.empty(); ++i) emit_phrases(utts[b0 + i], o.phrase_post[i]);
         for (int i = 0; i < n && !o.nearest.empty(); ++i) emit_nearest(utts[b0 + i], o.nearest[i]);
       }
     }

@@ -4,6 +4,7 @@
 #include <atomic>
 #include <thread>
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +25,7 @@
 // ... and the lattice edit distance's: NearestWords reports itself missing there
 #pragma weak wfst_decoder_nearest_words
 #pragma weak wfst_decoder_word_confidence
+#pragma weak wfst_decoder_sequence_posterior
 
 namespace datemoon {
 
@@ -1914,6 +1916,66 @@ void GpuLatticeDecoder::WordConfidences(const std::vector<std::vector<int> > &se
   StreamWordQuery("WordConfidences", _chan, seqs, out, [&](auto &&f) { OnDevice(f); },
                   [&](const auto &ch, const SeqLists &s, auto *o, auto *st) {
                     return WordConfidencesCall(_dec, ch, s, use_final_probs, graph_scale, acoustic_scale, 0, o, st);
+                  });
+}
+
+// ---- sentence and phrase posteriors (wfst_decoder_sequence_posterior) -------------------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i][q] for seqs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.  A lattice
+// with more frames than the first call's rows hold is asked for again with n_frames' room.
+static int SequencePosteriorsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const SeqLists &seqs, bool phrase, bool use_final_probs,
+                                  double graph_scale, double acoustic_scale, long long max_cells, bool hit_mass,
+                                  std::vector<std::vector<SequencePosterior> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_sequence_posterior)
+    throw std::runtime_error("SequencePosteriors: this build's device library has no wfst_decoder_sequence_posterior");
+  if (seqs.size() != ch.size()) throw std::runtime_error("SequencePosteriors: one list of sequences per listed channel");
+  const PackedSeqs in(seqs);
+  const size_t cnt = in.cnt, ns = in.ns, np = in.np;
+  const bool rows = phrase && hit_mass;
+  std::vector<int32_t> st(cnt), nf(cnt), found(np);
+  std::vector<double> lz(cnt), lp(np), hit;
+  size_t capf = rows ? 256 : 0;
+  for (int pass = 0;; ++pass) {
+    hit.assign(np * capf, 0.0);
+    const int rc = wfst_decoder_sequence_posterior(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, graph_scale, acoustic_scale, phrase ? 1 : 0,
+                                                   (int32_t)ns, (int32_t)in.cap, in.words.data(), in.len.data(), max_cells, (int32_t)capf, st.data(),
+                                                   lz.data(), nf.data(), found.data(), lp.data(), rows ? hit.data() : nullptr);
+    if (rc != WFST_OK) return rc;
+    const size_t most = (size_t)*std::max_element(nf.begin(), nf.end());
+    if (!rows || most <= capf || pass) break;
+    capf = most;
+  }
+  out->assign(cnt, std::vector<SequencePosterior>());
+  for (size_t i = 0; i < cnt; ++i) {
+    (*out)[i].resize(seqs[i].size());
+    for (size_t q = 0; q < seqs[i].size(); ++q) {
+      SequencePosterior &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.log_z = lz[i];
+      if (rows && (size_t)nf[i] <= capf) a.hit_mass.assign(hit.begin() + p * capf, hit.begin() + p * capf + nf[i]);
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.logpost = lp[p]; a.count = std::exp(lp[p]); a.conf = std::min(1.0, a.count);
+      if (!a.hit_mass.empty()) a.peak = (int)(std::max_element(a.hit_mass.begin(), a.hit_mass.end()) - a.hit_mass.begin());
+    }
+  }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::SequencePosteriors(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool phrase,
+                                         bool use_final_probs, double graph_scale, double acoustic_scale,
+                                         std::vector<std::vector<SequencePosterior> > *out, std::vector<int> *status, long long max_cells,
+                                         bool hit_mass) {
+  BatchWordQuery("SequencePosteriors", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return SequencePosteriorsCall(_dec, ch, seqs, phrase, use_final_probs, graph_scale, acoustic_scale, max_cells, hit_mass, o, st);
+  });
+}
+
+void GpuLatticeDecoder::SequencePosteriors(const std::vector<std::vector<int> > &seqs, std::vector<SequencePosterior> *out, bool phrase,
+                                           bool use_final_probs, double graph_scale, double acoustic_scale, bool hit_mass) {
+  StreamWordQuery("SequencePosteriors", _chan, seqs, out, [&](auto &&f) { OnDevice(f); },
+                  [&](const auto &ch, const SeqLists &s, auto *o, auto *st) {
+                    return SequencePosteriorsCall(_dec, ch, s, phrase, use_final_probs, graph_scale, acoustic_scale, 0, hit_mass, o, st);
                   });
 }
 

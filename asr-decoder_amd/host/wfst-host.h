@@ -422,6 +422,20 @@ struct WordConfidence : WordAlignment {
   double path_logpost = 0.0, log_z = 0.0;
 };
 
+// The posterior of a whole word sequence, or of a phrase, on a channel's raw lattice (wfst_decoder_sequence_posterior).  A sentence:
+// logpost = the log of the share of the lattice's weight on ALL paths that spell the sequence, count = exp(logpost).  A phrase: count
+// = the expected number of times a path says it (overlapping occurrences included: it may pass 1), logpost = log(count), and -- where
+// asked for -- hit_mass[f] = the count by the frame f at which the phrase's last word begins, peak = the lowest frame of its largest
+// entry (-1: no rows, or nothing found).  conf = min(1, count); log_z = the log of the lattice's total weight.  found = false
+// (logpost, count and conf zero): no path spells the sequence / says the phrase, or the channel has no lattice.  Arcs cost
+// graph_scale * graph + acoustic_scale * acoustic, in double.  The doubles are reproducible to rounding, not bit for bit.
+struct SequencePosterior {
+  bool found = false;
+  double logpost = 0.0, count = 0.0, conf = 0.0, log_z = 0.0;
+  std::vector<double> hit_mass;
+  int peak = -1;
+};
+
 // The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
 // cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
 // them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
@@ -527,6 +541,12 @@ class GpuLatticeDecoder : public DecoderItf {
   // The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void WordConfidences(const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *out, bool use_final_probs = true,
                        double graph_scale = 1.0, double acoustic_scale = 1.0);
+  // How sure the decoder is of each of `seqs` (at most 64) as a WHOLE -- the sum over every path of the RAW lattice that spells it,
+  // where WordConfidence::path_logpost is one path's -- or, with phrase = true, how often and when a path says each of them as a
+  // phrase (at least one word each; hit_mass: with the per-frame rows), in one device call (wfst_decoder_sequence_posterior):
+  // (*out)[k] for seqs[k].  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void SequencePosteriors(const std::vector<std::vector<int> > &seqs, std::vector<SequencePosterior> *out, bool phrase = false,
+                          bool use_final_probs = true, double graph_scale = 1.0, double acoustic_scale = 1.0, bool hit_mass = false);
   // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
   // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
@@ -641,6 +661,11 @@ class GpuBatchDecoder {
   void WordConfidences(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
                        double graph_scale, double acoustic_scale, std::vector<std::vector<WordConfidence> > *out,
                        std::vector<int> *status = nullptr, long long max_cells = 0);
+  // SequencePosteriors (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage;
+  // the arguments and the status rule are AlignWords'.  The hit_mass rows are given the room the lattices need.
+  void SequencePosteriors(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool phrase,
+                          bool use_final_probs, double graph_scale, double acoustic_scale, std::vector<std::vector<SequencePosterior> > *out,
+                          std::vector<int> *status = nullptr, long long max_cells = 0, bool hit_mass = false);
   // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
   // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.

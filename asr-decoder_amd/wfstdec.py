@@ -47,6 +47,7 @@ SYMBOLS = [
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
     "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
+    "wfst_decoder_sequence_posterior",
 ]
 
 
@@ -873,6 +874,63 @@ class BatchDecoder:
             out.append(row)
         return out
 
+    def _sequence_posterior(self, mode, seqs, channels, use_final_probs, graph_scale, acoustic_scale, max_cells, cap_frames):
+        """wfst_decoder_sequence_posterior: (lens, status[cnt], log_z[cnt], n_frames[cnt], found, logpost [cnt][ns],
+        hit_mass [cnt][ns][cap_frames] or None)"""
+        ch, cnt, ns, cap, words, lens = self._pack_seqs(seqs, channels, "sequences")
+        status, nf = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32)
+        log_z, found, lp = np.zeros(cnt, np.float64), np.zeros((cnt, ns), np.int32), np.zeros((cnt, ns), np.float64)
+        hit = np.zeros((cnt, ns, int(cap_frames)), np.float64) if cap_frames else None
+        f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+        _check(lib().wfst_decoder_sequence_posterior(self.h, _i32(ch), cnt, int(bool(use_final_probs)), C.c_double(float(graph_scale)),
+                                                     C.c_double(float(acoustic_scale)), int(mode), ns, cap, _i32(words), _i32(lens),
+                                                     C.c_int64(int(max_cells)), int(cap_frames), _i32(status), f64(log_z), _i32(nf),
+                                                     _i32(found), f64(lp), f64(hit)))
+        return lens, status, log_z, nf, found, lp, hit
+
+    def sentence_posteriors(self, seqs, channels=None, use_final_probs=True, graph_scale=1.0, acoustic_scale=1.0, max_cells=0):
+        """Sentence posteriors on the raw lattice, for a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_sequence_posterior, mode 0): seqs[i] = the word sequences on channels[i], as align_words takes them.  Per
+        channel a list with one dict per sequence: found, logpost (the log of the share of the lattice's weight on ALL paths that
+        spell the sequence; 0.0 where none does), log_z (the channel's) and status.  Reproducible to rounding, not bit for bit."""
+        _, status, log_z, _, found, lp, _ = self._sequence_posterior(0, seqs, channels, use_final_probs, graph_scale, acoustic_scale,
+                                                                      max_cells, 0)
+        return [[dict(found=bool(found[i, q]), logpost=float(lp[i, q]), log_z=float(log_z[i]), status=int(status[i]))
+                 for q in range(len(seqs[i]))] for i in range(len(seqs))]
+
+    def phrase_posteriors(self, phrases, channels=None, use_final_probs=True, graph_scale=1.0, acoustic_scale=1.0, max_cells=0,
+                          hit_mass=False, cap_frames=0):
+        """Phrase posteriors on the raw lattice (wfst_decoder_sequence_posterior, mode 1): phrases[i] = the phrases (each at least
+        one word id > 0; None: skipped) looked for on channels[i].  Per channel a list with one dict per phrase: found, count (the
+        expected number of times a path says the phrase, overlapping occurrences included: it may pass 1), log_count (what the
+        call returns: count = exp(log_count)), conf = min(1, count), log_z, n_frames (the channel's) and status; with
+        hit_mass=True also hit_mass, a float64 array of n_frames entries: the count by the frame at which the phrase's last word
+        begins.  cap_frames = 0: room for every lattice -- the rows are sized by the listed channels' decoded frames, and the call
+        is made again with n_frames' room if a lattice has more; a cap_frames of the caller's is taken as it is, and a channel whose
+        lattice outgrows it carries WFST_E_CAPACITY in status and hit_mass None."""
+        capf = 0
+        if hit_mass:
+            ch = range(self.n) if channels is None else channels
+            capf = int(cap_frames) if cap_frames else 1 + max([self.num_frames_decoded(c) for c in ch] + [0])
+        while True:
+            lens, status, log_z, nf, found, lp, hit = self._sequence_posterior(1, phrases, channels, use_final_probs, graph_scale,
+                                                                               acoustic_scale, max_cells, capf)
+            if not hit_mass or cap_frames or int(nf.max(initial=0)) <= capf:
+                break
+            capf = int(nf.max())   # (a lattice with more frames than the guess: once more, with room for it)
+        out = []
+        for i in range(len(phrases)):
+            row = []
+            for q in range(len(phrases[i])):
+                count = float(np.exp(lp[i, q])) if found[i, q] else 0.0
+                d = dict(found=bool(found[i, q]), count=count, log_count=float(lp[i, q]), conf=min(1.0, count), log_z=float(log_z[i]),
+                         n_frames=int(nf[i]), status=int(status[i]))
+                if hit_mass:
+                    d["hit_mass"] = hit[i, q, :int(nf[i])].copy() if int(nf[i]) <= capf else None
+                row.append(d)
+            out.append(row)
+        return out
+
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):
         """nbest_words(...) with word times: every path's words aligned on its channel's raw lattice (align_words); the dicts of
         nbest_words gain found, begin, end, n_arcs and align_tot / align_lm (the aligned path's own scores: the determinizer
@@ -888,10 +946,11 @@ class BatchDecoder:
         return res
 
     def nbest_words_conf(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0,
-                         graph_scale=1.0, acoustic_scale=1.0):
+                         graph_scale=1.0, acoustic_scale=1.0, sentence_post=False):
         """nbest_words_timed(...) with confidences: every path's words aligned on its channel's raw lattice and weighed against the
         lattice's posteriors (word_confidences); beside nbest_words_timed's keys the dicts carry conf, word_post, path_logpost and
-        log_z."""
+        log_z.  sentence_post=True: also sent_logpost, the log posterior of the path's word sequence over ALL lattice paths that
+        spell it (sentence_posteriors, at the same scales; 0.0 where found is False)."""
         res = self.nbest_words(n_paths, channels, old_lm, new_lm, use_final_probs, cap_words)
         ch = list(range(self.n)) if channels is None else [int(c) for c in channels]
         seqs = [[p["words"] if p["n_words"] <= int(cap_words) else None for p in paths] for _, paths in res]
@@ -901,6 +960,11 @@ class BatchDecoder:
                 p.update(found=x["found"], begin=x["begin"], end=x["end"], n_arcs=x["n_arcs"], align_tot=x["tot"], align_lm=x["lm"],
                          align_status=x["status"], conf=x["conf"], word_post=x["word_post"], path_logpost=x["path_logpost"],
                          log_z=x["log_z"])
+        if sentence_post:
+            sp = self.sentence_posteriors(seqs, ch, use_final_probs, graph_scale, acoustic_scale, max_cells)
+            for (_, paths), a in zip(res, sp):
+                for p, x in zip(paths, a):
+                    p.update(sent_logpost=x["logpost"], sent_found=x["found"])
         return res
 
     def raw_lattices(self, channels=None, use_final_probs=True, threads=0):

@@ -685,7 +685,8 @@ int wfst_decoder_nearest_words(wfst_decoder *d, const int32_t *channels, int32_t
  * is found where the alignment finds it and has no words.
  * Limitation: a word's arc sits where the graph put its olabel, so the cells follow label positions, not acoustic word boundaries.
  * Not computed here: a hypothesis' full sentence posterior (a log-semiring table of states x (L + 1)), per-frame transition-id
- * posteriors (lattice-to-post), minimum Bayes risk / confusion networks.
+ * posteriors (lattice-to-post), minimum Bayes risk / confusion networks.  (The sentence posterior is wfst_decoder_sequence_posterior's,
+ * below.)
  *
  * A failure of ONE channel goes into status[i] with all of that channel's outputs zero, and the call still returns WFST_OK: a
  * sequence whose alignment table of states x (seq_len + 1) cells is beyond max_cells (WFST_E_CAPACITY; 0 = wfst_decoder_align_words'
@@ -706,6 +707,69 @@ int wfst_decoder_word_confidence(wfst_decoder *d, const int32_t *channels, int32
                                  int32_t *begin_frame, int32_t *end_frame /* [n][n_seqs][cap_words] */,
                                  double *word_post /* [n][n_seqs][cap_words] */, double *path_logpost /* [n][n_seqs] */,
                                  float *tot_score, float *lm_score /* [n][n_seqs] */);
+
+/* ---- sentence and phrase posteriors ----------------------------------------------------------------------------------------------
+ * How sure the decoder is of a WHOLE hypothesis, and whether a phrase is in the lattice at all, and when.  The raw lattice is not
+ * determinized: a word sequence is spelled by many paths, and path_logpost above is the posterior of one of them.  This call sums
+ * over all of them -- the log-semiring twin of wfst_decoder_align_words' table -- for a list of channels, live and finalized ones
+ * mixed, n_seqs sequences per channel and one mode per call, one launch per stage (the live channels' lattices emitted,
+ * align_index_kernel, posterior_kernel, seqpost_kernel).
+ *
+ * The lattice R, the scales, the arc cost c(a) = graph_scale * (double)graph + acoustic_scale * (double)acoustic in float64, the rule
+ * that an arc whose float32 graph + acoustic is not finite is no arc, alpha, beta, log_z and the way every sum is taken (m - log(sum
+ * exp(-(x - m))) with m the least term; a cell without a finite term is +inf, never NaN) are exactly wfst_decoder_word_confidence's.
+ * A final state may have out-arcs; a complete path is a path from state 0 that ends in a final state.  The kinds go by OLABEL, not by
+ * ilabel: a word may sit on an epsilon arc.  The input is a sequence w[0..L) of word ids > 0.
+ *
+ * mode 0, sentence (L >= 0): a table S[s][k], 0 <= k <= L, with S[0][0] = 0 and every other cell
+ *   S[t][k] = -log( sum over the arcs a: s -> t with olabel 0                   of exp(-(S[s][k]     + c(a)))
+ *                 + sum over the arcs a: s -> t with olabel == w[k - 1], k >= 1, of exp(-(S[s][k - 1] + c(a))) )
+ * and there is no other transition.  seq_cost = -log sum over the final states s of exp(-S[s][L]), and
+ *   seq_logpost = -log_z - seq_cost
+ * is the log of the share of the lattice's total weight on the paths that spell exactly w (<= 0 up to rounding, >= the path_logpost
+ * of any one of them).  found = 0 and seq_logpost = 0 where no such path exists.  The empty sequence is the posterior of saying
+ * nothing.  The posteriors of all distinct word sequences of a lattice sum to 1.
+ *
+ * mode 1, phrase (L >= 1): a table P[s][k], 0 <= k < L.  P[s][0] = alpha[s] for EVERY state: the phrase may start after any prefix.
+ * For k >= 1 the recurrence is the one above: an arc with olabel 0 carries k -> k, an arc with olabel == w[k - 1] carries k - 1 -> k,
+ * any other word arc carries nothing -- the phrase is contiguous in the path's words.  An occurrence is completed by an arc
+ * a: s -> t with olabel == w[L - 1]:
+ *   occ(a) = exp(-(P[s][L - 1] + c(a) + beta[t] + log_z)),   count = sum of occ(a)
+ * count is the expected number of (path, position) occurrences; overlapping ones count, so it may pass 1, as word_post may.
+ * seq_logpost = log(count) and found = (count > 0); the confidence is min(1, count), and this call returns the count UNCLAMPED, as its
+ * logarithm.  hit_mass[i][q][f] = the sum of occ(a) over the arcs whose SOURCE state's frame is f -- wfst_decoder_align_words' begin
+ * frame of the phrase's last word, the frame wfst_decoder_word_confidence's cells go by; its sum over f is count, and for L = 1
+ * occ(a) = gamma(a).  A row has n_frames[i] entries: the state frames 0 .. frames decoded of the channel's lattice.
+ *
+ * The ORDER of every sum is the order of the device's arc index, which the launch that emits the lattice decides, and the
+ * occurrences are added up with atomic adds: the results are reproducible to rounding, NOT bit for bit.
+ *
+ * Per listed channel i: log_z[i], n_frames[i]; per sequence q (seq_len[i][q] words at seq_words[i][q][..]; -1: skipped, outputs
+ * zero): found[i][q], seq_logpost[i][q], and in mode 1, where hit_mass is given, hit_mass[i][q][0 .. n_frames[i]) of a row of
+ * cap_frames (hit_mass is not written in mode 0 beyond being zeroed).
+ * A failure of ONE channel goes into status[i] and the call still returns WFST_OK: a sequence whose table of states x (seq_len + 1)
+ * cells is beyond max_cells (WFST_E_CAPACITY, the channel's outputs zero; 0 = wfst_decoder_align_words' default bound), a device
+ * error of that channel's utterance (likewise), or, with hit_mass given, a lattice of more frames than cap_frames (WFST_E_CAPACITY:
+ * n_frames[i] is the room needed, the channel's rows stay zero and its other answers stand).  A cell is 8 bytes, 32.5 MiB of table
+ * per sequence at the default bound; the workspace is the decoder's, shared with wfst_decoder_align_words and
+ * wfst_decoder_word_confidence (24 bytes per state and 16 per arc of posteriors, 4 bytes per state and sequence of level flags) and
+ * grown on demand; lists whose tables pass 256 MiB together are taken in rounds.
+ * The call itself fails, before any device work, with WFST_E_ARG (a scale that is negative or not finite, mode outside 0..1, a
+ * seq_len of 0 in mode 1, cap_frames < 0, hit_mass given with cap_frames == 0, and everything wfst_decoder_align_words names) or
+ * WFST_E_STATE (as there).  Any output pointer may be NULL.  The decoder's state is only read: decoding goes on bit for bit as without
+ * the call, and the other getters answer afterwards what they would have answered.  Synchronous, as wfst_decoder_align_words is and
+ * for the same reason.
+ * Not computed here: minimum Bayes risk decoding and confusion networks, per-frame transition-id posteriors (lattice-to-post). */
+int wfst_decoder_sequence_posterior(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                                    double graph_scale, double acoustic_scale, int32_t mode /* 0 sentence, 1 phrase */,
+                                    int32_t n_seqs /* per channel, 1..64 */, int32_t cap_words,
+                                    const int32_t *seq_words /* [n][n_seqs][cap_words] */, const int32_t *seq_len /* [n][n_seqs], -1 = skip */,
+                                    int64_t max_cells /* states x (len + 1) per sequence; 0 = default */,
+                                    int32_t cap_frames /* row length of hit_mass; 0 with hit_mass NULL */,
+                                    int32_t *status /* [n] */, double *log_z /* [n] */,
+                                    int32_t *n_frames /* [n]: frames of the lattice = room hit_mass needs */,
+                                    int32_t *found, double *seq_logpost /* [n][n_seqs] */,
+                                    double *hit_mass /* [n][n_seqs][cap_frames], mode 1, may be NULL */);
 
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
