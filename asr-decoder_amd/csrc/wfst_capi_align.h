@@ -30,6 +30,9 @@ struct AlignState {
   DevBuf<double> post;
   DevBuf<int2> post_idx;
   PinBuf<double> post_pin;
+  // wfst_decoder_word_alternatives (wfst_capi_altern.h): what stays on the device -- A per state and sequence, the cells' "ended early"
+  // mass, the (cell, word) tables of the sequences whose keys outgrow LDS
+  DevBuf<double> alt;
 };
 
 // what the entry point sees of a decoder (sil_bits: the silence bitmap over transition-ids 1..sil_ntid, nullptr: none)
@@ -52,8 +55,8 @@ int align_channel_state(const wfst_decoder *d, int32_t channel);
 int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_final_probs, std::vector<int32_t> *sizes);
 
 // ---- the round driver of the word queries (wfst_capi_wordquery.cc) ----------------------------------------------------------
-// wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence and wfst_decoder_sequence_posterior ask the
-// listed channels' raw lattices about
+// wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence, wfst_decoder_sequence_posterior and
+// wfst_decoder_word_alternatives ask the listed channels' raw lattices about
 // n_seqs word sequences each: one table of states x (words + 1) cells per (channel, sequence) pair over the in-arc index
 // align_index_kernel builds.  word_query_run is the sequence they share; a WordQuery is what differs.
 

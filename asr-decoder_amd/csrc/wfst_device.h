@@ -576,6 +576,31 @@ struct SeqPostDev {
 };
 void launch_seqpost(const AlignDev &A, const PostDev &P, const SeqPostDev &Q, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- word alternatives per slot (wfst_altern.hip) ------------------------------------------------------------------------
+// A confusion network pinned to the sequences align_kernel has placed in time: per cell of confidence_kernel's time axis the words
+// the lattice says there with their posterior mass (slot_mass_kernel) and the mass of the paths that say nothing there
+// (slot_none_kernel), over the in-arc index (AlignDev::idx), align_kernel's results (AlignDev::out) and posterior_kernel's alpha, beta,
+// gamma, log_z and chan_err (PostDev).  One workgroup per (slot, sequence) pair each.  slot_none_kernel keeps its level flags in
+// AlignDev::path[p][ns_cap], behind confidence_kernel's last read of it.
+//   none[p][cap_words]             none_post (all zero where align_kernel found nothing)
+//   alt_post / alt_word[p][cap_words][n_alts], n_distinct[p][cap_words]
+//   acost[p][ns_cap]               A of a state, in the cell its frame lies in
+//   early[p][cap_words]            per cell the mass of the complete paths that end in it
+//   tab_key / tab_mass[p][tab_slots]  the table of a pair whose (cell, word) keys outgrow LDS: tab_slots a power of two above na_cap
+struct AltDev {
+  const int4 *lat_toks;       // DecoderDev::lat_toks, lat_tok_cap entries per channel
+  int64_t lat_tok_cap;
+  int32_t n_alts;
+  double *none, *alt_post;
+  int32_t *alt_word, *n_distinct;
+  double *acost, *early;
+  unsigned long long *tab_key;
+  double *tab_mass;
+  int64_t tab_slots;
+};
+void launch_slot_mass(const AlignDev &A, const PostDev &P, const AltDev &Q, int cnt, hipStream_t s);
+void launch_slot_none(const AlignDev &A, const PostDev &P, const AltDev &Q, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

@@ -1,5 +1,5 @@
 // The float64 arithmetic the log-semiring kernels share (posterior_kernel, confidence_kernel: wfst_posterior.hip; seqpost_kernel:
-// wfst_seqpost.hip): +inf, "is finite", and an in-arc record's cost c(a) with the "no arc" rule.  Device code only.
+// wfst_seqpost.hip; slot_none_kernel: wfst_altern.hip): +inf, "is finite", and an in-arc record's cost c(a) with the "no arc" rule.  Device code only.
 #ifndef WFST_POST_MATH_H_
 #define WFST_POST_MATH_H_
 

@@ -54,6 +54,11 @@
 //                  " sentpost=..", the log posterior of the path's WORD SEQUENCE over all paths of the RAW lattice that spell it
 //                  (SequencePosteriors: wfst_decoder_sequence_posterior), where logpost is one path's; the scales are
 //                  --word-confidence=GS,AS's when given, else 1,1
+//   --word-alternatives[=K]  with --nbest-word-times and/or --align-words=FILE: a confusion network pinned to every aligned sequence
+//                  (WordAlternatives: wfst_decoder_word_alternatives; K = 1..16, default 5) -- every "...#j word begin end" line gains
+//                  " none=.." (the share of the RAW lattice's weight on the paths that say nothing in the word's slot) and
+//                  " alts=word:post,..." (the K first words of the slot by posterior mass; "alts=-": the slot has none); the scales
+//                  are --word-confidence=GS,AS's when given, else 1,1
 //   --phrase-posterior=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being phrases of at least one
 //                  word; after the utterance's lines, per phrase "KEY phrase q found=0|1 count=.. conf=.. peak=FRAME": the expected
 //                  number of times a path of the RAW lattice says the phrase, min(1, count), and the lowest frame with the most of
@@ -145,9 +150,9 @@ struct Utt {
   int frames, cols;
   std::vector<float> m;
 };
-// an aligned sequence as the lines take it: the alignment, under --word-confidence the confidences, under --sentence-posterior the
-// posterior of the whole word sequence
-struct TimedSeq : WordConfidence {
+// an aligned sequence as the lines take it: the alignment, under --word-confidence the confidences, under --word-alternatives the
+// slots' alternatives, under --sentence-posterior the posterior of the whole word sequence
+struct TimedSeq : WordAlternatives {
   bool sent_found = false;
   double sentpost = 0.0;
 };
@@ -233,6 +238,7 @@ int main(int argc, char **argv) {
     bool pull = false, partial_words = false, word_times = false, live_prune = false, nbest_times = false;
     std::string align_file, nearest_file, phrase_file;
     bool word_conf = false, sent_post = false;
+    int word_alts = 0;   // --word-alternatives[=K]: K, 0 = off
     double conf_gs = 1.0, conf_as = 1.0;
     std::vector<int> wt_silence;
     long long max_tokens_per_frame = 0, arena_tokens = 0;
@@ -293,6 +299,13 @@ int main(int argc, char **argv) {
       }
       else if (a.compare(0, 16, "--nearest-words=") == 0) nearest_file = a.substr(16);
       else if (a == "--sentence-posterior") sent_post = true;
+      else if (a == "--word-alternatives") word_alts = 5;
+      else if (a.compare(0, 20, "--word-alternatives=") == 0) {
+        char *end = nullptr;
+        const long k = strtol(a.c_str() + 20, &end, 10);
+        if (end == a.c_str() + 20 || *end != 0 || k < 1 || k > 16) { std::cerr << "--word-alternatives=K, 1 <= K <= 16\n"; return 1; }
+        word_alts = (int)k;
+      }
       else if (a.compare(0, 19, "--phrase-posterior=") == 0) phrase_file = a.substr(19);
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
@@ -325,7 +338,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -344,6 +357,7 @@ int main(int argc, char **argv) {
     if (!nearest_file.empty() && n_threads > 0) { std::cerr << "--nearest-words goes with the batch shape or --single-stream\n"; return 1; }
     if (sent_post && !nbest_times && align_file.empty()) { std::cerr << "--sentence-posterior goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
     if (!phrase_file.empty() && n_threads > 0) { std::cerr << "--phrase-posterior goes with the batch shape or --single-stream\n"; return 1; }
+    if (word_alts && !nbest_times && align_file.empty()) { std::cerr << "--word-alternatives goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
     // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
     for (int which = 0; which < 3; ++which) {
@@ -426,7 +440,7 @@ int main(int argc, char **argv) {
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
     const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty();
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
-    // (--word-confidence: a fourth column conf)
+    // (--word-confidence: a fourth column conf; --word-alternatives: " none=.. alts=word:post,...")
     auto time_lines = [&](const std::string &head, const std::vector<int> &words, const TimedSeq &a) {
       std::string o;
       if (!a.found) return head + " notfound\n";
@@ -436,6 +450,16 @@ int main(int argc, char **argv) {
           char buf[32];
           snprintf(buf, sizeof(buf), " %.9g", a.conf[j]);
           o += buf;
+        }
+        if (word_alts) {
+          char buf[48];
+          snprintf(buf, sizeof(buf), " none=%.9g alts=", a.none_post[j]);
+          o += buf;
+          if (a.alts[j].empty()) o += "-";
+          for (size_t i = 0; i < a.alts[j].size(); ++i) {
+            snprintf(buf, sizeof(buf), "%s%d:%.9g", i ? "," : "", a.alts[j][i].first, a.alts[j][i].second);
+            o += buf;
+          }
         }
         o += "\n";
       }
@@ -466,10 +490,17 @@ int main(int argc, char **argv) {
       return o;
     };
     // the word times of one stream's sequences (GetNbestWordTimes), under --word-confidence with the confidences (WordConfidences),
+    // under --word-alternatives with the slots' alternatives as well (WordAlternatives),
     // under --sentence-posterior with the sequences' posteriors (SequencePosteriors)
     auto stream_times = [&](GpuLatticeDecoder &decode, const std::vector<std::vector<int> > &seqs, std::vector<TimedSeq> *o, bool use_final_probs) {
       std::vector<SequencePosterior> sp;
       if (sent_post) decode.SequencePosteriors(seqs, &sp, false, use_final_probs, conf_gs, conf_as);
+      if (word_alts) {   // (the confidences come with them)
+        std::vector<WordAlternatives> a;
+        decode.WordAlternatives(seqs, &a, word_alts, use_final_probs, conf_gs, conf_as);
+        *o = lift(a, sp);
+        return;
+      }
       if (word_conf) {
         std::vector<WordConfidence> a;
         decode.WordConfidences(seqs, &a, use_final_probs, conf_gs, conf_as);
@@ -488,6 +519,12 @@ int main(int argc, char **argv) {
       if (sent_post) decode.SequencePosteriors(ch, seqs, false, use_final_probs, conf_gs, conf_as, &sp, &sp_status);
       const std::vector<SequencePosterior> none;
       o->clear();
+      if (word_alts) {
+        std::vector<std::vector<WordAlternatives> > a;
+        decode.WordAlternatives(ch, seqs, word_alts, use_final_probs, conf_gs, conf_as, &a, status);
+        for (size_t i = 0; i < a.size(); ++i) o->push_back(lift(a[i], i < sp.size() ? sp[i] : none));
+        return;
+      }
       if (word_conf) {
         std::vector<std::vector<WordConfidence> > a;
         decode.WordConfidences(ch, seqs, use_final_probs, conf_gs, conf_as, &a, status);

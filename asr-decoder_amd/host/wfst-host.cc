@@ -26,6 +26,7 @@
 #pragma weak wfst_decoder_nearest_words
 #pragma weak wfst_decoder_word_confidence
 #pragma weak wfst_decoder_sequence_posterior
+#pragma weak wfst_decoder_word_alternatives
 
 namespace datemoon {
 
@@ -1916,6 +1917,66 @@ void GpuLatticeDecoder::WordConfidences(const std::vector<std::vector<int> > &se
   StreamWordQuery("WordConfidences", _chan, seqs, out, [&](auto &&f) { OnDevice(f); },
                   [&](const auto &ch, const SeqLists &s, auto *o, auto *st) {
                     return WordConfidencesCall(_dec, ch, s, use_final_probs, graph_scale, acoustic_scale, 0, o, st);
+                  });
+}
+
+// ---- word alternatives per slot (wfst_decoder_word_alternatives) -----------------------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i][q] for seqs[i][q], (*status)[i] the channel's own code.  Returns the call's own code.
+static int WordAlternativesCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const SeqLists &seqs, int n_alts, bool use_final_probs,
+                                double graph_scale, double acoustic_scale, long long max_cells,
+                                std::vector<std::vector<struct WordAlternatives> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_word_alternatives)
+    throw std::runtime_error("WordAlternatives: this build's device library has no wfst_decoder_word_alternatives");
+  if (seqs.size() != ch.size()) throw std::runtime_error("WordAlternatives: one list of sequences per listed channel");
+  const PackedSeqs in(seqs);
+  const size_t cnt = in.cnt, ns = in.ns, cap = in.cap, np = in.np, K = (size_t)std::max(n_alts, 1);
+  std::vector<int32_t> st(cnt), found(np), na(np), b(np * cap), e(np * cap), nd(np * cap), aw(np * cap * K);
+  std::vector<float> t(np), l(np);
+  std::vector<double> lz(cnt), wp(np * cap), nop(np * cap), ap(np * cap * K), plp(np);
+  const int rc = wfst_decoder_word_alternatives(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, graph_scale, acoustic_scale, n_alts,
+                                                (int32_t)ns, (int32_t)cap, in.words.data(), in.len.data(), max_cells, st.data(), lz.data(),
+                                                found.data(), na.data(), b.data(), e.data(), wp.data(), nop.data(), nd.data(), aw.data(),
+                                                ap.data(), plp.data(), t.data(), l.data());
+  if (rc != WFST_OK) return rc;
+  out->assign(cnt, std::vector<struct WordAlternatives>());
+  for (size_t i = 0; i < cnt; ++i) {
+    (*out)[i].resize(seqs[i].size());
+    for (size_t q = 0; q < seqs[i].size(); ++q) {
+      struct WordAlternatives &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.log_z = lz[i];
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.n_arcs = na[p]; a.tot = t[p]; a.lm = l[p]; a.path_logpost = plp[p];
+      for (size_t k = 0; k < seqs[i][q].size(); ++k) {
+        const size_t at = p * cap + k;
+        a.frames.push_back(std::make_pair(b[at], e[at]));
+        a.word_post.push_back(wp[at]);
+        a.conf.push_back(std::min(1.0, wp[at]));
+        a.none_post.push_back(nop[at]);
+        a.n_distinct.push_back(nd[at]);
+        a.alts.push_back(std::vector<std::pair<int, double> >());
+        for (size_t j = 0; j < std::min(K, (size_t)nd[at]); ++j) a.alts.back().push_back(std::make_pair((int)aw[at * K + j], ap[at * K + j]));
+      }
+    }
+  }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::WordAlternatives(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, int n_alts,
+                                       bool use_final_probs, double graph_scale, double acoustic_scale,
+                                       std::vector<std::vector<struct WordAlternatives> > *out, std::vector<int> *status, long long max_cells) {
+  BatchWordQuery("WordAlternatives", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return WordAlternativesCall(_dec, ch, seqs, n_alts, use_final_probs, graph_scale, acoustic_scale, max_cells, o, st);
+  });
+}
+
+void GpuLatticeDecoder::WordAlternatives(const std::vector<std::vector<int> > &seqs, std::vector<struct WordAlternatives> *out, int n_alts,
+                                         bool use_final_probs, double graph_scale, double acoustic_scale) {
+  StreamWordQuery("WordAlternatives", _chan, seqs, out, [&](auto &&f) { OnDevice(f); },
+                  [&](const auto &ch, const SeqLists &s, auto *o, auto *st) {
+                    return WordAlternativesCall(_dec, ch, s, n_alts, use_final_probs, graph_scale, acoustic_scale, 0, o, st);
                   });
 }
 

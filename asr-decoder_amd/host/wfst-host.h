@@ -422,6 +422,17 @@ struct WordConfidence : WordAlignment {
   double path_logpost = 0.0, log_z = 0.0;
 };
 
+// A WordConfidence with the alternatives of every word's slot (wfst_decoder_word_alternatives), a confusion network pinned to the
+// sequence: alts[k] = the words the lattice says in word k's cell of the time axis as (word, posterior mass), by mass descending and
+// word id ascending, the first n_alts of them (unclamped; the sequence's own word is among them where it ranks that high, and
+// word_post[k] is its mass); n_distinct[k] = how many words the cell has in all; none_post[k] = the share of the lattice's weight on the
+// paths that say nothing in the cell.  The doubles are reproducible to rounding, not bit for bit; a list is ordered on the device's sums.
+struct WordAlternatives : WordConfidence {
+  std::vector<std::vector<std::pair<int, double> > > alts;
+  std::vector<double> none_post;
+  std::vector<int> n_distinct;
+};
+
 // The posterior of a whole word sequence, or of a phrase, on a channel's raw lattice (wfst_decoder_sequence_posterior).  A sentence:
 // logpost = the log of the share of the lattice's weight on ALL paths that spell the sequence, count = exp(logpost).  A phrase: count
 // = the expected number of times a path says it (overlapping occurrences included: it may pass 1), logpost = log(count), and -- where
@@ -541,6 +552,11 @@ class GpuLatticeDecoder : public DecoderItf {
   // The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void WordConfidences(const std::vector<std::vector<int> > &seqs, std::vector<WordConfidence> *out, bool use_final_probs = true,
                        double graph_scale = 1.0, double acoustic_scale = 1.0);
+  // ... and with the alternatives of every word's slot, the n_alts (1..16) first words of its cell and the cell's "no word" mass
+  // (wfst_decoder_word_alternatives), in one device call: (*out)[k] for seqs[k] (at most 64).  The channel's own failure throws.  Over
+  // a pool the call runs in the batcher thread, like AlignWords.
+  void WordAlternatives(const std::vector<std::vector<int> > &seqs, std::vector<struct WordAlternatives> *out, int n_alts = 5,
+                        bool use_final_probs = true, double graph_scale = 1.0, double acoustic_scale = 1.0);
   // How sure the decoder is of each of `seqs` (at most 64) as a WHOLE -- the sum over every path of the RAW lattice that spells it,
   // where WordConfidence::path_logpost is one path's -- or, with phrase = true, how often and when a path says each of them as a
   // phrase (at least one word each; hit_mass: with the per-frame rows), in one device call (wfst_decoder_sequence_posterior):
@@ -661,6 +677,11 @@ class GpuBatchDecoder {
   void WordConfidences(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool use_final_probs,
                        double graph_scale, double acoustic_scale, std::vector<std::vector<WordConfidence> > *out,
                        std::vector<int> *status = nullptr, long long max_cells = 0);
+  // WordAlternatives (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage;
+  // the arguments and the status rule are AlignWords'
+  void WordAlternatives(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, int n_alts,
+                        bool use_final_probs, double graph_scale, double acoustic_scale, std::vector<std::vector<struct WordAlternatives> > *out,
+                        std::vector<int> *status = nullptr, long long max_cells = 0);
   // SequencePosteriors (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage;
   // the arguments and the status rule are AlignWords'.  The hit_mass rows are given the room the lattices need.
   void SequencePosteriors(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool phrase,

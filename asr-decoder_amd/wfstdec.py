@@ -47,7 +47,7 @@ SYMBOLS = [
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
     "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
-    "wfst_decoder_sequence_posterior",
+    "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives",
 ]
 
 
@@ -874,6 +874,40 @@ class BatchDecoder:
             out.append(row)
         return out
 
+    def word_alternatives(self, seqs, channels=None, use_final_probs=True, graph_scale=1.0, acoustic_scale=1.0, n_alts=5, max_cells=0):
+        """Word alternatives per slot -- a confusion network pinned to each sequence -- for a LIST of channels (None: all), live and
+        finalized ones mixed (wfst_decoder_word_alternatives): seqs[i] = the word sequences on channels[i], as align_words takes them.
+        Per channel a list with one dict per sequence: word_confidences' fields plus alts (per word a list of (word, post): the words
+        the lattice says in that word's cell of the time axis, by posterior mass descending and word id ascending, the first n_alts of
+        them, 1 <= n_alts <= 16, unclamped), n_distinct (int32 per word: how many words the cell has in all) and none_post (float64 per
+        word: the share of the lattice's weight on the paths that say nothing in the cell).  The floats are reproducible to rounding,
+        not bit for bit; a list is ordered on the device's own sums."""
+        ch, cnt, ns, cap, words, lens = self._pack_seqs(seqs, channels, "sequences")
+        K = int(n_alts)
+        status, found, na, begin, end, tot, lm = self._word_results(cnt, ns, cap)
+        log_z, wp, plp = np.zeros(cnt, np.float64), np.zeros((cnt, ns, cap), np.float64), np.zeros((cnt, ns), np.float64)
+        nonep, nd = np.zeros((cnt, ns, cap), np.float64), np.zeros((cnt, ns, cap), np.int32)
+        aw, ap = np.zeros((cnt, ns, cap, max(K, 1)), np.int32), np.zeros((cnt, ns, cap, max(K, 1)), np.float64)
+        f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        _check(lib().wfst_decoder_word_alternatives(self.h, _i32(ch), cnt, int(bool(use_final_probs)), C.c_double(float(graph_scale)),
+                                                    C.c_double(float(acoustic_scale)), K, ns, cap, _i32(words), _i32(lens),
+                                                    C.c_int64(int(max_cells)), _i32(status), f64(log_z), _i32(found), _i32(na), _i32(begin),
+                                                    _i32(end), f64(wp), f64(nonep), _i32(nd), _i32(aw), f64(ap), f64(plp), _f32(tot), _f32(lm)))
+        out = []
+        for i in range(cnt):
+            row = []
+            for q in range(len(seqs[i])):
+                ln = max(int(lens[i, q]), 0)
+                post = wp[i, q, :ln].copy()
+                w, p, cnt_k = aw[i, q, :ln].tolist(), ap[i, q, :ln].tolist(), nd[i, q, :ln].tolist()
+                alts = [list(zip(w[k][:cnt_k[k]], p[k][:cnt_k[k]])) for k in range(ln)]   # (rows of n_alts: a longer count takes all)
+                row.append(dict(found=bool(found[i, q]), begin=begin[i, q, :ln].copy(), end=end[i, q, :ln].copy(), tot=np.float32(tot[i, q]),
+                                lm=np.float32(lm[i, q]), n_arcs=int(na[i, q]), status=int(status[i]), word_post=post,
+                                conf=np.minimum(1.0, post), path_logpost=float(plp[i, q]), log_z=float(log_z[i]), alts=alts,
+                                none_post=nonep[i, q, :ln].copy(), n_distinct=nd[i, q, :ln].copy()))
+            out.append(row)
+        return out
+
     def _sequence_posterior(self, mode, seqs, channels, use_final_probs, graph_scale, acoustic_scale, max_cells, cap_frames):
         """wfst_decoder_sequence_posterior: (lens, status[cnt], log_z[cnt], n_frames[cnt], found, logpost [cnt][ns],
         hit_mass [cnt][ns][cap_frames] or None)"""
@@ -946,15 +980,22 @@ class BatchDecoder:
         return res
 
     def nbest_words_conf(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0,
-                         graph_scale=1.0, acoustic_scale=1.0, sentence_post=False):
+                         graph_scale=1.0, acoustic_scale=1.0, sentence_post=False, alternatives=0):
         """nbest_words_timed(...) with confidences: every path's words aligned on its channel's raw lattice and weighed against the
         lattice's posteriors (word_confidences); beside nbest_words_timed's keys the dicts carry conf, word_post, path_logpost and
         log_z.  sentence_post=True: also sent_logpost, the log posterior of the path's word sequence over ALL lattice paths that
-        spell it (sentence_posteriors, at the same scales; 0.0 where found is False)."""
+        spell it (sentence_posteriors, at the same scales; 0.0 where found is False).  alternatives=K > 0: also alts, none_post and
+        n_distinct, the K first alternatives of every word's slot (word_alternatives, which then answers in word_confidences' place)."""
         res = self.nbest_words(n_paths, channels, old_lm, new_lm, use_final_probs, cap_words)
         ch = list(range(self.n)) if channels is None else [int(c) for c in channels]
         seqs = [[p["words"] if p["n_words"] <= int(cap_words) else None for p in paths] for _, paths in res]
-        al = self.word_confidences(seqs, ch, use_final_probs, graph_scale, acoustic_scale, max_cells)
+        if alternatives:
+            al = self.word_alternatives(seqs, ch, use_final_probs, graph_scale, acoustic_scale, int(alternatives), max_cells)
+            for (_, paths), a in zip(res, al):
+                for p, x in zip(paths, a):
+                    p.update(alts=x["alts"], none_post=x["none_post"], n_distinct=x["n_distinct"])
+        else:
+            al = self.word_confidences(seqs, ch, use_final_probs, graph_scale, acoustic_scale, max_cells)
         for (_, paths), a in zip(res, al):
             for p, x in zip(paths, a):
                 p.update(found=x["found"], begin=x["begin"], end=x["end"], n_arcs=x["n_arcs"], align_tot=x["tot"], align_lm=x["lm"],

@@ -686,7 +686,8 @@ int wfst_decoder_nearest_words(wfst_decoder *d, const int32_t *channels, int32_t
  * Limitation: a word's arc sits where the graph put its olabel, so the cells follow label positions, not acoustic word boundaries.
  * Not computed here: a hypothesis' full sentence posterior (a log-semiring table of states x (L + 1)), per-frame transition-id
  * posteriors (lattice-to-post), minimum Bayes risk / confusion networks.  (The sentence posterior is wfst_decoder_sequence_posterior's,
- * below.)
+ * below.)  (The confusion network pinned to a hypothesis -- the other words of a slot, and "no word" -- is
+ * wfst_decoder_word_alternatives', below; minimum Bayes risk decoding stays out.)
  *
  * A failure of ONE channel goes into status[i] with all of that channel's outputs zero, and the call still returns WFST_OK: a
  * sequence whose alignment table of states x (seq_len + 1) cells is beyond max_cells (WFST_E_CAPACITY; 0 = wfst_decoder_align_words'
@@ -759,7 +760,8 @@ int wfst_decoder_word_confidence(wfst_decoder *d, const int32_t *channels, int32
  * WFST_E_STATE (as there).  Any output pointer may be NULL.  The decoder's state is only read: decoding goes on bit for bit as without
  * the call, and the other getters answer afterwards what they would have answered.  Synchronous, as wfst_decoder_align_words is and
  * for the same reason.
- * Not computed here: minimum Bayes risk decoding and confusion networks, per-frame transition-id posteriors (lattice-to-post). */
+ * Not computed here: minimum Bayes risk decoding and confusion networks, per-frame transition-id posteriors (lattice-to-post).
+ * (The confusion network pinned to a hypothesis is wfst_decoder_word_alternatives', below.) */
 int wfst_decoder_sequence_posterior(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
                                     double graph_scale, double acoustic_scale, int32_t mode /* 0 sentence, 1 phrase */,
                                     int32_t n_seqs /* per channel, 1..64 */, int32_t cap_words,
@@ -770,6 +772,71 @@ int wfst_decoder_sequence_posterior(wfst_decoder *d, const int32_t *channels, in
                                     int32_t *n_frames /* [n]: frames of the lattice = room hit_mass needs */,
                                     int32_t *found, double *seq_logpost /* [n][n_seqs] */,
                                     double *hit_mass /* [n][n_seqs][cap_frames], mode 1, may be NULL */);
+
+/* ---- word alternatives per slot: a confusion network pinned to a hypothesis ---------------------------------------------------------
+ * What else could have been said in a word's slot, and how likely it is that nothing was said there.  The pivot construction of a
+ * confusion network (Hakkani-Tur & Riccardi, "A general algorithm for word graph matrix decomposition", 2003), first half: the
+ * hypothesis is the pivot, its time cells are the slots, and every other word of the lattice falls into the slot its time lies in.
+ * For a list of channels, live and finalized ones mixed, n_seqs sequences per channel, one launch per stage (the live channels'
+ * lattices emitted, align_index_kernel, align_kernel, posterior_kernel, confidence_kernel, slot_mass_kernel, slot_none_kernel).
+ *
+ * Taken as it is from wfst_decoder_word_confidence: the lattice R, the scales, c(a), the rule that an arc whose float32 graph +
+ * acoustic is not finite is no arc, alpha, beta, log_z, gamma(a) and the way every sum is taken.  For a sequence w[0..L) of word ids
+ * > 0 the alignment runs first; found, n_arcs, begin_frame, end_frame, tot_score and lm_score are wfst_decoder_align_words' own, bit
+ * for bit; the cells are that call's: m[0] = 0, m[k] = (b[k - 1] + b[k] + 1) >> 1, m[L] = +inf, cell k = the frames m[k] <= f <
+ * m[k + 1]; word_post[k], path_logpost and log_z are that call's values.
+ * A state has a frame.  An arc with ilabel 0 stays inside its frame; every other arc goes from frame f to f + 1.
+ *
+ * mass and alternatives.  For a cell k and a word v > 0
+ *   mass(k, v) = the sum of gamma(a) over the arcs a with olabel(a) == v whose SOURCE state's frame lies in cell k
+ * -- emitting and epsilon arcs alike -- so mass(k, w[k]) = word_post[k].  The alternatives of slot k are the words with mass(k, v) > 0,
+ * ordered by mass DESCENDING and then by word id ASCENDING.  alt_word[k][0 .. n_alts) and alt_post[k][..] are the first n_alts of them
+ * (1 <= n_alts <= WFST_ALTERN_MAX_ALTS), alt_post UNCLAMPED as word_post is; n_distinct[k] is how many such words there are in all;
+ * the unused entries are zero.  The hypothesis' own word is one of them wherever it is among the first n_alts; word_post[k] beside
+ * the list says where it stands.  The order is taken on the device's own sums: a list is strictly ordered, and where two masses
+ * differ by less than their rounding, which of the two comes first (or falls off the list's end) is the device's.
+ *
+ * none_post[k] = the share of the lattice's weight on the complete paths that have NO word-carrying arc whose source state's frame
+ * lies in cell k: the slot's "no word" entry, none_post[k] + P(some word in the cell) = 1.  With lo = m[k], hi = m[k + 1]:
+ * an empty cell (lo >= hi: two words that begin at one frame make one) has none_post[k] = 1.  Otherwise, over the states of the
+ * cell's frames, A_k[start] = 0 if lo == 0, and
+ *   A_k[t] = -log( sum over a: s -> t with frame(s) < lo                          of exp(-(alpha[s] + c(a)))
+ *                + sum over a: s -> t with lo <= frame(s) < hi and olabel(a) == 0 of exp(-(A_k[s]   + c(a))) )
+ * -- a word on an arc that ENTERS the cell belongs to the cell before -- and none_post[k] is the sum of
+ *   exp(-(A_k[s] + c(a) + beta[t] + log_z))  over the arcs a: s -> t that leave the cell (frame(s) in it, frame(t) >= hi), olabel 0,
+ *   exp(-(A_k[s] + log_z))                   over the final states s in the cell,
+ *   exp(-(alpha[s] + log_z))                 over the final states s with frame(s) < lo: the paths that ended before the cell began.
+ * A state without a finite term is +inf; a result is never NaN.  For L = 1 the one cell is the whole time axis and none_post[0] is
+ * the posterior of saying nothing at all: exp of wfst_decoder_sequence_posterior's sentence posterior of the empty sequence.
+ * 1 - none_post[k] <= the sum of mass(k, v) over v, with equality where no path says two words inside the cell.
+ *
+ * found = 0: every new output is zero.  The empty sequence has no slots.  The ORDER of every sum is the order of the device's arc
+ * index and of its atomic adds: the results are reproducible to rounding, NOT bit for bit.
+ *
+ * The (cell, word) sums of a sequence are kept in an on-chip table where its distinct (cell, word) pairs number at most
+ * WFST_ALTERN_LDS_KEYS, and in the decoder's workspace otherwise; the answers do not depend on which.
+ * A failure of ONE channel goes into status[i] with all of that channel's outputs zero, and the call still returns WFST_OK, as
+ * wfst_decoder_word_confidence has it.  Beside that call's workspace (rounds included) this one takes, per sequence, 8 bytes per
+ * state (A), 8 per word, and 16 bytes per slot of a table with a power of two of slots above the arcs of the round's largest lattice.
+ * The call itself fails, before any device work, with WFST_E_ARG (n_alts outside 1..16, a scale that is negative or not finite, and
+ * everything wfst_decoder_word_confidence names) or WFST_E_STATE (as there).  Any output pointer may be NULL.  The decoder's state is
+ * only read: decoding goes on bit for bit as without the call.  Synchronous, as wfst_decoder_align_words is and for the same reason.
+ * Not computed here: minimum Bayes risk decoding, the merging of slots or new slots between the hypothesis' words (the pivot
+ * algorithm's second half), per-frame transition-id posteriors. */
+#define WFST_ALTERN_MAX_ALTS 16
+#define WFST_ALTERN_LDS_KEYS 1024 /* distinct (cell, word) pairs of a sequence the on-chip table takes */
+int wfst_decoder_word_alternatives(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                                   double graph_scale, double acoustic_scale, int32_t n_alts /* per slot, 1..16 */,
+                                   int32_t n_seqs /* per channel, 1..64 */, int32_t cap_words,
+                                   const int32_t *seq_words /* [n][n_seqs][cap_words] */, const int32_t *seq_len /* [n][n_seqs], -1 = skip */,
+                                   int64_t max_cells /* states x (len + 1) per sequence; 0 = default */,
+                                   int32_t *status /* [n] */, double *log_z /* [n] */,
+                                   int32_t *found, int32_t *n_arcs /* [n][n_seqs] */,
+                                   int32_t *begin_frame, int32_t *end_frame /* [n][n_seqs][cap_words] */,
+                                   double *word_post, double *none_post /* [n][n_seqs][cap_words] */,
+                                   int32_t *n_distinct /* [n][n_seqs][cap_words] */,
+                                   int32_t *alt_word, double *alt_post /* [n][n_seqs][cap_words][n_alts] */,
+                                   double *path_logpost /* [n][n_seqs] */, float *tot_score, float *lm_score /* [n][n_seqs] */);
 
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
