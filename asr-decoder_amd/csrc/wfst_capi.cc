@@ -93,6 +93,9 @@ struct wfst_lm {
   DevBuf<int2> wt;
   DevBuf<int4> hash;
   uint32_t hmask = 0;
+  // the (state, word) table as wfst_lm_from_arrays filled it (wfst_lm_table_stats): occupied slots, the longest cyclic run of them,
+  // the farthest an entry sits past its home slot, and whether an occupied run covers both the last slot and slot 0
+  int32_t tab_used = 0, tab_longest_run = 0, tab_max_displacement = 0, tab_wraps = 0;
   LmDev view() const {
     LmDev L;
     L.st = st.p;
@@ -810,16 +813,27 @@ int wfst_lm_from_arrays(int32_t bos, int32_t eos, int32_t unk, int32_t n_states,
   size_t hsize = 1024;
   while (hsize < 4 * (size_t)std::max(1, n_arcs - states[0].arc_num)) hsize <<= 1;   // (at most a quarter full: short probe sequences, lm_step)
   std::vector<int4> htab(hsize, make_int4(-1, -1, 0, 0));
+  int32_t tab_used = 0, tab_longest_run = 0, tab_max_displacement = 0;
   {
     int64_t o = 0;
     for (int32_t s = 0; s < n_states; ++s) {
       for (int32_t i = 0; i < states[s].arc_num && s != 0; ++i) {
         const wfst_lm_arc &a = arcs[o + i];
         uint32_t slot = lm_hash(s, a.wordid) & (uint32_t)(hsize - 1);
-        while (htab[slot].x >= 0) slot = (slot + 1) & (uint32_t)(hsize - 1);
+        int32_t disp = 0;
+        while (htab[slot].x >= 0) { slot = (slot + 1) & (uint32_t)(hsize - 1); ++disp; }
         htab[slot] = make_int4(s, a.wordid, wt[(size_t)(o + i)].x, a.tostateid);
+        tab_max_displacement = std::max(tab_max_displacement, disp);
+        ++tab_used;
       }
       o += states[s].arc_num;
+    }
+    // the longest CYCLIC run of occupied slots: scan from behind an empty slot (there is one: at most a quarter full)
+    size_t first_empty = 0;
+    while (htab[first_empty].x >= 0) ++first_empty;
+    for (size_t k = 1, run = 0; k <= hsize; ++k) {
+      run = htab[(first_empty + k) & (hsize - 1)].x >= 0 ? run + 1 : 0;
+      tab_longest_run = std::max(tab_longest_run, (int32_t)run);
     }
   }
   HIP_TRY(hipSetDevice(device));
@@ -832,6 +846,10 @@ int wfst_lm_from_arrays(int32_t bos, int32_t eos, int32_t unk, int32_t n_states,
   lm->n_arcs = n_arcs;
   lm->start_arcs = states[0].arc_num;
   lm->hmask = (uint32_t)(hsize - 1);
+  lm->tab_used = tab_used;
+  lm->tab_longest_run = tab_longest_run;
+  lm->tab_max_displacement = tab_max_displacement;
+  lm->tab_wraps = htab[hsize - 1].x >= 0 && htab[0].x >= 0;
   lm->start = arcs[bos].tostateid;  // ComposeArpaLm::Start: the arc of state 0 for <s> (compose-arpalm.cc:5-13)
   hipError_t e;
   if ((e = lm->st.alloc(st.size())) != hipSuccess || (e = lm->words.alloc(words.size())) != hipSuccess ||
@@ -890,6 +908,17 @@ int wfst_lm_info(const wfst_lm *lm, int32_t *bos, int32_t *eos, int32_t *n_state
   if (n_arcs) *n_arcs = lm->n_arcs;
   if (n_words) *n_words = lm->start_arcs;
   if (device_bytes) *device_bytes = (int64_t)(lm->st.bytes() + lm->words.bytes() + lm->wt.bytes() + lm->hash.bytes());
+  return WFST_OK;
+}
+
+int wfst_lm_table_stats(const wfst_lm *lm, int64_t *table_size, int32_t *used, int32_t *longest_run, int32_t *max_displacement,
+                        int32_t *wraps) {
+  if (!lm) return fail(WFST_E_ARG, "NULL LM");
+  if (table_size) *table_size = (int64_t)lm->hmask + 1;
+  if (used) *used = lm->tab_used;
+  if (longest_run) *longest_run = lm->tab_longest_run;
+  if (max_displacement) *max_displacement = lm->tab_max_displacement;
+  if (wraps) *wraps = lm->tab_wraps;
   return WFST_OK;
 }
 
@@ -2837,6 +2866,21 @@ int wfst_decoder_get_determinized_lattice(wfst_decoder *d, int32_t channel, int3
                       a_olabel, a_graph, a_acoustic);
 }
 
+// What every entry that hands an LM pair to the second pass (compose2_kernel: lm_getarc / lm_final_cost) asks of the pair, in ONE place
+// and before any launch or cache is touched: both on the decoder's device, and -- the rule of wfst_decoder_create_biglm -- every
+// output label of the decoder's graph a word id both empty-history states have an arc for.  fsa_getarc indexes state 0's arcs by
+// word id without a bound (as the reference does, arpa2fsa.cc:253-254): a larger label would be priced with another state's arc,
+// or read outside the LM.
+static int check_lm_pair(const wfst_decoder *d, const wfst_lm *old_lm, const wfst_lm *new_lm) {
+  if (!old_lm) return WFST_OK;   // (no second pass asked for; one LM without the other is the caller's WFST_E_ARG)
+  if (old_lm->device != d->device || new_lm->device != d->device) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
+  const int32_t nw = std::min(old_lm->start_arcs, new_lm->start_arcs);
+  if (d->graph->min_olabel < 0 || d->graph->max_olabel >= nw)
+    return fail(WFST_E_FORMAT, "the second pass: the graph has output label " + std::to_string(d->graph->max_olabel) +
+                                   " but the LMs' empty-history state only has arcs for word ids below " + std::to_string(nw));
+  return WFST_OK;
+}
+
 // ComposeLattice with the old LM and with the new one over the determinized lattices of workspace slots [0, cnt), on the device, in ONE
 // launch (a workgroup per lattice); res[4 * i ..] = {states, arcs, status, -} of slot i
 static int compose_slots(wfst_decoder *d, const wfst_lm *old_lm, const wfst_lm *new_lm, int32_t cnt, int32_t *res) {
@@ -3013,7 +3057,7 @@ static int postprocess_batch(wfst_decoder *d, const int32_t *channels, int32_t n
                              const wfst_lm *new_lm, int32_t n_paths) {
   if (!d || (old_lm == nullptr) != (new_lm == nullptr)) return fail(WFST_E_ARG, "bad argument (both LMs or neither)");
   if (!d->D.lattice) return fail(WFST_E_STATE, "GetLattice / GetNbest need a decoder created with wfst_limits.lattice_links > 0");
-  if (old_lm && (old_lm->device != d->device || new_lm->device != d->device)) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
+  if (const int rc_lm = check_lm_pair(d, old_lm, new_lm)) return rc_lm;
   if (n_paths < 0 || n_paths > 4096) return fail(WFST_E_ARG, "1 <= n <= 4096 paths");
   HIP_TRY(hipSetDevice(d->device));
   std::vector<int32_t> all;
@@ -3093,7 +3137,7 @@ int wfst_decoder_get_rescored_lattice(wfst_decoder *d, int32_t channel, int32_t 
                                       int32_t cap_states, int32_t cap_arcs, int32_t *n_states, int32_t *n_arcs, int32_t *st_final,
                                       int32_t *a_src, int32_t *a_dst, int32_t *a_ilabel, int32_t *a_olabel, float *a_graph, float *a_acoustic) {
   if (!d || channel < 0 || channel >= d->n_channels || !n_states || !n_arcs || !old_lm || !new_lm) return fail(WFST_E_ARG, "bad argument");
-  if (old_lm->device != d->device || new_lm->device != d->device) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
+  if (const int rc_lm = check_lm_pair(d, old_lm, new_lm)) return rc_lm;
   *n_states = 0;
   *n_arcs = 0;
   if (d->h_state[channel] == 0) return fail(WFST_E_STATE, "GetLattice before InitDecoding");
@@ -3118,7 +3162,7 @@ int wfst_decoder_get_nbest_paths(wfst_decoder *d, int32_t channel, int32_t n, in
                                  int32_t *path_off, float *path_tot, int32_t *a_olabel, float *a_graph, float *a_acoustic) {
   if (!d || channel < 0 || channel >= d->n_channels || !n_paths || !total_arcs || n < 1 || n > 4096 || (old_lm == nullptr) != (new_lm == nullptr))
     return fail(WFST_E_ARG, "bad argument (1 <= n <= 4096; both LMs or neither)");
-  if (old_lm && (old_lm->device != d->device || new_lm->device != d->device)) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
+  if (const int rc_lm = check_lm_pair(d, old_lm, new_lm)) return rc_lm;
   *n_paths = 0;
   *total_arcs = 0;
   if (d->h_state[channel] == 0) return fail(WFST_E_STATE, "GetNbest before InitDecoding");
@@ -3455,7 +3499,7 @@ int nbw_begin(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t n_pat
   if ((old_lm == nullptr) != (new_lm == nullptr)) return fail(WFST_E_ARG, "bad argument (both LMs or neither)");
   if (n_paths < 1 || n_paths > 64) return fail(WFST_E_ARG, "1 <= n <= 64 paths (more: wfst_decoder_get_nbest_paths)");
   if (cap_words <= 0) return fail(WFST_E_ARG, "cap_words <= 0");
-  if (old_lm && (old_lm->device != d->device || new_lm->device != d->device)) return fail(WFST_E_ARG, "the LMs must be on the decoder's device");
+  if (const int rc_lm = check_lm_pair(d, old_lm, new_lm)) return rc_lm;
   if (n <= 0 || n > d->n_channels) return fail(WFST_E_ARG, "bad channel count");
   if (!d->D.lattice) return fail(WFST_E_STATE, "GetNbestTxt needs a decoder created with wfst_limits.lattice_links > 0");
   int rc = check_channel_list(d, channels, n, "GetNbestTxt", nullptr);

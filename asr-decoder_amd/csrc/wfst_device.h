@@ -96,8 +96,9 @@ __host__ __device__ inline uint32_t lm_hash(int32_t state, int32_t word) {
 #if defined(__HIPCC__)
 // Fsa::GetArc (newlm/arpa2fsa.cc:244-262): the arc of LM state `id` for `word`, false if the state
 // has none (the caller backs off).  State 0 (empty history) is indexed by word id directly
-// (SearchStartArc, arpa2fsa.h:211-214; wfst_decoder_create_biglm checks the graph's labels against
-// its arc count); the others by binary search over their word-id sorted arcs (SearchArc, :194-210).
+// (SearchStartArc, arpa2fsa.h:211-214; wfst_decoder_create_biglm and, for the second pass, check_lm_pair
+// check the graph's labels against its arc count); the others by binary search over their word-id
+// sorted arcs (SearchArc, :194-210).
 __device__ __forceinline__ bool fsa_getarc(const LmDev &L, int id, int word, float *w, int *to) {
   if (id == 0) {   // (state 0's arcs start the arc array: wfst_lm_from_arrays)
     const int2 x = L.wt[word];

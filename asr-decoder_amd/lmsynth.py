@@ -143,8 +143,18 @@ class NgramLm:
             arcs.append(dict())
             return len(arcs) - 1
 
+        def legal(words, lp):
+            """AnalyLine (arpa2fsa.cc:470-506): a line with <unk> in it (the id every unknown word maps to), with <s> anywhere but
+            first or </s> anywhere but last, or with log10 prob below -98 (the <s> unigram excepted) is not added"""
+            for i, w in enumerate(words):
+                if w == self.unk or (w == self.bos and i != 0) or (w == self.eos and i != len(words) - 1):
+                    return False
+            return not (float(_ln(lp)) / M_LN10 < -98.0) or (len(words) == 1 and words[0] == self.bos)
+
         start_w = []
         for words, lp, bo in self.grams[0]:
+            if not legal(words, lp):
+                continue
             w = words[0]
             while len(start_to) - 1 < w:                 # arpa2fsa.cc:531-537
                 start_to.append(new_state())
@@ -172,6 +182,8 @@ class NgramLm:
         for k in range(1, order):
             last = k + 1 == order
             for words, lp, bo in self.grams[k]:
+                if not legal(words, lp):
+                    continue
                 ctx = walk(words[:-1])
                 if ctx is None:                           # "no A B, but have A B C": not added (:566-573)
                     continue

@@ -33,7 +33,7 @@ SYMBOLS = [
     "wfst_decoder_get_stats", "wfst_decoder_get_frontier", "wfst_decoder_set_profiling",
     "wfst_decoder_get_profile", "wfst_decoder_get_profile_busy", "wfst_decoder_channel_groups", "wfst_decoder_get_raw_lattice", "wfst_decoder_get_nbest",
     "wfst_options_default", "wfst_graph_options_default", "wfst_graph_load_ex", "wfst_graph_from_arrays_ex",
-    "wfst_decoder_create_ex", "wfst_lm_load", "wfst_lm_from_arrays", "wfst_lm_info", "wfst_lm_free",
+    "wfst_decoder_create_ex", "wfst_lm_load", "wfst_lm_from_arrays", "wfst_lm_info", "wfst_lm_table_stats", "wfst_lm_free",
     "wfst_decoder_create_biglm", "wfst_decoder_get_determinized_lattice", "wfst_decoder_get_lattice_stats", "wfst_decoder_get_rescored_lattice", "wfst_decoder_get_nbest_paths",
     "wfst_decoder_get_degraded_frames", "wfst_decoder_get_prune_raw_abandoned", "wfst_host_alloc", "wfst_host_free", "wfst_decoder_busy", "wfst_decoder_calls_in_flight", "wfst_decoder_get_determinizer_ms", "wfst_decoder_best_path_enqueue", "wfst_decoder_best_path_ready", "wfst_decoder_best_path_fetch", "wfst_decoder_prefetch_nbest", "wfst_decoder_get_prefetched_nbest_paths", "wfst_decoder_get_path_flags", "wfst_decoder_rescore_lattices", "wfst_decoder_nbest_paths_batch",
     "wfst_decoder_prefetch_determinized", "wfst_lattice_labels_batch",
@@ -341,6 +341,14 @@ class Lm:
         b = C.c_int64()
         _check(lib().wfst_lm_info(self.h, *[C.byref(x) for x in v], C.byref(b)))
         return dict(bos=v[0].value, eos=v[1].value, n_states=v[2].value, n_arcs=v[3].value, n_words=v[4].value, device_bytes=b.value)
+
+    def table_stats(self):
+        """The device (state, word) table as the upload left it (wfst_lm_table_stats): table_size slots, `used` occupied,
+        longest_run (cyclic) of occupied slots, max_displacement of an entry from its home slot, wraps (a run over the last slot and slot 0)."""
+        size = C.c_int64()
+        v = [C.c_int32() for _ in range(4)]
+        _check(lib().wfst_lm_table_stats(self.h, C.byref(size), *[C.byref(x) for x in v]))
+        return dict(table_size=size.value, used=v[0].value, longest_run=v[1].value, max_displacement=v[2].value, wraps=bool(v[3].value))
 
     def free(self):
         if self.h:

@@ -223,6 +223,13 @@ int wfst_lm_from_arrays(int32_t bos, int32_t eos, int32_t unk, int32_t n_states,
                         int32_t n_arcs, const wfst_lm_arc *arcs, float scale, int device, wfst_lm **out);
 int wfst_lm_info(const wfst_lm *lm, int32_t *bos, int32_t *eos, int32_t *n_states, int32_t *n_arcs,
                  int32_t *n_words /* arcs of the empty-history state */, int64_t *device_bytes);
+/* The shape of the LM's device look-up table, as the upload left it: every arc of a state other than the empty history sits in one
+ * open-addressed (state, word) table with linear probing.  table_size slots (a power of two), `used` of them occupied; longest_run
+ * = the longest cyclic run of occupied slots; max_displacement = the farthest an entry sits past its home slot; wraps = 1 if an
+ * occupied run covers both the last slot and slot 0.  Computed on the host at upload; any output pointer may be NULL.  For tests
+ * and tuning: nothing a result depends on. */
+int wfst_lm_table_stats(const wfst_lm *lm, int64_t *table_size, int32_t *used, int32_t *longest_run, int32_t *max_displacement,
+                        int32_t *wraps);
 void wfst_lm_free(wfst_lm *lm);
 
 /* ---- decoder ----------------------------------------------------------------------------- */
@@ -446,7 +453,12 @@ int wfst_decoder_get_determinized_lattice(wfst_decoder *d, int32_t channel, int3
  * one -- ComposeLattice twice (newfst/compose-lat-inl.h:15-130: pairs (lattice state, LM state) breadth first, a word-labelled arc
  * steps ComposeArpaLm and adds its cost, an arc into a final state adds the LM's final cost and makes the composed state final),
  * each followed by Connect -- on the device, over the determinized lattice resident there and the LM automata in HBM.  Outputs as
- * wfst_decoder_get_determinized_lattice (st_final here marks the composed final states).  One channel per call. */
+ * wfst_decoder_get_determinized_lattice (st_final here marks the composed final states).  One channel per call.
+ * THE LABEL CHECK of every call that takes an LM pair for the second pass (this one, wfst_decoder_get_nbest_paths,
+ * wfst_decoder_rescore_lattices, wfst_decoder_nbest_paths_batch, wfst_decoder_get_nbest_words): the rule of
+ * wfst_decoder_create_biglm -- the decoder's graph has no negative output label and its largest one is below the arc count of both
+ * LMs' empty-history states (wfst_lm_info's n_words); WFST_E_FORMAT otherwise, before any device work, and what the decoder holds
+ * for the channel stays as it was.  (The empty-history state is indexed by word id without a bound, arpa2fsa.cc:253-254.) */
 int wfst_decoder_get_rescored_lattice(wfst_decoder *d, int32_t channel, int32_t use_final_probs, const wfst_lm *old_lm,
                                       const wfst_lm *new_lm, int32_t cap_states, int32_t cap_arcs, int32_t *n_states,
                                       int32_t *n_arcs, int32_t *st_final, int32_t *a_src, int32_t *a_dst, int32_t *a_ilabel,
