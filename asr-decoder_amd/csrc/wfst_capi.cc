@@ -50,6 +50,7 @@ struct wfst_graph {
   int32_t max_col = 0;  // largest log-likelihood column any arc reads
   int32_t max_olabel = 0, min_olabel = 0;  // over all arcs (biglm: the LMs must know every word)
   std::vector<int32_t> ilabel_host;  // original ilabels (re-mapped when tid2pdf changes)
+  int32_t max_ilabel = 0;            // the largest of them (the frame posteriors hold a label map against it)
   std::vector<int32_t> tid2phone;    // wfst_graph_set_tid2phone (entry 0 unused); empty: none set
   std::vector<uint16_t> code_host;   // degree code of the target state of every arc slot (fused rows; wfst_device.h)
   int32_t packed = 0;                // the arcs' first word = column | code << kColBits (ilabels below 2^20)
@@ -667,6 +668,8 @@ int wfst_graph_from_arrays_ex(int32_t start, int32_t final_state, int32_t n_stat
   g->max_olabel = max_ol;
   g->min_olabel = min_ol;
   g->ilabel_host.swap(h_il);
+  for (int32_t il : g->ilabel_host)
+    if (il != kHeaderLabel) g->max_ilabel = std::max(g->max_ilabel, il);
   g->code_host.swap(h_code);
   g->packed = packed ? 1 : 0;
   g->pos_host.swap(pos);
@@ -3639,6 +3642,7 @@ int align_begin(wfst_decoder *d, const int32_t *channels, int32_t n, AlignView *
   return WFST_OK;
 }
 int align_channel_state(const wfst_decoder *d, int32_t channel) { return d->h_state[(size_t)channel]; }
+int32_t align_max_ilabel(const wfst_decoder *d) { return d->graph->max_ilabel; }
 int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_final_probs, std::vector<int32_t> *sizes) {
   HIP_TRY(hipSetDevice(d->device));
   int rc = finish_prefetch(d);

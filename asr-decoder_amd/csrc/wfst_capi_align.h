@@ -33,6 +33,10 @@ struct AlignState {
   // wfst_decoder_word_alternatives (wfst_capi_altern.h): what stays on the device -- A per state and sequence, the cells' "ended early"
   // mass, the (cell, word) tables of the sequences whose keys outgrow LDS
   DevBuf<double> alt;
+  // wfst_decoder_frame_posteriors (wfst_capi_framepost.h): the frames' staged lists and sums and the workspace of the frames whose
+  // records outgrow LDS; the caller's label map
+  DevBuf<double> fpost;
+  DevBuf<int32_t> fpost_idx, fpost_map;
 };
 
 // what the entry point sees of a decoder (sil_bits: the silence bitmap over transition-ids 1..sil_ntid, nullptr: none)
@@ -49,6 +53,8 @@ struct AlignView {
 int align_begin(wfst_decoder *d, const int32_t *channels, int32_t n, AlignView *v);
 // 0 never initialised, 1 decoding, 2 finalized
 int align_channel_state(const wfst_decoder *d, int32_t channel);
+// the largest ilabel of the decoder's graph, from the graph's host copy (what wfst_graph_set_tid2phone checks its map against)
+int32_t align_max_ilabel(const wfst_decoder *d);
 // A prefetch in flight harvested, the live channels of `list` emitted in one launch (launch_lattice_emit: the live-prune mode and
 // use_final_probs as GetRawLattice takes them), the control blocks read: sizes[4 i ..] = {states, arcs, frames decoded, error word}
 // of list[i]'s raw lattice as it sits on the device.  Synchronises the decoder's stream.
@@ -57,7 +63,7 @@ int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fi
 // ---- the round driver of the word queries (wfst_capi_wordquery.cc) ----------------------------------------------------------
 // wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence, wfst_decoder_sequence_posterior and
 // wfst_decoder_word_alternatives ask the listed channels' raw lattices about
-// n_seqs word sequences each: one table of states x (words + 1) cells per (channel, sequence) pair over the in-arc index
+// n_seqs word sequences each (wfst_decoder_frame_posteriors about one empty sequence each: wfst_capi_framepost.h): one table of states x (words + 1) cells per (channel, sequence) pair over the in-arc index
 // align_index_kernel builds.  word_query_run is the sequence they share; a WordQuery is what differs.
 
 #define ALIGN_TRY(expr)                                                                               \

@@ -602,6 +602,35 @@ struct AltDev {
 void launch_slot_mass(const AlignDev &A, const PostDev &P, const AltDev &Q, int cnt, hipStream_t s);
 void launch_slot_none(const AlignDev &A, const PostDev &P, const AltDev &Q, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- frame posteriors (wfst_framepost.hip) ---------------------------------------------------------------------------------
+// Per frame of a listed channel's raw lattice the posterior mass of every class (the ilabel of an emitting arc, or label_map of it),
+// over the in-arc index (AlignDev::idx) and posterior_kernel's gamma and chan_err (PostDev).  frame_post_kernel runs one workgroup
+// per (slot, frame), frame_pack_kernel one per slot.
+//   ws_key / ws_val[slot][na_cap]     the sort's pairs of a frame with more than kFramePostLdsRecs emitting arcs, at its record offset
+//   st_class / st_post[slot][na_cap]  a frame's list, by class ascending, at the frame's record offset
+//   st_cnt / st_distinct / st_mass[slot][fr_cap]  the list's length, n_distinct and frame_mass of a frame
+//   out[slot]   kFramePostHead ints {n_frames, n_entries, 1: the rows do not hold them, 0, error (kAln*), 0, 0, 0},
+//               frame_off[cap_frames + 1], n_distinct[cap_frames], entry_class[cap_entries]
+//   dout[slot]  frame_mass[cap_frames], entry_post[cap_entries]
+constexpr int32_t kFramePostHead = 8;
+constexpr int32_t kFramePostLdsRecs = 1024;   // WFST_FRAMEPOST_LDS_RECS
+struct FramePostDev {
+  const int32_t *label_map;   // [n_tid + 1], entry 0 unused; nullptr: the class is the ilabel
+  int32_t n_tid;
+  double min_post;
+  int32_t cap_frames, cap_entries;
+  uint32_t *ws_key;
+  double *ws_val;
+  int32_t *st_class;
+  double *st_post;
+  int32_t *st_cnt, *st_distinct;
+  double *st_mass;
+  int32_t *out;
+  double *dout;
+};
+constexpr int64_t frame_post_out_ints(int64_t cap_frames, int64_t cap_entries) { return kFramePostHead + 2 * cap_frames + 1 + cap_entries; }
+void launch_frame_post(const AlignDev &A, const PostDev &P, const FramePostDev &Q, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

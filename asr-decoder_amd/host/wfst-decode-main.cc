@@ -63,6 +63,12 @@
 //                  word; after the utterance's lines, per phrase "KEY phrase q found=0|1 count=.. conf=.. peak=FRAME": the expected
 //                  number of times a path of the RAW lattice says the phrase, min(1, count), and the lowest frame with the most of
 //                  that mass (the begin frame of the phrase's last word; -1: not found); scales as --sentence-posterior
+//   --frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]  batch shape and
+//                  --single-stream: FILE gets one line per utterance in Kaldi's text posterior form, "KEY [ c p c p ] [ ... ]", one
+//                  bracket per frame: the classes of the frame's emitting lattice arcs with their posterior mass, by class ascending
+//                  (FramePosteriors: wfst_decoder_frame_posteriors) -- the transition-ids (lattice-to-post), or their pdfs
+//                  (--tid2pdf=FILE) or phones (--tid2phone=FILE); the arcs cost GS * graph + AS * acoustic (default 1,1); X: only
+//                  the classes with a mass >= X.  The other output is what it is without the flag.
 //   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
 //                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
 //                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
@@ -129,6 +135,7 @@
 // prints the reference's "real-time factor assuming 100 frames/sec" (:189-192).
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <thread>
 #include <cstdio>
 #include <cstring>
@@ -237,6 +244,9 @@ int main(int argc, char **argv) {
     int nbest = 0, partial_nbest = 0, inflight = 1, chunk = 0, n_threads = 0, pool_channels = 0, linger_us = 50;
     bool pull = false, partial_words = false, word_times = false, live_prune = false, nbest_times = false;
     std::string align_file, nearest_file, phrase_file;
+    std::string frame_post_file, fp_class = "tid";
+    double fp_gs = 1.0, fp_as = 1.0, fp_min = 0.0;
+    bool fp_opts = false, fp_bad = false;
     bool word_conf = false, sent_post = false;
     int word_alts = 0;   // --word-alternatives[=K]: K, 0 = off
     double conf_gs = 1.0, conf_as = 1.0;
@@ -307,6 +317,17 @@ int main(int argc, char **argv) {
         word_alts = (int)k;
       }
       else if (a.compare(0, 19, "--phrase-posterior=") == 0) phrase_file = a.substr(19);
+      else if (a.compare(0, 13, "--frame-post=") == 0) frame_post_file = a.substr(13);
+      else if (a.compare(0, 19, "--frame-post-class=") == 0) { fp_class = a.substr(19); fp_opts = true; }
+      else if (a.compare(0, 20, "--frame-post-scales=") == 0) {
+        char tail = 0;
+        fp_opts = true;
+        if (sscanf(a.c_str() + 20, "%lf,%lf%c", &fp_gs, &fp_as, &tail) != 2 || !(fp_gs >= 0.0) || !(fp_as >= 0.0) || std::isinf(fp_gs) || std::isinf(fp_as)) fp_bad = true;
+      } else if (a.compare(0, 17, "--frame-post-min=") == 0) {
+        char tail = 0;
+        fp_opts = true;
+        if (sscanf(a.c_str() + 17, "%lf%c", &fp_min, &tail) != 1 || !(fp_min >= 0.0 && fp_min <= 1.0)) fp_bad = true;
+      }
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
           const size_t p1 = std::min(a.find(':', p0), a.size());
@@ -338,7 +359,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -358,6 +379,14 @@ int main(int argc, char **argv) {
     if (sent_post && !nbest_times && align_file.empty()) { std::cerr << "--sentence-posterior goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
     if (!phrase_file.empty() && n_threads > 0) { std::cerr << "--phrase-posterior goes with the batch shape or --single-stream\n"; return 1; }
     if (word_alts && !nbest_times && align_file.empty()) { std::cerr << "--word-alternatives goes with --nbest-word-times or --align-words=FILE\n"; return 1; }
+    const bool frame_post = !frame_post_file.empty();
+    if (frame_post_file.empty() && (fp_opts || fp_bad)) { std::cerr << "--frame-post-class / --frame-post-scales / --frame-post-min go with --frame-post=FILE\n"; return 1; }
+    if (frame_post && n_threads > 0) { std::cerr << "--frame-post goes with the batch shape or --single-stream\n"; return 1; }
+    if (fp_bad) { std::cerr << "--frame-post-scales=GS,AS: two finite numbers >= 0; --frame-post-min=X: 0 <= X <= 1\n"; return 1; }
+    if (frame_post && fp_class != "tid" && fp_class != "pdf" && fp_class != "phone") { std::cerr << "--frame-post-class=tid|pdf|phone\n"; return 1; }
+    if (frame_post && fp_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--frame-post-class=pdf needs --tid2pdf=FILE\n"; return 1; }
+    if (frame_post && fp_class == "phone" && tid2phone_file.empty()) { std::cerr << "--frame-post-class=phone needs --tid2phone=FILE\n"; return 1; }
+    const bool phones_for_frame_post = frame_post && fp_class == "phone";   // (--tid2phone given for this alone is no endpointing)
     // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
     for (int which = 0; which < 3; ++which) {
@@ -382,7 +411,7 @@ int main(int argc, char **argv) {
     if (live_prune && partial_nbest == 0) { std::cerr << "--live-lattice-prune goes with --chunk=N --partial-nbest=K\n"; return 1; }
     LatticeFasterDecoderConfig opt;
     opt.ReadConfigFile(pos[0]);
-    if (endpointing || print_endpoints || (!tid2phone_file.empty() && wt_silence.empty())) {
+    if (endpointing || print_endpoints || (!tid2phone_file.empty() && wt_silence.empty() && !phones_for_frame_post)) {
       // endpointing (v1-asr/asr-source.h:280-287): --tid2phone and --endpoint.silence-phones, a streaming shape, a search without LMs
       if (tid2phone_file.empty() || ep_opt.silence_phones.empty()) { std::cerr << "endpointing needs --tid2phone=FILE and --endpoint.silence-phones\n"; return 1; }
       if (chunk <= 0 || !(single || n_threads > 0)) { std::cerr << "endpointing goes with --chunk=N and --single-stream or --threads=N\n"; return 1; }
@@ -417,14 +446,38 @@ int main(int argc, char **argv) {
       // decodable ALSO maps, as the reference's does -- the decoder then asks it for one transition-id per pdf (Fst::SetTid2Pdf)
       for (auto &f : fsts) f->SetTid2Pdf(tid2pdf);
     }
+    std::vector<int32_t> tid2phone;
     if (!tid2phone_file.empty()) {   // TransitionModel::TransitionIdToPhone as a table (binary int32, entry 0 unused)
       std::ifstream t(tid2phone_file.c_str(), std::ios::binary | std::ios::ate);
       if (!t) { std::cerr << "cannot open " << tid2phone_file << "\n"; return 1; }
-      std::vector<int32_t> tid2phone((size_t)t.tellg() / 4);
+      tid2phone.resize((size_t)t.tellg() / 4);
       t.seekg(0);
       t.read((char *)tid2phone.data(), tid2phone.size() * 4);
       for (auto &f : fsts) f->SetTid2Phone(tid2phone);
     }
+    // --frame-post: the class of a transition-id, and the file
+    std::vector<int> fp_map;
+    if (frame_post && fp_class == "pdf") fp_map.assign(tid2pdf.begin(), tid2pdf.end());
+    if (frame_post && fp_class == "phone") fp_map.assign(tid2phone.begin(), tid2phone.end());
+    std::ofstream fp_out;
+    if (frame_post) {
+      fp_out.open(frame_post_file.c_str());
+      if (!fp_out) { std::cerr << "cannot write " << frame_post_file << "\n"; return 1; }
+    }
+    // "KEY [ c p c p ] [ ... ]": an utterance's line of --frame-post (a channel without a lattice: the key alone)
+    auto emit_frame_post = [&](const Utt &u, const FramePosteriors &fp) {
+      std::string o = u.key;
+      char buf[48];
+      for (int f = 0; f < fp.n_frames; ++f) {
+        o += " [";
+        for (int e = fp.frame_off[(size_t)f]; e < fp.frame_off[(size_t)f + 1]; ++e) {
+          snprintf(buf, sizeof(buf), " %d %.9g", fp.classes[(size_t)e], fp.posts[(size_t)e]);
+          o += buf;
+        }
+        o += " ]";
+      }
+      fp_out << o << "\n";
+    };
     std::ifstream in(pos[2].c_str(), std::ios::binary);
     if (!in) { std::cerr << "cannot open " << pos[2] << "\n"; return 1; }
     std::ofstream fout;
@@ -438,7 +491,7 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty();
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post;
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
     // (--word-confidence: a fourth column conf; --word-alternatives: " none=.. alts=word:post,...")
     auto time_lines = [&](const std::string &head, const std::vector<int> &words, const TimedSeq &a) {
@@ -994,6 +1047,11 @@ int main(int argc, char **argv) {
           decode.NearestWords(nearest_refs[u.key], &np);
           emit_nearest(u, np);
         }
+        if (frame_post) {
+          FramePosteriors fp;
+          decode.FramePosteriors(&fp, fp_map, fp_min, true, fp_gs, fp_as);
+          emit_frame_post(u, fp);
+        }
       }
     } else {  // the MI355X shape: `batch` utterances per pass, `inflight` passes at a time
       struct BatchOut {
@@ -1006,6 +1064,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<TimedSeq> > nb_times, al_times;  // --nbest-word-times, --align-words
         std::vector<std::vector<SequencePosterior> > phrase_post;     // --phrase-posterior
         std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
+        std::vector<FramePosteriors> frame_post;                      // --frame-post
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -1147,6 +1206,7 @@ int main(int argc, char **argv) {
               }
               decode.NearestWords(ch, refs, true, &o.nearest);
             }
+            if (frame_post) decode.FramePosteriors(ch, true, fp_gs, fp_as, fp_map, fp_min, &o.frame_post);   // every channel in one call
           }
         } catch (const std::exception &e) {
           errors[(size_t)k] = e.what();
@@ -1178,6 +1238,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && !o.al_times.empty(); ++i) emit_align(utts[b0 + i], o.al_times[i]);
         for (int i = 0; i < n && !o.phrase_post.empty(); ++i) emit_phrases(utts[b0 + i], o.phrase_post[i]);
         for (int i = 0; i < n && !o.nearest.empty(); ++i) emit_nearest(utts[b0 + i], o.nearest[i]);
+        for (int i = 0; i < n && !o.frame_post.empty(); ++i) emit_frame_post(utts[b0 + i], o.frame_post[i]);
       }
     }
     if (!nearest_refs.empty()) {   // errors over reference words, as nbest-compute-wer prints them

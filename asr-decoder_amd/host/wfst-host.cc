@@ -27,6 +27,7 @@
 #pragma weak wfst_decoder_word_confidence
 #pragma weak wfst_decoder_sequence_posterior
 #pragma weak wfst_decoder_word_alternatives
+#pragma weak wfst_decoder_frame_posteriors
 
 namespace datemoon {
 
@@ -2038,6 +2039,82 @@ void GpuLatticeDecoder::SequencePosteriors(const std::vector<std::vector<int> > 
                   [&](const auto &ch, const SeqLists &s, auto *o, auto *st) {
                     return SequencePosteriorsCall(_dec, ch, s, phrase, use_final_probs, graph_scale, acoustic_scale, 0, hit_mass, o, st);
                   });
+}
+
+// ---- frame posteriors (wfst_decoder_frame_posteriors) ----------------------------------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i] for listed channel i, its own code in status.  Returns the call's own code.  The rows take their
+// room from the frames decoded; a lattice that needs more is asked for again, once, with n_frames' and n_entries' room.
+static int FramePosteriorsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, bool use_final_probs, double graph_scale, double acoustic_scale,
+                               const std::vector<int> &label_map, double min_post, long long max_cells,
+                               std::vector<struct FramePosteriors> *out) {
+  if (!wfst_decoder_frame_posteriors)
+    throw std::runtime_error("FramePosteriors: this build's device library has no wfst_decoder_frame_posteriors");
+  const size_t cnt = ch.size();
+  const std::vector<int32_t> map(label_map.begin(), label_map.end());
+  size_t capf = 1;
+  for (int32_t c : ch) capf = std::max(capf, (size_t)std::max(wfst_decoder_num_frames_decoded(dec, c), 0));
+  size_t cape = 64 * capf;
+  std::vector<int32_t> st(cnt), nf(cnt), ne(cnt), off, nd, cls;
+  std::vector<double> lz(cnt), mass, post;
+  for (int pass = 0;; ++pass) {
+    off.assign(cnt * (capf + 1), 0); nd.assign(cnt * capf, 0); mass.assign(cnt * capf, 0.0);
+    cls.assign(cnt * cape, 0); post.assign(cnt * cape, 0.0);
+    const int rc = wfst_decoder_frame_posteriors(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, graph_scale, acoustic_scale,
+                                                 map.empty() ? nullptr : map.data(), map.empty() ? 0 : (int32_t)map.size() - 1, min_post, max_cells,
+                                                 (int32_t)capf, (int32_t)cape, st.data(), lz.data(), nf.data(), ne.data(), off.data(), nd.data(),
+                                                 mass.data(), cls.data(), post.data());
+    if (rc != WFST_OK) return rc;
+    size_t need_f = capf, need_e = cape;
+    for (size_t i = 0; i < cnt; ++i)
+      if (st[i] == WFST_E_CAPACITY) { need_f = std::max(need_f, (size_t)nf[i]); need_e = std::max(need_e, (size_t)ne[i]); }
+    if (pass || (need_f == capf && need_e == cape)) break;
+    capf = need_f; cape = need_e;
+  }
+  out->assign(cnt, FramePosteriors());
+  for (size_t i = 0; i < cnt; ++i) {
+    struct FramePosteriors &a = (*out)[i];
+    a.status = st[i];
+    a.log_z = lz[i];
+    a.n_frames = nf[i];
+    if (st[i] != WFST_OK) continue;
+    const size_t f = (size_t)nf[i], e = (size_t)ne[i];
+    a.frame_off.assign(off.begin() + i * (capf + 1), off.begin() + i * (capf + 1) + f + 1);
+    a.n_distinct.assign(nd.begin() + i * capf, nd.begin() + i * capf + f);
+    a.frame_mass.assign(mass.begin() + i * capf, mass.begin() + i * capf + f);
+    a.classes.assign(cls.begin() + i * cape, cls.begin() + i * cape + e);
+    a.posts.assign(post.begin() + i * cape, post.begin() + i * cape + e);
+  }
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::FramePosteriors(const std::vector<int> &channels, bool use_final_probs, double graph_scale, double acoustic_scale,
+                                      const std::vector<int> &label_map, double min_post, std::vector<struct FramePosteriors> *out,
+                                      std::vector<int> *status, long long max_cells) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<struct FramePosteriors> o;
+  if (FramePosteriorsCall(_dec, ch, use_final_probs, graph_scale, acoustic_scale, label_map, min_post, max_cells, &o) != WFST_OK)
+    Fatal("FramePosteriors");
+  if (status) status->clear();
+  for (const struct FramePosteriors &a : o) {
+    if (status) status->push_back(a.status);
+    else if (a.status != WFST_OK) Fatal("FramePosteriors");
+  }
+  if (out) out->swap(o);
+}
+
+void GpuLatticeDecoder::FramePosteriors(struct FramePosteriors *out, const std::vector<int> &label_map, double min_post, bool use_final_probs,
+                                        double graph_scale, double acoustic_scale) {
+  std::vector<struct FramePosteriors> o;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = FramePosteriorsCall(_dec, std::vector<int32_t>(1, _chan), use_final_probs, graph_scale, acoustic_scale, label_map, min_post, 0, &o);
+    if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("FramePosteriors: " + msg);
+  if (out) *out = o[0];
 }
 
 // ---- the lattice path nearest a transcript (wfst_decoder_nearest_words) ---------------------------------------------------------------

@@ -447,6 +447,18 @@ struct SequencePosterior {
   int peak = -1;
 };
 
+// Frame posteriors of a channel's raw lattice (wfst_decoder_frame_posteriors), Kaldi's lattice-to-post: per frame f the classes of the
+// frame's emitting arcs -- the transition-id, or label_map[transition-id]: a pdf, a phone -- with their posterior mass, as
+// classes / posts[frame_off[f] .. frame_off[f + 1]), by class ascending, only those with a mass > 0 and >= min_post; n_distinct[f] =
+// the classes with a mass > 0 and frame_mass[f] = their sum, both before the threshold.  n_frames = 0 (log_z 0, nothing listed): the
+// channel has no lattice.  status: WFST_OK or the channel's own error code.  The doubles are reproducible to rounding, not bit for bit.
+struct FramePosteriors {
+  int status = 0, n_frames = 0;
+  double log_z = 0.0;
+  std::vector<int> frame_off, classes, n_distinct;
+  std::vector<double> posts, frame_mass;
+};
+
 // The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
 // cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
 // them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
@@ -563,6 +575,11 @@ class GpuLatticeDecoder : public DecoderItf {
   // (*out)[k] for seqs[k].  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void SequencePosteriors(const std::vector<std::vector<int> > &seqs, std::vector<SequencePosterior> *out, bool phrase = false,
                           bool use_final_probs = true, double graph_scale = 1.0, double acoustic_scale = 1.0, bool hit_mass = false);
+  // What the channel's RAW lattice says at every frame, mid-utterance or after FinalizeDecoding: the posterior of each transition-id,
+  // or of each class of label_map (n_tid + 1 entries >= 0, entry 0 unused; empty: none), in one device call
+  // (wfst_decoder_frame_posteriors).  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void FramePosteriors(struct FramePosteriors *out, const std::vector<int> &label_map = std::vector<int>(), double min_post = 0.0,
+                       bool use_final_probs = true, double graph_scale = 1.0, double acoustic_scale = 1.0);
   // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
   // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
@@ -687,6 +704,12 @@ class GpuBatchDecoder {
   void SequencePosteriors(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &seqs, bool phrase,
                           bool use_final_probs, double graph_scale, double acoustic_scale, std::vector<std::vector<SequencePosterior> > *out,
                           std::vector<int> *status = nullptr, long long max_cells = 0, bool hit_mass = false);
+  // FramePosteriors (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
+  // (*out)[i] for listed channel i, its own error code in (*out)[i].status (without `status` it throws); the rows are given the room
+  // the lattices need.  max_cells: see wfst_decoder_frame_posteriors.
+  void FramePosteriors(const std::vector<int> &channels, bool use_final_probs, double graph_scale, double acoustic_scale,
+                       const std::vector<int> &label_map, double min_post, std::vector<struct FramePosteriors> *out,
+                       std::vector<int> *status = nullptr, long long max_cells = 0);
   // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
   // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.

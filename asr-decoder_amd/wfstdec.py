@@ -47,7 +47,7 @@ SYMBOLS = [
     "wfst_decoder_get_nbest_words", "wfst_decoder_get_determinizer_slots",
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
     "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
-    "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives",
+    "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives", "wfst_decoder_frame_posteriors",
 ]
 
 
@@ -111,6 +111,32 @@ class _BestPaths(object):
     def __iter__(self):
         for i in range(len(self._items)):
             yield self[i]
+
+
+# BatchDecoder.frame_posteriors: the entries per decoded frame its first call has room for
+FRAME_POST_ENTRIES_PER_FRAME = 64
+
+
+def frame_post_lookup(result, classes_per_frame):
+    """The posterior of ONE class per frame out of a BatchDecoder.frame_posteriors() dict: classes_per_frame[f] is looked up among the
+    entries of frame f, 0.0 where it is not listed.  With a best path's transition-ids (one per frame) this is the hypothesis'
+    frame-level confidence trace.  Pure numpy; frames beyond the result's n_frames give 0.0."""
+    want = np.asarray(classes_per_frame, dtype=np.int64).reshape(-1)
+    off, cls, post = np.asarray(result["frame_off"], np.int64), np.asarray(result["classes"], np.int64), np.asarray(result["posts"], np.float64)
+    out = np.zeros(len(want), np.float64)
+    n = min(len(want), max(len(off) - 1, 0))
+    if n == 0 or len(cls) == 0:
+        return out
+    # the entries are ordered by (frame, class): one search in the combined key
+    frame_of = np.repeat(np.arange(len(off) - 1, dtype=np.int64), np.diff(off))
+    span = int(max(cls.max(), want.max(initial=0))) + 2
+    key = frame_of * span + cls
+    ask = np.arange(n, dtype=np.int64) * span + np.clip(want[:n], -1, span - 2)
+    at = np.searchsorted(key, ask)
+    hit = (at < len(key)) & (want[:n] >= 0)
+    hit[hit] = key[at[hit]] == ask[hit]
+    out[:n][hit] = post[at[hit]]
+    return out
 
 
 class WfstError(RuntimeError):
@@ -971,6 +997,46 @@ class BatchDecoder:
                     d["hit_mass"] = hit[i, q, :int(nf[i])].copy() if int(nf[i]) <= capf else None
                 row.append(d)
             out.append(row)
+        return out
+
+    def frame_posteriors(self, channels=None, use_final_probs=True, graph_scale=1.0, acoustic_scale=1.0, label_map=None, min_post=0.0,
+                         max_cells=0):
+        """Frame posteriors on the raw lattice, for a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_frame_posteriors): per frame the posterior mass of every class of the frame's emitting arcs -- the
+        transition-id, or label_map[transition-id] (an int32 array of n_tid + 1 entries >= 0, entry 0 unused: a tid -> pdf or
+        tid -> phone map) -- Kaldi's lattice-to-post.  Per channel one dict: status, log_z, n_frames, frame_off (int32,
+        n_frames + 1), classes and posts (the entries of frame f are frame_off[f] .. frame_off[f + 1], by class ascending; only
+        classes with a mass > 0 and >= min_post), n_distinct (int32 per frame: the classes with a mass > 0, before the threshold)
+        and frame_mass (float64 per frame: the sum over all classes, before the threshold).  Room is taken from the frames decoded;
+        the call is made once more where a channel reports that it needs more.  Reproducible to rounding, not bit for bit."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        m, n_tid = None, 0
+        if label_map is not None:
+            m = np.ascontiguousarray(label_map, dtype=np.int32)
+            n_tid = int(m.shape[0]) - 1
+        frames = max([self.num_frames_decoded(int(c)) for c in ch] + [1]) if cnt else 1
+        capf, cape = max(frames, 1), max(frames, 1) * FRAME_POST_ENTRIES_PER_FRAME
+        f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        for attempt in range(2):
+            status, nf, ne = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32), np.zeros(cnt, np.int32)
+            log_z = np.zeros(cnt, np.float64)
+            off, nd, mass = np.zeros((cnt, capf + 1), np.int32), np.zeros((cnt, capf), np.int32), np.zeros((cnt, capf), np.float64)
+            cls, post = np.zeros((cnt, cape), np.int32), np.zeros((cnt, cape), np.float64)
+            _check(lib().wfst_decoder_frame_posteriors(self.h, _i32(ch), cnt, int(bool(use_final_probs)), C.c_double(float(graph_scale)),
+                                                       C.c_double(float(acoustic_scale)), _i32(m) if m is not None else None, n_tid,
+                                                       C.c_double(float(min_post)), C.c_int64(int(max_cells)), capf, cape, _i32(status),
+                                                       f64(log_z), _i32(nf), _i32(ne), _i32(off), _i32(nd), f64(mass), _i32(cls), f64(post)))
+            short = (status == -4) & ((nf > capf) | (ne > cape))
+            if attempt or not short.any():
+                break
+            capf, cape = max(capf, int(nf.max())), max(cape, int(ne.max()))   # (a channel needs more room: once more, with it)
+        out = []
+        for i in range(cnt):
+            k, e = (int(nf[i]), int(ne[i])) if status[i] == 0 else (0, 0)
+            out.append(dict(status=int(status[i]), log_z=float(log_z[i]), n_frames=int(nf[i]), n_entries=int(ne[i]),
+                            frame_off=off[i, :k + 1].copy(), classes=cls[i, :e].copy(), posts=post[i, :e].copy(),
+                            n_distinct=nd[i, :k].copy(), frame_mass=mass[i, :k].copy()))
         return out
 
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):

@@ -700,6 +700,7 @@ int wfst_decoder_nearest_words(wfst_decoder *d, const int32_t *channels, int32_t
  * posteriors (lattice-to-post), minimum Bayes risk / confusion networks.  (The sentence posterior is wfst_decoder_sequence_posterior's,
  * below.)  (The confusion network pinned to a hypothesis -- the other words of a slot, and "no word" -- is
  * wfst_decoder_word_alternatives', below; minimum Bayes risk decoding stays out.)
+ * (The per-frame transition-id posteriors are wfst_decoder_frame_posteriors', further below.)
  *
  * A failure of ONE channel goes into status[i] with all of that channel's outputs zero, and the call still returns WFST_OK: a
  * sequence whose alignment table of states x (seq_len + 1) cells is beyond max_cells (WFST_E_CAPACITY; 0 = wfst_decoder_align_words'
@@ -773,7 +774,8 @@ int wfst_decoder_word_confidence(wfst_decoder *d, const int32_t *channels, int32
  * the call, and the other getters answer afterwards what they would have answered.  Synchronous, as wfst_decoder_align_words is and
  * for the same reason.
  * Not computed here: minimum Bayes risk decoding and confusion networks, per-frame transition-id posteriors (lattice-to-post).
- * (The confusion network pinned to a hypothesis is wfst_decoder_word_alternatives', below.) */
+ * (The confusion network pinned to a hypothesis is wfst_decoder_word_alternatives', below.)
+ * (The per-frame transition-id posteriors are wfst_decoder_frame_posteriors', further below.) */
 int wfst_decoder_sequence_posterior(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
                                     double graph_scale, double acoustic_scale, int32_t mode /* 0 sentence, 1 phrase */,
                                     int32_t n_seqs /* per channel, 1..64 */, int32_t cap_words,
@@ -834,7 +836,8 @@ int wfst_decoder_sequence_posterior(wfst_decoder *d, const int32_t *channels, in
  * everything wfst_decoder_word_confidence names) or WFST_E_STATE (as there).  Any output pointer may be NULL.  The decoder's state is
  * only read: decoding goes on bit for bit as without the call.  Synchronous, as wfst_decoder_align_words is and for the same reason.
  * Not computed here: minimum Bayes risk decoding, the merging of slots or new slots between the hypothesis' words (the pivot
- * algorithm's second half), per-frame transition-id posteriors. */
+ * algorithm's second half), per-frame transition-id posteriors.
+ * (The per-frame transition-id posteriors are wfst_decoder_frame_posteriors', right below.) */
 #define WFST_ALTERN_MAX_ALTS 16
 #define WFST_ALTERN_LDS_KEYS 1024 /* distinct (cell, word) pairs of a sequence the on-chip table takes */
 int wfst_decoder_word_alternatives(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
@@ -849,6 +852,58 @@ int wfst_decoder_word_alternatives(wfst_decoder *d, const int32_t *channels, int
                                    int32_t *n_distinct /* [n][n_seqs][cap_words] */,
                                    int32_t *alt_word, double *alt_post /* [n][n_seqs][cap_words][n_alts] */,
                                    double *path_logpost /* [n][n_seqs] */, float *tot_score, float *lm_score /* [n][n_seqs] */);
+
+/* ---- frame posteriors: transition-id, pdf or phone per frame ------------------------------------------------------------------------
+ * What the lattice says at every FRAME: the posterior mass of each transition-id of the frame's emitting arcs (Kaldi's
+ * lattice-to-post), or of each pdf or phone where the caller maps the transition-ids -- state and phone occupancies for adaptation,
+ * phone-level confidences, the frame-level confidence trace of a hypothesis, "which pdfs was the decoder torn between at frame t".
+ * For a list of channels, live and finalized ones mixed, one launch per stage (the live channels' lattices emitted,
+ * align_index_kernel, posterior_kernel, frame_post_kernel, frame_pack_kernel), the results back in one copy per round.
+ *
+ * Taken as it is from wfst_decoder_word_confidence: the lattice R, the scales, c(a), the rule that an arc whose float32 graph +
+ * acoustic is not finite is no arc, alpha, beta, log_z, gamma(a) and the way every sum is taken.
+ * A state has a frame.  An arc with ilabel 0 stays inside its frame; every other arc goes from frame f to f + 1.
+ *   class(a)      = ilabel(a) where label_map is NULL, label_map[ilabel(a)] otherwise (n_tid + 1 entries >= 0, entry 0 unused)
+ *   post(f, v)    = the sum of gamma(a) over the emitting arcs a (ilabel > 0) whose SOURCE state's frame is f and whose class is v
+ *   frame_mass[f] = the sum of post(f, v) over all v, before any threshold: 1 minus the weight of the complete paths that ended
+ *                   before frame f + 1 (a final state may have out-arcs), so 1 to rounding wherever every path runs to the end
+ *   n_distinct[f] = the number of classes with post(f, v) > 0
+ * The entries of frame f are the classes with post(f, v) > 0 and post(f, v) >= min_post (0 <= min_post <= 1, taken on the device's own
+ * sum), by class id ASCENDING: the order does not depend on the sums, so near ties cannot reorder a list.  An arc with ilabel 0 is
+ * in no frame's list, whatever word it carries; an arc on no complete path has gamma 0 and counts nowhere.
+ * n_frames[i] = the frames the lattice spans (the frames decoded); an empty lattice, or a finalized channel asked without
+ * final-probs, has n_frames = 0, log_z = 0 and no entries, as the sibling calls report "no lattice".
+ *
+ * Per listed channel i: log_z[i], n_frames[i], n_entries[i]; frame_off[i][0 .. n_frames[i]] (frame f's entries are
+ * frame_off[i][f] .. frame_off[i][f + 1] of the channel's rows, frame_off[i][n_frames[i]] = n_entries[i]); n_distinct[i][f] and
+ * frame_mass[i][f] for f < n_frames[i]; entry_class[i][e] and entry_post[i][e] (UNCLAMPED, in (0, 1] up to rounding) for
+ * e < n_entries[i].  What lies beyond is zero.
+ * The ORDER of a class' sum follows the device's arc index, which the launch that emits the lattice decides: the results are
+ * reproducible to rounding, NOT bit for bit.  A frame's (class, gamma) pairs are sorted and summed on chip where the frame has at
+ * most WFST_FRAMEPOST_LDS_RECS emitting arcs, and in the decoder's workspace otherwise; the answers do not depend on which.
+ *
+ * A failure of ONE channel goes into status[i] with that channel's lists zero, and the call still returns WFST_OK: a device error of
+ * that channel's utterance, a lattice of more than max_cells states (WFST_E_CAPACITY; 0 = wfst_decoder_word_confidence's default
+ * bound), or a lattice with n_frames[i] > cap_frames or n_entries[i] > cap_entries (WFST_E_CAPACITY: n_frames[i] and n_entries[i] are
+ * the room needed, so that the call can be repeated once; log_z[i] stands).  Beside wfst_decoder_word_confidence's posterior
+ * workspace the call takes 24 bytes per arc of a listed lattice (the staged lists and the sort's workspace) and 16 per frame.
+ * The call itself fails, before any device work, with WFST_E_ARG (a NULL decoder or channel list, a scale that is negative or not
+ * finite, min_post that is NaN or outside 0..1, cap_frames < 1, cap_entries < 1, max_cells < 0, label_map given with n_tid < 1 or with
+ * a negative entry, label_map shorter than the graph's largest ilabel -- from the graph's host copy, as wfst_graph_set_tid2phone
+ * checks its map -- a bad or duplicate channel list) or WFST_E_STATE (a decoder without lattice_links, a listed channel never
+ * initialised).  Any output pointer may be NULL.  The decoder's state is only read: decoding goes on bit for bit as without the call.
+ * Synchronous, as wfst_decoder_align_words is and for the same reason.
+ * Not computed here: minimum Bayes risk decoding and the pivot algorithm's second half. */
+#define WFST_FRAMEPOST_LDS_RECS 1024 /* emitting arcs of one frame that are sorted and summed on chip */
+int wfst_decoder_frame_posteriors(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                                  double graph_scale, double acoustic_scale,
+                                  const int32_t *label_map /* NULL, or n_tid + 1 entries, entry 0 unused */, int32_t n_tid,
+                                  double min_post, int64_t max_cells /* lattice states; 0 = default */,
+                                  int32_t cap_frames, int32_t cap_entries,
+                                  int32_t *status /* [n] */, double *log_z /* [n] */, int32_t *n_frames /* [n] */,
+                                  int32_t *n_entries /* [n] */, int32_t *frame_off /* [n][cap_frames + 1] */,
+                                  int32_t *n_distinct /* [n][cap_frames] */, double *frame_mass /* [n][cap_frames] */,
+                                  int32_t *entry_class /* [n][cap_entries] */, double *entry_post /* [n][cap_entries] */);
 
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
