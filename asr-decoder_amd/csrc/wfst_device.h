@@ -631,6 +631,35 @@ struct FramePostDev {
 constexpr int64_t frame_post_out_ints(int64_t cap_frames, int64_t cap_entries) { return kFramePostHead + 2 * cap_frames + 1 + cap_entries; }
 void launch_frame_post(const AlignDev &A, const PostDev &P, const FramePostDev &Q, int cnt, hipStream_t s);
 
+// ---- best paths under new scales (wfst_rescale.hip) -------------------------------------------------------------------------
+// The cheapest path of a listed channel's raw lattice at arc costs (gs * graph + as * acoustic) + (olabel != 0 ? wip : 0), float64,
+// for n_set settings (gs, as, wip) shared by the listed channels, over the in-arc index align_index_kernel built (AlignDev::idx; the
+// other fields of the AlignDev are not read).  rescale_kernel runs one workgroup per (slot, setting) pair.
+//   cells[]              the pairs' cells v[state] (float64, +inf: not reached), pair p at cell_off[p] (< 0: the pair is not run)
+//   path[p][path_cap]    the in-arc records of the traced path, last arc first; path_cap >= ns_cap
+//   out[p]               kRescaleHead ints {found, arcs on the path, tot bits, lm bits, error (kAln*), n_hyp, n_tids, 0, the low and
+//                        the high word of scaled_cost's bits, 0, 0}, hyp_words[cap_words], begin[cap_words], end[cap_words],
+//                        tids[cap_tids]
+constexpr int32_t kRescaleHead = 12;
+constexpr int32_t kRescaleMaxSettings = 64;
+struct RescaleSet {   // passed by value: the settings reach the kernel with its arguments
+  double v[3 * kRescaleMaxSettings];   // {graph_scale, acoustic_scale, word_penalty} per setting
+};
+struct RescaleDev {
+  const int4 *lat_toks;       // DecoderDev::lat_toks, lat_tok_cap entries per channel
+  int64_t lat_tok_cap;
+  const int64_t *cell_off;    // [cnt][n_set], in cells
+  double *cells;
+  int32_t *path;
+  int32_t path_cap;
+  int32_t n_set, cap_words, cap_tids;
+  const uint32_t *sil_bits;   // the silence bitmap over transition-ids 1..n_tid, or nullptr
+  int32_t n_tid;
+  int32_t *out;
+};
+constexpr int64_t rescale_out_ints(int64_t cap_words, int64_t cap_tids) { return kRescaleHead + 3 * cap_words + cap_tids; }
+void launch_rescale(const AlignDev &A, const RescaleDev &Q, const RescaleSet &S, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

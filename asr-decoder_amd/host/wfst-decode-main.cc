@@ -69,6 +69,12 @@
 //                  (FramePosteriors: wfst_decoder_frame_posteriors) -- the transition-ids (lattice-to-post), or their pdfs
 //                  (--tid2pdf=FILE) or phones (--tid2phone=FILE); the arcs cost GS * graph + AS * acoustic (default 1,1); X: only
 //                  the classes with a mass >= X.  The other output is what it is without the flag.
+//   --rescale=GS,AS,WIP[:GS,AS,WIP...]  batch shape and --single-stream: after the utterance's other lines, per setting (at most 64:
+//                  graph scale, acoustic scale, word insertion penalty) the best path of the RAW lattice picked again under it,
+//                  without decoding again (RescaledWords: wfst_decoder_rescaled_words; Kaldi's lattice-best-path-score), as
+//                  "KEY rescale q gs=.. as=.. wip=.. found=0|1 cost=.. tot=.. lm=.. : word(begin,end) ..." -- cost the path's cost
+//                  at the setting (float64, 17 digits), tot / lm its unscaled LatticeToVector scores.  The other output is what it
+//                  is without the flag.
 //   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
 //                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
 //                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
@@ -247,6 +253,8 @@ int main(int argc, char **argv) {
     std::string frame_post_file, fp_class = "tid";
     double fp_gs = 1.0, fp_as = 1.0, fp_min = 0.0;
     bool fp_opts = false, fp_bad = false;
+    std::vector<RescaleSetting> rescale_set;   // --rescale
+    bool rescale_bad = false;
     bool word_conf = false, sent_post = false;
     int word_alts = 0;   // --word-alternatives[=K]: K, 0 = off
     double conf_gs = 1.0, conf_as = 1.0;
@@ -328,6 +336,21 @@ int main(int argc, char **argv) {
         fp_opts = true;
         if (sscanf(a.c_str() + 17, "%lf%c", &fp_min, &tail) != 1 || !(fp_min >= 0.0 && fp_min <= 1.0)) fp_bad = true;
       }
+      else if (a.compare(0, 10, "--rescale=") == 0) {
+        // GS,AS,WIP[:GS,AS,WIP...]: every number whole, the scales finite and >= 0, the penalty finite
+        if (a.size() == 10) rescale_bad = true;
+        for (size_t p0 = 10; p0 < a.size() && !rescale_bad;) {
+          const size_t p1 = std::min(a.find(':', p0), a.size());
+          RescaleSetting r;
+          char tail = 0;
+          if (sscanf(a.substr(p0, p1 - p0).c_str(), "%lf,%lf,%lf%c", &r.graph_scale, &r.acoustic_scale, &r.word_penalty, &tail) != 3 ||
+              !(r.graph_scale >= 0.0) || !(r.acoustic_scale >= 0.0) || std::isinf(r.graph_scale) || std::isinf(r.acoustic_scale) ||
+              !std::isfinite(r.word_penalty) || p1 + 1 == a.size())
+            rescale_bad = true;
+          rescale_set.push_back(r);
+          p0 = p1 + 1;
+        }
+      }
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
           const size_t p1 = std::min(a.find(':', p0), a.size());
@@ -359,7 +382,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -386,6 +409,10 @@ int main(int argc, char **argv) {
     if (frame_post && fp_class != "tid" && fp_class != "pdf" && fp_class != "phone") { std::cerr << "--frame-post-class=tid|pdf|phone\n"; return 1; }
     if (frame_post && fp_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--frame-post-class=pdf needs --tid2pdf=FILE\n"; return 1; }
     if (frame_post && fp_class == "phone" && tid2phone_file.empty()) { std::cerr << "--frame-post-class=phone needs --tid2phone=FILE\n"; return 1; }
+    if (rescale_bad) { std::cerr << "--rescale=GS,AS,WIP[:GS,AS,WIP...]: per setting two finite scales >= 0 and a finite word penalty\n"; return 1; }
+    if (rescale_set.size() > 64) { std::cerr << "--rescale: more than 64 settings\n"; return 1; }
+    const bool rescale = !rescale_set.empty();
+    if (rescale && n_threads > 0) { std::cerr << "--rescale goes with the batch shape or --single-stream\n"; return 1; }
     const bool phones_for_frame_post = frame_post && fp_class == "phone";   // (--tid2phone given for this alone is no endpointing)
     // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
@@ -491,7 +518,7 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post;
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post || rescale;
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
     // (--word-confidence: a fourth column conf; --word-alternatives: " none=.. alts=word:post,...")
     auto time_lines = [&](const std::string &head, const std::vector<int> &words, const TimedSeq &a) {
@@ -636,6 +663,18 @@ int main(int argc, char **argv) {
         for (size_t j = 0; j < a.words.size(); ++j)
           out << head << "#" << (j + 1) << " " << a.words[j] << " " << a.frames[j].first << " " << a.frames[j].second << "\n";
         nr_err += a.errors; nr_words += (long long)it->second[q].size(); nr_ins += a.ins; nr_del += a.del; nr_sub += a.sub;
+      }
+    };
+    // --rescale: an utterance's lines, one per setting
+    auto emit_rescale = [&](const Utt &u, const std::vector<RescaledWords> &rw) {
+      for (size_t q = 0; q < rescale_set.size() && q < rw.size(); ++q) {
+        const RescaledWords &a = rw[q];
+        char buf[256];
+        snprintf(buf, sizeof(buf), " gs=%.9g as=%.9g wip=%.9g found=%d cost=%.17g tot=%.9g lm=%.9g :", rescale_set[q].graph_scale,
+                 rescale_set[q].acoustic_scale, rescale_set[q].word_penalty, a.found ? 1 : 0, a.scaled_cost, (double)a.tot, (double)a.lm);
+        out << u.key << " rescale " << (q + 1) << buf;
+        for (size_t j = 0; j < a.words.size(); ++j) out << ' ' << a.words[j] << '(' << a.frames[j].first << ',' << a.frames[j].second << ')';
+        out << '\n';
       }
     };
     auto emit_nbest = [&](const Utt &u, std::vector<Lattice> &paths, const std::vector<TimedSeq> *times = nullptr) {
@@ -1052,6 +1091,11 @@ int main(int argc, char **argv) {
           decode.FramePosteriors(&fp, fp_map, fp_min, true, fp_gs, fp_as);
           emit_frame_post(u, fp);
         }
+        if (rescale) {
+          std::vector<RescaledWords> rw;
+          decode.RescaledWords(rescale_set, &rw);
+          emit_rescale(u, rw);
+        }
       }
     } else {  // the MI355X shape: `batch` utterances per pass, `inflight` passes at a time
       struct BatchOut {
@@ -1065,6 +1109,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<SequencePosterior> > phrase_post;     // --phrase-posterior
         std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
         std::vector<FramePosteriors> frame_post;                      // --frame-post
+        std::vector<std::vector<RescaledWords> > rescaled;            // --rescale
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -1207,6 +1252,7 @@ int main(int argc, char **argv) {
               decode.NearestWords(ch, refs, true, &o.nearest);
             }
             if (frame_post) decode.FramePosteriors(ch, true, fp_gs, fp_as, fp_map, fp_min, &o.frame_post);   // every channel in one call
+            if (rescale) decode.RescaledWords(ch, rescale_set, true, &o.rescaled);                           // every channel and setting in one call
           }
         } catch (const std::exception &e) {
           errors[(size_t)k] = e.what();
@@ -1239,6 +1285,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && !o.phrase_post.empty(); ++i) emit_phrases(utts[b0 + i], o.phrase_post[i]);
         for (int i = 0; i < n && !o.nearest.empty(); ++i) emit_nearest(utts[b0 + i], o.nearest[i]);
         for (int i = 0; i < n && !o.frame_post.empty(); ++i) emit_frame_post(utts[b0 + i], o.frame_post[i]);
+        for (int i = 0; i < n && !o.rescaled.empty(); ++i) emit_rescale(utts[b0 + i], o.rescaled[i]);
       }
     }
     if (!nearest_refs.empty()) {   // errors over reference words, as nbest-compute-wer prints them

@@ -28,6 +28,7 @@
 #pragma weak wfst_decoder_sequence_posterior
 #pragma weak wfst_decoder_word_alternatives
 #pragma weak wfst_decoder_frame_posteriors
+#pragma weak wfst_decoder_rescaled_words
 
 namespace datemoon {
 
@@ -2172,6 +2173,74 @@ void GpuLatticeDecoder::NearestWords(const std::vector<std::vector<int> > &refs,
                   [&](const auto &ch, const SeqLists &r, auto *o, auto *st) {
                     return NearestWordsCall(_dec, ch, r, use_final_probs, 0, o, st);
                   });
+}
+
+// ---- best paths under new scales (wfst_decoder_rescaled_words) -------------------------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i][q] for settings[q], (*status)[i] the channel's own code.  Returns the call's own code.  A path
+// with more words or transition-ids than the first call made room for is asked for again, once, with the room needed.
+static int RescaledWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<RescaleSetting> &settings, bool use_final_probs,
+                             bool alignment, long long max_cells, std::vector<std::vector<struct RescaledWords> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_rescaled_words) throw std::runtime_error("RescaledWords: this build's device library has no wfst_decoder_rescaled_words");
+  const size_t cnt = ch.size(), ns = settings.size(), np = cnt * ns;
+  std::vector<double> set;
+  for (const RescaleSetting &s : settings) { set.push_back(s.graph_scale); set.push_back(s.acoustic_scale); set.push_back(s.word_penalty); }
+  size_t cap = 256, tcap = 1;
+  if (alignment)
+    for (int32_t c : ch) tcap = std::max(tcap, (size_t)std::max(wfst_decoder_num_frames_decoded(dec, c), 0));
+  std::vector<int32_t> st(cnt), found(np), na(np), nh(np), nt(np), hyp, b, e, tids;
+  std::vector<double> cost(np);
+  std::vector<float> t(np), l(np);
+  for (int pass = 0;; ++pass) {
+    hyp.assign(np * cap, 0); b.assign(np * cap, 0); e.assign(np * cap, 0);
+    if (alignment) tids.assign(np * tcap, 0);
+    const int rc = wfst_decoder_rescaled_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, (int32_t)ns, set.data(), (int32_t)cap,
+                                               (int32_t)tcap, max_cells, st.data(), found.data(), na.data(), nh.data(), nt.data(), hyp.data(),
+                                               b.data(), e.data(), alignment ? tids.data() : nullptr, cost.data(), t.data(), l.data());
+    if (rc != WFST_OK) return rc;
+    const size_t most = np ? (size_t)*std::max_element(nh.begin(), nh.end()) : 0;
+    const size_t most_t = np && alignment ? (size_t)*std::max_element(nt.begin(), nt.end()) : 0;
+    if ((most <= cap && most_t <= tcap) || pass) break;
+    cap = std::max(cap, most);
+    tcap = std::max(tcap, most_t);
+  }
+  out->assign(cnt, std::vector<struct RescaledWords>(ns));
+  for (size_t i = 0; i < cnt; ++i)
+    for (size_t q = 0; q < ns; ++q) {
+      struct RescaledWords &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.n_arcs = na[p]; a.scaled_cost = cost[p]; a.tot = t[p]; a.lm = l[p];
+      for (size_t j = 0; j < std::min((size_t)nh[p], cap); ++j) {
+        a.words.push_back(hyp[p * cap + j]);
+        a.frames.push_back(std::make_pair(b[p * cap + j], e[p * cap + j]));
+      }
+      if (alignment) a.tids.assign(tids.begin() + p * tcap, tids.begin() + p * tcap + std::min((size_t)nt[p], tcap));
+    }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::RescaledWords(const std::vector<int> &channels, const std::vector<RescaleSetting> &settings, bool use_final_probs,
+                                    std::vector<std::vector<struct RescaledWords> > *out, std::vector<int> *status, bool alignment,
+                                    long long max_cells) {
+  BatchWordQuery("RescaledWords", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return RescaledWordsCall(_dec, ch, settings, use_final_probs, alignment, max_cells, o, st);
+  });
+}
+
+void GpuLatticeDecoder::RescaledWords(const std::vector<RescaleSetting> &settings, std::vector<struct RescaledWords> *out, bool use_final_probs,
+                                      bool alignment) {
+  std::vector<std::vector<struct RescaledWords> > o;
+  std::vector<int> st;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = RescaledWordsCall(_dec, std::vector<int32_t>(1, _chan), settings, use_final_probs, alignment, 0, &o, &st);
+    if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("RescaledWords: " + msg);
+  if (out) out->swap(o[0]);
 }
 
 // ---- pruned live lattices (wfst_decoder_set_live_lattice_prune) ------------------------------------------------------------------

@@ -472,6 +472,24 @@ struct NearestPath {
   std::vector<std::pair<int, int> > frames;
 };
 
+// A setting of RescaledWords: the graph (LM) scale, the acoustic scale and the word insertion penalty the best path is picked under.
+struct RescaleSetting {
+  double graph_scale = 1.0, acoustic_scale = 1.0, word_penalty = 0.0;
+};
+
+// The best path of a channel's raw lattice under a RescaleSetting (wfst_decoder_rescaled_words; Kaldi's lattice-best-path-score):
+// words / frames[j] = its words with (begin, end) as WordAlignment has them; tids = its transition-ids (the alignment), where asked
+// for; scaled_cost = its cost at the setting, float64, bit for bit reproducible; tot / lm = LatticeToVector's two scores of the path,
+// UNSCALED.  found = false (everything else empty / zero): the channel has no lattice, or no final state of it is reached.
+struct RescaledWords {
+  bool found = false;
+  int n_arcs = 0;
+  double scaled_cost = 0.0;
+  float tot = 0.0f, lm = 0.0f;
+  std::vector<int> words, tids;
+  std::vector<std::pair<int, int> > frames;
+};
+
 class GpuLatticeDecoder : public DecoderItf {
  public:
   GpuLatticeDecoder(Fst *graph, const LatticeFasterDecoderConfig &config, const wfst_limits *limits = nullptr);
@@ -585,6 +603,12 @@ class GpuLatticeDecoder : public DecoderItf {
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
   // 1-best's).  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void NearestWords(const std::vector<std::vector<int> > &refs, std::vector<NearestPath> *out, bool use_final_probs = true);
+  // The channel's best path again under each of `settings` (at most 64) -- another LM weight, another acoustic scale, a word
+  // penalty -- on its RAW lattice, mid-utterance or after FinalizeDecoding, without decoding again (wfst_decoder_rescaled_words):
+  // (*out)[q] for settings[q]; alignment: also the paths' transition-ids.  The channel's own failure throws.  Over a pool the call
+  // runs in the batcher thread, like AlignWords.
+  void RescaledWords(const std::vector<RescaleSetting> &settings, std::vector<struct RescaledWords> *out, bool use_final_probs = true,
+                     bool alignment = false);
   // Pruned live lattices (see GpuChannelPool::SetLiveLatticePrune) for this object's device decoder: the private one, or -- over a
   // pool, and so under ShareDevice -- the shared decoder of every object on it (set it before the other threads decode).
   void SetLiveLatticePrune(bool on);
@@ -715,6 +739,12 @@ class GpuBatchDecoder {
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.
   void NearestWords(const std::vector<int> &channels, const std::vector<std::vector<std::vector<int> > > &refs, bool use_final_probs,
                     std::vector<std::vector<NearestPath> > *out, std::vector<int> *status = nullptr, long long max_cells = 0);
+  // RescaledWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage: the
+  // settings (at most 64) are shared by the listed channels, (*out)[i][q] is the answer of listed channel i under settings[q];
+  // (*status)[i]: WFST_OK or the channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_rescaled_words.
+  void RescaledWords(const std::vector<int> &channels, const std::vector<RescaleSetting> &settings, bool use_final_probs,
+                     std::vector<std::vector<struct RescaledWords> > *out, std::vector<int> *status = nullptr, bool alignment = false,
+                     long long max_cells = 0);
   void SetLiveLatticePrune(bool on);   // pruned live lattices for every channel (see GpuChannelPool::SetLiveLatticePrune)
   wfst_decoder *Handle() { return _dec; }
 

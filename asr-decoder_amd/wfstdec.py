@@ -48,6 +48,7 @@ SYMBOLS = [
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
     "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
     "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives", "wfst_decoder_frame_posteriors",
+    "wfst_decoder_rescaled_words",
 ]
 
 
@@ -1037,6 +1038,50 @@ class BatchDecoder:
             out.append(dict(status=int(status[i]), log_z=float(log_z[i]), n_frames=int(nf[i]), n_entries=int(ne[i]),
                             frame_off=off[i, :k + 1].copy(), classes=cls[i, :e].copy(), posts=post[i, :e].copy(),
                             n_distinct=nd[i, :k].copy(), frame_mass=mass[i, :k].copy()))
+        return out
+
+    def rescaled_words(self, settings, channels=None, use_final_probs=True, cap_words=256, cap_tids=0, max_cells=0):
+        """The best path of the raw lattice again under other scales and a word penalty, for a LIST of channels (None: all), live and
+        finalized ones mixed (wfst_decoder_rescaled_words; Kaldi's lattice-best-path-score): settings = up to 64 triples
+        (graph_scale, acoustic_scale, word_penalty), shared by the listed channels.  Per channel a list with one dict per setting:
+        found, n_arcs, n_hyp, hyp_words, begin / end (int32 arrays per word, frames, end exclusive), scaled_cost (float64: the
+        path's cost at the setting), tot, lm (float32: the path's own UNSCALED LatticeToVector scores), status -- WFST_OK or the
+        CHANNEL's own error code -- and, with cap_tids > 0, n_tids and tids (the alignment: the path's transition-ids).  Bit for
+        bit reproducible.  A path with more words or transition-ids than cap_words / cap_tids hold: the call is made once more,
+        with the room needed."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        st = np.ascontiguousarray(settings, dtype=np.float64).reshape(-1, 3)
+        ns = int(st.shape[0])
+        cap, tcap, want_tids = int(cap_words), int(cap_tids), int(cap_tids) != 0
+        f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        for attempt in range(2):
+            status, found, na, begin, end, tot, lm = self._word_results(cnt, max(ns, 1), max(cap, 1))
+            nh, nt = np.zeros((cnt, max(ns, 1)), np.int32), np.zeros((cnt, max(ns, 1)), np.int32)
+            hyp, cost = np.zeros((cnt, max(ns, 1), max(cap, 1)), np.int32), np.zeros((cnt, max(ns, 1)), np.float64)
+            tids = np.zeros((cnt, max(ns, 1), max(tcap, 1)), np.int32)
+            _check(lib().wfst_decoder_rescaled_words(self.h, _i32(ch), cnt, int(bool(use_final_probs)), ns, f64(st), cap, tcap,
+                                                     C.c_int64(int(max_cells)), _i32(status), _i32(found), _i32(na), _i32(nh), _i32(nt),
+                                                     _i32(hyp), _i32(begin), _i32(end), _i32(tids) if want_tids else None, f64(cost),
+                                                     _f32(tot), _f32(lm)))
+            short = (nh > cap) | ((nt > tcap) if want_tids else False)
+            if attempt or not np.any(short):
+                break
+            cap = max(cap, int(nh.max()))   # (a path needs more room: once more, with it)
+            if want_tids:
+                tcap = max(tcap, int(nt.max()))
+        out = []
+        for i in range(cnt):
+            row = []
+            for q in range(ns):
+                m = min(int(nh[i, q]), cap)
+                d = dict(found=bool(found[i, q]), n_arcs=int(na[i, q]), n_hyp=int(nh[i, q]), hyp_words=hyp[i, q, :m].copy(),
+                         begin=begin[i, q, :m].copy(), end=end[i, q, :m].copy(), scaled_cost=float(cost[i, q]), tot=np.float32(tot[i, q]),
+                         lm=np.float32(lm[i, q]), status=int(status[i]))
+                if want_tids:
+                    d.update(n_tids=int(nt[i, q]), tids=tids[i, q, :min(int(nt[i, q]), tcap)].copy())
+                row.append(d)
+            out.append(row)
         return out
 
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):

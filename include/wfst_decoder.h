@@ -905,6 +905,69 @@ int wfst_decoder_frame_posteriors(wfst_decoder *d, const int32_t *channels, int3
                                   int32_t *n_distinct /* [n][cap_frames] */, double *frame_mass /* [n][cap_frames] */,
                                   int32_t *entry_class /* [n][cap_entries] */, double *entry_post /* [n][cap_entries] */);
 
+/* ---- best paths under new scales: the 1-best again at another LM weight, acoustic scale and word penalty -----------------------------
+ * Everything above is decided at the scales the search ran with.  This call picks the best path of a channel's RAW lattice again under
+ * another graph (LM) scale, another acoustic scale and a word insertion penalty, without decoding again: Kaldi's
+ * lattice-best-path-score (kaldi-bin/bin/lattice-best-path-score.cc:93-116: ScaleLattice(LatticeScale(lm_scale, acoustic_scale)), then
+ * the shortest path, then the words, the alignment and (graph, acoustic, sum)), the tool every scoring script sweeps over LMWT x word
+ * penalty.  With wfst_decoder_nearest_words for the error count, tuning both on a development set is one decode plus two lattice
+ * calls; and the posterior calls, which take scales already, can be asked about the hypothesis that is best AT those scales.  For a
+ * list of channels, live and finalized ones mixed, and n_set (1..64) settings shared by all listed channels, settings[q] =
+ * (graph_scale gs, acoustic_scale as, word_penalty wip), one launch per stage (the live channels' lattices emitted,
+ * align_index_kernel, one dynamic program per (channel, setting): rescale_kernel).
+ *
+ * The lattice R is exactly wfst_decoder_align_words': what wfst_decoder_get_raw_lattice(channel, use_final_probs) returns at this
+ * moment, wfst_decoder_set_live_lattice_prune, the use_final_probs rule after FinalizeDecoding and "no lattice" honoured as there.
+ * State 0 is the start, every arc goes to a higher state id, final states are flagged and carry no weight, and an arc whose float32
+ * graph + acoustic is not finite is no arc, so that all the word queries see the same paths.
+ * The cost of an arc a under setting q, in float64:
+ *   c_q(a) = (gs * (double)graph + as * (double)acoustic) + (olabel(a) != 0 ? wip : 0.0)
+ * with every product and every sum rounded on its own -- no fused multiply-add; the kernel switches the compiler's contraction off
+ * for this expression, and that is why the result is reproducible: it is numpy's arithmetic.  The penalty goes by OLABEL, as
+ * everywhere here: a word may sit on an epsilon arc.  gs and as are finite and >= 0; wip is finite and of either sign.
+ * The cells: v[0] = +0.0; v[t] = the minimum over the in-arcs a: s -> t of (v[s] + c_q(a)) + 0.0; a sum that is not finite is no
+ * transition; a state not reached is greater than every other.  Float addition is monotone, so v[t] is the minimum over the paths
+ * from state 0 to t of the sequential float64 sum of c_q along the path.  A minimum does not depend on the order it is taken in, so
+ * the result is bit for bit the same whatever the order of the device's arc index.
+ * The answer ends in the final state e with the least v[e], the least graph state among equals; found = 0 only if no final state is
+ * reached at all.  The traceback runs backwards from e to state 0 by exact equality, (v[s] + c_q(a)) + 0.0 == v[t]; among several
+ * qualifying arcs the least key wins, the key being wfst_decoder_align_words' tuple: ilabel == 0 last, graph state of the source
+ * token, ilabel, olabel, bits of graph, bits of acoustic.  Nothing depends on the numbering of states or arcs.  On biglm lattices two
+ * tokens of a frame may share a graph state: a tie that survives the rule is unspecified there.
+ *
+ * Per listed channel i and setting q: found[i][q]; n_arcs; n_hyp and hyp_words[i][q][..], the non-zero olabels of the path in
+ * order; begin_frame / end_frame[i][q][j] per word by wfst_decoder_align_words' own definition over the path's arcs (the list of
+ * wfst_decoder_set_silence_phones included); scaled_cost = v[e]; tot_score = the float32 sequential sum of graph + acoustic along the
+ * path, each arc's own sum rounded first, and lm_score = the float32 sequential sum of graph, both UNSCALED: LatticeToVector's, as the
+ * other calls define them.  Where tids is given, n_tids and tids[i][q][..], the non-zero ilabels in path order (the alignment); with
+ * tids NULL the alignment is skipped and cap_tids is not looked at beyond its sign.
+ * The lattice was PRUNED at scales (1, 1): a path that lattice_beam dropped is not found again however good it would be under the
+ * new scales -- Kaldi's own caveat for its lattices.  Keep lattice_beam wide enough for the range that is swept.
+ *
+ * A failure of ONE channel goes into status[i] and the call still returns WFST_OK: a device error of that channel's utterance
+ * (found[i][..] = 0), a lattice of more than max_cells states (WFST_E_CAPACITY, found[i][..] = 0; 0 = 65 536 states x 65, the
+ * bound wfst_decoder_align_words has by default), or a path with n_hyp > cap_words or, where tids is given, n_tids > cap_tids
+ * (WFST_E_CAPACITY: the counts are the room needed, the first cap_words words and times and the first cap_tids transition-ids are
+ * written as wfst_decoder_nearest_words does, and everything else of the channel's answers stands).  The call takes 8 bytes per state
+ * and setting for the cells and 4 for the traced path, beside the index (32 bytes per arc and 8 per state of a listed lattice); the
+ * workspace is the decoder's, shared with wfst_decoder_align_words and grown on demand; lists whose cells pass 256 MiB together are
+ * taken in rounds.
+ * The call itself fails, before any device work, with WFST_E_ARG (a NULL decoder or channel list, n_set outside 1..64, NULL
+ * settings, a scale that is negative or not finite, a penalty that is not finite, cap_words <= 0, cap_tids < 0, max_cells < 0, a
+ * bad or duplicate channel list) or WFST_E_STATE (a decoder without lattice_links, a listed channel never initialised).  Any output
+ * pointer may be NULL.  The decoder's state is only read: decoding goes on bit for bit as without the call.  Synchronous, as
+ * wfst_decoder_align_words is and for the same reason.
+ * Not computed here: n-best lists under new scales, a second LM, and pruning the search itself with other scales. */
+int wfst_decoder_rescaled_words(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                                int32_t n_set /* 1..64, shared by the listed channels */,
+                                const double *settings /* [n_set][3]: graph_scale, acoustic_scale, word_penalty */,
+                                int32_t cap_words, int32_t cap_tids, int64_t max_cells /* lattice states; 0 = default */,
+                                int32_t *status /* [n] */, int32_t *found, int32_t *n_arcs, int32_t *n_hyp,
+                                int32_t *n_tids /* [n][n_set] */,
+                                int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame /* [n][n_set][cap_words] */,
+                                int32_t *tids /* [n][n_set][cap_tids], or NULL */,
+                                double *scaled_cost /* [n][n_set] */, float *tot_score, float *lm_score /* [n][n_set] */);
+
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
  * ConvertNbestToVector, then LatticeToVector per path) of channels of a lattice-mode decoder, finalized
