@@ -1,7 +1,8 @@
 // The in-arc index align_index_kernel (wfst_align.hip) leaves in a slot's block of AlignDev::idx, as the kernels that read it carve it:
 // align_kernel, nearest_kernel (wfst_nearest.hip), posterior_kernel / confidence_kernel (wfst_posterior.hip), seqpost_kernel
 // (wfst_seqpost.hip), slot_mass_kernel / slot_none_kernel (wfst_altern.hip), frame_post_kernel / frame_pack_kernel
-// (wfst_framepost.hip) and rescale_kernel (wfst_rescale.hip).  Device code only: included by the .hip files.
+// (wfst_framepost.hip), rescale_kernel (wfst_rescale.hip) and acc_kernel / seqstat_frame_kernel / seqstat_pack_kernel /
+// seqstat_dense_kernel (wfst_seqstat.hip).  Device code only: included by the .hip files.
 #ifndef WFST_ALIGN_INDEX_H_
 #define WFST_ALIGN_INDEX_H_
 

@@ -37,6 +37,11 @@ struct AlignState {
   // records outgrow LDS; the caller's label map
   DevBuf<double> fpost;
   DevBuf<int32_t> fpost_idx, fpost_map;
+  // wfst_decoder_sequence_stats (wfst_capi_seqstat.h): fa, fb, w, the staged lists and the sort's workspace; the reference rows beside
+  // the frames' counts; the caller's label map; the dense rows' pointers, pitches and row counts
+  DevBuf<double> sstat;
+  DevBuf<int32_t> sstat_idx, sstat_map;
+  DevBuf<int64_t> sstat_in;
 };
 
 // what the entry point sees of a decoder (sil_bits: the silence bitmap over transition-ids 1..sil_ntid, nullptr: none)
@@ -63,7 +68,8 @@ int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fi
 // ---- the round driver of the word queries (wfst_capi_wordquery.cc) ----------------------------------------------------------
 // wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence, wfst_decoder_sequence_posterior and
 // wfst_decoder_word_alternatives ask the listed channels' raw lattices about
-// n_seqs word sequences each (wfst_decoder_frame_posteriors about one empty sequence each: wfst_capi_framepost.h;
+// n_seqs word sequences each (wfst_decoder_frame_posteriors and wfst_decoder_sequence_stats about one empty sequence each:
+// wfst_capi_framepost.h, wfst_capi_seqstat.h;
 // wfst_decoder_rescaled_words about one empty sequence per setting: wfst_capi_rescale.h): one table of states x (words + 1) cells per (channel, sequence) pair over the in-arc index
 // align_index_kernel builds.  word_query_run is the sequence they share; a WordQuery is what differs.
 

@@ -1,5 +1,6 @@
 // word_query_run: what wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence,
-// wfst_decoder_sequence_posterior, wfst_decoder_word_alternatives, wfst_decoder_frame_posteriors and wfst_decoder_rescaled_words do
+// wfst_decoder_sequence_posterior, wfst_decoder_word_alternatives, wfst_decoder_frame_posteriors, wfst_decoder_rescaled_words and
+// wfst_decoder_sequence_stats do
 // alike -- see
 // wfst_capi_align.h.  It launches nothing: the entry points' own units do, in their launch() hooks.
 #include "wfst_capi_align.h"

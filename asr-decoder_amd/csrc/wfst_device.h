@@ -631,6 +631,51 @@ struct FramePostDev {
 constexpr int64_t frame_post_out_ints(int64_t cap_frames, int64_t cap_entries) { return kFramePostHead + 2 * cap_frames + 1 + cap_entries; }
 void launch_frame_post(const AlignDev &A, const PostDev &P, const FramePostDev &Q, int cnt, hipStream_t s);
 
+// ---- sequence-training statistics (wfst_seqstat.hip) -------------------------------------------------------------------------
+// The expectation-semiring pass behind sMBR and the MMI occupation difference, per frame of a listed channel's raw lattice, over the
+// in-arc index (AlignDev::idx) and posterior_kernel's alpha, beta, gamma, log_z, chan_err and by-source table (PostDev), which is
+// still resident behind that launch.  acc_kernel runs one workgroup per slot (sMBR only), seqstat_frame_kernel one per
+// (slot, frame), seqstat_pack_kernel one per slot, seqstat_dense_kernel one per (slot, frame row).
+//   ref[slot][fr_cap]                 the reference class of a frame, -1: unlabelled (the host pads)
+//   fa / fb[slot][ns_cap]             the expected accuracy of the partial paths into / out of a state
+//   w[slot][na_cap]                   the signed weight of an arc, by in-arc record; tot[slot] = fb[0]
+//   ws_key / ws_val / ws_w[slot][na_cap]   the sort's triples of a frame with more than kSeqStatLdsRecs emitting arcs
+//   st_class / st_post / st_value[slot][na_cap + fr_cap]  a frame's list, by class ascending, at the frame's record offset + the
+//                                     frame's number (every frame before it may hold MMI's one extra entry)
+//   st_cnt / st_flag[slot][fr_cap]    the list's length; bit 0 "labelled", bit 1 "dropped"
+//   out[slot]   kSeqStatHead ints {n_frames, n_entries, 1: the rows do not hold them, n_ref_frames, error (kAln*), n_dropped, 0, 0},
+//               frame_off[cap_frames + 1], entry_class[cap_entries]
+//   dout[slot]  tot_acc, entry_post[cap_entries], entry_value[cap_entries]
+//   grad / grad_pitch / grad_rows[slot]  the dense rows of a slot (nullptr: none), their pitch in floats and their number
+constexpr int32_t kSeqStatHead = 8;
+constexpr int32_t kSeqStatLdsRecs = 1024;   // WFST_SEQSTAT_LDS_RECS
+constexpr int32_t kSeqStatMaxSil = 64;      // WFST_SEQSTAT_MAX_SIL
+constexpr int32_t kSeqMmi = 0, kSeqSmbr = 1;   // WFST_SEQ_MMI, WFST_SEQ_SMBR
+struct SeqStatSil { int32_t v[kSeqStatMaxSil]; };   // passed by value: the list reaches the kernel with its arguments
+struct SeqStatDev {
+  const int32_t *label_map;   // [n_tid + 1], entry 0 unused; nullptr: the class is the ilabel
+  int32_t n_tid;
+  int32_t criterion, drop_frames, n_sil;
+  const int32_t *ref;
+  int32_t cap_frames, cap_entries;   // both 0: no lists are handed out
+  double *fa, *fb, *w, *tot;
+  uint32_t *ws_key;
+  double *ws_val, *ws_w;
+  int32_t *st_class;
+  double *st_post, *st_value;
+  int32_t *st_cnt, *st_flag;
+  int32_t *out;
+  double *dout;
+  float *const *grad;
+  const int64_t *grad_pitch;
+  const int32_t *grad_rows;
+  int32_t n_cols;
+  double grad_scale;
+};
+constexpr int64_t seq_stat_out_ints(int64_t cap_frames, int64_t cap_entries) { return kSeqStatHead + cap_frames + 1 + cap_entries; }
+constexpr int64_t seq_stat_out_doubles(int64_t cap_entries) { return 1 + 2 * cap_entries; }
+void launch_seq_stat(const AlignDev &A, const PostDev &P, const SeqStatDev &Q, const SeqStatSil &sil, int cnt, bool dense, hipStream_t s);
+
 // ---- best paths under new scales (wfst_rescale.hip) -------------------------------------------------------------------------
 // The cheapest path of a listed channel's raw lattice at arc costs (gs * graph + as * acoustic) + (olabel != 0 ? wip : 0), float64,
 // for n_set settings (gs, as, wip) shared by the listed channels, over the in-arc index align_index_kernel built (AlignDev::idx; the

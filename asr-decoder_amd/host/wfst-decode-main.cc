@@ -69,6 +69,16 @@
 //                  (FramePosteriors: wfst_decoder_frame_posteriors) -- the transition-ids (lattice-to-post), or their pdfs
 //                  (--tid2pdf=FILE) or phones (--tid2phone=FILE); the arcs cost GS * graph + AS * acoustic (default 1,1); X: only
 //                  the classes with a mass >= X.  The other output is what it is without the flag.
+//   --seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c]
+//                  [--seq-drop-frames]  batch shape and --single-stream: the sequence-training statistics of every utterance's RAW
+//                  lattice (SequenceStats: wfst_decoder_sequence_stats; Kaldi's lattice-to-smbr-post / lattice-to-mpe-post and the
+//                  MMI occupation difference).  --seq-ref=FILE holds one line "KEY c c c ..." per utterance, the numerator alignment's
+//                  class per frame (< 0: unlabelled; an utterance without a line is unlabelled throughout).  FILE gets two lines per
+//                  utterance: "KEY [ c v c v ] [ ... ]", Kaldi's text posterior form with the SIGNED values (17 digits), one bracket
+//                  per frame, by class ascending, and "KEY seq-stats criterion=.. tot_acc=.. n_frames=.. n_ref_frames=..
+//                  n_dropped=.. log_z=..".  Classes as --frame-post-class has them; the arcs cost GS * graph + AS * acoustic
+//                  (default 1,1); --seq-silence: classes that never count as correct (sMBR); --seq-drop-frames: MMI's
+//                  --drop-frames.  The other output is what it is without the flag.
 //   --rescale=GS,AS,WIP[:GS,AS,WIP...]  batch shape and --single-stream: after the utterance's other lines, per setting (at most 64:
 //                  graph scale, acoustic scale, word insertion penalty) the best path of the RAW lattice picked again under it,
 //                  without decoding again (RescaledWords: wfst_decoder_rescaled_words; Kaldi's lattice-best-path-score), as
@@ -253,6 +263,9 @@ int main(int argc, char **argv) {
     std::string frame_post_file, fp_class = "tid";
     double fp_gs = 1.0, fp_as = 1.0, fp_min = 0.0;
     bool fp_opts = false, fp_bad = false;
+    std::string seq_stats_file, seq_ref_file, seq_class = "tid", seq_criterion = "smbr";   // --seq-stats
+    SequenceStatsOptions seq_opt;
+    bool seq_opts = false, seq_bad = false;
     std::vector<RescaleSetting> rescale_set;   // --rescale
     bool rescale_bad = false;
     bool word_conf = false, sent_post = false;
@@ -336,6 +349,33 @@ int main(int argc, char **argv) {
         fp_opts = true;
         if (sscanf(a.c_str() + 17, "%lf%c", &fp_min, &tail) != 1 || !(fp_min >= 0.0 && fp_min <= 1.0)) fp_bad = true;
       }
+      else if (a.compare(0, 12, "--seq-stats=") == 0) seq_stats_file = a.substr(12);
+      else if (a.compare(0, 10, "--seq-ref=") == 0) { seq_ref_file = a.substr(10); seq_opts = true; }
+      else if (a.compare(0, 16, "--seq-criterion=") == 0) { seq_criterion = a.substr(16); seq_opts = true; }
+      else if (a.compare(0, 12, "--seq-class=") == 0) { seq_class = a.substr(12); seq_opts = true; }
+      else if (a == "--seq-drop-frames") { seq_opt.drop_frames = true; seq_opts = true; }
+      else if (a.compare(0, 13, "--seq-scales=") == 0) {
+        char tail = 0;
+        seq_opts = true;
+        if (sscanf(a.c_str() + 13, "%lf,%lf%c", &seq_opt.graph_scale, &seq_opt.acoustic_scale, &tail) != 2 || !(seq_opt.graph_scale >= 0.0) ||
+            !(seq_opt.acoustic_scale >= 0.0) || std::isinf(seq_opt.graph_scale) || std::isinf(seq_opt.acoustic_scale))
+          seq_bad = true;
+      } else if (a.compare(0, 14, "--seq-silence=") == 0) {
+        // a:b:c, every class whole and >= 0, strictly ascending, at most 64
+        seq_opts = true;
+        if (a.size() == 14) seq_bad = true;
+        for (size_t p0 = 14; p0 < a.size() && !seq_bad;) {
+          const size_t p1 = std::min(a.find(':', p0), a.size());
+          char *end = nullptr;
+          const std::string tok = a.substr(p0, p1 - p0);
+          const long v = strtol(tok.c_str(), &end, 10);
+          if (tok.empty() || *end != 0 || v < 0 || v > 0x7FFFFFFF || p1 + 1 == a.size() ||
+              (!seq_opt.sil_classes.empty() && v <= seq_opt.sil_classes.back()) || seq_opt.sil_classes.size() >= 64)
+            seq_bad = true;
+          seq_opt.sil_classes.push_back((int)v);
+          p0 = p1 + 1;
+        }
+      }
       else if (a.compare(0, 10, "--rescale=") == 0) {
         // GS,AS,WIP[:GS,AS,WIP...]: every number whole, the scales finite and >= 0, the penalty finite
         if (a.size() == 10) rescale_bad = true;
@@ -382,7 +422,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -409,11 +449,21 @@ int main(int argc, char **argv) {
     if (frame_post && fp_class != "tid" && fp_class != "pdf" && fp_class != "phone") { std::cerr << "--frame-post-class=tid|pdf|phone\n"; return 1; }
     if (frame_post && fp_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--frame-post-class=pdf needs --tid2pdf=FILE\n"; return 1; }
     if (frame_post && fp_class == "phone" && tid2phone_file.empty()) { std::cerr << "--frame-post-class=phone needs --tid2phone=FILE\n"; return 1; }
+    const bool seq_stats = !seq_stats_file.empty();
+    if (!seq_stats && (seq_opts || seq_bad)) { std::cerr << "--seq-ref / --seq-criterion / --seq-class / --seq-scales / --seq-silence / --seq-drop-frames go with --seq-stats=FILE\n"; return 1; }
+    if (seq_stats && seq_ref_file.empty()) { std::cerr << "--seq-stats=FILE needs --seq-ref=FILE\n"; return 1; }
+    if (seq_stats && n_threads > 0) { std::cerr << "--seq-stats goes with the batch shape or --single-stream\n"; return 1; }
+    if (seq_bad) { std::cerr << "--seq-scales=GS,AS: two finite numbers >= 0; --seq-silence=a:b:c: at most 64 classes >= 0, ascending\n"; return 1; }
+    if (seq_stats && seq_criterion != "smbr" && seq_criterion != "mmi") { std::cerr << "--seq-criterion=smbr|mmi\n"; return 1; }
+    if (seq_stats && seq_class != "tid" && seq_class != "pdf" && seq_class != "phone") { std::cerr << "--seq-class=tid|pdf|phone\n"; return 1; }
+    if (seq_stats && seq_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--seq-class=pdf needs --tid2pdf=FILE\n"; return 1; }
+    if (seq_stats && seq_class == "phone" && tid2phone_file.empty()) { std::cerr << "--seq-class=phone needs --tid2phone=FILE\n"; return 1; }
+    seq_opt.mmi = seq_criterion == "mmi";
     if (rescale_bad) { std::cerr << "--rescale=GS,AS,WIP[:GS,AS,WIP...]: per setting two finite scales >= 0 and a finite word penalty\n"; return 1; }
     if (rescale_set.size() > 64) { std::cerr << "--rescale: more than 64 settings\n"; return 1; }
     const bool rescale = !rescale_set.empty();
     if (rescale && n_threads > 0) { std::cerr << "--rescale goes with the batch shape or --single-stream\n"; return 1; }
-    const bool phones_for_frame_post = frame_post && fp_class == "phone";   // (--tid2phone given for this alone is no endpointing)
+    const bool phones_for_frame_post = (frame_post && fp_class == "phone") || (seq_stats && seq_class == "phone");   // (--tid2phone given for this alone is no endpointing)
     // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
     for (int which = 0; which < 3; ++which) {
@@ -505,6 +555,46 @@ int main(int argc, char **argv) {
       }
       fp_out << o << "\n";
     };
+    // --seq-stats: the class of a transition-id, the references by utterance key, and the file
+    if (seq_stats && seq_class == "pdf") seq_opt.label_map.assign(tid2pdf.begin(), tid2pdf.end());
+    if (seq_stats && seq_class == "phone") seq_opt.label_map.assign(tid2phone.begin(), tid2phone.end());
+    std::map<std::string, std::vector<int> > seq_refs;
+    std::ofstream seq_out;
+    if (seq_stats) {
+      std::ifstream rf(seq_ref_file.c_str());
+      if (!rf) { std::cerr << "cannot read " << seq_ref_file << "\n"; return 1; }
+      std::string line;
+      while (std::getline(rf, line)) {
+        std::istringstream ls(line);
+        std::string key;
+        if (!(ls >> key)) continue;
+        std::vector<int> &r = seq_refs[key];
+        r.clear();
+        for (int x; ls >> x;) r.push_back(x);
+      }
+      seq_out.open(seq_stats_file.c_str());
+      if (!seq_out) { std::cerr << "cannot write " << seq_stats_file << "\n"; return 1; }
+    }
+    auto seq_ref_of = [&](const Utt &u) {
+      auto it = seq_refs.find(u.key);
+      return it == seq_refs.end() ? std::vector<int>() : it->second;
+    };
+    // "KEY [ c v c v ] [ ... ]" and "KEY seq-stats ...": an utterance's two lines of --seq-stats
+    auto emit_seq_stats = [&](const Utt &u, const SequenceStats &ss) {
+      std::string o = u.key;
+      char buf[192];
+      for (int f = 0; f < ss.n_frames; ++f) {
+        o += " [";
+        for (int e = ss.frame_off[(size_t)f]; e < ss.frame_off[(size_t)f + 1]; ++e) {
+          snprintf(buf, sizeof(buf), " %d %.17g", ss.classes[(size_t)e], ss.values[(size_t)e]);
+          o += buf;
+        }
+        o += " ]";
+      }
+      snprintf(buf, sizeof(buf), " seq-stats criterion=%s tot_acc=%.17g n_frames=%d n_ref_frames=%d n_dropped=%d log_z=%.17g", seq_criterion.c_str(),
+               ss.tot_acc, ss.n_frames, ss.n_ref_frames, ss.n_dropped, ss.log_z);
+      seq_out << o << "\n" << u.key << buf << "\n";
+    };
     std::ifstream in(pos[2].c_str(), std::ios::binary);
     if (!in) { std::cerr << "cannot open " << pos[2] << "\n"; return 1; }
     std::ofstream fout;
@@ -518,7 +608,7 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post || rescale;
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post || rescale || seq_stats;
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
     // (--word-confidence: a fourth column conf; --word-alternatives: " none=.. alts=word:post,...")
     auto time_lines = [&](const std::string &head, const std::vector<int> &words, const TimedSeq &a) {
@@ -1091,6 +1181,11 @@ int main(int argc, char **argv) {
           decode.FramePosteriors(&fp, fp_map, fp_min, true, fp_gs, fp_as);
           emit_frame_post(u, fp);
         }
+        if (seq_stats) {
+          SequenceStats ss;
+          decode.SequenceStats(seq_ref_of(u), &ss, seq_opt);
+          emit_seq_stats(u, ss);
+        }
         if (rescale) {
           std::vector<RescaledWords> rw;
           decode.RescaledWords(rescale_set, &rw);
@@ -1110,6 +1205,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
         std::vector<FramePosteriors> frame_post;                      // --frame-post
         std::vector<std::vector<RescaledWords> > rescaled;            // --rescale
+        std::vector<SequenceStats> seq_stats;                         // --seq-stats
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -1253,6 +1349,11 @@ int main(int argc, char **argv) {
             }
             if (frame_post) decode.FramePosteriors(ch, true, fp_gs, fp_as, fp_map, fp_min, &o.frame_post);   // every channel in one call
             if (rescale) decode.RescaledWords(ch, rescale_set, true, &o.rescaled);                           // every channel and setting in one call
+            if (seq_stats) {                                                                                 // every channel in one call
+              std::vector<std::vector<int> > refs(n);
+              for (int i = 0; i < n; ++i) refs[i] = seq_ref_of(utts[b0 + i]);
+              decode.SequenceStats(ch, refs, seq_opt, &o.seq_stats);
+            }
           }
         } catch (const std::exception &e) {
           errors[(size_t)k] = e.what();
@@ -1286,6 +1387,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && !o.nearest.empty(); ++i) emit_nearest(utts[b0 + i], o.nearest[i]);
         for (int i = 0; i < n && !o.frame_post.empty(); ++i) emit_frame_post(utts[b0 + i], o.frame_post[i]);
         for (int i = 0; i < n && !o.rescaled.empty(); ++i) emit_rescale(utts[b0 + i], o.rescaled[i]);
+        for (int i = 0; i < n && !o.seq_stats.empty(); ++i) emit_seq_stats(utts[b0 + i], o.seq_stats[i]);
       }
     }
     if (!nearest_refs.empty()) {   // errors over reference words, as nbest-compute-wer prints them

@@ -29,6 +29,7 @@
 #pragma weak wfst_decoder_word_alternatives
 #pragma weak wfst_decoder_frame_posteriors
 #pragma weak wfst_decoder_rescaled_words
+#pragma weak wfst_decoder_sequence_stats
 
 namespace datemoon {
 
@@ -2115,6 +2116,93 @@ void GpuLatticeDecoder::FramePosteriors(struct FramePosteriors *out, const std::
     if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
   });
   if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("FramePosteriors: " + msg);
+  if (out) *out = o[0];
+}
+
+// ---- sequence-training statistics (wfst_decoder_sequence_stats) -------------------------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i] for listed channel i, its own code in status.  Returns the call's own code.  The rows take their
+// room from the frames decoded; a lattice that needs more is asked for again, once, with n_frames' and n_entries' room.
+static int SequenceStatsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const std::vector<std::vector<int> > &refs,
+                             const SequenceStatsOptions &opt, std::vector<struct SequenceStats> *out) {
+  if (!wfst_decoder_sequence_stats) throw std::runtime_error("SequenceStats: this build's device library has no wfst_decoder_sequence_stats");
+  const size_t cnt = ch.size();
+  if (refs.size() != cnt) throw std::runtime_error("SequenceStats: one reference per listed channel");
+  if (!opt.grad.empty() && (opt.grad.size() != cnt || opt.grad_frames.size() != cnt || (!opt.grad_pitch.empty() && opt.grad_pitch.size() != cnt)))
+    throw std::runtime_error("SequenceStats: grad, grad_frames and grad_pitch hold one entry per listed channel");
+  const std::vector<int32_t> map(opt.label_map.begin(), opt.label_map.end()), sil(opt.sil_classes.begin(), opt.sil_classes.end());
+  size_t cap_ref = 1;
+  for (const std::vector<int> &r : refs) cap_ref = std::max(cap_ref, r.size());
+  std::vector<int32_t> ref(cnt * cap_ref, -1), n_ref(cnt), rows(opt.grad_frames.begin(), opt.grad_frames.end());
+  for (size_t i = 0; i < cnt; ++i) {
+    std::copy(refs[i].begin(), refs[i].end(), ref.begin() + i * cap_ref);
+    n_ref[i] = (int32_t)refs[i].size();
+  }
+  const std::vector<int64_t> pitch(opt.grad_pitch.begin(), opt.grad_pitch.end());
+  size_t capf = 1;
+  for (int32_t c : ch) capf = std::max(capf, (size_t)std::max(wfst_decoder_num_frames_decoded(dec, c), 0));
+  size_t cape = 64 * capf;
+  std::vector<int32_t> st(cnt), nf(cnt), nr(cnt), nd(cnt), ne(cnt), off, cls;
+  std::vector<double> lz(cnt), tot(cnt), post, val;
+  for (int pass = 0;; ++pass) {
+    off.assign(cnt * (capf + 1), 0); cls.assign(cnt * cape, 0); post.assign(cnt * cape, 0.0); val.assign(cnt * cape, 0.0);
+    const int rc = wfst_decoder_sequence_stats(dec, ch.data(), (int32_t)cnt, opt.mmi ? WFST_SEQ_MMI : WFST_SEQ_SMBR, opt.use_final_probs ? 1 : 0,
+                                               opt.graph_scale, opt.acoustic_scale, map.empty() ? nullptr : map.data(),
+                                               map.empty() ? 0 : (int32_t)map.size() - 1, ref.data(), n_ref.data(), (int32_t)cap_ref,
+                                               sil.empty() ? nullptr : sil.data(), (int32_t)sil.size(), opt.drop_frames ? 1 : 0, opt.max_cells,
+                                               (int32_t)capf, (int32_t)cape, opt.grad.empty() ? nullptr : opt.grad.data(),
+                                               pitch.empty() ? nullptr : pitch.data(), rows.empty() ? nullptr : rows.data(), opt.n_cols,
+                                               opt.grad_scale, opt.consumer_stream, st.data(), lz.data(), tot.data(), nf.data(), nr.data(),
+                                               nd.data(), ne.data(), off.data(), cls.data(), post.data(), val.data());
+    if (rc != WFST_OK) return rc;
+    size_t need_f = capf, need_e = cape;
+    for (size_t i = 0; i < cnt; ++i)
+      if (st[i] == WFST_E_CAPACITY) { need_f = std::max(need_f, (size_t)nf[i]); need_e = std::max(need_e, (size_t)ne[i]); }
+    if (pass || (need_f == capf && need_e == cape)) break;
+    capf = need_f; cape = need_e;
+  }
+  out->assign(cnt, SequenceStats());
+  for (size_t i = 0; i < cnt; ++i) {
+    struct SequenceStats &a = (*out)[i];
+    a.status = st[i];
+    a.log_z = lz[i];
+    a.n_frames = nf[i];
+    if (st[i] != WFST_OK) continue;
+    a.tot_acc = tot[i];
+    a.n_ref_frames = nr[i];
+    a.n_dropped = nd[i];
+    const size_t f = (size_t)nf[i], e = (size_t)ne[i];
+    a.frame_off.assign(off.begin() + i * (capf + 1), off.begin() + i * (capf + 1) + f + 1);
+    a.classes.assign(cls.begin() + i * cape, cls.begin() + i * cape + e);
+    a.posts.assign(post.begin() + i * cape, post.begin() + i * cape + e);
+    a.values.assign(val.begin() + i * cape, val.begin() + i * cape + e);
+  }
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::SequenceStats(const std::vector<int> &channels, const std::vector<std::vector<int> > &refs, const SequenceStatsOptions &opt,
+                                    std::vector<struct SequenceStats> *out, std::vector<int> *status) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<struct SequenceStats> o;
+  if (SequenceStatsCall(_dec, ch, refs, opt, &o) != WFST_OK) Fatal("SequenceStats");
+  if (status) status->clear();
+  for (const struct SequenceStats &a : o) {
+    if (status) status->push_back(a.status);
+    else if (a.status != WFST_OK) Fatal("SequenceStats");
+  }
+  if (out) out->swap(o);
+}
+
+void GpuLatticeDecoder::SequenceStats(const std::vector<int> &ref, struct SequenceStats *out, const SequenceStatsOptions &opt) {
+  std::vector<struct SequenceStats> o;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = SequenceStatsCall(_dec, std::vector<int32_t>(1, _chan), std::vector<std::vector<int> >(1, ref), opt, &o);
+    if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("SequenceStats: " + msg);
   if (out) *out = o[0];
 }
 

@@ -459,6 +459,35 @@ struct FramePosteriors {
   std::vector<double> posts, frame_mass;
 };
 
+// Sequence-training statistics of a channel's raw lattice against a reference alignment (wfst_decoder_sequence_stats), Kaldi's
+// LatticeForwardBackwardMpeVariants "smbr" and LatticeForwardBackwardMmi: per frame f the classes with a posterior mass > 0 as
+// classes / posts / values[frame_off[f] .. frame_off[f + 1]), by class ascending; values = the derivative of the criterion with
+// respect to the class' score at that frame (under MMI with one more entry where the reference class is outside the lattice, or the
+// frame dropped: n_dropped); tot_acc = the expected number of correct frames (0 under MMI).  n_frames = 0: the channel has no
+// lattice.  status: WFST_OK or the channel's own error code.  The doubles are reproducible to rounding, not bit for bit.
+struct SequenceStats {
+  int status = 0, n_frames = 0, n_ref_frames = 0, n_dropped = 0;
+  double log_z = 0.0, tot_acc = 0.0;
+  std::vector<int> frame_off, classes;
+  std::vector<double> posts, values;
+};
+// What SequenceStats is asked with.  label_map: n_tid + 1 entries >= 0, entry 0 unused (empty: the class is the transition-id);
+// sil_classes: up to 64 class ids, ascending.  The dense output (see wfst_decoder_sequence_stats): grad[i] = a DEVICE pointer to
+// float32 [grad_frames[i]][n_cols] rows of grad_pitch[i] floats for listed channel i, or nullptr (grad empty: none; grad_pitch empty:
+// n_cols); consumer_stream: the hipStream_t that reads the rows next (nullptr: the default stream; WFST_STREAM_NONE: none).
+struct SequenceStatsOptions {
+  bool mmi = false, use_final_probs = true, drop_frames = false;
+  double graph_scale = 1.0, acoustic_scale = 1.0;
+  std::vector<int> label_map, sil_classes;
+  std::vector<void *> grad;
+  std::vector<long long> grad_pitch;
+  std::vector<int> grad_frames;
+  int n_cols = 0;
+  double grad_scale = 1.0;
+  void *consumer_stream = WFST_STREAM_NONE;
+  long long max_cells = 0;
+};
+
 // The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
 // cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
 // them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
@@ -598,6 +627,10 @@ class GpuLatticeDecoder : public DecoderItf {
   // (wfst_decoder_frame_posteriors).  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void FramePosteriors(struct FramePosteriors *out, const std::vector<int> &label_map = std::vector<int>(), double min_post = 0.0,
                        bool use_final_probs = true, double graph_scale = 1.0, double acoustic_scale = 1.0);
+  // The sMBR / MMI statistics of the channel's RAW lattice against `ref`, the numerator alignment's class per frame (< 0 or beyond its
+  // end: unlabelled), mid-utterance or after FinalizeDecoding, in one device call (wfst_decoder_sequence_stats); opt.grad holds at most
+  // one pointer.  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void SequenceStats(const std::vector<int> &ref, struct SequenceStats *out, const SequenceStatsOptions &opt = SequenceStatsOptions());
   // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
   // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
@@ -734,6 +767,11 @@ class GpuBatchDecoder {
   void FramePosteriors(const std::vector<int> &channels, bool use_final_probs, double graph_scale, double acoustic_scale,
                        const std::vector<int> &label_map, double min_post, std::vector<struct FramePosteriors> *out,
                        std::vector<int> *status = nullptr, long long max_cells = 0);
+  // SequenceStats (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
+  // refs[i] and (*out)[i] for listed channel i, its own error code in (*out)[i].status (without `status` it throws); the rows are
+  // given the room the lattices need.
+  void SequenceStats(const std::vector<int> &channels, const std::vector<std::vector<int> > &refs, const SequenceStatsOptions &opt,
+                     std::vector<struct SequenceStats> *out, std::vector<int> *status = nullptr);
   // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
   // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.

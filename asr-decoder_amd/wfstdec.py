@@ -20,6 +20,8 @@ WFST_OK = 0
 # wfst_decoder_advance_chunk: element types of a chunk, and "no producer stream" (the rows are complete)
 WFST_DTYPE_F32, WFST_DTYPE_F16, WFST_DTYPE_BF16 = 0, 1, 2
 WFST_STREAM_NONE = C.c_void_p(-1).value
+# wfst_decoder_sequence_stats: the criteria
+WFST_SEQ_MMI, WFST_SEQ_SMBR = 0, 1
 ERR_NAMES = {-1: "WFST_E_ARG", -2: "WFST_E_IO", -3: "WFST_E_DEVICE", -4: "WFST_E_CAPACITY",
              -5: "WFST_E_STATE", -6: "WFST_E_FORMAT"}
 
@@ -48,7 +50,7 @@ SYMBOLS = [
     "wfst_decoder_set_live_lattice_prune", "wfst_decoder_get_live_lattice_prune",
     "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
     "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives", "wfst_decoder_frame_posteriors",
-    "wfst_decoder_rescaled_words",
+    "wfst_decoder_rescaled_words", "wfst_decoder_sequence_stats",
 ]
 
 
@@ -1038,6 +1040,100 @@ class BatchDecoder:
             out.append(dict(status=int(status[i]), log_z=float(log_z[i]), n_frames=int(nf[i]), n_entries=int(ne[i]),
                             frame_off=off[i, :k + 1].copy(), classes=cls[i, :e].copy(), posts=post[i, :e].copy(),
                             n_distinct=nd[i, :k].copy(), frame_mass=mass[i, :k].copy()))
+        return out
+
+    def sequence_stats(self, refs, channels=None, criterion="smbr", use_final_probs=True, graph_scale=1.0, acoustic_scale=1.0,
+                       label_map=None, sil_classes=(), drop_frames=False, grad=None, grad_scale=1.0, stream="current", max_cells=0,
+                       lists=True):
+        """Sequence-training statistics on the raw lattice, for a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_sequence_stats; Kaldi's LatticeForwardBackwardMpeVariants "smbr" and LatticeForwardBackwardMmi): refs = per
+        listed channel the numerator alignment's class per frame (an int sequence; < 0 or beyond its end: unlabelled), classes as
+        frame_posteriors takes them (transition-ids, or label_map of them).  Per channel one dict: status, log_z, tot_acc (the
+        expected number of correct frames; 0 under "mmi"), n_frames, n_ref_frames, n_dropped, n_entries, frame_off (int32,
+        n_frames + 1), classes, posts and values (the entries of frame f are frame_off[f] .. frame_off[f + 1], by class ascending):
+        value is the derivative of the criterion with respect to the class' score at that frame.
+        grad: None, or per listed channel a 2-D float32 DEVICE tensor [frames][n_cols] (anything with data_ptr(), shape and stride(),
+        the last dimension contiguous; one width for all) or None: rows 0 .. min(n_frames, frames) - 1 become zeros with
+        float32(grad_scale * value) at each listed class' column.  stream: "current" = torch's current stream, which then waits for the
+        rows; a raw hipStream_t (int); None = WFST_STREAM_NONE.  lists=False: no lists are fetched (the dense rows and the numbers
+        only).  The call is made once more where a channel reports that its lists need more room."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        crit = {"mmi": WFST_SEQ_MMI, "smbr": WFST_SEQ_SMBR}.get(criterion, criterion)
+        if not isinstance(crit, int):
+            raise ValueError("criterion is 'smbr' or 'mmi'")
+        refs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in refs]
+        if len(refs) != cnt:
+            raise ValueError("one reference per listed channel")
+        cap_ref = max([len(r) for r in refs] + [1])
+        ref, n_ref = np.full((max(cnt, 1), cap_ref), -1, np.int32), np.zeros(max(cnt, 1), np.int32)
+        for i, r in enumerate(refs):
+            ref[i, :len(r)] = r
+            n_ref[i] = len(r)
+        m, n_tid = None, 0
+        if label_map is not None:
+            m = np.ascontiguousarray(label_map, dtype=np.int32)
+            n_tid = int(m.shape[0]) - 1
+        sil = np.ascontiguousarray(list(sil_classes), dtype=np.int32).reshape(-1)
+        ptrs = pitch = rows = None
+        n_cols = 0
+        if grad is not None:
+            grad = list(grad)
+            if len(grad) != cnt:
+                raise ValueError("one grad tensor (or None) per listed channel")
+            ptrs, pitch, rows = (C.c_void_p * max(cnt, 1))(), np.zeros(max(cnt, 1), np.int64), np.zeros(max(cnt, 1), np.int32)
+            for i, t in enumerate(grad):
+                if t is None:
+                    continue
+                if len(t.shape) != 2:
+                    raise ValueError("grad %d is not 2-D" % i)
+                if "float32" not in str(t.dtype):
+                    raise ValueError("grad %d is not float32" % i)
+                cols = int(t.shape[1])
+                if n_cols and cols != n_cols:
+                    raise ValueError("grad tensors differ in width")
+                n_cols = cols
+                st = t.stride()
+                if cols > 1 and int(st[1]) != 1:
+                    raise ValueError("the last dimension of grad %d is not contiguous" % i)
+                ptrs[i] = int(t.data_ptr())
+                rows[i] = int(t.shape[0])
+                pitch[i] = int(st[0]) if int(t.shape[0]) > 1 else max(int(st[0]), cols)
+            if not n_cols:
+                ptrs = None
+        if stream == "current":
+            stream = WFST_STREAM_NONE
+            if ptrs is not None:
+                import torch
+                stream = int(torch.cuda.current_stream().cuda_stream)
+        elif stream is None:
+            stream = WFST_STREAM_NONE
+        frames = max([self.num_frames_decoded(int(c)) for c in ch] + [1]) if cnt else 1
+        capf, cape = (max(frames, 1), max(frames, 1) * FRAME_POST_ENTRIES_PER_FRAME) if lists else (0, 0)
+        f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        for attempt in range(2):
+            status, nf, ne = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32), np.zeros(cnt, np.int32)
+            nr, ndrop = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32)
+            log_z, tot = np.zeros(cnt, np.float64), np.zeros(cnt, np.float64)
+            off = np.zeros((cnt, capf + 1), np.int32)
+            cls, post, val = np.zeros((cnt, cape), np.int32), np.zeros((cnt, cape), np.float64), np.zeros((cnt, cape), np.float64)
+            _check(lib().wfst_decoder_sequence_stats(
+                self.h, _i32(ch), cnt, int(crit), int(bool(use_final_probs)), C.c_double(float(graph_scale)), C.c_double(float(acoustic_scale)),
+                _i32(m) if m is not None else None, n_tid, _i32(ref), _i32(n_ref), cap_ref, _i32(sil) if len(sil) else None, int(len(sil)),
+                int(bool(drop_frames)), C.c_int64(int(max_cells)), capf, cape, ptrs,
+                pitch.ctypes.data_as(C.POINTER(C.c_int64)) if ptrs is not None else None, _i32(rows) if ptrs is not None else None,
+                int(n_cols), C.c_double(float(grad_scale)), C.c_void_p(int(stream)), _i32(status), f64(log_z), f64(tot), _i32(nf), _i32(nr),
+                _i32(ndrop), _i32(ne), _i32(off), _i32(cls), f64(post), f64(val)))
+            short = (status == -4) & ((nf > capf) | (ne > cape))
+            if attempt or not lists or not short.any():
+                break
+            capf, cape = max(capf, int(nf.max())), max(cape, int(ne.max()))   # (a channel needs more room: once more, with it)
+        out = []
+        for i in range(cnt):
+            k, e = (int(nf[i]), int(ne[i])) if status[i] == 0 and lists else (0, 0)
+            out.append(dict(status=int(status[i]), log_z=float(log_z[i]), tot_acc=float(tot[i]), n_frames=int(nf[i]),
+                            n_ref_frames=int(nr[i]), n_dropped=int(ndrop[i]), n_entries=int(ne[i]), frame_off=off[i, :k + 1].copy(),
+                            classes=cls[i, :e].copy(), posts=post[i, :e].copy(), values=val[i, :e].copy()))
         return out
 
     def rescaled_words(self, settings, channels=None, use_final_probs=True, cap_words=256, cap_tids=0, max_cells=0):

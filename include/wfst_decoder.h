@@ -905,6 +905,82 @@ int wfst_decoder_frame_posteriors(wfst_decoder *d, const int32_t *channels, int3
                                   int32_t *n_distinct /* [n][cap_frames] */, double *frame_mass /* [n][cap_frames] */,
                                   int32_t *entry_class /* [n][cap_entries] */, double *entry_post /* [n][cap_entries] */);
 
+/* ---- sequence-training statistics: MMI and sMBR on the raw lattice ----------------------------------------------------------------------
+ * The way back from the lattice to the acoustic model: per frame the derivative of the MMI or the sMBR criterion with respect to the
+ * scores of the frame's classes, for discriminative (sequence) training -- Kaldi's LatticeForwardBackwardMpeVariants with criterion
+ * "smbr" (kaldi/src/lat/lattice-functions.cc), the expectation-semiring pass, and the occupation difference of
+ * LatticeForwardBackwardMmi with --drop-frames.  For a list of channels, live and finalized ones mixed, one launch per stage (the live
+ * channels' lattices emitted, align_index_kernel, posterior_kernel, acc_kernel, seqstat_frame_kernel, seqstat_pack_kernel and, with
+ * dense rows, seqstat_dense_kernel), the lists back in one copy per round.
+ *
+ * The lattice is exactly wfst_decoder_frame_posteriors': the live-prune mode, use_final_probs, the rule that an arc whose float32
+ * graph + acoustic is not finite is no arc, c(a) = graph_scale * graph + acoustic_scale * acoustic, alpha, beta, log_z, gamma(a) and
+ * class(a) of an emitting arc (its transition-id, or label_map[tid]) are taken from there unchanged.  Float64 throughout.
+ * The caller gives ref[i][f] for f < n_ref[i], the numerator alignment's class per frame (ref[i][f] < 0 and f >= n_ref[i]: the frame is
+ * unlabelled), and sil_classes, up to WFST_SEQSTAT_MAX_SIL class ids >= 0, strictly ascending.
+ *   acc(a)     = 1 if a is an emitting arc out of frame f, ref[f] >= 0, class(a) == ref[f] and the class is not in sil_classes;
+ *                0 otherwise, and for every arc with ilabel 0
+ *   p_in(a)    = exp(-(alpha[s] + c(a) - alpha[t])),   p_out(a) = exp(-(c(a) + beta[t] - beta[s]))      (0 where not finite)
+ *   fa[0] = 0, fa[t] = sum over in-arcs  a: s -> t of p_in(a)  * (fa[s] + acc(a))
+ *              fb[s] = sum over out-arcs a: s -> t of p_out(a) * (fb[t] + acc(a))      (a final state's "stop here" term adds 0)
+ *   tot_acc    = fb[0]: the expected number of correct frames
+ *   w(a)       = gamma(a) * (fa[s] + acc(a) + fb[t] - tot_acc), signed
+ * level by level, as posterior_kernel orders a frame with arcs between its own states.  Per frame f and class v of an emitting arc
+ * out of f:
+ *   post(f, v)  = the sum of gamma(a)                     (wfst_decoder_frame_posteriors' number)
+ *   value(f, v) = the sum of w(a)                         under WFST_SEQ_SMBR
+ *   value(f, v) = [v == ref[f]] - post(f, v)              under WFST_SEQ_MMI, 0 everywhere on an unlabelled frame
+ * The list of frame f holds the classes with post(f, v) > 0 by class id ASCENDING (frame_posteriors' membership at min_post = 0),
+ * each entry (class, post, value).  Under MMI a labelled frame whose ref[f] is no such class gets one more entry (ref[f], 0, 1) at
+ * its place in the order; with drop_frames != 0 (Kaldi's --drop-frames) it gets none, every value of that frame is 0 and the frame
+ * counts in n_dropped.  drop_frames is not looked at under sMBR.  tot_acc is 0 under MMI.
+ *
+ * Per listed channel i: log_z, tot_acc, n_frames, n_ref_frames (the labelled frames below n_frames), n_dropped, n_entries,
+ * frame_off[i][0 .. n_frames[i]], entry_class / entry_post / entry_value[i][e] for e < n_entries[i].  What lies beyond is zero.
+ * cap_frames = cap_entries = 0: no lists are handed out (the channels' numbers and the dense rows only) and none can be too small.
+ * The dense output: grad NULL, or per listed channel a DEVICE pointer (NULL: none) to float32 [grad_frames[i]][n_cols] with a row
+ * pitch of grad_pitch[i] floats (grad_pitch NULL: n_cols).  Rows 0 .. min(n_frames[i], grad_frames[i]) - 1 are written: n_cols
+ * zeros, then float32(grad_scale * value(f, v)) at column v for every entry of the frame's list.  Nothing beyond n_cols in a row and
+ * no other row is touched.  A class is a column: a label_map entry or a ref class >= n_cols is refused, and without a map n_cols
+ * must exceed the graph's largest transition-id.  The writes run on the decoder's stream, ordered against consumer_stream (a
+ * hipStream_t, NULL: the legacy default stream) both ways, as wfst_decoder_advance_chunk orders a chunk against its producer_stream: the
+ * writes wait for what that stream was given before the call (a fill of the rows, the previous step's read of them), and the stream
+ * waits on an event recorded behind the writes.  WFST_STREAM_NONE: the rows are free to be written when the call is made, and the
+ * call returns with them complete (it does in either case today: the call is synchronous).
+ * The ORDER of a sum follows the device's arc index: the results are reproducible to rounding, NOT bit for bit.  A frame's triples
+ * are sorted and summed on chip where the frame has at most WFST_SEQSTAT_LDS_RECS emitting arcs, and in the decoder's workspace
+ * otherwise; the answers do not depend on which.
+ *
+ * A failure of ONE channel goes into status[i] with that channel's outputs zero and its dense rows untouched, and the call still
+ * returns WFST_OK: a device error of that channel's utterance, a lattice of more than max_cells states (WFST_E_CAPACITY; 0 =
+ * wfst_decoder_word_confidence's default bound), or n_frames[i] > cap_frames or n_entries[i] > cap_entries (WFST_E_CAPACITY: n_frames[i]
+ * and n_entries[i] are the room needed, so that the call can be repeated once; log_z[i] stands, and so do the dense rows).  Beside
+ * wfst_decoder_word_confidence's posterior workspace the call takes 48 bytes per arc, 16 per state and 32 per frame of a listed lattice
+ * (fa, fb, w, the staged lists and the sort's workspace).
+ * The call itself fails, before any device work, with WFST_E_ARG (everything wfst_decoder_frame_posteriors names; an unknown
+ * criterion; sil_classes negative, not strictly ascending or more than WFST_SEQSTAT_MAX_SIL; n_ref[i] < 0 or above cap_ref; a
+ * grad_scale that is not finite; grad without grad_frames, n_cols < 1, a negative grad_frames, a pitch below n_cols, a grad pointer not
+ * aligned to 4 bytes, a class beyond n_cols as above) or WFST_E_STATE as there.  Any output pointer may be NULL.  The decoder's state
+ * is only read: decoding goes on bit for bit as without the call.
+ * Not computed here: minimum Bayes risk decoding and the pivot algorithm's second half, the MMI numerator's log-probability,
+ * Kaldi's one_silence_class variant, a half-precision dense output. */
+#define WFST_SEQ_MMI 0
+#define WFST_SEQ_SMBR 1
+#define WFST_SEQSTAT_LDS_RECS 1024 /* emitting arcs of one frame that are sorted and summed on chip */
+#define WFST_SEQSTAT_MAX_SIL 64    /* silence classes */
+int wfst_decoder_sequence_stats(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t criterion, int32_t use_final_probs,
+                                double graph_scale, double acoustic_scale,
+                                const int32_t *label_map /* NULL, or n_tid + 1 entries, entry 0 unused */, int32_t n_tid,
+                                const int32_t *ref /* [n][cap_ref] */, const int32_t *n_ref /* [n] */, int32_t cap_ref,
+                                const int32_t *sil_classes, int32_t n_sil, int32_t drop_frames,
+                                int64_t max_cells /* lattice states; 0 = default */, int32_t cap_frames, int32_t cap_entries,
+                                void *const *grad /* NULL, or [n] device pointers */, const int64_t *grad_pitch /* [n], floats */,
+                                const int32_t *grad_frames /* [n] */, int32_t n_cols, double grad_scale, void *consumer_stream,
+                                int32_t *status /* [n] */, double *log_z /* [n] */, double *tot_acc /* [n] */,
+                                int32_t *n_frames, int32_t *n_ref_frames, int32_t *n_dropped, int32_t *n_entries /* [n] each */,
+                                int32_t *frame_off /* [n][cap_frames + 1] */, int32_t *entry_class /* [n][cap_entries] */,
+                                double *entry_post, double *entry_value /* [n][cap_entries] */);
+
 /* ---- best paths under new scales: the 1-best again at another LM weight, acoustic scale and word penalty -----------------------------
  * Everything above is decided at the scales the search ran with.  This call picks the best path of a channel's RAW lattice again under
  * another graph (LM) scale, another acoustic scale and a word insertion penalty, without decoding again: Kaldi's
