@@ -21,7 +21,7 @@ SRCS = [os.path.join(HERE, "csrc", "wfst_kernels.hip"), os.path.join(HERE, "csrc
         os.path.join(HERE, "csrc", "wfst_rescale.hip"), os.path.join(HERE, "csrc", "wfst_capi_rescale.cc"),
         os.path.join(HERE, "csrc", "wfst_seqstat.hip"), os.path.join(HERE, "csrc", "wfst_capi_seqstat.cc"),
         os.path.join(HERE, "csrc", "wfst_openfst.cc")]
-HDRS = [os.path.join(HERE, "csrc", "wfst_device.h"), os.path.join(HERE, "csrc", "wfst_determinize.h"), os.path.join(HERE, "csrc", "wfst_determinize_wave.h"), os.path.join(HERE, "csrc", "wfst_openfst.h"), os.path.join(HERE, "csrc", "wfst_hip_own.h"), os.path.join(HERE, "csrc", "wfst_capi_words.h"), os.path.join(HERE, "csrc", "wfst_capi_ingest.h"), os.path.join(HERE, "csrc", "wfst_ingest.h"), os.path.join(HERE, "csrc", "wfst_capi_nbwords.h"), os.path.join(HERE, "csrc", "wfst_capi_liveprune.h"), os.path.join(HERE, "csrc", "wfst_capi_align.h"), os.path.join(HERE, "csrc", "wfst_align_index.h"), os.path.join(HERE, "csrc", "wfst_capi_nearest.h"), os.path.join(HERE, "csrc", "wfst_capi_posterior.h"), os.path.join(HERE, "csrc", "wfst_post_math.h"), os.path.join(HERE, "csrc", "wfst_capi_seqpost.h"), os.path.join(HERE, "csrc", "wfst_capi_altern.h"), os.path.join(HERE, "csrc", "wfst_capi_framepost.h"), os.path.join(HERE, "csrc", "wfst_capi_rescale.h"), os.path.join(HERE, "csrc", "wfst_capi_seqstat.h"),
+HDRS = [os.path.join(HERE, "csrc", "wfst_device.h"), os.path.join(HERE, "csrc", "wfst_determinize.h"), os.path.join(HERE, "csrc", "wfst_determinize_wave.h"), os.path.join(HERE, "csrc", "wfst_openfst.h"), os.path.join(HERE, "csrc", "wfst_hip_own.h"), os.path.join(HERE, "csrc", "wfst_capi_words.h"), os.path.join(HERE, "csrc", "wfst_capi_ingest.h"), os.path.join(HERE, "csrc", "wfst_ingest.h"), os.path.join(HERE, "csrc", "wfst_capi_nbwords.h"), os.path.join(HERE, "csrc", "wfst_capi_liveprune.h"), os.path.join(HERE, "csrc", "wfst_capi_align.h"), os.path.join(HERE, "csrc", "wfst_align_index.h"), os.path.join(HERE, "csrc", "wfst_capi_nearest.h"), os.path.join(HERE, "csrc", "wfst_capi_posterior.h"), os.path.join(HERE, "csrc", "wfst_lattice_sweep.h"), os.path.join(HERE, "csrc", "wfst_capi_seqpost.h"), os.path.join(HERE, "csrc", "wfst_capi_altern.h"), os.path.join(HERE, "csrc", "wfst_capi_framepost.h"), os.path.join(HERE, "csrc", "wfst_capi_rescale.h"), os.path.join(HERE, "csrc", "wfst_capi_seqstat.h"),
         os.path.join(HERE, "..", "include", "wfst_decoder.h")]
 LIB = os.path.join(HERE, "lib", "libwfstdec.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -64,7 +64,7 @@ def kernel_resources(extra=(), source=None):
     """What the compiler made of the kernels of `source` (default: the decode kernels, wfst_kernels.hip; device code only, the library's own flags):
     {kernel name: {"vgprs", "agprs", "sgprs", "vgpr_spill", "sgpr_spill", "scratch", "occupancy", "lds"}} from
     -Rpass-analysis=kernel-resource-usage; "lds" is the static LDS in bytes.  Template instantiations keep their mangled names,
-    plain kernels go by their function name.  (tests/test_kernel_resources.py; `python build.py --resources` prints the lines.)"""
+    plain kernels go by their function name.  (tests/test_kernel_resources.py; `python build.py --resources [source]` prints the lines.)"""
     import re
     import tempfile
     flags = [f for f in FLAGS if f not in ("-shared", "-fPIC")]
@@ -94,8 +94,9 @@ def kernel_resources(extra=(), source=None):
 
 
 if __name__ == "__main__":
-    if "--resources" in sys.argv:
-        for k, v in sorted(kernel_resources().items()):
+    if "--resources" in sys.argv:   # --resources [source file]
+        src = sys.argv[sys.argv.index("--resources") + 1:]
+        for k, v in sorted(kernel_resources(source=src[0] if src else None).items()):
             print(k, " ".join("%s=%d" % kv for kv in sorted(v.items())))
     elif "--variant" in sys.argv:
         i = sys.argv.index("--variant")

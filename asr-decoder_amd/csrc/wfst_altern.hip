@@ -2,7 +2,7 @@
 // pivot, confidence_kernel's cells (wfst_posterior.hip) are the slots, and every other word of the lattice falls into the slot its
 // arc's source frame lies in.  Both kernels run behind align_index_kernel, align_kernel, posterior_kernel and confidence_kernel, one
 // workgroup per (channel, sequence), over the in-arc index (wfst_align_index.h) and posterior_kernel's alpha, beta, gamma and log_z.
-// Arc costs, the "no arc" rule and the way a sum is taken are posterior_kernel's (wfst_post_math.h).
+// Arc costs, the "no arc" rule and the way a sum is taken are posterior_kernel's (wfst_lattice_sweep.h).
 //
 // slot_mass_kernel: mass(k, v) = the sum of gamma(a) over the arcs with olabel v > 0 whose source frame lies in cell k.
 //  - the lanes stride over the in-arc records; a word-carrying record with gamma > 0 finds its cell by a binary search of the cut
@@ -33,7 +33,7 @@
 #include "../../include/wfst_decoder.h"   // WFST_ALTERN_LDS_KEYS
 #include "wfst_align_index.h"
 #include "wfst_device.h"
-#include "wfst_post_math.h"
+#include "wfst_lattice_sweep.h"
 
 namespace wfst {
 namespace {
@@ -44,21 +44,6 @@ constexpr int kAltLdsSlots = 2 * kAltLdsKeys;   // a power of two
 constexpr int kAltCells = 2048;                 // sequences up to this many words keep their cut points (and none sums) in LDS
 constexpr unsigned long long kAltEmpty = ~0ull;
 static_assert((kAltLdsSlots & (kAltLdsSlots - 1)) == 0, "the LDS table's size is a power of two");
-
-// the cut points: m[0] = 0, m[k] = (b[k - 1] + b[k] + 1) >> 1
-struct AltCuts {
-  const int32_t *s_m, *begin;   // s_m: in LDS, or nullptr
-  __device__ __forceinline__ int at(int k) const { return s_m ? s_m[k] : (k ? (begin[k - 1] + begin[k] + 1) >> 1 : 0); }
-  // the last k with m[k] <= f
-  __device__ __forceinline__ int cell_of(int f, int L) const {
-    int lo = 0, hi = L;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (at(mid) <= f) lo = mid; else hi = mid;
-    }
-    return lo;
-  }
-};
 
 __device__ __forceinline__ uint32_t alt_hash(unsigned long long key) {
   key *= 0x9E3779B97F4A7C15ull;
@@ -148,19 +133,7 @@ __device__ __forceinline__ bool none_term(const PostDev &P, const AlnIndex &X, c
 
 __device__ double none_forward(const PostDev &P, const AlnIndex &X, const double *alpha, const double *acost, int t, int f, int lo) {
   if (t == 0) return 0.0;
-  const int a0 = X.off[t], a1 = X.off[t + 1];
-  double m = post_inf();
-  for (int a = a0; a < a1; ++a) {
-    double x;
-    if (none_term(P, X, alpha, acost, a, f, lo, &x) && x < m) m = x;
-  }
-  if (!post_finite(m)) return post_inf();
-  double sum = 0.0;
-  for (int a = a0; a < a1; ++a) {
-    double x;
-    if (none_term(P, X, alpha, acost, a, f, lo, &x)) sum += exp(-(x - m));
-  }
-  return m - log(sum);
+  return post_logsum(X.off[t], X.off[t + 1], [&](int a, double *x) { return none_term(P, X, alpha, acost, a, f, lo, x); });
 }
 
 // what a finished state of cell k adds where it is final: its wordless mass to the cell, its whole mass to the cell's "ended early"
@@ -195,13 +168,12 @@ __global__ __launch_bounds__(kAltThreads) void slot_mass_kernel(AlignDev A, Post
   __shared__ unsigned long long s_key[kAltLdsSlots];
   __shared__ double s_mass[kAltLdsSlots];
   __shared__ int s_count, s_over;
-  const bool cuts_in_lds = L <= kAltCells;
-  if (cuts_in_lds)
-    for (int k = tid; k < L; k += kAltThreads) s_m[k] = k ? (o_begin[k - 1] + o_begin[k] + 1) >> 1 : 0;
+  const AltCuts C = {L <= kAltCells ? s_m : nullptr, o_begin};
+  if (C.s_m)
+    for (int k = tid; k < L; k += kAltThreads) s_m[k] = C.raw(k);
   for (int i = tid; i < kAltLdsSlots; i += kAltThreads) { s_key[i] = kAltEmpty; s_mass[i] = 0.0; }
   if (tid == 0) { s_count = 0; s_over = 0; }
   __syncthreads();   // (orders the zeroes of the outputs before the stores of the other lanes as well)
-  const AltCuts C = {cuts_in_lds ? s_m : nullptr, o_begin};
   alt_accumulate(X, gamma, na, C, L, s_key, s_mass, kAltLdsSlots, kAltLdsKeys, &s_count, &s_over, tid);
   __syncthreads();
   if (!s_over) {   // (the same in every lane)
@@ -240,14 +212,14 @@ __global__ __launch_bounds__(kAltThreads) void slot_none_kernel(AlignDev A, Post
   __shared__ int32_t s_m[kAltCells];
   __shared__ double s_none[kAltCells], s_early[kAltCells];
   const bool in_lds = L <= kAltCells;
+  const AltCuts C = {in_lds ? s_m : nullptr, o_begin};
   if (in_lds)
     for (int k = tid; k < L; k += kAltThreads) {
-      s_m[k] = k ? (o_begin[k - 1] + o_begin[k] + 1) >> 1 : 0;
+      s_m[k] = C.raw(k);
       s_none[k] = 0.0;
       s_early[k] = 0.0;
     }
   __syncthreads();   // (orders the zeroes of the global rows before the additions of the other lanes as well)
-  const AltCuts C = {in_lds ? s_m : nullptr, o_begin};
   double *none = in_lds ? s_none : out, *early = in_lds ? s_early : g_early;
   int err = 0, k = 0;   // k: the cell of frame f, the last with m[k] <= f (the same in every lane)
   for (int f = 0; f <= nd && !err; ++f) {
@@ -266,39 +238,11 @@ __global__ __launch_bounds__(kAltThreads) void slot_none_kernel(AlignDev A, Post
           if (post_finite(x)) atomicAdd(&none[kprev], exp(-x));
         }
       }
-    if (!X.feps[f]) {   // every in-arc leaves an earlier frame
-      for (int t = b + tid; t < e; t += kAltThreads) {
-        const double v = none_forward(P, X, alpha, acost, t, f, lo);
-        acost[t] = v;
-        if ((toks[t].w >> 30) & 1) none_final(v, alpha[t], log_z, none, early, k);
-      }
-      __syncthreads();
-      continue;
-    }
-    for (int t = b + tid; t < e; t += kAltThreads) done[t] = 0;
-    __syncthreads();
-    for (int round = 0;; ++round) {
-      int pending = 0;
-      for (int t = b + tid; t < e; t += kAltThreads) {
-        if (done[t]) continue;
-        bool ready = true;
-        const int a1 = X.off[t + 1];
-        for (int a = X.off[t]; a < a1 && ready; ++a) {
-          const int src = X.recA[a].x;
-          if (src >= 0) continue;   // an emitting arc
-          const int dn = done[src & 0x7FFFFFFF];
-          ready = dn != 0 && dn <= round;
-        }
-        if (!ready) { pending = 1; continue; }
-        const double v = none_forward(P, X, alpha, acost, t, f, lo);
-        acost[t] = v;
-        if ((toks[t].w >> 30) & 1) none_final(v, alpha[t], log_z, none, early, k);
-        done[t] = round + 1;
-      }
-      pending = __syncthreads_or(pending);   // (the barrier also orders this round's stores before the next round's loads)
-      if (!pending) break;
-      if (round > e - b) { err = kAlnCycle; break; }   // (posterior_kernel has reported it: not reached)
-    }
+    err = sweep_in<kAltThreads>(X, b, e, X.feps[f], done, [&](int t) {   // (a cycle: posterior_kernel has reported it, not reached)
+      const double v = none_forward(P, X, alpha, acost, t, f, lo);
+      acost[t] = v;
+      if ((toks[t].w >> 30) & 1) none_final(v, alpha[t], log_z, none, early, k);
+    });
   }
   __syncthreads();
   if (tid != 0) return;

@@ -67,11 +67,11 @@ int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fi
 
 // ---- the round driver of the word queries (wfst_capi_wordquery.cc) ----------------------------------------------------------
 // wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence, wfst_decoder_sequence_posterior and
-// wfst_decoder_word_alternatives ask the listed channels' raw lattices about
-// n_seqs word sequences each (wfst_decoder_frame_posteriors and wfst_decoder_sequence_stats about one empty sequence each:
-// wfst_capi_framepost.h, wfst_capi_seqstat.h;
-// wfst_decoder_rescaled_words about one empty sequence per setting: wfst_capi_rescale.h): one table of states x (words + 1) cells per (channel, sequence) pair over the in-arc index
-// align_index_kernel builds.  word_query_run is the sequence they share; a WordQuery is what differs.
+// wfst_decoder_word_alternatives ask the listed channels' raw lattices about n_seqs word sequences each: one table of
+// states x (words + 1) cells per (channel, sequence) pair over the in-arc index align_index_kernel builds.
+// wfst_decoder_frame_posteriors and wfst_decoder_sequence_stats ask about one empty sequence each (wfst_capi_framepost.h,
+// wfst_capi_seqstat.h), wfst_decoder_rescaled_words about one empty sequence per setting (wfst_capi_rescale.h).
+// word_query_run is the sequence they share; a WordQuery is what differs.
 
 #define ALIGN_TRY(expr)                                                                               \
   do {                                                                                                \

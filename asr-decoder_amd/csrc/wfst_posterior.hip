@@ -12,9 +12,8 @@
 //    lattice_emit_kernel appends a channel's arcs in whatever order its waves retire, not grouped by source;
 //  - forward, frames ascending, a lane per state of the frame (strided beyond 1024): a state PULLS the sum over its in-arcs from
 //    finished values, no atomic on a cost.  A frame with epsilon arcs between its own states goes by LEVELS: a minimum may iterate
-//    to a fixpoint, a sum may not, so a state is summed in the round after the last of its same-frame sources was (done[] holds
-//    1 + that round: a flag written in this round reads as "not yet" whether or not the store has landed); one barrier per round,
-//    as many rounds as the frame's longest epsilon chain, more rounds than states is a cycle;
+//    to a fixpoint, a sum may not, so a state is summed in the round after the last of its same-frame sources was (the sweep of
+//    wfst_lattice_sweep.h over done[]);
 //  - backward, frames descending, the same over the out-arcs;
 //  - gamma per in-arc record.
 // confidence_kernel, one workgroup per (channel, sequence): the cut points m[] of the aligned words' begin frames, a binary search
@@ -26,7 +25,7 @@
 
 #include "wfst_align_index.h"   // AlnIndex / aln_carve
 #include "wfst_device.h"
-#include "wfst_post_math.h"     // post_inf / post_finite / post_cost
+#include "wfst_lattice_sweep.h"   // post_cost / post_logsum, sweep_in / sweep_out, AltCuts
 
 namespace wfst {
 namespace {
@@ -37,49 +36,25 @@ constexpr int kConfWords = 4096;   // sequences up to this many words keep their
 // alpha of state t from the finished values of its sources
 __device__ double post_forward(const PostDev &P, const AlnIndex &X, const double *alpha, int t) {
   if (t == 0) return 0.0;
-  const int a0 = X.off[t], a1 = X.off[t + 1];
-  double m = post_inf();
-  for (int a = a0; a < a1; ++a) {
+  return post_logsum(X.off[t], X.off[t + 1], [&](int a, double *x) {
     const int4 R = X.recA[a];
     double c;
-    if (!post_cost(P, R, &c)) continue;
-    const double x = alpha[R.x & 0x7FFFFFFF] + c;
-    if (post_finite(x) && x < m) m = x;
-  }
-  if (!post_finite(m)) return post_inf();
-  double sum = 0.0;
-  for (int a = a0; a < a1; ++a) {
-    const int4 R = X.recA[a];
-    double c;
-    if (!post_cost(P, R, &c)) continue;
-    const double x = alpha[R.x & 0x7FFFFFFF] + c;
-    if (post_finite(x)) sum += exp(-(x - m));
-  }
-  return m - log(sum);
+    if (!post_cost(P, R, &c)) return false;
+    *x = alpha[R.x & 0x7FFFFFFF] + c;
+    return post_finite(*x);
+  });
 }
 
-// beta of state s from the finished values of its destinations
+// beta of state s from the finished values of its destinations, and its final weight 0 where it is final
 __device__ double post_backward(const PostDev &P, const AlnIndex &X, const int2 *sarc, const int32_t *soff, const double *beta, int s,
                                 bool is_final) {
-  const int p0 = s ? soff[s - 1] : 0, p1 = soff[s];
-  double m = is_final ? 0.0 : post_inf();
-  for (int p = p0; p < p1; ++p) {
+  return post_logsum(s ? soff[s - 1] : 0, soff[s], [&](int p, double *x) {
     const int2 E = sarc[p];
     double c;
-    if (!post_cost(P, X.recA[E.x], &c)) continue;
-    const double x = c + beta[E.y];
-    if (post_finite(x) && x < m) m = x;
-  }
-  if (!post_finite(m)) return post_inf();
-  double sum = is_final ? exp(-(0.0 - m)) : 0.0;
-  for (int p = p0; p < p1; ++p) {
-    const int2 E = sarc[p];
-    double c;
-    if (!post_cost(P, X.recA[E.x], &c)) continue;
-    const double x = c + beta[E.y];
-    if (post_finite(x)) sum += exp(-(x - m));
-  }
-  return m - log(sum);
+    if (!post_cost(P, X.recA[E.x], &c)) return false;
+    *x = c + beta[E.y];
+    return post_finite(*x);
+  }, is_final, 0.0);
 }
 
 }  // namespace
@@ -124,69 +99,13 @@ __global__ __launch_bounds__(kPostThreads) void posterior_kernel(DecoderDev D, A
     for (int a = X.off[t]; a < a1; ++a) sarc[atomicAdd(&soff[X.recA[a].x & 0x7FFFFFFF], 1)] = make_int2(a, t);
   }
   __syncthreads();
-  // ---- forward ---------------------------------------------------------------------------------------------------------------
+  // ---- forward, backward: frame by frame, by levels inside a frame (wfst_lattice_sweep.h) --------------------------------------
   int err = 0;
-  for (int f = 0; f <= nd && !err; ++f) {
-    const int b = X.fbeg[f], e = X.fend[f];
-    if (!X.feps[f]) {   // every in-arc leaves an earlier frame
-      for (int t = b + tid; t < e; t += kPostThreads) alpha[t] = post_forward(P, X, alpha, t);
-      __syncthreads();
-      continue;
-    }
-    for (int t = b + tid; t < e; t += kPostThreads) done[t] = 0;
-    __syncthreads();
-    for (int round = 0;; ++round) {
-      int pending = 0;
-      for (int t = b + tid; t < e; t += kPostThreads) {
-        if (done[t]) continue;
-        bool ready = true;
-        const int a1 = X.off[t + 1];
-        for (int a = X.off[t]; a < a1 && ready; ++a) {
-          const int src = X.recA[a].x;
-          if (src >= 0) continue;   // an emitting arc
-          const int dn = done[src & 0x7FFFFFFF];
-          ready = dn != 0 && dn <= round;
-        }
-        if (!ready) { pending = 1; continue; }
-        alpha[t] = post_forward(P, X, alpha, t);
-        done[t] = round + 1;
-      }
-      pending = __syncthreads_or(pending);   // (the barrier also orders this round's stores before the next round's loads)
-      if (!pending) break;
-      if (round > e - b) { err = kAlnCycle; break; }   // an epsilon path visits a state of the frame once
-    }
-  }
-  // ---- backward --------------------------------------------------------------------------------------------------------------
-  for (int f = nd; f >= 0 && !err; --f) {
-    const int b = X.fbeg[f], e = X.fend[f];
-    if (!X.feps[f]) {
-      for (int s = b + tid; s < e; s += kPostThreads) beta[s] = post_backward(P, X, sarc, soff, beta, s, (toks[s].w >> 30) & 1);
-      __syncthreads();
-      continue;
-    }
-    for (int s = b + tid; s < e; s += kPostThreads) done[s] = 0;
-    __syncthreads();
-    for (int round = 0;; ++round) {
-      int pending = 0;
-      for (int s = b + tid; s < e; s += kPostThreads) {
-        if (done[s]) continue;
-        bool ready = true;
-        const int p1 = soff[s];
-        for (int p = s ? soff[s - 1] : 0; p < p1 && ready; ++p) {
-          const int2 E = sarc[p];
-          if (X.recA[E.x].x >= 0) continue;
-          const int dn = done[E.y];
-          ready = dn != 0 && dn <= round;
-        }
-        if (!ready) { pending = 1; continue; }
-        beta[s] = post_backward(P, X, sarc, soff, beta, s, (toks[s].w >> 30) & 1);
-        done[s] = round + 1;
-      }
-      pending = __syncthreads_or(pending);
-      if (!pending) break;
-      if (round > e - b) { err = kAlnCycle; break; }
-    }
-  }
+  for (int f = 0; f <= nd && !err; ++f)
+    err = sweep_in<kPostThreads>(X, X.fbeg[f], X.fend[f], X.feps[f], done, [&](int t) { alpha[t] = post_forward(P, X, alpha, t); });
+  for (int f = nd; f >= 0 && !err; --f)
+    err = sweep_out<kPostThreads>(X, sarc, soff, X.fbeg[f], X.fend[f], X.feps[f], done,
+                                  [&](int s) { beta[s] = post_backward(P, X, sarc, soff, beta, s, (toks[s].w >> 30) & 1); });
   if (err) {
     if (tid == 0) { P.log_z[slot] = 0.0; P.chan_err[slot] = err; }
     return;
@@ -224,10 +143,10 @@ __global__ __launch_bounds__(kPostThreads) void confidence_kernel(AlignDev A, Po
   __shared__ int32_t s_m[kConfWords + 1];
   __shared__ double s_acc[kConfWords];
   const bool in_lds = L <= kConfWords;
-  // m[0] = 0, m[k] = (b[k - 1] + b[k] + 1) >> 1, m[L] = +inf: cell k is the frames m[k] <= f < m[k + 1]
+  const AltCuts C = {in_lds ? s_m : nullptr, o_begin};   // cell k is the frames m[k] <= f < m[k + 1], m[L] = +inf
   if (in_lds)
     for (int k = tid; k < L; k += kPostThreads) {
-      s_m[k] = k ? (o_begin[k - 1] + o_begin[k] + 1) >> 1 : 0;
+      s_m[k] = C.raw(k);
       s_acc[k] = 0.0;
     }
   __syncthreads();   // (orders the zeroes of out[] before the additions of the other lanes as well)
@@ -247,13 +166,7 @@ __global__ __launch_bounds__(kPostThreads) void confidence_kernel(AlignDev A, Po
     for (int a = tid; a < na; a += kPostThreads) {
       const int word = X.recA[a].y;
       if (word == 0) continue;
-      const int f = X.recB[a].z;
-      int lo = 0, hi = L;   // the last k with m[k] <= f
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        const int cut = in_lds ? s_m[mid] : (o_begin[mid - 1] + o_begin[mid] + 1) >> 1;
-        if (cut <= f) lo = mid; else hi = mid;
-      }
+      const int lo = C.cell_of(X.recB[a].z, L);
       if (w[lo] == word) atomicAdd(&acc[lo], gamma[a]);
     }
   }

@@ -1,7 +1,7 @@
 // Sentence and phrase posteriors (wfst_decoder_sequence_posterior): the log-semiring twin of align_kernel (wfst_align.hip) and
 // nearest_kernel (wfst_nearest.hip).  The same lattice, in-arc index (align_index_kernel's, AlignDev::idx) and frame-ordered table of
 // states x (L + 1) cells -- but a cell is the float64 cost of the SUM over the paths that reach it, where align_kernel keeps the
-// minimum.  Arc costs, the "no arc" rule and the way a sum is taken are posterior_kernel's (wfst_posterior.hip, wfst_post_math.h),
+// minimum.  Arc costs, the "no arc" rule and the way a sum is taken are posterior_kernel's (wfst_posterior.hip, wfst_lattice_sweep.h),
 // whose alpha, beta and log_z this kernel reads.
 //   mode 0, sentence:  S[0][0] = 0;  S[t][k] = -log( sum over a: s -> t, olabel 0           of exp(-(S[s][k]     + c(a)))
 //                                                  + sum over a: s -> t, olabel == w[k - 1] of exp(-(S[s][k - 1] + c(a))) )
@@ -15,8 +15,8 @@
 //    PULLS over its state's in-arcs from finished cells in two passes, the least term and then the sum: no atomic on a cost.
 //  - a frame with arcs between its own states goes by LEVELS, posterior_kernel's rule: a sum may not iterate to a fixpoint, so a
 //    state's row is summed in the round after the last of its same-frame sources.  The level of a state does not depend on k: it is
-//    worked out first, a lane per state (lvl[] = 1 + the round; a flag written in this round reads as "not yet" whether or not the
-//    store has landed), more rounds than states is a cycle; then one pass over the frame's cells per level, a barrier between.
+//    worked out first, a lane per state (the sweep of wfst_lattice_sweep.h with nothing to compute: lvl[] = 1 + the round, more rounds
+//    than states is a cycle); then one pass over the frame's cells per level, a barrier between.
 //    A word on an arc inside a frame moves k - 1 -> k at the destination's higher level of the same frame.
 //  - the end, mode 0: a block reduction over the final states' S[s][L], the least term and then the sum.  Mode 1: the lanes stride over
 //    the states' in-arcs, add occ(a) to the frame's entry of hit_mass with a float64 atomic add -- to LDS where the row fits, to the
@@ -28,7 +28,7 @@
 
 #include "wfst_align_index.h"
 #include "wfst_device.h"
-#include "wfst_post_math.h"
+#include "wfst_lattice_sweep.h"
 
 namespace wfst {
 namespace {
@@ -58,41 +58,7 @@ __device__ __forceinline__ bool sp_term(const PostDev &P, const SpTable &T, cons
 __device__ double sp_cell(const PostDev &P, const AlnIndex &X, const SpTable &T, int t, int k) {
   if (T.mode && k == 0) return T.alpha[t];
   if (t == 0) return k == 0 ? 0.0 : post_inf();
-  const int a0 = X.off[t], a1 = X.off[t + 1];
-  double m = post_inf();
-  for (int a = a0; a < a1; ++a) {
-    double x;
-    if (sp_term(P, T, X.recA[a], k, &x) && x < m) m = x;
-  }
-  if (!post_finite(m)) return post_inf();
-  double sum = 0.0;
-  for (int a = a0; a < a1; ++a) {
-    double x;
-    if (sp_term(P, T, X.recA[a], k, &x)) sum += exp(-(x - m));
-  }
-  return m - log(sum);
-}
-
-// the block's minimum / sum of one value per lane, in every lane (s_red: kSpThreads doubles)
-__device__ double sp_block_min(double v, double *s_red, int tid) {
-  __syncthreads();   // (s_red may still be read from the reduction before)
-  s_red[tid] = v;
-  __syncthreads();
-  for (int step = kSpThreads / 2; step >= 1; step >>= 1) {
-    if (tid < step) { const double o = s_red[tid + step]; if (o < s_red[tid]) s_red[tid] = o; }
-    __syncthreads();
-  }
-  return s_red[0];
-}
-__device__ double sp_block_sum(double v, double *s_red, int tid) {
-  __syncthreads();
-  s_red[tid] = v;
-  __syncthreads();
-  for (int step = kSpThreads / 2; step >= 1; step >>= 1) {
-    if (tid < step) s_red[tid] += s_red[tid + step];
-    __syncthreads();
-  }
-  return s_red[0];
+  return post_logsum(X.off[t], X.off[t + 1], [&](int a, double *x) { return sp_term(P, T, X.recA[a], k, x); });
 }
 
 }  // namespace
@@ -139,31 +105,9 @@ __global__ __launch_bounds__(kSpThreads) void seqpost_kernel(AlignDev A, PostDev
       __syncthreads();
       continue;
     }
-    // the states' levels inside the frame
-    for (int t = b + tid; t < e; t += kSpThreads) lvl[t] = 0;
-    __syncthreads();
+    // the states' levels inside the frame: the sweep with nothing to compute leaves lvl[] = 1 + the round; then the rows, level by level
     int rounds = 0;
-    for (int round = 0;; ++round) {
-      int pending = 0;
-      for (int t = b + tid; t < e; t += kSpThreads) {
-        if (lvl[t]) continue;
-        bool ready = true;
-        const int a1 = X.off[t + 1];
-        for (int a = X.off[t]; a < a1 && ready; ++a) {
-          const int src = X.recA[a].x;
-          if (src >= 0) continue;   // an emitting arc
-          const int dn = lvl[src & 0x7FFFFFFF];
-          ready = dn != 0 && dn <= round;
-        }
-        if (!ready) { pending = 1; continue; }
-        lvl[t] = round + 1;
-      }
-      pending = __syncthreads_or(pending);   // (the barrier also orders this round's stores before the next round's loads)
-      rounds = round + 1;
-      if (!pending) break;
-      if (round > e - b) { err = kAlnCycle; break; }   // an epsilon path visits a state of the frame once
-    }
-    // the rows, level by level
+    err = sweep_in<kSpThreads>(X, b, e, true, lvl, [](int) {}, &rounds);
     for (int r = 1; r <= rounds && !err; ++r) {
       for (int64_t cell = tid; cell < ncell; cell += kSpThreads) {
         const int i = (int)(cell / W);
@@ -189,7 +133,7 @@ __global__ __launch_bounds__(kSpThreads) void seqpost_kernel(AlignDev A, PostDev
       const double x = T.cell[(size_t)s * W + L];
       if (post_finite(x) && x < m) m = x;
     }
-    m = sp_block_min(m, s_red, tid);
+    m = blk_min<kSpThreads>(m, s_red, tid);
     if (post_finite(m)) {   // (the same m in every lane)
       double sum = 0.0;
       for (int s = tid; s < nt; s += kSpThreads) {
@@ -197,7 +141,7 @@ __global__ __launch_bounds__(kSpThreads) void seqpost_kernel(AlignDev A, PostDev
         const double x = T.cell[(size_t)s * W + L];
         if (post_finite(x)) sum += exp(-(x - m));
       }
-      sum = sp_block_sum(sum, s_red, tid);
+      sum = blk_sum<kSpThreads>(sum, s_red, tid);
       answer = -log_z - (m - log(sum));
       found = 1;
     }
@@ -225,7 +169,7 @@ __global__ __launch_bounds__(kSpThreads) void seqpost_kernel(AlignDev A, PostDev
         if (rows) atomicAdd(&acc[X.recB[a].z], occ);
       }
     }
-    const double count = sp_block_sum(mine, s_red, tid);   // (its barriers also finish the additions to s_hit[])
+    const double count = blk_sum<kSpThreads>(mine, s_red, tid);   // (its barriers also finish the additions to s_hit[])
     if (in_lds)
       for (int f = tid; f < nf; f += kSpThreads) hit[f] = s_hit[f];
     if (count > 0.0) { answer = log(count); found = 1; }
