@@ -58,6 +58,11 @@ class Result:
     path_ac: np.ndarray
     frame_ntoks: np.ndarray | None = None
     frame_best: np.ndarray | None = None
+    # (oracle traces only) per expanded frame f < T: GetCutoff's adaptive_beam and cutoff over the frontier of frame f, and the
+    # final next_cutoff of its expansion, below which every token of frame f + 1 lies
+    frame_adaptive_beam: np.ndarray | None = None
+    frame_cutoff: np.ndarray | None = None
+    frame_next_cutoff: np.ndarray | None = None
     dump: tuple | None = None
     num_toks_end: int = 0
     num_links_end: int = 0
@@ -154,7 +159,7 @@ class _Base:
             dump = (ds[:k].copy(), dc[:k].copy(), dn.value)
         return Result(bool(ok), words[: n_words.value].copy(), tids[: n_tids.value].copy(),
                       float(tot.value), float(lm.value), pi[:n].copy(), po[:n].copy(),
-                      pg[:n].copy(), pa[:n].copy(), fn, fb, dump, nt.value, nl.value)
+                      pg[:n].copy(), pa[:n].copy(), fn, fb, None, None, None, dump, nt.value, nl.value)
 
 
 class RefDecoder(_Base):
@@ -197,8 +202,31 @@ class OracleDecoder(_Base):
         2: the same with the HIGHEST source LM pair key (biglm; the other end of the set of optimal predecessors: what a wrong source choice would give)."""
         self.lib.oracle_set_tie_rule(int(rule))
 
+    def frame_trace(self, T):
+        """Context: decodes of this thread record adaptive_beam, cutoff and next_cutoff of frames 0 .. T - 1 into the three arrays
+        it yields (oracle/wfst_oracle.c oracle_set_frame_trace)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            arr = [np.full(max(T, 1), np.nan, np.float32) for _ in range(3)]
+            f = self.lib.oracle_set_frame_trace
+            f.restype = None
+            f(_fp(arr[0]), _fp(arr[1]), _fp(arr[2]), int(T))
+            try:
+                yield [a[:T] for a in arr]
+            finally:
+                f(None, None, None, 0)
+        return cm()
+
     def decode(self, *a, **kw):
-        r = super().decode(*a, **kw)
+        if kw.get("trace"):
+            ll = kw["loglikes"] if "loglikes" in kw else a[2]
+            with self.frame_trace(int(np.asarray(ll).shape[0])) as tr:
+                r = super().decode(*a, **kw)
+            r.frame_adaptive_beam, r.frame_cutoff, r.frame_next_cutoff = tr
+        else:
+            r = super().decode(*a, **kw)
         e = self._tls.extra
         r.extra = dict(N=int(e[0]), E=int(e[1]), Z=int(e[2]), tokens_created=int(e[3]), links_created=int(e[4]),
                        ties=int(e[5]), quirk_hops=int(e[6]))
@@ -473,7 +501,7 @@ class Lm:
 
 
 def biglm_decode(dec, graph_handle, cfg, lm1, lm2, loglikes, tid2pdf=None, chunk=0, finalize=True, use_final_probs=True,
-                 trace=False, fixed=True):
+                 trace=False, fixed=True, dump_frame=-1, dump_cap=0):
     """One utterance through the biglm decoder of `dec` (RefDecoder: the reference's
     OnlineLatticeDecoderMempoolBiglm as it is; OracleDecoder: the restatement, `fixed` chooses the
     DiffArpaLm mode).  lm1 = old LM loaded with scale -1, lm2 = new LM."""
@@ -502,17 +530,38 @@ def biglm_decode(dec, graph_handle, cfg, lm1, lm2, loglikes, tid2pdf=None, chunk
     if not is_ref:
         head.append(int(bool(fixed)))
     ex = np.zeros(10, np.int64)
+    head_len = len(head)
     args = head + [_fp(ll), T, stride, _ip(tid2pdf), n_tid, int(chunk), int(bool(finalize)), int(bool(use_final_probs)),
                    _ip(pi), _ip(po), _fp(pg), _fp(pa), max_path, C.byref(n_path), C.byref(tot), C.byref(lm), _ip(words), max_path,
                    C.byref(n_words), _ip(tids), max_path, C.byref(n_tids), _ip(fn), _fp(fb), C.byref(nt), C.byref(nl)]
     if not is_ref:
         args.append(ex.ctypes.data_as(C.POINTER(C.c_int64)))
-    ok = f(*args)
+    tr = (None, None, None)
+    dump = None
+    if dump_frame >= 0:
+        # (oracle only: the (graph state, cost) of every token -- one per (state, LM state) pair -- of that frame, fed frame by frame)
+        assert not is_ref and not trace and chunk <= 1
+        args[head_len + 5] = 1   # chunk
+        ds, dc, dn = np.zeros(max(dump_cap, 1), np.int32), np.zeros(max(dump_cap, 1), np.float32), C.c_int(0)
+        hook = dec.lib.oracle_set_frame_dump
+        hook.restype = None
+        hook(int(dump_frame), _ip(ds), _fp(dc), int(dump_cap), C.byref(dn))
+        try:
+            ok = f(*args)
+        finally:
+            hook(-1, None, None, 0, None)
+        k = min(dn.value, dump_cap)
+        dump = (ds[:k].copy(), dc[:k].copy(), dn.value)
+    elif trace and not is_ref:
+        with dec.frame_trace(T) as tr:
+            ok = f(*args)
+    else:
+        ok = f(*args)
     n = n_path.value
     if n > max_path:
         raise RuntimeError("best path of %d hops does not fit the binding's %d-hop buffers" % (n, max_path))
     r = Result(bool(ok), words[: n_words.value].copy(), tids[: n_tids.value].copy(), float(tot.value), float(lm.value),
-               pi[:n].copy(), po[:n].copy(), pg[:n].copy(), pa[:n].copy(), fn, fb, None, nt.value, nl.value)
+               pi[:n].copy(), po[:n].copy(), pg[:n].copy(), pa[:n].copy(), fn, fb, tr[0], tr[1], tr[2], dump, nt.value, nl.value)
     if not is_ref:
         r.extra = dict(N=int(ex[0]), E=int(ex[1]), Z=int(ex[2]), tokens_created=int(ex[3]), links_created=int(ex[4]),
                        ties=int(ex[5]), quirk_hops=int(ex[6]), lm_pairs=int(ex[7] & ((1 << 40) - 1)), lm_oob=int(ex[7] >> 40), L=int(ex[8]), L_eps=int(ex[9]))

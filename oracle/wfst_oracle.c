@@ -540,6 +540,15 @@ static void process_nonemitting(Decoder *d, float cutoff) {
  * tokens/links that does not depend on the visiting order.  Default 0 = the reference's behaviour. */
 void oracle_set_order_free(int on) { g_order_free = on; }
 
+/* Per-frame trace of GetCutoff and next_cutoff (tests/selection_util.py): while set, process_emitting writes, at the index of the
+ * frame it expands, the frame's adaptive_beam, its cutoff and its FINAL next_cutoff (order-free mode: the one applied to every
+ * arc).  Three arrays of `cap` floats, or NULL to stop.  Per thread, as the decodes are. */
+static _Thread_local float *g_tr_ab, *g_tr_cutoff, *g_tr_next;
+static _Thread_local int g_tr_cap;
+void oracle_set_frame_trace(float *adaptive_beam, float *cutoff, float *next_cutoff, int cap) {
+  g_tr_ab = adaptive_beam; g_tr_cutoff = cutoff; g_tr_next = next_cutoff; g_tr_cap = (adaptive_beam && cutoff && next_cutoff) ? cap : 0;
+}
+
 static float process_emitting(Decoder *d) {
   const Graph *g = d->g;
   int nnetframe = d->num_frames_decoded;
@@ -612,6 +621,7 @@ static float process_emitting(Decoder *d) {
     e_tail = e->tail;
     hl_delete(&d->toks, e);
   }
+  if (nnetframe < g_tr_cap) { g_tr_ab[nnetframe] = adaptive_beam; g_tr_cutoff[nnetframe] = cur_cutoff; g_tr_next[nnetframe] = next_cutoff; }
   d->num_frames_decoded++;
   return next_cutoff;
 }
@@ -790,6 +800,15 @@ static void advance_decoding(Decoder *d, int max_num_frames) {
   }
 }
 
+/* A frame's token list from a decode whose own arguments ask for none (the biglm entry point; tests/selection_util.py): while set,
+ * a decode fed frame by frame (chunk 1) writes the graph state and cost of every token of `frame` -- a biglm decode one entry per
+ * (state, LM state) pair -- as dump_frame does.  n NULL: stop.  Per thread. */
+static _Thread_local int g_fd_frame = -1, g_fd_cap, *g_fd_states, *g_fd_n;
+static _Thread_local float *g_fd_costs;
+void oracle_set_frame_dump(int frame, int *states, float *costs, int cap, int *n) {
+  g_fd_frame = n ? frame : -1; g_fd_states = states; g_fd_costs = costs; g_fd_cap = cap; g_fd_n = n;
+}
+
 /* ---- graph loading ---- */
 static void graph_index(Graph *g) {
   g->off = (int64_t *)malloc(((size_t)g->n_states + 1) * sizeof(int64_t));
@@ -832,6 +851,7 @@ static int decode_impl(void *gp, const Config *rc, DiffLm *dlm, const float *log
                      float *dump_costs, int dump_cap, int *dump_n, int *num_toks_end,
                      int *num_links_end, int64_t *extra) {
   (void)n_tid;
+  if (dump_frame < 0 && g_fd_n && g_fd_frame >= 0) { dump_frame = g_fd_frame; dump_states = g_fd_states; dump_costs = g_fd_costs; dump_cap = g_fd_cap; dump_n = g_fd_n; }
   Decoder D; memset(&D, 0, sizeof(D));
   Decoder *d = &D;
   d->g = (const Graph *)gp; d->cfg = *rc; d->dlm = dlm;

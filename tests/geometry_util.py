@@ -470,3 +470,41 @@ class World:
         kw = dict(chunk=1, finalize=False, use_final_probs=False) if partial else {}
         return self._cached(("biglm", name, cfg, ui, frames, partial),
                             lambda: pyoracle.biglm_decode(self.oracle, self.handle(name), self._cfg(cfg), o1, o2, x, None, fixed=True, **kw))
+
+
+# ---- what the GPU tests over a World share (nothing here touches the GPU until it is used) ----------------------------------------
+class Gpu:
+    """The device side of a World: each graph file loaded once per option set, the LM pair once; free() at the module's end."""
+
+    def __init__(self, world):
+        import gpu_util as G
+
+        self.G, self.W, self.world = G, G.wfstdec, world
+        self.graphs, self.lms = {}, None
+
+    def graph(self, name, gopt):
+        key = (name, tuple(sorted((gopt or {}).items())))
+        if key not in self.graphs:
+            self.graphs[key] = self.W.Graph.load(self.world.path(name), options=self.W.GraphOptions(**gopt) if gopt else None)
+        return self.graphs[key]
+
+    def lm_pair(self):
+        if self.lms is None:
+            p1, p2 = self.world.lm_paths()
+            self.lms = (self.W.Lm.load(p1, -1.0), self.W.Lm.load(p2, 1.0))
+        return self.lms
+
+    def free(self):
+        for g in self.graphs.values():
+            g.free()
+        for lm in self.lms or ():
+            lm.free()
+
+
+def same_lattice(d, O, what):
+    from test_gpu_lattice import as_raw, nodes
+
+    assert (d is not None) == bool(O.ok), what
+    L = as_raw(d)
+    assert np.array_equal(nodes(L), nodes(O)), what + " lattice states"
+    assert np.array_equal(L.labelled_arcs(), O.labelled_arcs()), what + " lattice arcs"

@@ -58,30 +58,7 @@ CASES = [(leg, name, cfg) for leg, cases in U.leg_cases().items() for name, cfg 
 assert set(LEGS) == set(U.leg_cases())
 
 
-class _Gpu:
-    def __init__(self, world):
-        import gpu_util as G
-
-        self.G, self.W, self.world = G, G.wfstdec, world
-        self.graphs, self.lms = {}, None
-
-    def graph(self, name, gopt):
-        key = (name, tuple(sorted((gopt or {}).items())))
-        if key not in self.graphs:
-            self.graphs[key] = self.W.Graph.load(self.world.path(name), options=self.W.GraphOptions(**gopt) if gopt else None)
-        return self.graphs[key]
-
-    def lm_pair(self):
-        if self.lms is None:
-            p1, p2 = self.world.lm_paths()
-            self.lms = (self.W.Lm.load(p1, -1.0), self.W.Lm.load(p2, 1.0))
-        return self.lms
-
-    def free(self):
-        for g in self.graphs.values():
-            g.free()
-        for lm in self.lms or ():
-            lm.free()
+_Gpu = U.Gpu
 
 
 @pytest.fixture(scope="module")
@@ -110,13 +87,7 @@ def _upload(mats, off4):
     return out
 
 
-def _same_lattice(d, O, what):
-    from test_gpu_lattice import as_raw, nodes
-
-    assert (d is not None) == bool(O.ok), what
-    L = as_raw(d)
-    assert np.array_equal(nodes(L), nodes(O)), what + " lattice states"
-    assert np.array_equal(L.labelled_arcs(), O.labelled_arcs()), what + " lattice arcs"
+_same_lattice = U.same_lattice
 
 
 def _tile_tokens(n, max_active):
