@@ -22,6 +22,7 @@
 #include "wfst_capi_liveprune.h"
 #include "wfst_capi_nbwords.h"
 #include "wfst_capi_align.h"
+#include "wfst_capi_forced.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -52,6 +53,7 @@ struct wfst_graph {
   std::vector<int32_t> ilabel_host;  // original ilabels (re-mapped when tid2pdf changes)
   int32_t max_ilabel = 0;            // the largest of them (the frame posteriors hold a label map against it)
   std::vector<int32_t> tid2phone;    // wfst_graph_set_tid2phone (entry 0 unused); empty: none set
+  std::vector<int32_t> tid2pdf;      // wfst_graph_set_tid2pdf's map as it was given (entry 0 unused); empty: the column is the ilabel
   std::vector<uint16_t> code_host;   // degree code of the target state of every arc slot (fused rows; wfst_device.h)
   int32_t packed = 0;                // the arcs' first word = column | code << kColBits (ilabels below 2^20)
   DevBuf<int4> arcs;  // interleaved rows: header + arcs per state
@@ -285,6 +287,7 @@ struct wfst_decoder {
   IngestState ing; // wfst_decoder_set_score_transform / _advance_chunk / _get_scores (wfst_capi_ingest.cc)
   NbWordsState nbw; // wfst_decoder_get_nbest_words (wfst_capi_nbwords.cc)
   AlignState aln;  // wfst_decoder_align_words (wfst_capi_align.cc)
+  ForcedState fal; // wfst_decoder_force_align (wfst_capi_forced.cc)
   LivePruneState lpr; // wfst_decoder_set_live_lattice_prune (wfst_capi_liveprune.cc): the scratch behind D.snap_extra
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
@@ -727,7 +730,12 @@ int wfst_graph_convert_file(const char *in_path, const char *flat_out_path) {
 int wfst_graph_set_tid2pdf(wfst_graph *g, const int32_t *tid2pdf, int32_t n_tid) {
   if (!g) return fail(WFST_E_ARG, "NULL graph");
   HIP_TRY(hipSetDevice(g->device));
-  return upload_columns(g, tid2pdf, n_tid, nullptr);
+  const int rc = upload_columns(g, tid2pdf, n_tid, nullptr);
+  if (rc != WFST_OK) return rc;
+  // (the host copy: wfst_decoder_force_align prices other graphs' transition-ids by the same map.  upload_columns has checked the
+  // entries THIS graph's arcs use; the others are taken as given, and force_align checks every column it reads against the stride)
+  if (tid2pdf) g->tid2pdf.assign(tid2pdf, tid2pdf + (size_t)n_tid + 1); else g->tid2pdf.clear();
+  return WFST_OK;
 }
 
 int wfst_graph_set_tid2phone(wfst_graph *g, const int32_t *tid2phone, int32_t n_tid) {   // TransitionModel::TransitionIdToPhone
@@ -3667,6 +3675,18 @@ int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fi
     const ChanCtl &cc = d->p_ctl.p[list[i]];
     (*sizes)[4 * i] = cc.lat_toks; (*sizes)[4 * i + 1] = cc.lat_arcs; (*sizes)[4 * i + 2] = cc.n_decoded; (*sizes)[4 * i + 3] = cc.error;
   }
+  return WFST_OK;
+}
+
+// What wfst_capi_forced.cc -- wfst_decoder_force_align, the entry point that launches forced_align_kernel -- needs of a decoder.
+ForcedView forced_view(wfst_decoder *d) {
+  return ForcedView{d->device, d->n_channels, &d->fal, d->h_state.data(), d->h_decoded.data(), d->hist_rows.data(), d->hist_dev.data(),
+                    d->h_ll_base.data(), d->hist_stride, d->D.stride, &d->graph->tid2pdf};
+}
+int forced_stream(wfst_decoder *d, hipStream_t *s) {
+  HIP_TRY(hipSetDevice(d->device));
+  if (!d->copy_stream) HIP_TRY(d->copy_stream.create());
+  *s = d->copy_stream;
   return WFST_OK;
 }
 

@@ -705,6 +705,55 @@ struct RescaleDev {
 constexpr int64_t rescale_out_ints(int64_t cap_words, int64_t cap_tids) { return kRescaleHead + 3 * cap_words + cap_tids; }
 void launch_rescale(const AlignDev &A, const RescaleDev &Q, const RescaleSet &S, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- forced alignment against per-utterance graphs (wfst_forced.hip) -----------------------------------------------------------
+// Exact float32 Viterbi of a listed channel's scores against one small graph of a wfst_align_graphs set (include/wfst_decoder.h,
+// wfst_decoder_force_align).  forced_align_kernel runs one workgroup per list entry.  A graph of the set, all offsets into the set's
+// concatenated arrays:
+//   hdr[g][kFalignHdr]   {start, final state, states S, arcs, epsilon depth, distinct ilabels, offset of in_off, of rec, of lvl_state,
+//                         of lvl_off, of labels, of arcs, largest ilabel, 0, 0, 0}
+//   in_off[S + 1]        per destination state {its first in-arc record, its first EPSILON record}; the emitting records come first,
+//                        each kind by arc index ascending: the first exact minimum in record order is the tie rule's winner
+//   rec[]                {source state, slot of the ilabel in labels[] (-1: an epsilon arc), bits of the weight, arc index}
+//   lvl_state[], lvl_off[depth + 1]   the states with epsilon in-arcs by level of the epsilon DAG, level L at lvl_off[L - 1] .. lvl_off[L]
+//   labels[]             the graph's distinct non-zero ilabels, ascending
+//   arcs[]               the caller's arcs {ilabel, olabel, bits of the weight, nextstate}
+constexpr int32_t kFalignLdsStates = 4096;   // = WFST_FALIGN_LDS_STATES: the two cost rows of a graph up to this size live in LDS
+constexpr int32_t kFalignLdsLabels = 1024;   // distinct ilabels whose scores are staged in LDS one frame ahead (beyond: gathered)
+constexpr int32_t kFalignHdr = 16;
+struct ForcedGraphsDev {
+  const int32_t *hdr;
+  const int2 *in_off;
+  const int4 *rec;
+  const int32_t *lvl_state, *lvl_off, *labels;
+  const int4 *arcs;
+};
+struct ForcedChan {        // one list entry
+  const float *ll;         // row 0 of the channel's scores (not read where T == 0)
+  int64_t bp_off;          // of its (T + 1) x S backpointers, in cells
+  int64_t row_off;         // of its two cost rows in the workspace, in floats (a graph beyond kFalignLdsStates)
+  int64_t path_off;        // of its traced path, in ints
+  int32_t graph, T, stride, path_cap;
+};
+//   bp[]                 per (frame, state) the winning in-arc record + 1, 0: the seed or not reached
+//   out[i]               falign_out_ints(): kFalignHead ints {found, T, bits of path_cost, of tot_score, of lm_score, n_hops, n_words,
+//                        error (1: the walk left the table)}, hop_arc[cap_hops], alignment[cap_frames], words[cap_words],
+//                        word_frame[cap_words]; zero-filled by the host before the launch
+constexpr int32_t kFalignHead = 8;
+struct ForcedDev {
+  ForcedGraphsDev G;
+  const ForcedChan *chan;
+  const int32_t *col_map;     // the decoder graph's tid2pdf (nullptr: the column is the transition-id)
+  const int32_t *label_map;   // the caller's class per transition-id (nullptr: none)
+  int32_t *bp, *path;
+  float *rows;
+  int32_t cap_frames, cap_hops, cap_words;
+  int32_t *out;
+};
+constexpr int64_t falign_out_ints(int64_t cap_frames, int64_t cap_hops, int64_t cap_words) {
+  return kFalignHead + cap_hops + cap_frames + 2 * cap_words;
+}
+void launch_forced_align(const ForcedDev &Q, int cnt, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

@@ -79,6 +79,12 @@
 //                  n_dropped=.. log_z=..".  Classes as --frame-post-class has them; the arcs cost GS * graph + AS * acoustic
 //                  (default 1,1); --seq-silence: classes that never count as correct (sMBR); --seq-drop-frames: MMI's
 //                  --drop-frames.  The other output is what it is without the flag.
+//   --force-align=DIR [--force-align-class=tid|pdf|phone]  batch shape and --single-stream: after the utterance's other lines the
+//                  forced alignment of its scores against its own graph DIR/KEY.fst, in any format the decoding graph may have
+//                  (ForceAlign: wfst_decoder_force_align; Kaldi's align-compiled-mapped), as "KEY forced found=0|1 cost=.. ali=t0 t1
+//                  ..." -- cost the path's cost (float32, 9 digits), one class per frame: transition-ids, or pdfs (--tid2pdf=FILE)
+//                  or phones (--tid2phone=FILE) -- and "KEY forced-words w@frame ...", every word with the frame it begins at.
+//                  The other output is what it is without the flag.
 //   --rescale=GS,AS,WIP[:GS,AS,WIP...]  batch shape and --single-stream: after the utterance's other lines, per setting (at most 64:
 //                  graph scale, acoustic scale, word insertion penalty) the best path of the RAW lattice picked again under it,
 //                  without decoding again (RescaledWords: wfst_decoder_rescaled_words; Kaldi's lattice-best-path-score), as
@@ -266,6 +272,8 @@ int main(int argc, char **argv) {
     std::string seq_stats_file, seq_ref_file, seq_class = "tid", seq_criterion = "smbr";   // --seq-stats
     SequenceStatsOptions seq_opt;
     bool seq_opts = false, seq_bad = false;
+    std::string force_dir, force_class = "tid";   // --force-align
+    bool force_opts = false;
     std::vector<RescaleSetting> rescale_set;   // --rescale
     bool rescale_bad = false;
     bool word_conf = false, sent_post = false;
@@ -349,6 +357,8 @@ int main(int argc, char **argv) {
         fp_opts = true;
         if (sscanf(a.c_str() + 17, "%lf%c", &fp_min, &tail) != 1 || !(fp_min >= 0.0 && fp_min <= 1.0)) fp_bad = true;
       }
+      else if (a.compare(0, 14, "--force-align=") == 0) force_dir = a.substr(14);
+      else if (a.compare(0, 20, "--force-align-class=") == 0) { force_class = a.substr(20); force_opts = true; }
       else if (a.compare(0, 12, "--seq-stats=") == 0) seq_stats_file = a.substr(12);
       else if (a.compare(0, 10, "--seq-ref=") == 0) { seq_ref_file = a.substr(10); seq_opts = true; }
       else if (a.compare(0, 16, "--seq-criterion=") == 0) { seq_criterion = a.substr(16); seq_opts = true; }
@@ -422,7 +432,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -463,7 +473,13 @@ int main(int argc, char **argv) {
     if (rescale_set.size() > 64) { std::cerr << "--rescale: more than 64 settings\n"; return 1; }
     const bool rescale = !rescale_set.empty();
     if (rescale && n_threads > 0) { std::cerr << "--rescale goes with the batch shape or --single-stream\n"; return 1; }
-    const bool phones_for_frame_post = (frame_post && fp_class == "phone") || (seq_stats && seq_class == "phone");   // (--tid2phone given for this alone is no endpointing)
+    const bool force_align = !force_dir.empty();
+    if (!force_align && force_opts) { std::cerr << "--force-align-class goes with --force-align=DIR\n"; return 1; }
+    if (force_align && n_threads > 0) { std::cerr << "--force-align goes with the batch shape or --single-stream\n"; return 1; }
+    if (force_align && force_class != "tid" && force_class != "pdf" && force_class != "phone") { std::cerr << "--force-align-class=tid|pdf|phone\n"; return 1; }
+    if (force_align && force_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--force-align-class=pdf needs --tid2pdf=FILE\n"; return 1; }
+    if (force_align && force_class == "phone" && tid2phone_file.empty()) { std::cerr << "--force-align-class=phone needs --tid2phone=FILE\n"; return 1; }
+    const bool phones_for_frame_post = (frame_post && fp_class == "phone") || (seq_stats && seq_class == "phone") || (force_align && force_class == "phone");   // (--tid2phone given for this alone is no endpointing)
     // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
     for (int which = 0; which < 3; ++which) {
@@ -754,6 +770,20 @@ int main(int argc, char **argv) {
           out << head << "#" << (j + 1) << " " << a.words[j] << " " << a.frames[j].first << " " << a.frames[j].second << "\n";
         nr_err += a.errors; nr_words += (long long)it->second[q].size(); nr_ins += a.ins; nr_del += a.del; nr_sub += a.sub;
       }
+    };
+    // --force-align: the class of a transition-id, an utterance's graph file and its two lines
+    std::vector<int> force_map;
+    if (force_align && force_class == "pdf") force_map.assign(tid2pdf.begin(), tid2pdf.end());
+    if (force_align && force_class == "phone") force_map.assign(tid2phone.begin(), tid2phone.end());
+    auto force_file = [&](const Utt &u) { return force_dir + "/" + u.key + ".fst"; };
+    auto emit_forced = [&](const Utt &u, const ForcedAlignment &fa) {
+      char buf[96];
+      snprintf(buf, sizeof(buf), " forced found=%d cost=%.9g ali=", fa.found ? 1 : 0, (double)fa.path_cost);
+      out << u.key << buf;
+      for (size_t f = 0; f < fa.alignment.size(); ++f) out << (f ? " " : "") << fa.alignment[f];
+      out << '\n' << u.key << " forced-words";
+      for (size_t k = 0; k < fa.words.size(); ++k) out << ' ' << fa.words[k] << '@' << fa.word_frame[k];
+      out << '\n';
     };
     // --rescale: an utterance's lines, one per setting
     auto emit_rescale = [&](const Utt &u, const std::vector<RescaledWords> &rw) {
@@ -1191,6 +1221,13 @@ int main(int argc, char **argv) {
           decode.RescaledWords(rescale_set, &rw);
           emit_rescale(u, rw);
         }
+        if (force_align) {
+          AlignGraphs ag;
+          if (!ag.Read(std::vector<std::string>(1, force_file(u)), devices[0])) throw std::runtime_error("--force-align: cannot load " + force_file(u));
+          ForcedAlignment fa;
+          decode.ForceAlign(ag, 0, &fa, force_map);
+          emit_forced(u, fa);
+        }
       }
     } else {  // the MI355X shape: `batch` utterances per pass, `inflight` passes at a time
       struct BatchOut {
@@ -1206,6 +1243,7 @@ int main(int argc, char **argv) {
         std::vector<FramePosteriors> frame_post;                      // --frame-post
         std::vector<std::vector<RescaledWords> > rescaled;            // --rescale
         std::vector<SequenceStats> seq_stats;                         // --seq-stats
+        std::vector<ForcedAlignment> forced;                          // --force-align
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -1354,6 +1392,13 @@ int main(int argc, char **argv) {
               for (int i = 0; i < n; ++i) refs[i] = seq_ref_of(utts[b0 + i]);
               decode.SequenceStats(ch, refs, seq_opt, &o.seq_stats);
             }
+            if (force_align) {                                                                               // every channel in one launch
+              std::vector<std::string> files(n);
+              for (int i = 0; i < n; ++i) files[i] = force_file(utts[b0 + i]);
+              AlignGraphs ag;
+              if (!ag.Read(files, devices[(size_t)di])) throw std::runtime_error("--force-align: cannot load the graphs of " + force_dir);
+              decode.ForceAlign(ch, ag, std::vector<int>(), force_map, &o.forced);
+            }
           }
         } catch (const std::exception &e) {
           errors[(size_t)k] = e.what();
@@ -1388,6 +1433,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && !o.frame_post.empty(); ++i) emit_frame_post(utts[b0 + i], o.frame_post[i]);
         for (int i = 0; i < n && !o.rescaled.empty(); ++i) emit_rescale(utts[b0 + i], o.rescaled[i]);
         for (int i = 0; i < n && !o.seq_stats.empty(); ++i) emit_seq_stats(utts[b0 + i], o.seq_stats[i]);
+        for (int i = 0; i < n && !o.forced.empty(); ++i) emit_forced(utts[b0 + i], o.forced[i]);
       }
     }
     if (!nearest_refs.empty()) {   // errors over reference words, as nbest-compute-wer prints them

@@ -30,6 +30,9 @@
 #pragma weak wfst_decoder_frame_posteriors
 #pragma weak wfst_decoder_rescaled_words
 #pragma weak wfst_decoder_sequence_stats
+#pragma weak wfst_decoder_force_align
+#pragma weak wfst_align_graphs_load
+#pragma weak wfst_align_graphs_free
 
 namespace datemoon {
 
@@ -2203,6 +2206,100 @@ void GpuLatticeDecoder::SequenceStats(const std::vector<int> &ref, struct Sequen
     if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
   });
   if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("SequenceStats: " + msg);
+  if (out) *out = o[0];
+}
+
+// ---- forced alignment against per-utterance graphs (wfst_decoder_force_align) -----------------------------------------------------------
+AlignGraphs::~AlignGraphs() {
+  if (_g && wfst_align_graphs_free) wfst_align_graphs_free(_g);
+}
+
+bool AlignGraphs::Read(const std::vector<std::string> &files, int device) {
+  if (!wfst_align_graphs_load) throw std::runtime_error("AlignGraphs: this build's device library has no wfst_align_graphs_load");
+  if (_g) { wfst_align_graphs_free(_g); _g = nullptr; _n = 0; }
+  std::vector<const char *> paths;
+  for (const std::string &f : files) paths.push_back(f.c_str());
+  if (wfst_align_graphs_load((int32_t)paths.size(), paths.data(), device, &_g) != WFST_OK) {
+    Warn(std::string("AlignGraphs: ") + wfst_last_error());
+    _g = nullptr;
+    return false;
+  }
+  _n = (int)files.size();
+  return true;
+}
+
+// One C-ABI call for `ch`: (*out)[i] for listed channel i, its own code in status.  Returns the call's own code.  The rows take their
+// room from the frames decoded; a path that needs more is asked for again, once, with the room it reports.
+static int ForceAlignCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const AlignGraphs &graphs, const std::vector<int> &graph_of,
+                          const std::vector<int> &label_map, long long max_cells, std::vector<ForcedAlignment> *out) {
+  if (!wfst_decoder_force_align) throw std::runtime_error("ForceAlign: this build's device library has no wfst_decoder_force_align");
+  const size_t cnt = ch.size();
+  if (!graph_of.empty() && graph_of.size() != cnt) throw std::runtime_error("ForceAlign: one graph per listed channel");
+  std::vector<int32_t> gof(graph_of.begin(), graph_of.end());
+  if (gof.empty())
+    for (size_t i = 0; i < cnt; ++i) gof.push_back((int32_t)i);
+  const std::vector<int32_t> map(label_map.begin(), label_map.end());
+  size_t capf = 1;
+  for (int32_t c : ch) capf = std::max(capf, (size_t)std::max(wfst_decoder_num_frames_decoded(dec, c), 0));
+  size_t caph = 2 * capf + 8, capw = capf + 8;
+  std::vector<int32_t> st(cnt), fnd(cnt), nf(cnt), nh(cnt), nw(cnt), hops, ali, words, wf;
+  std::vector<float> cost(cnt), tot(cnt), lm(cnt);
+  for (int pass = 0;; ++pass) {
+    hops.assign(cnt * caph, 0); ali.assign(cnt * capf, 0); words.assign(cnt * capw, 0); wf.assign(cnt * capw, 0);
+    const int rc = wfst_decoder_force_align(dec, ch.data(), (int32_t)cnt, graphs.Handle(), gof.data(), nullptr, map.empty() ? nullptr : map.data(),
+                                            map.empty() ? 0 : (int32_t)map.size() - 1, max_cells, (int32_t)capf, (int32_t)caph, (int32_t)capw,
+                                            st.data(), fnd.data(), nf.data(), cost.data(), tot.data(), lm.data(), nh.data(), hops.data(),
+                                            ali.data(), nw.data(), words.data(), wf.data());
+    if (rc != WFST_OK) return rc;
+    size_t need_f = capf, need_h = caph, need_w = capw;
+    for (size_t i = 0; i < cnt; ++i)
+      if (st[i] == WFST_E_CAPACITY) {
+        need_f = std::max(need_f, (size_t)nf[i]); need_h = std::max(need_h, (size_t)nh[i]); need_w = std::max(need_w, (size_t)nw[i]);
+      }
+    if (pass || (need_f == capf && need_h == caph && need_w == capw)) break;
+    capf = need_f; caph = need_h; capw = need_w;
+  }
+  out->assign(cnt, ForcedAlignment());
+  for (size_t i = 0; i < cnt; ++i) {
+    ForcedAlignment &a = (*out)[i];
+    a.status = st[i];
+    if (st[i] != WFST_OK || !fnd[i]) continue;
+    a.found = true;
+    a.n_frames = nf[i];
+    a.path_cost = cost[i]; a.tot = tot[i]; a.lm = lm[i];
+    a.hop_arc.assign(hops.begin() + i * caph, hops.begin() + i * caph + nh[i]);
+    a.alignment.assign(ali.begin() + i * capf, ali.begin() + i * capf + nf[i]);
+    a.words.assign(words.begin() + i * capw, words.begin() + i * capw + nw[i]);
+    a.word_frame.assign(wf.begin() + i * capw, wf.begin() + i * capw + nw[i]);
+  }
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::ForceAlign(const std::vector<int> &channels, const AlignGraphs &graphs, const std::vector<int> &graph_of,
+                                 const std::vector<int> &label_map, std::vector<ForcedAlignment> *out, std::vector<int> *status,
+                                 long long max_cells) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<ForcedAlignment> o;
+  if (ForceAlignCall(_dec, ch, graphs, graph_of, label_map, max_cells, &o) != WFST_OK) Fatal("ForceAlign");
+  if (status) status->clear();
+  for (const ForcedAlignment &a : o) {
+    if (status) status->push_back(a.status);
+    else if (a.status != WFST_OK) Fatal("ForceAlign");
+  }
+  if (out) out->swap(o);
+}
+
+void GpuLatticeDecoder::ForceAlign(const AlignGraphs &graphs, int graph, ForcedAlignment *out, const std::vector<int> &label_map) {
+  std::vector<ForcedAlignment> o;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = ForceAlignCall(_dec, std::vector<int32_t>(1, _chan), graphs, std::vector<int>(1, graph), label_map, 0, &o);
+    if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("ForceAlign: " + msg);
   if (out) *out = o[0];
 }
 

@@ -488,6 +488,34 @@ struct SequenceStatsOptions {
   long long max_cells = 0;
 };
 
+// Forced alignment of a channel's scores against the utterance's own graph (wfst_decoder_force_align; Kaldi's align-compiled-mapped):
+// exact float32 Viterbi, bit for bit reproducible.  hop_arc = the path's arcs as indices into the graph's arc array; alignment = one
+// class per frame (the transition-id, or label_map of it: SequenceStats' `ref` as it stands); words / word_frame = the path's words
+// with the frame each begins at; path_cost = the table's cost of the path, tot / lm = LatticeToVector's two scores of it.
+// found = false (everything else empty / zero): the graph does not accept the channel's frames.
+struct ForcedAlignment {
+  int status = 0;
+  bool found = false;
+  int n_frames = 0;
+  float path_cost = 0.0f, tot = 0.0f, lm = 0.0f;
+  std::vector<int> hop_arc, alignment, words, word_frame;
+};
+// A set of per-utterance graphs resident on a device (wfst_align_graphs): files[i] in any format Fst::ReadFst reads.
+class AlignGraphs {
+ public:
+  AlignGraphs() : _g(nullptr), _n(0) {}
+  ~AlignGraphs();
+  bool Read(const std::vector<std::string> &files, int device = 0);  // false (with a message on stderr) on failure
+  int Size() const { return _n; }
+  const wfst_align_graphs *Handle() const { return _g; }
+
+ private:
+  AlignGraphs(const AlignGraphs &);
+  AlignGraphs &operator=(const AlignGraphs &);
+  wfst_align_graphs *_g;
+  int _n;
+};
+
 // The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
 // cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
 // them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
@@ -631,6 +659,10 @@ class GpuLatticeDecoder : public DecoderItf {
   // end: unlabelled), mid-utterance or after FinalizeDecoding, in one device call (wfst_decoder_sequence_stats); opt.grad holds at most
   // one pointer.  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void SequenceStats(const std::vector<int> &ref, struct SequenceStats *out, const SequenceStatsOptions &opt = SequenceStatsOptions());
+  // The forced alignment of the channel's scores -- the frames handed over so far -- against graph `graph` of `graphs`, mid-utterance
+  // or after FinalizeDecoding, in one device call (wfst_decoder_force_align); label_map as FramePosteriors takes it.  The channel's
+  // own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void ForceAlign(const AlignGraphs &graphs, int graph, ForcedAlignment *out, const std::vector<int> &label_map = std::vector<int>());
   // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
   // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
@@ -772,6 +804,12 @@ class GpuBatchDecoder {
   // given the room the lattices need.
   void SequenceStats(const std::vector<int> &channels, const std::vector<std::vector<int> > &refs, const SequenceStatsOptions &opt,
                      std::vector<struct SequenceStats> *out, std::vector<int> *status = nullptr);
+  // ForceAlign (see GpuLatticeDecoder) of many channels (none listed: all) in one launch: graph_of[i] = the graph of listed channel i
+  // (empty: graph i), (*out)[i] its answer, its own error code in (*out)[i].status (without `status` it throws); the rows are given
+  // the room the paths need.  max_cells: see wfst_decoder_force_align.
+  void ForceAlign(const std::vector<int> &channels, const AlignGraphs &graphs, const std::vector<int> &graph_of,
+                  const std::vector<int> &label_map, std::vector<ForcedAlignment> *out, std::vector<int> *status = nullptr,
+                  long long max_cells = 0);
   // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
   // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.

@@ -51,6 +51,8 @@ SYMBOLS = [
     "wfst_decoder_align_words", "wfst_decoder_nearest_words", "wfst_decoder_word_confidence",
     "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives", "wfst_decoder_frame_posteriors",
     "wfst_decoder_rescaled_words", "wfst_decoder_sequence_stats",
+    "wfst_align_graphs_create", "wfst_align_graphs_load", "wfst_align_graphs_info", "wfst_align_graphs_free", "wfst_decoder_force_align",
+    "wfst_decoder_force_align_workspace",
 ]
 
 
@@ -340,6 +342,72 @@ class Graph:
         if self.h:
             lib().wfst_graph_free(self.h)
             self.h = None
+
+
+class AlignGraphs:
+    """A set of small per-utterance graphs resident in HBM, for BatchDecoder.force_align (wfst_align_graphs)."""
+
+    def __init__(self, handle, n_graphs):
+        self.h = handle
+        self.n_graphs = int(n_graphs)
+
+    @staticmethod
+    def from_arrays(graphs, device=0):
+        """graphs: a list of (start, final_state, state_info, arcs), each as Graph.from_arrays takes them."""
+        graphs = list(graphs)
+        k = len(graphs)
+        start = np.ascontiguousarray([int(g[0]) for g in graphs], dtype=np.int32)
+        final = np.ascontiguousarray([int(g[1]) for g in graphs], dtype=np.int32)
+        sis = [np.ascontiguousarray(g[2]) for g in graphs]
+        ars = [np.ascontiguousarray(g[3]) for g in graphs]
+        assert all(x.dtype.itemsize == 12 for x in sis) and all(x.dtype.itemsize == 16 for x in ars)
+        ns = np.ascontiguousarray([x.shape[0] for x in sis], dtype=np.int32)
+        na = np.ascontiguousarray([x.shape[0] for x in ars], dtype=np.int32)
+        si = np.frombuffer(b"".join(x.tobytes() for x in sis), dtype=np.uint8)
+        ar = np.frombuffer(b"".join(x.tobytes() for x in ars), dtype=np.uint8)
+        h = C.c_void_p()
+        _check(lib().wfst_align_graphs_create(k, _i32(start), _i32(final), _i32(ns), _i32(na),
+                                              si.ctypes.data_as(C.c_void_p) if si.size else None,
+                                              ar.ctypes.data_as(C.c_void_p) if ar.size else None, int(device), C.byref(h)))
+        return AlignGraphs(h, k)
+
+    @staticmethod
+    def load(paths, device=0):
+        """One graph per file, in any format Graph.load reads (wfst_align_graphs_load)."""
+        paths = [p.encode() for p in paths]
+        h = C.c_void_p()
+        _check(lib().wfst_align_graphs_load(len(paths), (C.c_char_p * max(len(paths), 1))(*paths), int(device), C.byref(h)))
+        return AlignGraphs(h, len(paths))
+
+    def info(self):
+        k = self.n_graphs
+        n, ts, ta, b = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        v = [np.zeros(k, np.int32) for _ in range(5)]
+        _check(lib().wfst_align_graphs_info(self.h, C.byref(n), C.byref(ts), C.byref(ta), *[_i32(x) for x in v], C.byref(b)))
+        return dict(n_graphs=n.value, total_states=ts.value, total_arcs=ta.value, n_states=v[0], n_arcs=v[1], max_ilabel=v[2],
+                    eps_depth=v[3], n_labels=v[4], device_bytes=b.value)
+
+    def free(self):
+        if self.h:
+            lib().wfst_align_graphs_free(self.h)
+            self.h = None
+
+
+class ForcedAlignment(object):
+    """One channel's answer of BatchDecoder.force_align: status (WFST_OK or the CHANNEL's own error code), found, n_frames,
+    path_cost / tot_score / lm_score (numpy float32), hop_arc (arc indices of the channel's graph), alignment (one class per
+    frame), words and word_frame (int32 arrays)."""
+
+    __slots__ = ("status", "found", "n_frames", "path_cost", "tot_score", "lm_score", "n_hops", "hop_arc", "alignment", "n_words",
+                 "words", "word_frame")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def __repr__(self):
+        return "ForcedAlignment(status=%d, found=%r, n_frames=%d, path_cost=%r, n_hops=%d, n_words=%d)" % (
+            self.status, self.found, self.n_frames, self.path_cost, self.n_hops, self.n_words)
 
 
 class Lm:
@@ -1179,6 +1247,64 @@ class BatchDecoder:
                 row.append(d)
             out.append(row)
         return out
+
+    def force_align(self, graphs, graph_of=None, channels=None, n_frames=None, label_map=None, max_cells=0, cap_frames=None,
+                    cap_hops=None, cap_words=None):
+        """Forced alignment of the listed channels' scores (None: all) against per-utterance graphs (wfst_decoder_force_align):
+        graphs = an AlignGraphs set, graph_of[i] = the graph of listed channel i (None: graph i), n_frames[i] = the frames to
+        align (None or -1: all the channel holds), label_map = class per transition-id for `alignment` (entry 0 unused).  Works on
+        every kind of decoder and on live, finalized and never-decoded channels alike; only reads the decoder.  Per channel one
+        ForcedAlignment, bit for bit reproducible.  The capacities are chosen from the frames held; where a channel answers that
+        its path needs more room the call is made once more, with it."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        gof = np.ascontiguousarray(list(range(cnt)) if graph_of is None else [int(g) for g in graph_of], dtype=np.int32)
+        if gof.shape[0] != cnt:
+            raise ValueError("one graph per listed channel")
+        nfi = None
+        if n_frames is not None:
+            nfi = np.ascontiguousarray([-1 if t is None else int(t) for t in n_frames], dtype=np.int32)
+            if nfi.shape[0] != cnt:
+                raise ValueError("one frame count per listed channel")
+        m, n_tid = None, 0
+        if label_map is not None:
+            m = np.ascontiguousarray(label_map, dtype=np.int32)
+            n_tid = int(m.shape[0]) - 1
+        # (a first guess at the frames: a channel that holds more than it has decoded answers with the room it needs)
+        guess = max([int(t) for t in nfi if t >= 0] + [1]) if nfi is not None and (nfi >= 0).all() else \
+            max([max(self.num_frames_decoded(int(c)), 0) for c in ch] + [1]) if cnt else 1
+        capf = int(cap_frames) if cap_frames is not None else guess
+        caph = int(cap_hops) if cap_hops is not None else 2 * guess + 8
+        capw = int(cap_words) if cap_words is not None else guess + 8
+        for attempt in range(2):
+            k = max(cnt, 1)
+            status, found, nf, nh, nw = (np.zeros(k, np.int32) for _ in range(5))
+            cost, tot, lm = (np.zeros(k, np.float32) for _ in range(3))
+            hops, ali = np.zeros((k, max(caph, 1)), np.int32), np.zeros((k, max(capf, 1)), np.int32)
+            words, wf = np.zeros((k, max(capw, 1)), np.int32), np.zeros((k, max(capw, 1)), np.int32)
+            _check(lib().wfst_decoder_force_align(self.h, _i32(ch), cnt, graphs.h, _i32(gof), _i32(nfi), _i32(m), n_tid,
+                                                  C.c_int64(int(max_cells)), max(capf, 1), max(caph, 1), max(capw, 1), _i32(status),
+                                                  _i32(found), _i32(nf), _f32(cost), _f32(tot), _f32(lm), _i32(nh), _i32(hops),
+                                                  _i32(ali), _i32(nw), _i32(words), _i32(wf)))
+            short = (status[:cnt] == -4) & ((nf[:cnt] > max(capf, 1)) | (nh[:cnt] > max(caph, 1)) | (nw[:cnt] > max(capw, 1)))
+            if attempt or not short.any():
+                break
+            capf, caph, capw = max(capf, int(nf.max())), max(caph, int(nh.max())), max(capw, int(nw.max()))
+        out = []
+        for i in range(cnt):
+            ok = bool(found[i])
+            t, h, w = (min(int(nf[i]), max(capf, 1)), min(int(nh[i]), max(caph, 1)), min(int(nw[i]), max(capw, 1))) if ok else (0, 0, 0)
+            out.append(ForcedAlignment(status=int(status[i]), found=ok, n_frames=int(nf[i]), path_cost=np.float32(cost[i]),
+                                       tot_score=np.float32(tot[i]), lm_score=np.float32(lm[i]), n_hops=int(nh[i]),
+                                       hop_arc=hops[i, :h].copy(), alignment=ali[i, :t].copy(), n_words=int(nw[i]),
+                                       words=words[i, :w].copy(), word_frame=wf[i, :w].copy()))
+        return out
+
+    def force_align_workspace(self):
+        """Bytes of the decoder's forced-alignment workspace (wfst_decoder_force_align_workspace)."""
+        b = C.c_int64()
+        _check(lib().wfst_decoder_force_align_workspace(self.h, C.byref(b)))
+        return int(b.value)
 
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):
         """nbest_words(...) with word times: every path's words aligned on its channel's raw lattice (align_words); the dicts of

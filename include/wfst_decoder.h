@@ -963,7 +963,8 @@ int wfst_decoder_frame_posteriors(wfst_decoder *d, const int32_t *channels, int3
  * aligned to 4 bytes, a class beyond n_cols as above) or WFST_E_STATE as there.  Any output pointer may be NULL.  The decoder's state
  * is only read: decoding goes on bit for bit as without the call.
  * Not computed here: minimum Bayes risk decoding and the pivot algorithm's second half, the MMI numerator's log-probability,
- * Kaldi's one_silence_class variant, a half-precision dense output. */
+ * Kaldi's one_silence_class variant, a half-precision dense output.
+ * (The numerator alignment `ref` and its cost come from wfst_decoder_force_align with label_map = the same map.) */
 #define WFST_SEQ_MMI 0
 #define WFST_SEQ_SMBR 1
 #define WFST_SEQSTAT_LDS_RECS 1024 /* emitting arcs of one frame that are sorted and summed on chip */
@@ -1043,6 +1044,94 @@ int wfst_decoder_rescaled_words(wfst_decoder *d, const int32_t *channels, int32_
                                 int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame /* [n][n_set][cap_words] */,
                                 int32_t *tids /* [n][n_set][cap_tids], or NULL */,
                                 double *scaled_cost /* [n][n_set] */, float *tot_score, float *lm_score /* [n][n_set] */);
+
+/* ---- forced alignment: exact Viterbi of a channel's scores against the utterance's own graph -----------------------------------------
+ * Everything above reads the lattice the search left behind; a transcript that is not in the lattice is not found there.  This call
+ * aligns a channel's SCORES against a small graph the caller brings per utterance -- a compiled training graph, a transcript
+ * acceptor -- as Kaldi's align-compiled-mapped does: the numerator alignment and its cost for MMI / sMBR (wfst_decoder_sequence_stats'
+ * `ref`), word and phone times of a known transcript, "does this transcript fit this audio at all", realignment between training
+ * stages.  The scores are the ones the decoder holds on the device; one launch per round (forced_align_kernel), one workgroup per
+ * listed channel.
+ *
+ * A graph G is given in the reference format, exactly as wfst_graph_from_arrays takes it: start, ONE final_state, wfst_state_info x S,
+ * wfst_arc x A, every state's input-epsilon arcs first.  An arc's INDEX is its position in G's arc array.  ll(f, tid) is row f of the
+ * channel's scores at column tid2pdf[tid] of the DECODER's own graph (wfst_graph_set_tid2pdf), column tid without a map: what the
+ * search itself reads.  T is the number of frames aligned.
+ * The table V[f][s], 0 <= f <= T, float32, every operation rounded on its own (no fused multiply-add):
+ *   V[0][start] has the seed 0.
+ *   an emitting arc a: s -> t (ilabel != 0) out of frame f < T offers (V[f][s] + (-ll(f, ilabel))) + w(a) to V[f + 1][t]: the acoustic
+ *     cost first, then the graph cost (cur_cost + ac_cost + graph_cost, as the search adds them);
+ *   an epsilon arc a: s -> t (ilabel 0) offers V[f][s] + w(a) to V[f][t], inside frame f;
+ *   a candidate x that is not finite (x - x != 0: NaN or an infinity) is no candidate;
+ *   V[f][t] is the least candidate, +inf without one.
+ * Epsilon weights may be negative.  A graph whose epsilon arcs form a cycle, of any weight, is refused when the set is created, so a
+ * frame is a DAG and V is well defined.
+ * The backpointer of a reached (f, t): the seed at (0, start); everywhere else, among the candidates that equal V[f][t] exactly, an
+ * emitting arc before an epsilon arc, then the least arc index: the oracle's tie rule 1 for arrivals.  It does not depend on any
+ * order in which the device visits arcs.
+ * found = V[T][final_state] is finite; path_cost = V[T][final_state]; the path follows the backpointers from (T, final_state) to the
+ * seed.  With the path's arcs in order: hop_arc[0 .. n_hops) their arc indices; alignment[f] the ilabel of the emitting arc out of
+ * frame f, or label_map[ilabel] where the caller gives a map (n_tid + 1 entries >= 0, entry 0 unused, as
+ * wfst_decoder_frame_posteriors takes it: the row is wfst_decoder_sequence_stats' ref as it stands); words[0 .. n_words) the non-zero
+ * olabels in path order; word_frame[k] the frame of the SOURCE state of the arc that carries word k (wfst_decoder_align_words' begin
+ * frame); tot_score and lm_score wfst_lattice_to_vector's two sums over the hop list: sequential float32 sums of graph + acoustic and
+ * of graph, epsilon hops included, the acoustic cost being -ll(f, ilabel), 0 on an epsilon hop.  found = 0 zeroes every output of
+ * that channel with status OK.  T = 0 is legal: the path is epsilon arcs from start to final_state, or nothing if they are one state.
+ * Min-plus in float32 with a fixed tie rule: the results are bit for bit reproducible.
+ *
+ * wfst_align_graphs: n_graphs graphs uploaded together; states and arcs are the graphs' arrays one behind the other.  Creation
+ * validates on the host BEFORE it touches a device: everything wfst_graph_from_arrays checks of the format, labels >= 0, nextstate in
+ * range, no epsilon cycle (WFST_E_FORMAT, the graph and a state of the cycle named in wfst_last_error).  It then builds an in-arc
+ * index by destination state (emitting records first, arc index ascending: the first exact minimum in record order is the tie
+ * rule's winner), every state's level in the epsilon DAG (a frame's epsilon arcs are settled in `depth` ordered passes) and the list
+ * of distinct ilabels of each graph: 32 bytes per arc and 8 to 12 per state on the device.  wfst_align_graphs_info: the totals, per graph
+ * (arrays of n_graphs, any may be NULL) n_states, n_arcs, the largest ilabel, the epsilon depth and the distinct ilabels, and the
+ * device bytes.
+ *
+ * wfst_decoder_force_align works on best-path, lattice and biglm decoders alike and on every initialised channel -- live, finalized,
+ * or fed with max_num_frames = 0 and never decoded -- because it reads scores only.  The frames: those a library-held history holds
+ * (wfst_decoder_advance_host, wfst_decoder_advance_chunk); for a channel fed through wfst_decoder_advance the frames DECODED of the
+ * caller's matrix, whose rows that call's contract keeps valid.  n_frames_in[i] (NULL: all -1) may ask for fewer, -1 = all; more is
+ * WFST_E_ARG.  graph_of[i] is the graph of listed channel i.  The call runs behind the channels' ingests, as wfst_decoder_get_scores
+ * does, and is synchronous, as wfst_decoder_align_words is.  The decoder's state is only read: decoding goes on bit for bit as
+ * without the call.  Any output pointer may be NULL; a capacity is looked at only where its rows are given.
+ * A failure of ONE channel goes into status[i] and the call still returns WFST_OK: a table of (T + 1) x n_states cells beyond
+ * max_cells (WFST_E_CAPACITY, n_frames[i] = T, everything else zero; 0 = wfst_decoder_align_words' default bound, 65 536 x 65), or
+ * T > cap_frames, n_hops > cap_hops or n_words > cap_words (WFST_E_CAPACITY: n_frames / n_hops / n_words are the room needed, so that
+ * the call can be repeated once; what fits is written and the scores stand).
+ * The call itself fails, before any device work, with WFST_E_ARG (a NULL decoder, channel list, graph set or graph_of; a graph_of
+ * out of range; a graph whose largest ilabel lies beyond the tid2pdf map or whose transition-ids read a column beyond the score
+ * stride; n_frames_in below -1 or above the frames held; a negative capacity or max_cells; label_map given with n_tid < 1, with a
+ * negative entry or shorter than a listed graph's largest ilabel; a bad or duplicate channel list; a graph set on another device)
+ * or WFST_E_STATE (a listed channel never initialised).
+ * The workspace is the decoder's, grown on demand: 4 bytes per (frame, state) cell for the backpointers, 4 per possible hop for the
+ * traced path, and 8 per state for the two cost rows of a graph of more than WFST_FALIGN_LDS_STATES states -- up to that size the rows
+ * live on chip, and the answers do not depend on which.  Lists whose cells pass 256 MiB together are taken in rounds; an explicit
+ * max_cells bounds the cells of one round as well (at least one channel per round), and with them the workspace.
+ * wfst_decoder_force_align_workspace: the bytes held.
+ * Not computed here: a beam (the table is dense), graphs compiled from transcripts and lexicons, Kaldi table I/O, device-resident
+ * outputs, per-arc posteriors of the numerator graph. */
+#define WFST_FALIGN_LDS_STATES 4096 /* states of a graph whose two float32 cost rows live in LDS (32 KiB of a workgroup's 64) */
+typedef struct wfst_align_graphs wfst_align_graphs;
+int wfst_align_graphs_create(int32_t n_graphs, const int32_t *start, const int32_t *final_state, const int32_t *n_states,
+                             const int32_t *n_arcs /* [n_graphs] each */, const wfst_state_info *states /* concatenated */,
+                             const wfst_arc *arcs /* concatenated */, int device, wfst_align_graphs **out);
+/* The same from files, one graph each, in any format wfst_graph_load reads (WFST_E_IO / WFST_E_FORMAT with the file named). */
+int wfst_align_graphs_load(int32_t n_graphs, const char *const *paths, int device, wfst_align_graphs **out);
+int wfst_align_graphs_info(const wfst_align_graphs *g, int32_t *n_graphs, int64_t *total_states, int64_t *total_arcs,
+                           int32_t *n_states, int32_t *n_arcs, int32_t *max_ilabel, int32_t *eps_depth,
+                           int32_t *n_labels /* [n_graphs] each */, int64_t *device_bytes);
+void wfst_align_graphs_free(wfst_align_graphs *g);
+int wfst_decoder_force_align(wfst_decoder *d, const int32_t *channels, int32_t n, const wfst_align_graphs *graphs,
+                             const int32_t *graph_of /* [n] */, const int32_t *n_frames_in /* [n], -1 = all; NULL: all */,
+                             const int32_t *label_map /* NULL, or n_tid + 1 entries, entry 0 unused */, int32_t n_tid,
+                             int64_t max_cells /* (T + 1) x states; 0 = default */,
+                             int32_t cap_frames, int32_t cap_hops, int32_t cap_words,
+                             int32_t *status /* [n] */, int32_t *found, int32_t *n_frames /* [n] */,
+                             float *path_cost, float *tot_score, float *lm_score /* [n] */,
+                             int32_t *n_hops /* [n] */, int32_t *hop_arc /* [n][cap_hops] */, int32_t *alignment /* [n][cap_frames] */,
+                             int32_t *n_words /* [n] */, int32_t *words, int32_t *word_frame /* [n][cap_words] */);
+int wfst_decoder_force_align_workspace(wfst_decoder *d, int64_t *bytes);
 
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
