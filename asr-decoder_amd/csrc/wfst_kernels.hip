@@ -3659,6 +3659,7 @@ __device__ __forceinline__ void gc_pass(const DecoderDev &D, int c, ScanShared &
   int32_t *foff = D.frame_off + (size_t)c * (D.max_frames + 2);
   const int end = foff[nd + 1];
   const uint32_t idx_mask = D.tok_idx_bits >= 31 ? 0x7FFFFFFFu : ((1u << D.tok_idx_bits) - 1u);
+  if (tid == 0) ps.err = 0;   // (once, for both phases: the barrier below stands between this and either phase's `ps.err = ...`)
   // (1) mark: the frontier, then what it reaches
   for (int i = tid; i < end; i += kBT) remap[i] = i >= foff[nd] ? 1 : 0;
   __syncthreads();
@@ -3753,8 +3754,6 @@ __device__ __forceinline__ void gc_pass(const DecoderDev &D, int c, ScanShared &
   // (2) move the survivors down, frame by frame
   constexpr int kCU = 8;
   int new_end = 0, old_lo = 0;
-  if (tid == 0) ps.err = 0;
-  __syncthreads();
   for (int f = 0; f <= nd; ++f) {
     const int old_hi = foff[f + 1];
     int base = new_end;

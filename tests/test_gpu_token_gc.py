@@ -1,6 +1,7 @@
 """-m gpu: token collection of BEST-PATH decoders ("tokens are never reclaimed").  A best-path decoder keeps
-no forward links to prune its arena by; when the arena is half full it keeps what the frontier's backpointers reach
-and moves it down (gc_pass in wfst_kernels.hip).  GetBestPath must not notice: long utterances in arenas a small
+no forward links to prune its arena by; when less than its reserve (DecoderDev::gc_reserve: an eighth to a quarter of
+the arena, half only as a clamp for small arenas) is left it keeps what the frontier's backpointers reach
+and moves it down (gc_pass in wfst_kernels.hip; its table, sweep, chunk and mark edges: tests/test_gpu_gc_edges.py).  GetBestPath must not notice: long utterances in arenas a small
 fraction of what they create decode to the oracle's path bit for bit -- fused and plain closure passes, biglm,
 ragged batches, chunked advances with partial results in between."""
 import numpy as np
