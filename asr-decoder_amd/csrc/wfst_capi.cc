@@ -23,6 +23,7 @@
 #include "wfst_capi_nbwords.h"
 #include "wfst_capi_align.h"
 #include "wfst_capi_forced.h"
+#include "wfst_capi_graphpost.h"
 #include "wfst_openfst.h"
 
 using namespace wfst;
@@ -288,6 +289,7 @@ struct wfst_decoder {
   NbWordsState nbw; // wfst_decoder_get_nbest_words (wfst_capi_nbwords.cc)
   AlignState aln;  // wfst_decoder_align_words (wfst_capi_align.cc)
   ForcedState fal; // wfst_decoder_force_align (wfst_capi_forced.cc)
+  GraphPostState gpo; // wfst_decoder_graph_posteriors (wfst_capi_graphpost.cc)
   LivePruneState lpr; // wfst_decoder_set_live_lattice_prune (wfst_capi_liveprune.cc): the scratch behind D.snap_extra
   std::vector<int32_t> lat_cache_nd;
   DevBuf<float> hist_slab;             // advance_host's device copy of the rows handed over: ONE allocation, hist_cap rows per channel
@@ -3689,6 +3691,8 @@ int forced_stream(wfst_decoder *d, hipStream_t *s) {
   *s = d->copy_stream;
   return WFST_OK;
 }
+// ... and wfst_capi_graphpost.cc -- wfst_decoder_graph_posteriors -- beside them: its workspace.
+GraphPostState *graphpost_state(wfst_decoder *d) { return &d->gpo; }
 
 // What wfst_capi_liveprune.cc -- wfst_decoder_set_live_lattice_prune / _get_live_lattice_prune -- needs of a decoder.
 LivePruneView live_prune_view(wfst_decoder *d) {

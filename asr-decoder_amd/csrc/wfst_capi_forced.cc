@@ -12,23 +12,6 @@
 
 using namespace wfst;
 
-// A set of small graphs resident on one device.  Every HIP resource is an owner (wfst_hip_own.h) and goes with the set;
-// wfst_align_graphs_free makes the set's device current first.
-struct wfst_align_graphs {
-  int device = 0;
-  int32_t n_graphs = 0;
-  int64_t total_states = 0, total_arcs = 0;
-  std::vector<int32_t> hdr;                    // [n_graphs][kFalignHdr], as on the device
-  std::vector<int32_t> labels;                 // the graphs' distinct ilabels, concatenated (hdr[10]: where a graph's begin)
-  DevBuf<int32_t> d_hdr, d_lvl_state, d_lvl_off, d_labels;
-  DevBuf<int2> d_in_off;
-  DevBuf<int4> d_rec, d_arcs;
-  int64_t device_bytes() const {
-    return (int64_t)(d_hdr.bytes() + d_lvl_state.bytes() + d_lvl_off.bytes() + d_labels.bytes() + d_in_off.bytes() + d_rec.bytes() + d_arcs.bytes());
-  }
-  ForcedGraphsDev view() const { return ForcedGraphsDev{d_hdr.p, d_in_off.p, d_rec.p, d_lvl_state.p, d_lvl_off.p, d_labels.p, d_arcs.p}; }
-};
-
 namespace {
 template <class T>
 int upload(DevBuf<T> &buf, const std::vector<T> &v) {
@@ -128,13 +111,17 @@ int wfst_align_graphs_create(int32_t n_graphs, const int32_t *start, const int32
     for (int32_t a = 0; a < A; ++a) ++(ar[a].ilabel ? n_emit : n_eps)[(size_t)ar[a].nextstate];
     std::vector<int32_t> at_emit((size_t)S), at_eps((size_t)S);
     int32_t at = 0;
+    int32_t first_arc = 0;
     for (int32_t s = 0; s < S; ++s) {
       at_emit[(size_t)s] = at;
       at_eps[(size_t)s] = at + n_emit[(size_t)s];
       in_off.push_back(make_int2(at, at + n_emit[(size_t)s]));
       at += n_emit[(size_t)s] + n_eps[(size_t)s];
+      gs->h_out_off.push_back(make_int2(first_arc, first_arc + (int32_t)st[s].niepsilons));
+      first_arc += (int32_t)st[s].num_arcs;
     }
     in_off.push_back(make_int2(at, at));
+    gs->h_out_off.push_back(make_int2(first_arc, first_arc));
     const size_t r0 = rec.size();
     rec.resize(r0 + (size_t)A);
     for (int32_t a = 0; a < A; ++a) {
@@ -173,6 +160,7 @@ int wfst_align_graphs_create(int32_t n_graphs, const int32_t *start, const int32
   if (rc == WFST_OK) rc = upload(gs->d_labels, gs->labels);
   if (rc == WFST_OK) rc = upload(gs->d_arcs, arcs_dev);
   if (rc != WFST_OK) return rc;
+  gs->h_arcs = std::move(arcs_dev);
   *out = gs.release();
   return WFST_OK;
 }
@@ -220,6 +208,7 @@ int wfst_align_graphs_info(const wfst_align_graphs *g, int32_t *n_graphs, int64_
 void wfst_align_graphs_free(wfst_align_graphs *g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
+  gpost_tables_free(g->gpost);
   delete g;
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -42,8 +43,36 @@ struct ForcedView {
   const std::vector<int32_t> *tid2pdf;   // of the decoder's graph (empty: the column is the transition-id)
 };
 ForcedView forced_view(wfst_decoder *d);
+
+// the by-source tables wfst_decoder_graph_posteriors adds to a set on its first call (wfst_capi_graphpost.cc)
+struct GpostTables;
+void gpost_tables_free(GpostTables *t);
 // the stream the histories are written on (made if there is none yet): work enqueued on it runs behind the channels' ingests
 int forced_stream(wfst_decoder *d, hipStream_t *s);
 
 }  // namespace wfst
+
+// A set of small graphs resident on one device.  Every HIP resource is an owner (wfst_hip_own.h) and goes with the set;
+// wfst_align_graphs_free makes the set's device current first.
+struct wfst_align_graphs {
+  int device = 0;
+  int32_t n_graphs = 0;
+  int64_t total_states = 0, total_arcs = 0;
+  std::vector<int32_t> hdr;                    // [n_graphs][kFalignHdr], as on the device
+  std::vector<int32_t> labels;                 // the graphs' distinct ilabels, concatenated (hdr[10]: where a graph's begin)
+  // host copies for the by-source tables: per state {first arc, first emitting arc} at hdr[6] (S + 1 entries a graph), and the
+  // caller's arcs {ilabel, olabel, bits of the weight, nextstate} at hdr[11]
+  std::vector<int2> h_out_off;
+  std::vector<int4> h_arcs;
+  wfst::DevBuf<int32_t> d_hdr, d_lvl_state, d_lvl_off, d_labels;
+  wfst::DevBuf<int2> d_in_off;
+  wfst::DevBuf<int4> d_rec, d_arcs;
+  // built by the set's first wfst_decoder_graph_posteriors, under the lock: a set is shared between decoders and threads
+  mutable std::mutex gpost_mu;
+  mutable wfst::GpostTables *gpost = nullptr;
+  int64_t device_bytes() const {
+    return (int64_t)(d_hdr.bytes() + d_lvl_state.bytes() + d_lvl_off.bytes() + d_labels.bytes() + d_in_off.bytes() + d_rec.bytes() + d_arcs.bytes());
+  }
+  wfst::ForcedGraphsDev view() const { return wfst::ForcedGraphsDev{d_hdr.p, d_in_off.p, d_rec.p, d_lvl_state.p, d_lvl_off.p, d_labels.p, d_arcs.p}; }
+};
 #endif

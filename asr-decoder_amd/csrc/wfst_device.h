@@ -754,6 +754,59 @@ constexpr int64_t falign_out_ints(int64_t cap_frames, int64_t cap_hops, int64_t 
 }
 void launch_forced_align(const ForcedDev &Q, int cnt, hipStream_t s);
 
+// ---- graph posteriors: forward-backward over per-utterance graphs (wfst_graphpost.hip) -------------------------------------------
+// The log-semiring pass of a listed channel's scores against one graph of a wfst_align_graphs set (include/wfst_decoder.h,
+// wfst_decoder_graph_posteriors), float64.  graphpost_kernel runs one workgroup per list entry, graphpost_pack_kernel one per entry,
+// graphpost_dense_kernel one per (entry, frame row).  Beside ForcedGraphsDev the backward pass reads a graph by SOURCE state, built on
+// the set's first call (all offsets into the concatenated arrays):
+//   bhdr[g][kGpostHdr]   {offset of out_off, of orec, of blvl_state, of blvl_off, the depth counted from the other end, 0, 0, 0}
+//   out_off[S + 1]       per source state {its first arc, its first EMITTING arc}: the caller's own order, epsilon arcs first
+//   orec[]               per arc, by arc index {destination state, slot of the ilabel in labels[] (-1: epsilon), bits of the weight, 0}
+//   blvl_state[], blvl_off[bdepth + 2]   every state by the longest epsilon path OUT of it, level L at blvl_off[L] .. blvl_off[L + 1]
+// and, per call and distinct graph of the list, the classes of its emitting arcs as a CSR (cls[] at GpostChan::cls_off):
+//   {slot_class[n_slots] ascending, slot_off[n_slots + 1], slot_arc[]: the emitting arcs of a slot, arc index ascending}
+constexpr int32_t kGpostLdsStates = 2048;   // = WFST_GPOST_LDS_STATES: the two float64 rows of a graph up to this size live in LDS
+constexpr int32_t kGpostHdr = 8;
+constexpr int32_t kGpostHead = 8;
+struct GpostGraphsDev {
+  const int32_t *bhdr;
+  const int2 *out_off;
+  const int4 *orec;
+  const int32_t *blvl_state, *blvl_off;
+};
+struct GpostChan {         // one list entry
+  const float *ll;         // row 0 of the channel's scores (not read where T == 0)
+  int64_t tab_off;         // of its (T + 1) x S alpha table, in cells
+  int64_t row_off;         // of its two rolling rows in the workspace, in cells (a graph beyond kGpostLdsStates)
+  int64_t gam_off;         // of gamma[A] of the frame in hand and occ[A], in cells
+  int64_t post_off;        // of its [T][n_slots] class sums, in cells
+  int64_t cnt_off;         // of its per-frame list lengths, in ints
+  int64_t cls_off;         // of its graph's class CSR, in ints
+  float *grad;             // its dense rows (nullptr: none)
+  int64_t grad_pitch;      // in floats
+  int32_t grad_rows;
+  int32_t graph, T, stride, n_slots, want_occ;
+};
+//   out[i]    gpost_out_ints(): kGpostHead ints {found, T, n_entries, 1: the rows do not hold them, 0, 0, 0, 0},
+//             frame_off[cap_frames + 1], n_distinct[cap_frames], entry_class[cap_entries]; zero-filled by the host before the launch
+//   dout[i]   gpost_out_doubles(): log_like, frame_mass[cap_frames], entry_post[cap_entries], arc_occ[cap_arcs]
+struct GpostDev {
+  ForcedGraphsDev G;
+  GpostGraphsDev B;
+  const GpostChan *chan;
+  const int32_t *col_map;     // the decoder graph's tid2pdf (nullptr: the column is the transition-id)
+  const int32_t *cls;
+  double graph_scale, acoustic_scale, min_post, grad_scale;
+  double *tab, *rows, *gam, *post;
+  int32_t *cnt;
+  int32_t cap_frames, cap_entries, cap_arcs, n_cols;
+  int32_t *out;
+  double *dout;
+};
+constexpr int64_t gpost_out_ints(int64_t cap_frames, int64_t cap_entries) { return kGpostHead + 2 * cap_frames + 1 + cap_entries; }
+constexpr int64_t gpost_out_doubles(int64_t cap_frames, int64_t cap_entries, int64_t cap_arcs) { return 1 + cap_frames + cap_entries + cap_arcs; }
+void launch_graph_post(const GpostDev &Q, int cnt, int max_T, bool dense, hipStream_t s);
+
 // ---- second-pass LM composition on determinized lattices (wfst_compose.hip) ------------------------------------
 // ComposeLattice (newfst/compose-lat-inl.h:15-130) of the determinized lattice of workspace slot 0 (DetDev::out_a / out_w, as
 // determinize_kernel left it) with ComposeArpaLm(lm1), then of the result with ComposeArpaLm(lm2) -- what the service's GetLattice

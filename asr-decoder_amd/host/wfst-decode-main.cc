@@ -85,6 +85,12 @@
 //                  ..." -- cost the path's cost (float32, 9 digits), one class per frame: transition-ids, or pdfs (--tid2pdf=FILE)
 //                  or phones (--tid2phone=FILE) -- and "KEY forced-words w@frame ...", every word with the frame it begins at.
 //                  The other output is what it is without the flag.
+//   --graph-post=DIR [--graph-post-class=tid|pdf|phone] [--graph-post-scales=GS,AS] [--graph-post-out=FILE]  batch shape and
+//                  --single-stream: after the utterance's other lines the forward-backward pass of its scores over its own graph
+//                  DIR/KEY.fst (GraphPosteriors: wfst_decoder_graph_posteriors), as "KEY graph-post found=0|1 loglike=.. frames=..
+//                  entries=.." -- loglike the log of the sum over the graph's paths (9 digits) at arc costs GS * graph + AS *
+//                  acoustic (default 1,1); with --graph-post-out the per-frame class posteriors go to FILE in --frame-post's format.
+//                  The other output is what it is without the flag.
 //   --rescale=GS,AS,WIP[:GS,AS,WIP...]  batch shape and --single-stream: after the utterance's other lines, per setting (at most 64:
 //                  graph scale, acoustic scale, word insertion penalty) the best path of the RAW lattice picked again under it,
 //                  without decoding again (RescaledWords: wfst_decoder_rescaled_words; Kaldi's lattice-best-path-score), as
@@ -273,6 +279,9 @@ int main(int argc, char **argv) {
     SequenceStatsOptions seq_opt;
     bool seq_opts = false, seq_bad = false;
     std::string force_dir, force_class = "tid";   // --force-align
+    std::string gpost_dir, gpost_class = "tid", gpost_file;   // --graph-post
+    double gpost_gs = 1.0, gpost_as = 1.0;
+    bool gpost_opts = false, gpost_bad = false;
     bool force_opts = false;
     std::vector<RescaleSetting> rescale_set;   // --rescale
     bool rescale_bad = false;
@@ -359,6 +368,14 @@ int main(int argc, char **argv) {
       }
       else if (a.compare(0, 14, "--force-align=") == 0) force_dir = a.substr(14);
       else if (a.compare(0, 20, "--force-align-class=") == 0) { force_class = a.substr(20); force_opts = true; }
+      else if (a.compare(0, 13, "--graph-post=") == 0) gpost_dir = a.substr(13);
+      else if (a.compare(0, 19, "--graph-post-class=") == 0) { gpost_class = a.substr(19); gpost_opts = true; }
+      else if (a.compare(0, 17, "--graph-post-out=") == 0) { gpost_file = a.substr(17); gpost_opts = true; }
+      else if (a.compare(0, 20, "--graph-post-scales=") == 0) {
+        char tail = 0;
+        gpost_opts = true;
+        if (sscanf(a.c_str() + 20, "%lf,%lf%c", &gpost_gs, &gpost_as, &tail) != 2 || !(gpost_gs >= 0.0) || !(gpost_as >= 0.0) || std::isinf(gpost_gs) || std::isinf(gpost_as)) gpost_bad = true;
+      }
       else if (a.compare(0, 12, "--seq-stats=") == 0) seq_stats_file = a.substr(12);
       else if (a.compare(0, 10, "--seq-ref=") == 0) { seq_ref_file = a.substr(10); seq_opts = true; }
       else if (a.compare(0, 16, "--seq-criterion=") == 0) { seq_criterion = a.substr(16); seq_opts = true; }
@@ -432,7 +449,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--graph-post=DIR [--graph-post-class=tid|pdf|phone] [--graph-post-scales=GS,AS] [--graph-post-out=FILE]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -479,7 +496,14 @@ int main(int argc, char **argv) {
     if (force_align && force_class != "tid" && force_class != "pdf" && force_class != "phone") { std::cerr << "--force-align-class=tid|pdf|phone\n"; return 1; }
     if (force_align && force_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--force-align-class=pdf needs --tid2pdf=FILE\n"; return 1; }
     if (force_align && force_class == "phone" && tid2phone_file.empty()) { std::cerr << "--force-align-class=phone needs --tid2phone=FILE\n"; return 1; }
-    const bool phones_for_frame_post = (frame_post && fp_class == "phone") || (seq_stats && seq_class == "phone") || (force_align && force_class == "phone");   // (--tid2phone given for this alone is no endpointing)
+    const bool graph_post = !gpost_dir.empty();
+    if (!graph_post && gpost_opts) { std::cerr << "--graph-post-class / --graph-post-scales / --graph-post-out go with --graph-post=DIR\n"; return 1; }
+    if (graph_post && n_threads > 0) { std::cerr << "--graph-post goes with the batch shape or --single-stream\n"; return 1; }
+    if (gpost_bad) { std::cerr << "--graph-post-scales=GS,AS: two finite numbers >= 0\n"; return 1; }
+    if (graph_post && gpost_class != "tid" && gpost_class != "pdf" && gpost_class != "phone") { std::cerr << "--graph-post-class=tid|pdf|phone\n"; return 1; }
+    if (graph_post && gpost_class == "pdf" && tid2pdf_file.empty()) { std::cerr << "--graph-post-class=pdf needs --tid2pdf=FILE\n"; return 1; }
+    if (graph_post && gpost_class == "phone" && tid2phone_file.empty()) { std::cerr << "--graph-post-class=phone needs --tid2phone=FILE\n"; return 1; }
+    const bool phones_for_frame_post = (frame_post && fp_class == "phone") || (seq_stats && seq_class == "phone") || (force_align && force_class == "phone") || (graph_post && gpost_class == "phone");   // (--tid2phone given for this alone is no endpointing)
     // --align-words / --nearest-words / --phrase-posterior: the sequences to align, the references and the phrases, by utterance key
     std::map<std::string, std::vector<std::vector<int> > > align_seqs, nearest_refs, phrases;
     for (int which = 0; which < 3; ++which) {
@@ -784,6 +808,35 @@ int main(int argc, char **argv) {
       out << '\n' << u.key << " forced-words";
       for (size_t k = 0; k < fa.words.size(); ++k) out << ' ' << fa.words[k] << '@' << fa.word_frame[k];
       out << '\n';
+    };
+    // --graph-post: the class of a transition-id, an utterance's graph file, its line and, with --graph-post-out, its lists in
+    // --frame-post's format
+    GraphPosteriorsOptions gpost_opt;
+    gpost_opt.graph_scale = gpost_gs;
+    gpost_opt.acoustic_scale = gpost_as;
+    if (graph_post && gpost_class == "pdf") gpost_opt.label_map.assign(tid2pdf.begin(), tid2pdf.end());
+    if (graph_post && gpost_class == "phone") gpost_opt.label_map.assign(tid2phone.begin(), tid2phone.end());
+    std::ofstream gpost_out;
+    if (graph_post && !gpost_file.empty()) {
+      gpost_out.open(gpost_file.c_str());
+      if (!gpost_out) { std::cerr << "cannot write " << gpost_file << "\n"; return 1; }
+    }
+    auto gpost_graph = [&](const Utt &u) { return gpost_dir + "/" + u.key + ".fst"; };
+    auto emit_graph_post = [&](const Utt &u, const GraphPosteriors &gp) {
+      char buf[128];
+      snprintf(buf, sizeof(buf), " graph-post found=%d loglike=%.9g frames=%d entries=%d\n", gp.found ? 1 : 0, gp.log_like, gp.n_frames, (int)gp.classes.size());
+      out << u.key << buf;
+      if (gpost_file.empty()) return;
+      std::string o = u.key;
+      for (int f = 0; f < gp.n_frames; ++f) {
+        o += " [";
+        for (int e = gp.frame_off[(size_t)f]; e < gp.frame_off[(size_t)f + 1]; ++e) {
+          snprintf(buf, sizeof(buf), " %d %.9g", gp.classes[(size_t)e], gp.posts[(size_t)e]);
+          o += buf;
+        }
+        o += " ]";
+      }
+      gpost_out << o << "\n";
     };
     // --rescale: an utterance's lines, one per setting
     auto emit_rescale = [&](const Utt &u, const std::vector<RescaledWords> &rw) {
@@ -1228,6 +1281,13 @@ int main(int argc, char **argv) {
           decode.ForceAlign(ag, 0, &fa, force_map);
           emit_forced(u, fa);
         }
+        if (graph_post) {
+          AlignGraphs ag;
+          if (!ag.Read(std::vector<std::string>(1, gpost_graph(u)), devices[0])) throw std::runtime_error("--graph-post: cannot load " + gpost_graph(u));
+          GraphPosteriors gp;
+          decode.GraphPosteriors(ag, 0, &gp, gpost_opt);
+          emit_graph_post(u, gp);
+        }
       }
     } else {  // the MI355X shape: `batch` utterances per pass, `inflight` passes at a time
       struct BatchOut {
@@ -1244,6 +1304,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<RescaledWords> > rescaled;            // --rescale
         std::vector<SequenceStats> seq_stats;                         // --seq-stats
         std::vector<ForcedAlignment> forced;                          // --force-align
+        std::vector<GraphPosteriors> graph_post;                      // --graph-post
       };
       const size_t n_batches = (utts.size() + batch - 1) / batch;
       std::vector<BatchOut> outs(n_batches);
@@ -1399,6 +1460,13 @@ int main(int argc, char **argv) {
               if (!ag.Read(files, devices[(size_t)di])) throw std::runtime_error("--force-align: cannot load the graphs of " + force_dir);
               decode.ForceAlign(ch, ag, std::vector<int>(), force_map, &o.forced);
             }
+            if (graph_post) {                                                                                // every channel in one launch
+              std::vector<std::string> files(n);
+              for (int i = 0; i < n; ++i) files[i] = gpost_graph(utts[b0 + i]);
+              AlignGraphs ag;
+              if (!ag.Read(files, devices[(size_t)di])) throw std::runtime_error("--graph-post: cannot load the graphs of " + gpost_dir);
+              decode.GraphPosteriors(ch, ag, std::vector<int>(), gpost_opt, &o.graph_post);
+            }
           }
         } catch (const std::exception &e) {
           errors[(size_t)k] = e.what();
@@ -1434,6 +1502,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && !o.rescaled.empty(); ++i) emit_rescale(utts[b0 + i], o.rescaled[i]);
         for (int i = 0; i < n && !o.seq_stats.empty(); ++i) emit_seq_stats(utts[b0 + i], o.seq_stats[i]);
         for (int i = 0; i < n && !o.forced.empty(); ++i) emit_forced(utts[b0 + i], o.forced[i]);
+        for (int i = 0; i < n && !o.graph_post.empty(); ++i) emit_graph_post(utts[b0 + i], o.graph_post[i]);
       }
     }
     if (!nearest_refs.empty()) {   // errors over reference words, as nbest-compute-wer prints them

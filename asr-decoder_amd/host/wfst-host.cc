@@ -33,6 +33,7 @@
 #pragma weak wfst_decoder_force_align
 #pragma weak wfst_align_graphs_load
 #pragma weak wfst_align_graphs_free
+#pragma weak wfst_decoder_graph_posteriors
 
 namespace datemoon {
 
@@ -2300,6 +2301,92 @@ void GpuLatticeDecoder::ForceAlign(const AlignGraphs &graphs, int graph, ForcedA
     if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
   });
   if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("ForceAlign: " + msg);
+  if (out) *out = o[0];
+}
+
+// ---- graph posteriors over per-utterance graphs (wfst_decoder_graph_posteriors) ---------------------------------------------------------
+// One C-ABI call for `ch`: (*out)[i] for listed channel i, its own code in status.  Returns the call's own code.  The rows take their
+// room from the frames decoded and the graphs' arcs; a channel that needs more is asked for again, once, with the room it reports.
+static int GraphPosteriorsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const AlignGraphs &graphs, const std::vector<int> &graph_of,
+                               const GraphPosteriorsOptions &opt, std::vector<struct GraphPosteriors> *out) {
+  if (!wfst_decoder_graph_posteriors) throw std::runtime_error("GraphPosteriors: this build's device library has no wfst_decoder_graph_posteriors");
+  const size_t cnt = ch.size();
+  if (!graph_of.empty() && graph_of.size() != cnt) throw std::runtime_error("GraphPosteriors: one graph per listed channel");
+  if (!opt.grad.empty() && (opt.grad.size() != cnt || opt.grad_frames.size() != cnt || (!opt.grad_pitch.empty() && opt.grad_pitch.size() != cnt)))
+    throw std::runtime_error("GraphPosteriors: one grad pointer, frame count and pitch per listed channel");
+  std::vector<int32_t> gof(graph_of.begin(), graph_of.end());
+  if (gof.empty())
+    for (size_t i = 0; i < cnt; ++i) gof.push_back((int32_t)i);
+  const std::vector<int32_t> map(opt.label_map.begin(), opt.label_map.end());
+  const std::vector<int64_t> pitch(opt.grad_pitch.begin(), opt.grad_pitch.end());
+  const std::vector<int32_t> rows(opt.grad_frames.begin(), opt.grad_frames.end());
+  size_t capf = 1, capa = 0;
+  for (int32_t c : ch) capf = std::max(capf, (size_t)std::max(wfst_decoder_num_frames_decoded(dec, c), 0));
+  size_t cape = capf * 64;
+  if (opt.arc_occupancy) capa = 1;
+  std::vector<int32_t> st(cnt), fnd(cnt), nf(cnt), ne(cnt), na(cnt), off, nd, cls;
+  std::vector<double> ll(cnt), mass, post, occ;
+  for (int pass = 0;; ++pass) {
+    off.assign(cnt * (capf + 1), 0); nd.assign(cnt * capf, 0); cls.assign(cnt * cape, 0);
+    mass.assign(cnt * capf, 0.0); post.assign(cnt * cape, 0.0); occ.assign(cnt * capa, 0.0);
+    const int rc = wfst_decoder_graph_posteriors(
+        dec, ch.data(), (int32_t)cnt, graphs.Handle(), gof.data(), nullptr, map.empty() ? nullptr : map.data(), map.empty() ? 0 : (int32_t)map.size() - 1,
+        opt.graph_scale, opt.acoustic_scale, opt.min_post, opt.max_cells, (int32_t)capf, (int32_t)cape, (int32_t)capa,
+        opt.grad.empty() ? nullptr : opt.grad.data(), pitch.empty() ? nullptr : pitch.data(), rows.empty() ? nullptr : rows.data(), opt.n_cols,
+        opt.grad_scale, opt.consumer_stream, st.data(), fnd.data(), nf.data(), ll.data(), ne.data(), na.data(), off.data(), nd.data(), mass.data(),
+        cls.data(), post.data(), opt.arc_occupancy ? occ.data() : nullptr);
+    if (rc != WFST_OK) return rc;
+    size_t need_f = capf, need_e = cape, need_a = capa;
+    for (size_t i = 0; i < cnt; ++i)
+      if (st[i] == WFST_E_CAPACITY) {
+        need_f = std::max(need_f, (size_t)nf[i]); need_e = std::max(need_e, (size_t)ne[i]);
+        if (opt.arc_occupancy) need_a = std::max(need_a, (size_t)na[i]);
+      }
+    if (pass || (need_f == capf && need_e == cape && need_a == capa)) break;
+    capf = need_f; cape = need_e; capa = need_a;
+  }
+  out->assign(cnt, GraphPosteriors());
+  for (size_t i = 0; i < cnt; ++i) {
+    struct GraphPosteriors &a = (*out)[i];
+    a.status = st[i];
+    if (st[i] != WFST_OK || !fnd[i]) continue;
+    a.found = true;
+    a.n_frames = nf[i];
+    a.log_like = ll[i];
+    a.frame_off.assign(off.begin() + i * (capf + 1), off.begin() + i * (capf + 1) + nf[i] + 1);
+    a.n_distinct.assign(nd.begin() + i * capf, nd.begin() + i * capf + nf[i]);
+    a.frame_mass.assign(mass.begin() + i * capf, mass.begin() + i * capf + nf[i]);
+    a.classes.assign(cls.begin() + i * cape, cls.begin() + i * cape + ne[i]);
+    a.posts.assign(post.begin() + i * cape, post.begin() + i * cape + ne[i]);
+    if (opt.arc_occupancy) a.arc_occ.assign(occ.begin() + i * capa, occ.begin() + i * capa + na[i]);
+  }
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::GraphPosteriors(const std::vector<int> &channels, const AlignGraphs &graphs, const std::vector<int> &graph_of,
+                                      const GraphPosteriorsOptions &opt, std::vector<struct GraphPosteriors> *out, std::vector<int> *status) {
+  std::vector<int32_t> ch(channels.begin(), channels.end());
+  if (ch.empty())
+    for (int c = 0; c < _n; ++c) ch.push_back(c);
+  std::vector<struct GraphPosteriors> o;
+  if (GraphPosteriorsCall(_dec, ch, graphs, graph_of, opt, &o) != WFST_OK) Fatal("GraphPosteriors");
+  if (status) status->clear();
+  for (const struct GraphPosteriors &a : o) {
+    if (status) status->push_back(a.status);
+    else if (a.status != WFST_OK) Fatal("GraphPosteriors");
+  }
+  if (out) out->swap(o);
+}
+
+void GpuLatticeDecoder::GraphPosteriors(const AlignGraphs &graphs, int graph, struct GraphPosteriors *out, const GraphPosteriorsOptions &opt) {
+  std::vector<struct GraphPosteriors> o;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = GraphPosteriorsCall(_dec, std::vector<int32_t>(1, _chan), graphs, std::vector<int>(1, graph), opt, &o);
+    if (rc != WFST_OK || o[0].status != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || o[0].status != WFST_OK) throw std::runtime_error("GraphPosteriors: " + msg);
   if (out) *out = o[0];
 }
 

@@ -516,6 +516,34 @@ class AlignGraphs {
   int _n;
 };
 
+// Graph posteriors of a channel's scores over the utterance's own graph (wfst_decoder_graph_posteriors): the forward-backward pass
+// force_align takes the best path of.  log_like = the log of the sum over the graph's paths (MMI's numerator term); per frame f the
+// classes of the graph's emitting arcs with their posterior, in FramePosteriors' list format; arc_occ[a] = the expected count of arc a
+// of the graph (empty unless asked for).  found = false (everything else empty / zero): the graph does not accept the channel's
+// frames.  status: WFST_OK or the channel's own error code.  The doubles are reproducible to rounding, not bit for bit.
+struct GraphPosteriors {
+  int status = 0;
+  bool found = false;
+  int n_frames = 0;
+  double log_like = 0.0;
+  std::vector<int> frame_off, classes, n_distinct;
+  std::vector<double> posts, frame_mass, arc_occ;
+};
+// What GraphPosteriors is asked with.  label_map and the dense output (grad .. consumer_stream) as SequenceStatsOptions has them;
+// the scales are finite and >= 0.
+struct GraphPosteriorsOptions {
+  double graph_scale = 1.0, acoustic_scale = 1.0, min_post = 0.0;
+  bool arc_occupancy = false;
+  std::vector<int> label_map;
+  std::vector<void *> grad;
+  std::vector<long long> grad_pitch;
+  std::vector<int> grad_frames;
+  int n_cols = 0;
+  double grad_scale = 1.0;
+  void *consumer_stream = WFST_STREAM_NONE;
+  long long max_cells = 0;
+};
+
 // The path of a channel's raw lattice nearest a reference word sequence (wfst_decoder_nearest_words): least word edit distance, the
 // cheapest among those.  errors = sub + ins + del; words / frames[j] = the path's own words with (begin, end) as WordAlignment has
 // them; ref_hyp[k] = the index in `words` that reference word k was matched or substituted with, -1: deleted; tot / lm =
@@ -663,6 +691,11 @@ class GpuLatticeDecoder : public DecoderItf {
   // or after FinalizeDecoding, in one device call (wfst_decoder_force_align); label_map as FramePosteriors takes it.  The channel's
   // own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void ForceAlign(const AlignGraphs &graphs, int graph, ForcedAlignment *out, const std::vector<int> &label_map = std::vector<int>());
+  // The forward-backward pass of the channel's scores over graph `graph` of `graphs`, mid-utterance or after FinalizeDecoding, in one
+  // device call (wfst_decoder_graph_posteriors); opt.grad holds at most one pointer.  The channel's own failure throws.  Over a pool the
+  // call runs in the batcher thread, like ForceAlign.
+  void GraphPosteriors(const AlignGraphs &graphs, int graph, struct GraphPosteriors *out,
+                       const GraphPosteriorsOptions &opt = GraphPosteriorsOptions());
   // The lattice path nearest each of `refs` (at most 64) -- a transcript with a wrong word, a caption file, another system's
   // hypothesis -- on the channel's RAW lattice, mid-utterance or after FinalizeDecoding (wfst_decoder_nearest_words): (*out)[q] for
   // refs[q]; out->errors of a correct transcript is the lattice's oracle error (kaldi-bin/bin/nbest-compute-wer.cc:111-167 counts the
@@ -810,6 +843,11 @@ class GpuBatchDecoder {
   void ForceAlign(const std::vector<int> &channels, const AlignGraphs &graphs, const std::vector<int> &graph_of,
                   const std::vector<int> &label_map, std::vector<ForcedAlignment> *out, std::vector<int> *status = nullptr,
                   long long max_cells = 0);
+  // GraphPosteriors (see GpuLatticeDecoder) of many channels (none listed: all) in one launch per stage: graph_of[i] = the graph of
+  // listed channel i (empty: graph i), (*out)[i] its answer, its own error code in (*out)[i].status (without `status` it throws); the
+  // rows are given the room the lists need.
+  void GraphPosteriors(const std::vector<int> &channels, const AlignGraphs &graphs, const std::vector<int> &graph_of,
+                       const GraphPosteriorsOptions &opt, std::vector<struct GraphPosteriors> *out, std::vector<int> *status = nullptr);
   // NearestWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
   // refs[i] = the references for listed channel i (at most 64), (*out)[i][q] the answer for refs[i][q]; (*status)[i]: WFST_OK or the
   // channel's own error code (without `status` it throws).  max_cells: see wfst_decoder_nearest_words.

@@ -52,7 +52,7 @@ SYMBOLS = [
     "wfst_decoder_sequence_posterior", "wfst_decoder_word_alternatives", "wfst_decoder_frame_posteriors",
     "wfst_decoder_rescaled_words", "wfst_decoder_sequence_stats",
     "wfst_align_graphs_create", "wfst_align_graphs_load", "wfst_align_graphs_info", "wfst_align_graphs_free", "wfst_decoder_force_align",
-    "wfst_decoder_force_align_workspace",
+    "wfst_decoder_force_align_workspace", "wfst_decoder_graph_posteriors", "wfst_decoder_graph_posteriors_workspace",
 ]
 
 
@@ -408,6 +408,28 @@ class ForcedAlignment(object):
     def __repr__(self):
         return "ForcedAlignment(status=%d, found=%r, n_frames=%d, path_cost=%r, n_hops=%d, n_words=%d)" % (
             self.status, self.found, self.n_frames, self.path_cost, self.n_hops, self.n_words)
+
+
+class GraphPosteriors(object):
+    """One channel's answer of BatchDecoder.graph_posteriors: status (WFST_OK or the CHANNEL's own error code), found, n_frames,
+    log_like (float: the log of the sum over the graph's paths of exp(-cost)), n_entries, frame_off (int32, n_frames + 1), classes and posts (the
+    entries of frame f are frame_off[f] .. frame_off[f + 1], by class ascending), n_distinct (int32 per frame), frame_mass (float64
+    per frame) and arc_occ (float64 per arc of the channel's graph, or None).  r["frame_off"] reads a field as r.frame_off does, so
+    that frame_post_lookup takes the object as it stands."""
+
+    __slots__ = ("status", "found", "n_frames", "log_like", "n_entries", "n_arcs", "frame_off", "classes", "posts", "n_distinct",
+                 "frame_mass", "arc_occ")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def __getitem__(self, key):
+        return getattr(self, key)
+
+    def __repr__(self):
+        return "GraphPosteriors(status=%d, found=%r, n_frames=%d, log_like=%r, n_entries=%d)" % (
+            self.status, self.found, self.n_frames, self.log_like, self.n_entries)
 
 
 class Lm:
@@ -1304,6 +1326,114 @@ class BatchDecoder:
         """Bytes of the decoder's forced-alignment workspace (wfst_decoder_force_align_workspace)."""
         b = C.c_int64()
         _check(lib().wfst_decoder_force_align_workspace(self.h, C.byref(b)))
+        return int(b.value)
+
+    def graph_posteriors(self, graphs, graph_of=None, channels=None, n_frames=None, label_map=None, graph_scale=1.0, acoustic_scale=1.0,
+                         min_post=0.0, arc_occupancy=False, grad=None, grad_scale=1.0, n_cols=None, consumer_stream=None, max_cells=0,
+                         lists=True, cap_frames=None, cap_entries=None, cap_arcs=None):
+        """Forward-backward of the listed channels' scores (None: all) over per-utterance graphs (wfst_decoder_graph_posteriors):
+        graphs, graph_of, n_frames and label_map as force_align takes them; the scales are finite and >= 0.  Per channel one
+        GraphPosteriors: log_like = the log of the sum over the graph's paths, per frame the posterior of every class (the
+        transition-id, or label_map of it) in frame_posteriors' list format (frame_post_lookup reads it), and with
+        arc_occupancy=True arc_occ, the expected count of every arc of the channel's graph.
+        grad: None, or per listed channel a 2-D float32 DEVICE tensor [frames][n_cols] or None, as sequence_stats takes them: rows
+        0 .. min(n_frames, frames) - 1 become zeros with float32(grad_scale * post) at each class' column.  consumer_stream: None =
+        torch's current stream where there are dense rows; a torch stream; a raw hipStream_t (int), WFST_STREAM_NONE among them.
+        lists=False: no lists are fetched.  Works on every kind of decoder and on live, finalized and never-decoded channels alike;
+        only reads the decoder.  The call is made once more where a channel reports that it needs more room."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        gof = np.ascontiguousarray(list(range(cnt)) if graph_of is None else [int(g) for g in graph_of], dtype=np.int32)
+        if gof.shape[0] != cnt:
+            raise ValueError("one graph per listed channel")
+        nfi = None
+        if n_frames is not None:
+            nfi = np.ascontiguousarray([-1 if t is None else int(t) for t in n_frames], dtype=np.int32)
+            if nfi.shape[0] != cnt:
+                raise ValueError("one frame count per listed channel")
+        m, n_tid = None, 0
+        if label_map is not None:
+            m = np.ascontiguousarray(label_map, dtype=np.int32)
+            n_tid = int(m.shape[0]) - 1
+        ptrs = pitch = rows = None
+        width = 0
+        if grad is not None:
+            grad = list(grad)
+            if len(grad) != cnt:
+                raise ValueError("one grad tensor (or None) per listed channel")
+            ptrs, pitch, rows = (C.c_void_p * max(cnt, 1))(), np.zeros(max(cnt, 1), np.int64), np.zeros(max(cnt, 1), np.int32)
+            for i, t in enumerate(grad):
+                if t is None:
+                    continue
+                if len(t.shape) != 2:
+                    raise ValueError("grad %d is not 2-D" % i)
+                if "float32" not in str(t.dtype):
+                    raise ValueError("grad %d is not float32" % i)
+                cols = int(t.shape[1]) if n_cols is None else int(n_cols)
+                if cols > int(t.shape[1]) or (width and cols != width):
+                    raise ValueError("grad tensors differ in width, or are narrower than n_cols")
+                width = cols
+                st = t.stride()
+                if int(t.shape[1]) > 1 and int(st[1]) != 1:
+                    raise ValueError("the last dimension of grad %d is not contiguous" % i)
+                ptrs[i] = int(t.data_ptr())
+                rows[i] = int(t.shape[0])
+                pitch[i] = int(st[0]) if int(t.shape[0]) > 1 else max(int(st[0]), cols)
+            if not width:
+                ptrs = None
+        if consumer_stream is None:
+            consumer_stream = WFST_STREAM_NONE
+            if ptrs is not None:
+                import torch
+                consumer_stream = int(torch.cuda.current_stream().cuda_stream)
+        elif hasattr(consumer_stream, "cuda_stream"):
+            consumer_stream = int(consumer_stream.cuda_stream)
+        # (a first guess at the frames: a channel that holds more than it has decoded answers with the room it needs)
+        guess = max([int(t) for t in nfi if t >= 0] + [1]) if nfi is not None and (nfi >= 0).all() else \
+            max([max(self.num_frames_decoded(int(c)), 0) for c in ch] + [1]) if cnt else 1
+        capf, cape = (0, 0) if not lists else (int(cap_frames) if cap_frames is not None else guess,
+                                               int(cap_entries) if cap_entries is not None else guess * FRAME_POST_ENTRIES_PER_FRAME)
+        capa = 0
+        if arc_occupancy:
+            capa = int(cap_arcs) if cap_arcs is not None else max([int(graphs.info()["n_arcs"][g]) for g in gof] + [1])
+        f64 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        k = max(cnt, 1)
+        for attempt in range(2):
+            status, found, nf, ne, na = (np.zeros(k, np.int32) for _ in range(5))
+            ll = np.zeros(k, np.float64)
+            off = nd = mass = cls = post = occ = None
+            if lists:
+                off, nd, mass = np.zeros((k, capf + 1), np.int32), np.zeros((k, capf), np.int32), np.zeros((k, capf), np.float64)
+                cls, post = np.zeros((k, cape), np.int32), np.zeros((k, cape), np.float64)
+            if arc_occupancy:
+                occ = np.zeros((k, max(capa, 1)), np.float64)
+            _check(lib().wfst_decoder_graph_posteriors(
+                self.h, _i32(ch), cnt, graphs.h, _i32(gof), _i32(nfi), _i32(m), n_tid, C.c_double(float(graph_scale)),
+                C.c_double(float(acoustic_scale)), C.c_double(float(min_post)), C.c_int64(int(max_cells)), capf, cape, capa, ptrs,
+                pitch.ctypes.data_as(C.POINTER(C.c_int64)) if ptrs is not None else None, _i32(rows) if ptrs is not None else None,
+                int(width), C.c_double(float(grad_scale)), C.c_void_p(int(consumer_stream)), _i32(status), _i32(found), _i32(nf), f64(ll),
+                _i32(ne), _i32(na), _i32(off), _i32(nd), f64(mass), _i32(cls), f64(post), f64(occ)))
+            short = (status[:cnt] == -4) & (((nf[:cnt] > capf) | (ne[:cnt] > cape) if lists else False) | ((na[:cnt] > capa) if arc_occupancy else False))
+            if attempt or not np.any(short):
+                break
+            capf, cape, capa = max(capf, int(nf.max())) if lists else 0, max(cape, int(ne.max())) if lists else 0, max(capa, int(na.max())) if arc_occupancy else 0
+        out = []
+        for i in range(cnt):
+            ok = bool(found[i]) and lists and int(nf[i]) <= capf and int(ne[i]) <= cape
+            t, e = (int(nf[i]), int(ne[i])) if ok else (0, 0)
+            z = lambda dt: np.zeros(0, dt)
+            out.append(GraphPosteriors(
+                status=int(status[i]), found=bool(found[i]), n_frames=int(nf[i]), log_like=float(ll[i]), n_entries=int(ne[i]), n_arcs=int(na[i]),
+                frame_off=off[i, :t + 1].copy() if lists else np.zeros(1, np.int32), classes=cls[i, :e].copy() if lists else z(np.int32),
+                posts=post[i, :e].copy() if lists else z(np.float64), n_distinct=nd[i, :t].copy() if lists else z(np.int32),
+                frame_mass=mass[i, :t].copy() if lists else z(np.float64),
+                arc_occ=occ[i, :int(na[i])].copy() if arc_occupancy and int(na[i]) <= capa else None))
+        return out
+
+    def graph_posteriors_workspace(self):
+        """Bytes of the decoder's graph-posterior workspace (wfst_decoder_graph_posteriors_workspace)."""
+        b = C.c_int64()
+        _check(lib().wfst_decoder_graph_posteriors_workspace(self.h, C.byref(b)))
         return int(b.value)
 
     def nbest_words_timed(self, n_paths, channels=None, old_lm=None, new_lm=None, use_final_probs=True, cap_words=256, max_cells=0):

@@ -962,8 +962,8 @@ int wfst_decoder_frame_posteriors(wfst_decoder *d, const int32_t *channels, int3
  * grad_scale that is not finite; grad without grad_frames, n_cols < 1, a negative grad_frames, a pitch below n_cols, a grad pointer not
  * aligned to 4 bytes, a class beyond n_cols as above) or WFST_E_STATE as there.  Any output pointer may be NULL.  The decoder's state
  * is only read: decoding goes on bit for bit as without the call.
- * Not computed here: minimum Bayes risk decoding and the pivot algorithm's second half, the MMI numerator's log-probability,
- * Kaldi's one_silence_class variant, a half-precision dense output.
+ * Not computed here: minimum Bayes risk decoding and the pivot algorithm's second half, Kaldi's one_silence_class variant, a
+ * half-precision dense output.  (The MMI numerator's log-probability: wfst_decoder_graph_posteriors' log_like.)
  * (The numerator alignment `ref` and its cost come from wfst_decoder_force_align with label_map = the same map.) */
 #define WFST_SEQ_MMI 0
 #define WFST_SEQ_SMBR 1
@@ -1110,7 +1110,7 @@ int wfst_decoder_rescaled_words(wfst_decoder *d, const int32_t *channels, int32_
  * max_cells bounds the cells of one round as well (at least one channel per round), and with them the workspace.
  * wfst_decoder_force_align_workspace: the bytes held.
  * Not computed here: a beam (the table is dense), graphs compiled from transcripts and lexicons, Kaldi table I/O, device-resident
- * outputs, per-arc posteriors of the numerator graph. */
+ * outputs.  (Per-arc posteriors of the numerator graph: wfst_decoder_graph_posteriors.) */
 #define WFST_FALIGN_LDS_STATES 4096 /* states of a graph whose two float32 cost rows live in LDS (32 KiB of a workgroup's 64) */
 typedef struct wfst_align_graphs wfst_align_graphs;
 int wfst_align_graphs_create(int32_t n_graphs, const int32_t *start, const int32_t *final_state, const int32_t *n_states,
@@ -1132,6 +1132,82 @@ int wfst_decoder_force_align(wfst_decoder *d, const int32_t *channels, int32_t n
                              int32_t *n_hops /* [n] */, int32_t *hop_arc /* [n][cap_hops] */, int32_t *alignment /* [n][cap_frames] */,
                              int32_t *n_words /* [n] */, int32_t *words, int32_t *word_frame /* [n][cap_words] */);
 int wfst_decoder_force_align_workspace(wfst_decoder *d, int64_t *bytes);
+
+/* ---- graph posteriors: forward-backward of a channel's scores over the utterance's own graph ------------------------------------------
+ * wfst_decoder_force_align gives the BEST path through a per-utterance graph; this call sums over ALL of them, in the log semiring:
+ * the log-likelihood of the graph given the scores (the numerator term of MMI: objective = log_like - log_z, with log_z from
+ * wfst_decoder_sequence_stats), per frame the posterior of every class (soft numerators: CTC-style graphs, lattice-free MMI numerators,
+ * flat-start training, transcripts with alternative pronunciations or optional silence; how sure an alignment is) and per arc its
+ * expected count.  One launch per stage and round (graphpost_kernel, graphpost_pack_kernel and, with dense rows,
+ * graphpost_dense_kernel), one workgroup per listed channel.
+ *
+ * The graph G, ll(f, tid) (the column through the DECODER's tid2pdf), T, the frames a channel holds, n_frames_in, graph_of, "runs
+ * behind the channels' ingests" and "the decoder's state is only read" are wfst_decoder_force_align's, unchanged.  Everything below is
+ * float64.  graph_scale gs and acoustic_scale as are finite and >= 0.
+ *   An epsilon arc a costs c(a) = gs * (double)w(a); an emitting arc out of frame f costs c(f, a) = as * (double)x + gs * (double)w(a)
+ *   with x = float32(-ll(f, ilabel)): two products and one sum, each rounded on its own (no fused multiply-add).  An arc whose w(a) is
+ *   not finite is no arc; an emitting arc whose x is not finite (NaN or either infinity) is no arc at that frame.
+ *   Forward: alpha[0][start] has the seed 0; alpha[f][t] is -log sum exp(-x) over its terms: the seed where it applies,
+ *   alpha[f - 1][s] + c(f - 1, a) over its emitting in-arcs and alpha[f][s] + c(a) over its epsilon in-arcs.  A state has its terms
+ *   complete before a state with an epsilon path from it reads it (the graph set's epsilon levels).  A sum is m - log(sum exp(-(x - m)))
+ *   with m the least term, +inf without a finite term.
+ *   Backward: beta[T][final_state] has the term 0; beta[f][s] is the same sum over its out-arcs: c(f, a) + beta[f + 1][t] for emitting
+ *   arcs while f < T, c(a) + beta[f][t] for epsilon arcs; the levels -- the longest epsilon path OUT of a state -- ascending.
+ *   tot = alpha[T][final_state]; found = tot is finite; log_like = -tot.  found = 0 zeroes every output of that channel with status OK
+ *   and leaves its dense rows untouched.
+ *   gamma(f, a) = exp(-(alpha[f][s] + c + beta[f'][t] - tot)), f' = f + 1 for an emitting arc and f for an epsilon arc; 0 where the
+ *   exponent is not finite.
+ * Per frame f < T and class v -- the ilabel of an emitting arc out of f, or label_map[ilabel] exactly as wfst_decoder_frame_posteriors
+ * takes a map -- post(f, v) is the sum of gamma(f, a) over the arcs of that class.  The list of frame f holds the classes with
+ * post > 0 and post >= min_post by class id ASCENDING; n_distinct[f] counts the classes with post > 0 before the threshold and
+ * frame_mass[f] sums them all: 1 to rounding on a found channel.  frame_off, entry_class, entry_post, n_entries and the cap_frames /
+ * cap_entries answers have wfst_decoder_frame_posteriors' format; cap_frames = cap_entries = 0: no lists are handed out, as in
+ * wfst_decoder_sequence_stats.
+ * arc_occ (NULL: none) gets per listed channel arc_occ[i][a] for a < n_arcs[i], the arcs of its graph by arc index: the expected
+ * number of times a path takes arc a, the sum of gamma(f, a) over f < T for an emitting arc and over f <= T for an epsilon arc.
+ * The dense output: grad, grad_pitch, grad_frames, n_cols, grad_scale and consumer_stream are exactly
+ * wfst_decoder_sequence_stats'.  Rows 0 .. min(T, grad_frames[i]) - 1 get n_cols zeros, then float32(grad_scale * post(f, v)) at column
+ * v for every class with post > 0; min_post does not thin the dense rows; nothing else is touched.  A label_map class >= n_cols is
+ * refused, without a map n_cols must exceed the largest ilabel of every listed graph, and the writes are ordered against
+ * consumer_stream both ways, as there.
+ * The ORDER of a sum follows the device's records: results are reproducible to rounding, NOT bit for bit against another
+ * implementation.  No float is accumulated by an atomic: two identical calls return identical bytes.
+ * Beside wfst_decoder_force_align: at scales (1, 1) and with finite scores and weights found is that call's, except that force_align
+ * drops a path whose float32 running sum overflows, while here the "no arc" rule is per arc, in float64.
+ *
+ * A failure of ONE channel goes into status[i] and the call still returns WFST_OK: a table of (T + 1) x n_states cells beyond
+ * max_cells (WFST_E_CAPACITY, n_frames[i] = T, everything else zero; 0 = wfst_decoder_force_align's default bound), T > cap_frames or
+ * n_entries > cap_entries (WFST_E_CAPACITY: n_frames[i] and n_entries[i] are the room needed, the lists stay zero, log_like, the
+ * occupancies and the dense rows stand), or arc_occ given with n_arcs[i] > cap_arcs (WFST_E_CAPACITY: n_arcs[i] is the room needed,
+ * that row stays zero and everything else stands), so that the call can be repeated once.
+ * The call itself fails, before any device work, with WFST_E_ARG (everything wfst_decoder_force_align names; a scale that is
+ * negative or not finite; min_post that is NaN or outside 0..1; cap_frames or cap_entries < 1 unless both are 0; cap_arcs < 0; a
+ * grad_scale that is not finite; grad without grad_frames, n_cols < 1, a negative grad_frames, a pitch below n_cols, a grad pointer
+ * not aligned to 4 bytes, a class beyond n_cols as above) or WFST_E_STATE (a listed channel never initialised).  Any output pointer
+ * may be NULL.
+ * The workspace is the decoder's, grown on demand: 8 bytes per (frame, state) cell for alpha, 24 per arc, 8 per (frame, class of the
+ * graph), and 16 per state for the two rolling rows of a graph of more than WFST_GPOST_LDS_STATES states -- up to that size the rows
+ * live on chip, and the answers do not depend on which.  Lists whose cells pass 256 MiB together are taken in rounds; an explicit
+ * max_cells bounds the cells of one round as well.  The by-source tables of a graph set are built on the set's first call, under
+ * a lock (a set may be shared between decoders and threads), take 16 bytes per arc and 12 per state on the device, and go with
+ * wfst_align_graphs_free; wfst_align_graphs_info answers what it did before.  wfst_decoder_graph_posteriors_workspace: the bytes held.
+ * Not computed here: a beam (the table is dense), an "add into the rows" dense mode and a soft-numerator MMI in one call (the caller
+ * combines the tensors of this call and wfst_decoder_sequence_stats), a half-precision dense output, graph compilation. */
+#define WFST_GPOST_LDS_STATES 2048 /* states of a graph whose two float64 rows live in LDS (32 KiB of a workgroup's 64) */
+int wfst_decoder_graph_posteriors(wfst_decoder *d, const int32_t *channels, int32_t n, const wfst_align_graphs *graphs,
+                                  const int32_t *graph_of /* [n] */, const int32_t *n_frames_in /* [n], -1 = all; NULL: all */,
+                                  const int32_t *label_map /* NULL, or n_tid + 1 entries, entry 0 unused */, int32_t n_tid,
+                                  double graph_scale, double acoustic_scale, double min_post,
+                                  int64_t max_cells /* (T + 1) x states; 0 = default */,
+                                  int32_t cap_frames, int32_t cap_entries, int32_t cap_arcs,
+                                  void *const *grad /* NULL, or [n] device pointers */, const int64_t *grad_pitch /* [n], floats */,
+                                  const int32_t *grad_frames /* [n] */, int32_t n_cols, double grad_scale, void *consumer_stream,
+                                  int32_t *status /* [n] */, int32_t *found, int32_t *n_frames /* [n] */, double *log_like /* [n] */,
+                                  int32_t *n_entries, int32_t *n_arcs /* [n] */, int32_t *frame_off /* [n][cap_frames + 1] */,
+                                  int32_t *n_distinct /* [n][cap_frames] */, double *frame_mass /* [n][cap_frames] */,
+                                  int32_t *entry_class /* [n][cap_entries] */, double *entry_post /* [n][cap_entries] */,
+                                  double *arc_occ /* [n][cap_arcs], or NULL */);
+int wfst_decoder_graph_posteriors_workspace(wfst_decoder *d, int64_t *bytes);
 
 /* The service's n-best (OnlineClgLatticeFastDecoder::GetNbest, kaldi-nnet3/kaldi-online-nnet3-my-
  * decoder.cc:50-105: GetRawLattice -> DeterminizeLatticeWrapper -> NShortestPath ->
