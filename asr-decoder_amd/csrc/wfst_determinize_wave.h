@@ -48,6 +48,33 @@ constexpr int kDwMap = 2048;     // state -> element index, open addressing
 constexpr int kDwArcs = DETW_ARCS;   // epsilon arcs priced per entry in a window (an entry with more is priced alone, a lane per arc); 1, 2 or 4
 constexpr int kDwWin = 64 / kDwArcs;   // queue entries priced side by side
 
+// (tests/test_gpu_detwave_edges.py builds the harness with -DDETW_COUNT: one counter per branch below, bumped by lane 0 in LDS and
+// printed by name per lattice -- a constructed lattice must MOVE the counter of the branch it was built for.  Undefined, as in the
+// product, every DWC*() is empty and nothing of this exists.)
+#ifdef DETW_COUNT
+#define DETW_COUNTERS(X) \
+  X(closure) X(fb_entry_n) X(fb_entry_states) X(fb_mid_cur) X(fb_mid_queue) X(fb_inorder) X(fallback) \
+  X(window) X(win_peak) X(win_full) X(win_over) X(win_cut) X(entry_priced) X(entry_arcs_full) X(big_head) X(big_round) X(big_zero) X(zero_arc) X(stale_entry) \
+  X(dropped) X(killed) X(meet) X(meet_new) X(meet_old) X(meet_tie) X(meet_str_len) X(meet_str_label) X(mixed) X(ring_wrap) \
+  X(cur_full) X(sort_pad) X(stage_over) \
+  X(pairs_wave) X(pairs_lane0_n) X(pairs_lane0_tot) X(pairs_shell40) X(final_multi) X(final_tie) \
+  X(run_sub) X(run_te) X(unique_merge) X(subset_64) X(subset_big) \
+  X(norm_wave) X(norm_k1) X(norm_plen0) X(norm_prefix) X(norm_depths) X(norm_at_labs) X(norm_long) X(norm_best_tie) X(norm_lane0) \
+  X(init_found) X(init_found_approx) X(init_new) \
+  X(trie_lost_same_key) X(trie_lost_same_slot) X(trie_lost_alias) X(trie_retry)
+enum DwCounter {
+#define X(n) kDwc_##n,
+  DETW_COUNTERS(X)
+#undef X
+  kDwCounters
+};
+#define DWC(S_, name, cond) do { const unsigned long long b_ = __ballot(cond); if (lane == 0 && b_) (S_).cnt[kDwc_##name] += __popcll(b_); } while (0)   /* every lane of the wave gets here */
+#define DWC1(S_, name) do { (S_).cnt[kDwc_##name] += 1; } while (0)                                                                                       /* one lane gets here */
+#else
+#define DWC(S_, name, cond) do { } while (0)
+#define DWC1(S_, name) do { } while (0)
+#endif
+
 struct DwShared {
   DetElem cur[kDwCur];
   DetElem queue[kDwQueue];
@@ -66,6 +93,9 @@ struct DwShared {
   DetElem sub[64];               // hashes and compares next -- and the initial subset it came from -- read at LDS latency
   int32_t bc[16];                // lane 0 -> wave
   long long tm[16];              // (development timers)
+#ifdef DETW_COUNT
+  int32_t cnt[kDwCounters];
+#endif
 };
 
 __host__ __device__ inline int64_t detw_extra_words(const DetCaps &, int32_t) { return 0; }
@@ -120,6 +150,19 @@ __device__ inline int32_t detw_succ_wave(DetWs &W, uint16_t *claim /* [256] */, 
       else { want = true; claim[s & 255u] = (uint16_t)lane; }
     }
     DETW_SYNC();
+#ifdef DETW_COUNT
+    {  // a lane that loses the claim: to the same string (it finds the node next round), to another key after the same slot, or to
+       // another slot that shares the claim word
+      DwShared &Sc = *reinterpret_cast<DwShared *>(reinterpret_cast<char *>(claim) - __builtin_offsetof(DwShared, claim));
+      const int wl = want ? (int)claim[s & 255u] : lane;
+      const uint32_t ws = (uint32_t)__shfl((int)s, wl, 64);
+      const uint32_t wk_lo = (uint32_t)__shfl((int)(uint32_t)key, wl, 64), wk_hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), wl, 64);
+      const bool lost = want && wl != lane, same_key = wk_lo == (uint32_t)key && wk_hi == (uint32_t)(key >> 32);
+      DWC(Sc, trie_lost_same_key, lost && same_key);
+      DWC(Sc, trie_lost_same_slot, lost && !same_key && ws == s);
+      DWC(Sc, trie_lost_alias, lost && ws != s);
+    }
+#endif
     if (want && claim[s & 255u] == (uint16_t)lane) {
       *(DW_G(uint64_t) *)(W.tr_key + s) = key;
       dw_st(W.tr_depth + s, pd + 1);
@@ -209,12 +252,16 @@ __device__ inline void detw_commit_in_order(DetWs &W, DwShared &S, unsigned long
     }
   }
   S.bc[0] = nc; S.bc[1] = tail; S.bc[2] = over ? 1 : 0;
+  if (over) DWC1(S, fb_inorder);
 }
 
 // EpsilonClosure of e[0..n) (global, one element per state) in place, by the wave; returns the new size (sorted by state),
 // -1 when the LDS buffers were outgrown (nothing changed then but the trie: the caller runs det_closure()).
 // minimal: ConvertToMinimal (:940-957) on the way out -- only the elements whose state has a labelled arc or is final are written.
 __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int lane, bool minimal) {
+  DWC(S, closure, lane == 0);
+  DWC(S, fb_entry_n, lane == 0 && n > kDwCur);
+  DWC(S, fb_entry_states, lane == 0 && W.n_states >= (1 << 21));
   if (n > kDwCur || W.n_states >= (1 << 21)) return -1;
   for (int i = lane; i < n; i += 64) {
     const DetElem x = dw_ld_elem(e + i);
@@ -253,6 +300,13 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
       const DetElem c = S.cur[S.qidx[qp]];
       live_e = (c.str == el.str && c.w1 == el.w1 && c.w2 == el.w2);
     }
+    DWC(S, window, lane == 0);
+    DWC(S, win_full, lane == 0 && qn >= kDwWin);
+    DWC(S, win_over, lane == 0 && qn > kDwWin);
+#ifdef DETW_COUNT
+    if (lane == 0 && win > S.cnt[kDwc_win_peak]) S.cnt[kDwc_win_peak] = win;   // (the one counter that is a maximum)
+#endif
+    DWC(S, stale_entry, en < win && j == 0 && !live_e);
     DWT(0);
     int32_t a0 = 0, ne = 0;
     if (live_e) { a0 = dw_ld(W.off + el.state); ne = dw_ld(W.neps + el.state); }
@@ -260,7 +314,10 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
     DetArc arc; arc.ilabel = 0; arc.olabel = 0; arc.w1 = 0; arc.w2 = 0; arc.to = 0;
     big = live_e && ne > kDwArcs;
     const bool mine = live_e && j < ne && !big;
+    DWC(S, entry_priced, mine && j == 0);
+    DWC(S, entry_arcs_full, mine && j == 0 && ne == kDwArcs);
     if (mine) arc = dw_ld_arc(W.arcs + a0 + j);
+    DWC(S, zero_arc, mine && det_is_zero(arc.w1, arc.w2));
     DWT(2);
     if (mine && !det_is_zero(arc.w1, arc.w2)) {
       have = true;
@@ -287,6 +344,8 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
     const unsigned long long bigmask = __ballot(big);
     int use = win;
     if (bigmask) use = (__ffsll((long long)bigmask) - 1) / kDwArcs;
+    DWC(S, win_cut, lane == 0 && bigmask && use > 0);
+    DWC(S, big_head, lane == 0 && use == 0);
     if (use == 0) {
       // ---- the head entry has more epsilon arcs than a window prices: a lane per arc, 64 at a time, committed in order ----
       DETW_SYNC();
@@ -300,6 +359,8 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
           arc2 = dw_ld_arc(W.arcs + a0 + base + lane);
           live = !det_is_zero(arc2.w1, arc2.w2);
         }
+        DWC(S, big_round, lane == 0);
+        DWC(S, big_zero, base + lane < ne && !live);
         {
           const int32_t ns = detw_succ_wave(W, S.claim, live && arc2.olabel != 0, el.str, arc2.olabel, lane);
           if (live) {
@@ -318,6 +379,7 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
         nc = S.bc[0]; qn = S.bc[1]; over = S.bc[2] != 0;
         DETW_SYNC();
       }
+      DWC(S, ring_wrap, lane == 0 && qh + 1 >= kDwQueue);
       qh = (qh + 1) & (kDwQueue - 1);
       --qn;
       continue;
@@ -346,7 +408,9 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
           if (me < use0 && me > en) kill = me;                                            // (2)
         }
       }
+      DWC(S, dropped, have0 && tgt >= 0 && !have);
       for (int d = 32; d > 0; d >>= 1) kill = min(kill, __shfl_xor(kill, d, 64));
+      DWC(S, killed, lane == 0 && kill < use0);
       use = kill;
       if (en >= use) have = false;
       DETW_SYNC();
@@ -369,6 +433,26 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
           beat = cmp == 1 || (cmp == 0 && lane < champ);
           if (!beat) cand = false;
         }
+#ifdef DETW_COUNT
+        {  // a lane that meets another state's champion: the state new to the closure or not; equal in weight AND string (the lower
+           // lane wins); equal in weight, the strings differing in length or, at equal length, in a label
+          const bool met = champ != lane && S.offer[champ].state == nx.state;   // (champ != lane: a candidate that read another lane's mark)
+          int wc = 1, dl = 0;
+          bool same_str = false;
+          if (met) {
+            const DetElem o = S.offer[champ];
+            wc = det_wcmp(nx.w1, nx.w2, o.w1, o.w2);
+            same_str = nx.str == o.str;
+            dl = dw_ld(W.tr_depth + nx.str) - dw_ld(W.tr_depth + o.str);
+          }
+          DWC(S, meet, met);
+          DWC(S, meet_new, met && tgt < 0);
+          DWC(S, meet_old, met && tgt >= 0);
+          DWC(S, meet_tie, met && wc == 0 && same_str);
+          DWC(S, meet_str_len, met && wc == 0 && !same_str && dl != 0);
+          DWC(S, meet_str_label, met && wc == 0 && !same_str && dl == 0);
+        }
+#endif
         DETW_SYNC();
         if (beat) *mk = (uint16_t)lane;   // (tells the champion it is beaten)
         DETW_SYNC();
@@ -379,13 +463,16 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
       have = cand;
     }
     const unsigned long long valid = __ballot(have);
+    DWC(S, mixed, mixed);   // (lanes that met another state's offer after their slot)
     if (__ballot(mixed)) {
-      // (never seen on a lattice of the bench: two states new to the closure whose probes of the state index end in one slot)
+      // (never seen on a lattice of the bench: two states new to the closure whose probes of the state index end in one slot --
+      // tests/det_edge_util.py constructs one, "two_new_states_after_one_slot")
       const unsigned long long all = __ballot(have0 && en < use);   // the window's offers as priced: the in-order commit judges them itself
       DETW_SYNC();
       if (lane == 0) detw_commit_in_order(W, S, all, kDwArcs, use, qh, nc, qn);
       DETW_SYNC();
       nc = S.bc[0]; qn = S.bc[1] - use; over = S.bc[2] != 0;
+      DWC(S, ring_wrap, lane == 0 && qh + use >= kDwQueue);
       qh = (qh + use) & (kDwQueue - 1);
       DETW_SYNC();
       DWT(6);
@@ -394,6 +481,8 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
     const bool is_new = have && tgt < 0;
     const unsigned long long newmask = __ballot(is_new);
     const int n_new = __popcll(newmask), n_push = __popcll(valid);
+    DWC(S, fb_mid_cur, lane == 0 && nc + n_new > kDwCur);
+    DWC(S, fb_mid_queue, lane == 0 && nc + n_new <= kDwCur && qn + n_push > kDwQueue);
     if (nc + n_new > kDwCur || qn + n_push > kDwQueue) { over = true; break; }
     if (have) {
       int idx = tgt;
@@ -410,6 +499,7 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
     }
     nc += n_new;
     qn += n_push - use;
+    DWC(S, ring_wrap, lane == 0 && qh + use >= kDwQueue);
     qh = (qh + use) & (kDwQueue - 1);
     DETW_SYNC();
     DWT(5);
@@ -421,6 +511,8 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
   }
   DETW_SYNC();
   if (over || W.err) return -1;
+  DWC(S, cur_full, lane == 0 && nc == kDwCur);
+  DWC(S, sort_pad, lane == 0 && (nc & (nc - 1)) != 0);
   detw_sort_keys(S, nc, lane);
   int nout = 0;
   for (int i0 = 0; i0 < nc; i0 += 64) {
@@ -440,6 +532,7 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
     nout += __popcll(km);
   }
   DETW_SYNC();
+  DWC(S, stage_over, lane == 0 && nout > 64);
   return nout;
 }
 
@@ -447,6 +540,7 @@ __device__ inline int detw_closure(DetWs &W, DwShared &S, DetElem *e, int n, int
 __device__ inline int detw_closure_any(DetWs &W, DwShared &S, DetElem *e, int n, int lane, bool minimal) {
   int m = detw_closure(W, S, e, n, lane, minimal);
   if (m >= 0) return m;
+  DWC(S, fallback, lane == 0);
   if (lane == 0) {
     int k = W.err ? 0 : det_closure(W, e, n);
     if (minimal && !W.err) k = det_minimal(W, e, k);
@@ -520,14 +614,18 @@ __device__ inline int32_t detw_pairs_wave(DetWs &W, DwShared &S, int32_t out, in
   }
   int32_t tot = cnt, mx = cnt;
   for (int d = 32; d > 0; d >>= 1) { tot += __shfl_xor(tot, d, 64); mx = max(mx, __shfl_xor(mx, d, 64)); }
+  DWC(S, pairs_lane0_n, lane == 0 && n > 64);
+  DWC(S, pairs_lane0_tot, lane == 0 && n <= 64 && tot > 64);
+  DWC(S, pairs_wave, lane == 0 && n <= 64 && tot <= 64);
   if (n > 64 || tot > 64) {
-    if (lane == 0) S.bc[5] = detw_pairs(W, out);
+    if (lane == 0) { S.bc[5] = detw_pairs(W, out); if (S.bc[5] > 64) DWC1(S, pairs_shell40); }
     DETW_SYNC();
     *in_lds = false;
     return S.bc[5];
   }
   // ProcessFinal (:1029-1060): the best final element, the first of equals
   unsigned long long fm = __ballot(fin);
+  DWC(S, final_multi, lane == 0 && (fm & (fm - 1)) != 0);
   if (fm) {
     int best = __ffsll((long long)fm) - 1;
     float f1 = __shfl(el.w1, best, 64), f2 = __shfl(el.w2, best, 64);
@@ -536,6 +634,7 @@ __device__ inline int32_t detw_pairs_wave(DetWs &W, DwShared &S, int32_t out, in
       const int k = __ffsll((long long)mk) - 1;
       const float g1 = __shfl(el.w1, k, 64), g2 = __shfl(el.w2, k, 64);
       const int32_t gs = __shfl(el.str, k, 64);
+      DWC(S, final_tie, lane == 0 && det_cmp(W, g1, g2, gs, f1, f2, fs) == 0);
       if (det_cmp(W, g1, g2, gs, f1, f2, fs) == 1) { f1 = g1; f2 = g2; fs = gs; }
     }
     if (lane == 0) det_add_arc(W, out, 0, -1, f1, f2);
@@ -603,6 +702,9 @@ __device__ inline void detw_normalize_wave(DetWs &W, DwShared &S, DetElem *e, in
     const int c = (bi >= 64) ? -1 : (oi >= 64) ? 1 : det_wcmp(b1, b2, o1, o2);
     if (c == -1 || (c == 0 && oi < bi)) { b1 = o1; b2 = o2; bi = oi; }
   }
+  DWC(S, norm_wave, lane == 0);
+  DWC(S, norm_k1, lane == 0 && k == 1);
+  DWC(S, norm_best_tie, on && lane != bi && det_wcmp(x.w1, x.w2, b1, b2) == 0);
   // the strings' lowest common ancestor
   int32_t node = x.str;
   const int32_t dep0 = on ? dw_ld(W.tr_depth + node) : 0x7FFFFFFF;
@@ -625,6 +727,11 @@ __device__ inline void detw_normalize_wave(DetWs &W, DwShared &S, DetElem *e, in
   // the prefix off every string
   int32_t left = on ? dep0 - plen : 0, mx = left;
   for (int d = 32; d > 0; d >>= 1) mx = max(mx, __shfl_xor(mx, d, 64));
+  DWC(S, norm_plen0, lane == 0 && k > 1 && plen == 0);
+  DWC(S, norm_prefix, lane == 0 && plen > 0);
+  DWC(S, norm_depths, plen > 0 && on && dep0 != dmin);   // (lanes whose string is deeper than the shallowest)
+  DWC(S, norm_at_labs, lane == 0 && plen > 0 && mx == kDwLabs);
+  DWC(S, norm_long, lane == 0 && plen > 0 && mx > kDwLabs);
   if (plen > 0 && mx > kDwLabs) {   // (a string too long for a lane's label buffer: the sequential way, from the untouched elements)
     if (lane == 0) { det_normalize(W, e, k, t1, t2, common); S.bc[14] = __float_as_int(*t1); S.bc[15] = __float_as_int(*t2); S.bc[3] = *common; }
     DETW_SYNC();
@@ -693,6 +800,7 @@ __device__ inline int detw_run(DetWs &W, DwShared &S, long long *timers) {
           while (i + run < mp && run <= 64 && plab[i + run] == ilabel) ++run;
           DetElem *sub = run <= 64 ? S.sub : W.te;   // (a handful of elements as a rule: kept in LDS)
           S.bc[13] = run <= 64 ? 1 : 0;
+          if (run <= 64) DWC1(S, run_sub); else DWC1(S, run_te);
           int32_t k = 0;
           // MakeSubsetUnique (:1184-1216): the elements of one state merged, the better (weight, string) kept
           while (i < mp && plab[i] == ilabel) {
@@ -701,11 +809,14 @@ __device__ inline int detw_run(DetWs &W, DwShared &S, long long *timers) {
             while (i < mp && plab[i] == ilabel && pel[i].state == cur.state) {
               const DetElem x = pel[i];
               if (det_cmp(W, x.w1, x.w2, x.str, cur.w1, cur.w2, cur.str) == 1) { cur.w1 = x.w1; cur.w2 = x.w2; cur.str = x.str; }
+              DWC1(S, unique_merge);
               ++i;
             }
             sub[k++] = cur;
           }
           S.bc[6] = i; S.bc[8] = k; S.bc[9] = ilabel;
+          if (k == 64) DWC1(S, subset_64);
+          if (k > 64) DWC1(S, subset_big);
         }
         DETW_SYNC();
         {
@@ -722,8 +833,14 @@ __device__ inline int detw_run(DetWs &W, DwShared &S, long long *timers) {
             for (int32_t q = W.ih_head[b]; q >= 0; q = W.ih_next[q])
               if (det_subset_equal(sub, k, W.pool + W.ih_off[q], W.ih_len[q], W.delta)) { found = q; break; }
             if (found >= 0) {
+#ifdef DETW_COUNT
+              DWC1(S, init_found);
+              for (int32_t q = 0; q < k; ++q)
+                if (sub[q].w1 != W.pool[W.ih_off[found] + q].w1 || sub[q].w2 != W.pool[W.ih_off[found] + q].w2) { DWC1(S, init_found_approx); break; }
+#endif
               det_add_arc(W, o, S.bc[9], W.ih_state[found], t1 + W.ih_w1[found], t2 + W.ih_w2[found]);
             } else {
+              DWC1(S, init_new);
               if (k > W.cap.tmp) W.err = 6;
               for (int32_t q = 0; q < k && !W.err; ++q) W.ta[q] = sub[q];
             }
@@ -745,7 +862,7 @@ __device__ inline int detw_run(DetWs &W, DwShared &S, long long *timers) {
           int32_t str = 0;
           if (!W.err) {
             if (m2 <= 64) detw_normalize_wave(W, S, s, m2, lane, &w1, &w2, &str);
-            else if (lane == 0) det_normalize(W, s, m2, &w1, &w2, &str);
+            else if (lane == 0) { det_normalize(W, s, m2, &w1, &w2, &str); DWC1(S, norm_lane0); }
           }
           if (lane == 0 && !W.err) {
             // InitialToStateId, second half
@@ -788,6 +905,9 @@ __device__ inline void detw_run_block(const int32_t *off, const DetArc *arcs, co
   }
   for (int i = tid; i < kDwMap; i += blockDim.x) S.map[i] = 0u;
   if (tid < 16) S.tm[tid] = 0;
+#ifdef DETW_COUNT
+  for (int i = tid; i < kDwCounters; i += blockDim.x) S.cnt[i] = 0;
+#endif
   __syncthreads();
   const int32_t hcap_full = W.tr_hcap;
   for (int attempt = 0; attempt < 2; ++attempt) {
@@ -805,8 +925,12 @@ __device__ inline void detw_run_block(const int32_t *off, const DetArc *arcs, co
     }
     __syncthreads();
     if (!(s_err == 1 && W.tr_hcap < hcap_full)) break;
+    if (tid == 0) DWC1(S, trie_retry);
   }
   if (tid >= 64) return;
+#ifdef DETW_COUNT
+  for (int i = lane; i < kDwCounters; i += 64) timers[16 + i] = S.cnt[i];   // (the harness reads them behind the 16 timers)
+#endif
   if (lane == 0) { res[0] = W.os_n; res[1] = W.oa_n; res[2] = W.err; res[3] = W.tr_n; }
   if (out) {
     const int32_t na = W.oa_n < caps.arcs ? W.oa_n : caps.arcs;

@@ -14,8 +14,11 @@ using namespace wfst;
 // the closure's fast buffers (LDS on the device) emulated at a tiny size, so that closures outgrow them (det_host_set_low)
 static int g_low_tmp = 0;
 
+static int g_last_trie = 0;   // trie nodes the last det_host_run made (the empty string included)
+
 extern "C" {
 void det_host_set_low(int tmp_lo) { g_low_tmp = tmp_lo; }
+int det_host_last_trie() { return g_last_trie; }
 // Raw lattice in: states 0..S-1 (0 = start), final flags, arcs {src, dst, ilabel (transition-id), olabel (word),
 // graph, acoustic}.  Determinized lattice out, in the wrapper's output form (after its last Invert): arcs
 // {src, dst, ilabel 0, olabel word or 0, graph, acoustic}; a final weight is an arc to an extra final state.
@@ -55,6 +58,7 @@ int det_host_run(int S, const int *is_final, int A, const int *a_src, const int 
   if (g_low_tmp > 0) { W.tb_lo = lo_b.data(); W.tc_lo = lo_c.data(); W.tmp_lo = g_low_tmp; }
   det_init(W, 0, 1);
   const int err = det_run(W);
+  g_last_trie = W.tr_n;
   // OutputNoolabel (:307-377) + Invert
   int ns = W.os_n, na = 0;
   for (int s = 0; s < W.os_n && s < max_states; ++s) st_final[s] = 0;

@@ -11,19 +11,11 @@ import numpy as np
 import pytest
 
 import pyoracle
+from det_edge_util import write_bin as _write_bin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _write_bin(path, L):
-    with open(path, "wb") as f:
-        np.asarray([L.n_states, len(L.a_src)], np.int32).tofile(f)
-        np.asarray(L.st_final, np.int32).tofile(f)
-        rec = np.zeros(len(L.a_src), dtype=[("src", "<i4"), ("dst", "<i4"), ("il", "<i4"), ("ol", "<i4"), ("g", "<f4"), ("ac", "<f4")])
-        rec["src"], rec["dst"], rec["il"], rec["ol"], rec["g"], rec["ac"] = L.a_src, L.a_dst, L.a_il, L.a_ol, L.a_graph, L.a_ac
-        rec.tofile(f)
 
 
 def test_wave_determinizer_equals_the_host_build_at_every_size(synth, oracle, tmp_path):

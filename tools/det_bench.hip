@@ -1,7 +1,11 @@
 // Development harness (not part of the product): the determinizer's device code on raw lattices read from files, one workgroup
 // per lattice, against the HOST build of the same header -- times per lattice, phase timers, correctness (arc multiset).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I asr-decoder_amd/csrc -o tools/det_bench tools/det_bench.hip
-//   tools/det_bench [--variant N] [--reps R] lat0.bin lat1.bin ...
+//   tools/det_bench [--variant N] [--reps R] [--expect-err] [--cap-states N] [--cap-arcs N] lat0.bin lat1.bin ...
+// --cap-states / --cap-arcs: the output-state / output-arc capacity of the workspaces of the files that FOLLOW (0: the default again).
+// --expect-err: a file the host build refuses (a capacity exceeded) does not end the run: its line shows the host's code beside the
+// device's (REFUSED host_err N ... err M) and the caller decides what to make of them.
+// Built with -DDETW_COUNT (variant 1), every line ends in the wave's branch counters, name=value (wfst_determinize_wave.h).
 // File: int32 S, A; int32 is_final[S]; A x {int32 src, dst, ilabel (transition-id), olabel (word); float graph, acoustic}
 // (tools/det_bench_data.py writes them from the reference's on-disk lattices).
 #include <hip/hip_runtime.h>
@@ -69,17 +73,29 @@ static std::vector<OutArc> canon(const DetOutArc *a, int n) {
 
 constexpr int kThreads = 256;
 constexpr int kLowTmp = 1024;
+#ifdef DETW_COUNT
+constexpr int kTimerWords = 16 + kDwCounters;
+static const char *const kCounterName[] = {
+#define X(n) #n,
+    DETW_COUNTERS(X)
+#undef X
+};
+#else
+constexpr int kTimerWords = 16;
+#endif
 
 struct Job {
   const int32_t *off; const DetArc *arcs; const int32_t *fin;
   int32_t S, A;
+  DetCaps caps;
   int32_t *ws;            // det_words(caps, S)
   DetOutArc *out; int32_t *res;   // res {os_n, oa_n, err, tr_n, timers...}
-  long long *timers;      // [16]
+  long long *timers;      // [kTimerWords]
 };
 
-__global__ __launch_bounds__(kThreads) void det_kernel_lane(const Job *jobs, DetCaps caps) {   // the product's kernel as of round 4
+__global__ __launch_bounds__(kThreads) void det_kernel_lane(const Job *jobs) {   // the product's kernel as of round 4
   const Job J = jobs[blockIdx.x];
+  const DetCaps caps = J.caps;
   const int tid = threadIdx.x;
   __shared__ DetWs W;
   __shared__ DetElem s_tb[kLowTmp], s_tc[kLowTmp];
@@ -112,8 +128,9 @@ __global__ __launch_bounds__(kThreads) void det_kernel_lane(const Job *jobs, Det
   }
 }
 
-__global__ __launch_bounds__(kThreads) void det_kernel_lane_private(const Job *jobs, DetCaps caps) {   // the same, W in registers
+__global__ __launch_bounds__(kThreads) void det_kernel_lane_private(const Job *jobs) {   // the same, W in registers
   const Job J = jobs[blockIdx.x];
+  const DetCaps caps = J.caps;
   const int tid = threadIdx.x;
   __shared__ DetWs Ws;
   __shared__ DetElem s_tb[kLowTmp], s_tc[kLowTmp];
@@ -137,24 +154,29 @@ __global__ __launch_bounds__(kThreads) void det_kernel_lane_private(const Job *j
   }
 }
 
-__global__ __launch_bounds__(kThreads) void det_kernel_wave(const Job *jobs, DetCaps caps, int variant) {
+__global__ __launch_bounds__(kThreads) void det_kernel_wave(const Job *jobs, int variant) {
   const Job J = jobs[blockIdx.x];
-  detw_run_block(J.off, J.arcs, J.fin, J.S, J.A, J.ws, caps, J.out, J.res, J.timers, variant);
+  detw_run_block(J.off, J.arcs, J.fin, J.S, J.A, J.ws, J.caps, J.out, J.res, J.timers, variant);
 }
 
-static void launch(const Job *jobs, int n, const DetCaps &caps, int variant) {
-  if (variant == 0) hipLaunchKernelGGL(det_kernel_lane, dim3((unsigned)n), dim3(kThreads), 0, 0, jobs, caps);
-  else if (variant == 2) hipLaunchKernelGGL(det_kernel_lane_private, dim3((unsigned)n), dim3(kThreads), 0, 0, jobs, caps);
-  else hipLaunchKernelGGL(det_kernel_wave, dim3((unsigned)n), dim3(kThreads), 0, 0, jobs, caps, variant);
+static void launch(const Job *jobs, int n, int variant) {
+  if (variant == 0) hipLaunchKernelGGL(det_kernel_lane, dim3((unsigned)n), dim3(kThreads), 0, 0, jobs);
+  else if (variant == 2) hipLaunchKernelGGL(det_kernel_lane_private, dim3((unsigned)n), dim3(kThreads), 0, 0, jobs);
+  else hipLaunchKernelGGL(det_kernel_wave, dim3((unsigned)n), dim3(kThreads), 0, 0, jobs, variant);
 }
 
 int main(int argc, char **argv) {
-  int variant = 0, reps = 3;
+  int variant = 0, reps = 3, cap_states = 0, cap_arcs = 0;
+  bool expect_err = false;
   std::vector<std::string> files;
+  std::vector<int> file_cap_states, file_cap_arcs;
   for (int i = 1; i < argc; ++i) {
-    if (!strcmp(argv[i], "--variant")) variant = atoi(argv[++i]);
-    else if (!strcmp(argv[i], "--reps")) reps = atoi(argv[++i]);
-    else files.push_back(argv[i]);
+    if (!strcmp(argv[i], "--variant") && i + 1 < argc) variant = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--reps") && i + 1 < argc) reps = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--cap-states") && i + 1 < argc) cap_states = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--cap-arcs") && i + 1 < argc) cap_arcs = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--expect-err")) expect_err = true;
+    else { files.push_back(argv[i]); file_cap_states.push_back(cap_states); file_cap_arcs.push_back(cap_arcs); }
   }
   std::vector<Lat> lats(files.size());
   for (size_t i = 0; i < files.size(); ++i)
@@ -167,9 +189,13 @@ int main(int argc, char **argv) {
   caps.tmp = std::max(8192, 2 * (maxA + maxS));
   // ---- host reference (the same header, sequential) ----------------------------------------------------
   std::vector<std::vector<OutArc>> want(lats.size());
-  std::vector<int> want_states(lats.size());
+  std::vector<int> want_states(lats.size()), host_err(lats.size(), 0);
+  std::vector<DetCaps> fcaps(lats.size(), caps);
   for (size_t i = 0; i < lats.size(); ++i) {
     Lat &L = lats[i];
+    if (file_cap_states[i] > 0) fcaps[i].states = file_cap_states[i];
+    if (file_cap_arcs[i] > 0) fcaps[i].arcs = file_cap_arcs[i];
+    const DetCaps &caps = fcaps[i];
     std::vector<int32_t> ws((size_t)det_words(caps, L.S));
     DetWs W;
     memset(&W, 0, sizeof(W));
@@ -177,7 +203,9 @@ int main(int argc, char **argv) {
     det_carve(W, ws.data(), caps, L.S);
     det_init(W, 0, 1);
     const int err = det_run(W);
-    if (err) { fprintf(stderr, "host determinizer: err %d on %s\n", err, files[i].c_str()); return 1; }
+    if (err && !expect_err) { fprintf(stderr, "host determinizer: err %d on %s\n", err, files[i].c_str()); return 1; }
+    host_err[i] = err;
+    if (err) continue;
     want[i] = canon(W.oarcs, W.oa_n);
     want_states[i] = W.os_n;
   }
@@ -186,14 +214,16 @@ int main(int argc, char **argv) {
   for (size_t i = 0; i < lats.size(); ++i) {
     Lat &L = lats[i];
     Job &J = jobs[i];
+    const DetCaps &caps = fcaps[i];
     int32_t *off, *fin, *ws, *res; DetArc *arcs; DetOutArc *out; long long *tm;
     CK(hipMalloc(&off, 4 * (L.S + 1))); CK(hipMalloc(&fin, 4 * std::max(L.S, 1))); CK(hipMalloc(&arcs, sizeof(DetArc) * std::max(L.A, 1)));
     CK(hipMemcpy(off, L.off.data(), 4 * (L.S + 1), hipMemcpyHostToDevice));
     CK(hipMemcpy(fin, L.fin.data(), 4 * L.S, hipMemcpyHostToDevice));
     CK(hipMemcpy(arcs, L.arcs.data(), sizeof(DetArc) * L.A, hipMemcpyHostToDevice));
     CK(hipMalloc(&ws, 4 * (size_t)det_words(caps, L.S) + 4 * (size_t)detw_extra_words(caps, L.S)));
-    CK(hipMalloc(&out, sizeof(DetOutArc) * caps.arcs)); CK(hipMalloc(&res, 64)); CK(hipMalloc(&tm, 16 * 8));
-    CK(hipMemset(tm, 0, 16 * 8));
+    CK(hipMalloc(&out, sizeof(DetOutArc) * caps.arcs)); CK(hipMalloc(&res, 64)); CK(hipMalloc(&tm, kTimerWords * 8));
+    CK(hipMemset(tm, 0, kTimerWords * 8));
+    J.caps = caps;
     J.off = off; J.arcs = arcs; J.fin = fin; J.S = L.S; J.A = L.A; J.ws = ws; J.out = out; J.res = res; J.timers = tm;
   }
   Job *djobs;
@@ -205,7 +235,7 @@ int main(int argc, char **argv) {
   for (int r = 0; r < reps; ++r) {
     // all lattices side by side (the product's launch), then each alone
     CK(hipEventRecord(e0));
-    launch(djobs, (int)jobs.size(), caps, variant);
+    launch(djobs, (int)jobs.size(), variant);
     CK(hipEventRecord(e1));
     CK(hipEventSynchronize(e1));
     CK(hipGetLastError());
@@ -215,22 +245,32 @@ int main(int argc, char **argv) {
   }
   for (size_t i = 0; i < jobs.size(); ++i) {
     CK(hipEventRecord(e0));
-    launch(djobs + i, 1, caps, variant);
+    launch(djobs + i, 1, variant);
     CK(hipEventRecord(e1));
     CK(hipEventSynchronize(e1));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
     int32_t res[4];
-    long long tm[16];
+    long long tm[kTimerWords];
     CK(hipMemcpy(res, jobs[i].res, 16, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(tm, jobs[i].timers, 128, hipMemcpyDeviceToHost));
-    std::vector<DetOutArc> out(std::max(res[1], 1));
-    CK(hipMemcpy(out.data(), jobs[i].out, sizeof(DetOutArc) * std::max(0, std::min(res[1], caps.arcs)), hipMemcpyDeviceToHost));
-    const bool ok = res[2] == 0 && res[0] == want_states[i] && canon(out.data(), res[1]) == want[i];
+    CK(hipMemcpy(tm, jobs[i].timers, kTimerWords * 8, hipMemcpyDeviceToHost));
+    const int n_out = std::max(0, std::min(res[1], fcaps[i].arcs));
+    std::vector<DetOutArc> out(std::max(n_out, 1));
+    CK(hipMemcpy(out.data(), jobs[i].out, sizeof(DetOutArc) * n_out, hipMemcpyDeviceToHost));
+    if (host_err[i]) {   // (--expect-err: nothing to compare the lattice with; the two codes side by side)
+      printf("  %-28s S %6d A %6d -> REFUSED host_err %d states %5d arcs %5d err %d trie %6d  alone %.3f ms |", files[i].c_str(), lats[i].S, lats[i].A,
+             host_err[i], res[0], res[1], res[2], res[3], ms);
+    } else {
+    const bool ok = res[2] == 0 && res[0] == want_states[i] && n_out == res[1] && canon(out.data(), n_out) == want[i];
     bad += !ok;
     printf("  %-28s S %6d A %6d -> states %5d arcs %5d err %d trie %6d  alone %.3f ms  %s | clk(M):", files[i].c_str(), lats[i].S, lats[i].A, res[0], res[1],
            res[2], res[3], ms, ok ? "OK" : "MISMATCH");
     for (int k = 0; k < 16; ++k) printf(" %.3f", tm[k] / 1e6);
+    }
+#ifdef DETW_COUNT
+    printf(" | cnt:");
+    for (int k = 0; k < kDwCounters; ++k) printf(" %s=%lld", kCounterName[k], tm[16 + k]);
+#endif
     printf("\n");
   }
   printf("%s\n", bad ? "FAILED" : "all equal to the host build");
