@@ -1,7 +1,7 @@
 // The in-arc index align_index_kernel (wfst_align.hip) leaves in a slot's block of AlignDev::idx, as the kernels that read it carve it:
 // align_kernel, nearest_kernel (wfst_nearest.hip), posterior_kernel / confidence_kernel (wfst_posterior.hip), seqpost_kernel
 // (wfst_seqpost.hip), slot_mass_kernel / slot_none_kernel (wfst_altern.hip), frame_post_kernel / frame_pack_kernel
-// (wfst_framepost.hip), rescale_kernel (wfst_rescale.hip) and acc_kernel / seqstat_frame_kernel / seqstat_pack_kernel /
+// (wfst_framepost.hip), rescale_kernel (wfst_rescale.hip), bias_kernel (wfst_bias.hip) and acc_kernel / seqstat_frame_kernel / seqstat_pack_kernel /
 // seqstat_dense_kernel (wfst_seqstat.hip).  What the log-semiring kernels among them do alike over this index -- the levelled frame
 // sweep, the log-sum, the frame-class reduction -- is in wfst_lattice_sweep.h.  Device code only: included by the .hip files.
 #ifndef WFST_ALIGN_INDEX_H_

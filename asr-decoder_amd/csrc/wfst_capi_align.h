@@ -42,6 +42,8 @@ struct AlignState {
   DevBuf<double> sstat;
   DevBuf<int32_t> sstat_idx, sstat_map;
   DevBuf<int64_t> sstat_in;
+  // wfst_decoder_biased_words (wfst_capi_bias.h): the bias list of every slot of a round
+  DevBuf<int32_t> bias_list;
 };
 
 // what the entry point sees of a decoder (sil_bits: the silence bitmap over transition-ids 1..sil_ntid, nullptr: none)
@@ -70,7 +72,8 @@ int align_emit(wfst_decoder *d, const std::vector<int32_t> &list, int32_t use_fi
 // wfst_decoder_word_alternatives ask the listed channels' raw lattices about n_seqs word sequences each: one table of
 // states x (words + 1) cells per (channel, sequence) pair over the in-arc index align_index_kernel builds.
 // wfst_decoder_frame_posteriors and wfst_decoder_sequence_stats ask about one empty sequence each (wfst_capi_framepost.h,
-// wfst_capi_seqstat.h), wfst_decoder_rescaled_words about one empty sequence per setting (wfst_capi_rescale.h).
+// wfst_capi_seqstat.h), wfst_decoder_rescaled_words about one empty sequence per setting (wfst_capi_rescale.h),
+// wfst_decoder_biased_words about one sequence of (nodes - 1) per setting, so that a table is states x nodes (wfst_capi_bias.h).
 // word_query_run is the sequence they share; a WordQuery is what differs.
 
 #define ALIGN_TRY(expr)                                                                               \
@@ -110,6 +113,7 @@ struct WordRound {
   int64_t cells;               // of the round's tables
   int32_t n_seqs, cap_words;
   const int32_t *seq_len;      // the caller's [n][n_seqs]
+  std::vector<int32_t> caller_pos;   // slot j's position in the caller's channel list
   AlignDev A;                  // the index fields: idx, idx_ints, ns_cap, na_cap, fr_cap
   // the staged inputs on the device: the pairs' table offsets (in cells, < 0: not run), the round's channels, the lengths, the words
   const int64_t *cell_off;
@@ -144,6 +148,7 @@ struct WordQuery {
   size_t pair_ints, chan_ints = 0; // of the packed results, per pair and per slot
   int64_t arc_limit = 0;           // > 0: a lattice of this many arcs or more is refused as a table beyond max_cells is
   const char *invariant;           // what a pair's unknown error word means
+  const char *table_cols = "(words + 1)";   // what a table's second dimension is called in the "beyond max_cells" message
   virtual ~WordQuery() = default;
   // the caller's result arrays zeroed (the arguments are valid)
   virtual void clear() = 0;

@@ -1,6 +1,6 @@
 // word_query_run: what wfst_decoder_align_words, wfst_decoder_nearest_words, wfst_decoder_word_confidence,
-// wfst_decoder_sequence_posterior, wfst_decoder_word_alternatives, wfst_decoder_frame_posteriors, wfst_decoder_rescaled_words and
-// wfst_decoder_sequence_stats do
+// wfst_decoder_sequence_posterior, wfst_decoder_word_alternatives, wfst_decoder_frame_posteriors, wfst_decoder_rescaled_words,
+// wfst_decoder_sequence_stats and wfst_decoder_biased_words do
 // alike -- see
 // wfst_capi_align.h.  It launches nothing: the entry points' own units do, in their launch() hooks.
 #include "wfst_capi_align.h"
@@ -68,7 +68,7 @@ int word_query_run(WordQuery &q, wfst_decoder *d, const int32_t *channels, int32
     }
     if (over) {
       const int code = capi_fail(WFST_E_CAPACITY, "channel " + std::to_string(list[i]) + ": " + q.name + ": a table of " + std::to_string(z[0]) +
-                                                      " lattice states x (words + 1) is beyond max_cells (" + std::to_string(limit) + ")");
+                                                      " lattice states x " + q.table_cols + " is beyond max_cells (" + std::to_string(limit) + ")");
       if (status) status[o] = code;
       continue;
     }
@@ -84,6 +84,7 @@ int word_query_run(WordQuery &q, wfst_decoder *d, const int32_t *channels, int32
     WordRound R = {};
     R.V = &V; R.cnt = cnt; R.pairs = pairs; R.cells = cut.cells;
     R.n_seqs = n_seqs; R.cap_words = cap_words; R.seq_len = seq_len;
+    for (size_t i : rnd) R.caller_pos.push_back(pos[i]);
     AlignDev &A = R.A;
     A.ns_cap = 1; A.na_cap = 1; A.fr_cap = 2;
     for (size_t i : rnd) {

@@ -705,6 +705,52 @@ struct RescaleDev {
 constexpr int64_t rescale_out_ints(int64_t cap_words, int64_t cap_tids) { return kRescaleHead + 3 * cap_words + cap_tids; }
 void launch_rescale(const AlignDev &A, const RescaleDev &Q, const RescaleSet &S, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- phrase boosting: biased best paths (wfst_bias.hip) ------------------------------------------------------------------------
+// rescale_kernel's sweep over cells (lattice state, node of the slot's phrase automaton): an arc costs c_q(a) - r, r = bs * beta(node
+// reached) on a word arc (olabel != 0) and 0.0 otherwise, float64, for n_set settings (gs, as, wip, bs) shared by the listed channels,
+// over the in-arc index align_index_kernel built.  bias_kernel runs one workgroup per (slot, setting) pair.  A list of a
+// wfst_bias_lists set, all offsets into the set's concatenated arrays:
+//   hdr[l][kBiasHdr]     {nodes J, distinct words W, offset of its ints, of its beta (= of its nodes), of its table, phrases, 0, 0}
+//   ints[]               per list: word[J] (a node's last word, 0: the root), fail[J], phrase[J] (index in the list, -1: none),
+//                        pred_off[J + 1], words[W] (the distinct word ids, ascending), pred[]: for node j the nodes i with
+//                        delta(i, word[j]) = j, ascending, at pred_off[j] .. pred_off[j + 1]
+//   beta[]               per node, float64
+//   table[]              per list [J][W] bytes: delta(i, words[k]); a word that is not in words[] leads to the root from every node
+//   list_of[slot]        the list of a round's slot, -1: none (J = 1)
+//   cells[]              the pairs' tables v[state][J] (float64, +inf: not reached), pair p at cell_off[p] (< 0: the pair is not run)
+//   path[p][path_cap]    the in-arc records of the traced path, last arc first; path_cap >= ns_cap
+//   out[p]               kBiasHead ints {found, arcs on the path, tot bits, lm bits, error (kAln*), n_hyp, n_hits, 0, the low and the
+//                        high word of biased_cost's bits, of bonus' bits, 0, 0, 0, 0}, hyp_words[cap_words], begin[cap_words],
+//                        end[cap_words], hit_phrase[cap_hits], hit_word[cap_hits]
+constexpr int32_t kBiasHead = 16;
+constexpr int32_t kBiasHdr = 8;
+constexpr int32_t kBiasMaxNodes = 256;      // = WFST_BIAS_MAX_NODES
+constexpr int32_t kBiasMaxSettings = 16;
+struct BiasSet {   // passed by value: the settings reach the kernel with its arguments
+  double v[4 * kBiasMaxSettings];   // {graph_scale, acoustic_scale, word_penalty, boost_scale} per setting
+};
+struct BiasListsDev {
+  const int32_t *hdr, *ints;
+  const double *beta;
+  const uint8_t *table;
+};
+struct BiasDev {
+  BiasListsDev L;
+  const int32_t *list_of;     // [cnt]
+  const int4 *lat_toks;       // DecoderDev::lat_toks, lat_tok_cap entries per channel
+  int64_t lat_tok_cap;
+  const int64_t *cell_off;    // [cnt][n_set], in cells
+  double *cells;
+  int32_t *path;
+  int32_t path_cap;
+  int32_t n_set, cap_words, cap_hits;
+  const uint32_t *sil_bits;   // the silence bitmap over transition-ids 1..n_tid, or nullptr
+  int32_t n_tid;
+  int32_t *out;
+};
+constexpr int64_t bias_out_ints(int64_t cap_words, int64_t cap_hits) { return kBiasHead + 3 * cap_words + 2 * cap_hits; }
+void launch_bias(const AlignDev &A, const BiasDev &Q, const BiasSet &S, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- forced alignment against per-utterance graphs (wfst_forced.hip) -----------------------------------------------------------
 // Exact float32 Viterbi of a listed channel's scores against one small graph of a wfst_align_graphs set (include/wfst_decoder.h,
 // wfst_decoder_force_align).  forced_align_kernel runs one workgroup per list entry.  A graph of the set, all offsets into the set's

@@ -97,6 +97,14 @@
 //                  "KEY rescale q gs=.. as=.. wip=.. found=0|1 cost=.. tot=.. lm=.. : word(begin,end) ..." -- cost the path's cost
 //                  at the setting (float64, 17 digits), tot / lm its unscaled LatticeToVector scores.  The other output is what it
 //                  is without the flag.
+//   --bias=FILE [--bias-settings=GS,AS,WIP,BS[:GS,AS,WIP,BS...]]  batch shape and --single-stream: phrase boosting.  FILE holds lines
+//                  "KEY bonus w1 w2 ..." (a bonus >= 0, 1..16 word ids); the phrases of KEY "*" go into every utterance's list, in
+//                  front of its own.  After the utterance's other lines, per setting (at most 16: graph scale, acoustic scale, word
+//                  penalty, boost scale; without the flag one setting 1,1,0,1) the best path of the RAW lattice picked again with
+//                  boost scale x bonus taken off for every occurrence of a phrase (BiasedWords: wfst_decoder_biased_words), as
+//                  "KEY bias q gs=.. as=.. wip=.. bs=.. found=0|1 cost=.. bonus=.. tot=.. lm=.. hits=phrase@word,... : word(begin,end) ..."
+//                  -- cost and bonus float64 at 17 digits, phrase the phrase's index in the utterance's list, word the index of the
+//                  occurrence's last word.  The other output is what it is without the flag.
 //   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
 //                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
 //                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
@@ -285,6 +293,9 @@ int main(int argc, char **argv) {
     bool force_opts = false;
     std::vector<RescaleSetting> rescale_set;   // --rescale
     bool rescale_bad = false;
+    std::string bias_file;                     // --bias
+    std::vector<BiasSetting> bias_set;         // --bias-settings
+    bool bias_given = false, bias_set_given = false, bias_bad = false;
     bool word_conf = false, sent_post = false;
     int word_alts = 0;   // --word-alternatives[=K]: K, 0 = off
     double conf_gs = 1.0, conf_as = 1.0;
@@ -418,6 +429,23 @@ int main(int argc, char **argv) {
           p0 = p1 + 1;
         }
       }
+      else if (a.compare(0, 7, "--bias=") == 0) { bias_file = a.substr(7); bias_given = true; }
+      else if (a.compare(0, 16, "--bias-settings=") == 0) {
+        // GS,AS,WIP,BS[:GS,AS,WIP,BS...]: every number whole, the scales finite and >= 0, the penalty finite
+        bias_set_given = true;
+        if (a.size() == 16) bias_bad = true;
+        for (size_t p0 = 16; p0 < a.size() && !bias_bad;) {
+          const size_t p1 = std::min(a.find(':', p0), a.size());
+          BiasSetting r;
+          char tail = 0;
+          if (sscanf(a.substr(p0, p1 - p0).c_str(), "%lf,%lf,%lf,%lf%c", &r.graph_scale, &r.acoustic_scale, &r.word_penalty, &r.boost_scale, &tail) != 4 ||
+              !(r.graph_scale >= 0.0) || !(r.acoustic_scale >= 0.0) || !(r.boost_scale >= 0.0) || std::isinf(r.graph_scale) ||
+              std::isinf(r.acoustic_scale) || std::isinf(r.boost_scale) || !std::isfinite(r.word_penalty) || p1 + 1 == a.size())
+            bias_bad = true;
+          bias_set.push_back(r);
+          p0 = p1 + 1;
+        }
+      }
       else if (a.compare(0, 17, "--silence-phones=") == 0) {
         for (size_t p0 = 17; p0 <= a.size();) {
           const size_t p1 = std::min(a.find(':', p0), a.size());
@@ -449,7 +477,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--graph-post=DIR [--graph-post-class=tid|pdf|phone] [--graph-post-scales=GS,AS] [--graph-post-out=FILE]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--bias=FILE [--bias-settings=GS,AS,WIP,BS[:GS,AS,WIP,BS...]]] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--graph-post=DIR [--graph-post-class=tid|pdf|phone] [--graph-post-scales=GS,AS] [--graph-post-out=FILE]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -490,6 +518,13 @@ int main(int argc, char **argv) {
     if (rescale_set.size() > 64) { std::cerr << "--rescale: more than 64 settings\n"; return 1; }
     const bool rescale = !rescale_set.empty();
     if (rescale && n_threads > 0) { std::cerr << "--rescale goes with the batch shape or --single-stream\n"; return 1; }
+    if (bias_set_given && !bias_given) { std::cerr << "--bias-settings goes with --bias=FILE\n"; return 1; }
+    if (bias_given && bias_file.empty()) { std::cerr << "--bias=FILE: the file of the phrases, lines KEY bonus w1 w2 ...\n"; return 1; }
+    if (bias_bad) { std::cerr << "--bias-settings=GS,AS,WIP,BS[:GS,AS,WIP,BS...]: per setting two finite scales >= 0, a finite word penalty and a finite boost scale >= 0\n"; return 1; }
+    if (bias_set.size() > 16) { std::cerr << "--bias-settings: more than 16 settings\n"; return 1; }
+    const bool bias = bias_given;
+    if (bias && n_threads > 0) { std::cerr << "--bias goes with the batch shape or --single-stream\n"; return 1; }
+    if (bias && bias_set.empty()) bias_set.push_back(BiasSetting());
     const bool force_align = !force_dir.empty();
     if (!force_align && force_opts) { std::cerr << "--force-align-class goes with --force-align=DIR\n"; return 1; }
     if (force_align && n_threads > 0) { std::cerr << "--force-align goes with the batch shape or --single-stream\n"; return 1; }
@@ -525,6 +560,34 @@ int main(int argc, char **argv) {
         if (into[key].size() > 64) { std::cerr << flag << ": more than 64 sequences for " << key << "\n"; return 1; }
       }
     }
+    // --bias: the phrases by utterance key, "*": of every utterance (they come first in an utterance's list)
+    std::map<std::string, std::vector<BiasPhrase> > bias_phrases;
+    if (bias) {
+      std::ifstream bf(bias_file.c_str());
+      if (!bf) { std::cerr << "cannot read " << bias_file << "\n"; return 1; }
+      std::string line;
+      for (int ln = 1; std::getline(bf, line); ++ln) {
+        std::istringstream ls(line);
+        std::string key;
+        if (!(ls >> key)) continue;
+        BiasPhrase ph;
+        bool ok = static_cast<bool>(ls >> ph.bonus) && std::isfinite(ph.bonus) && ph.bonus >= 0.0;
+        for (int x; ok && ls >> x;) { ok = x > 0; ph.words.push_back(x); }
+        if (!ok || !ls.eof() || ph.words.empty() || ph.words.size() > 16) {
+          std::cerr << "--bias: line " << ln << " of " << bias_file << ": KEY bonus w1 w2 ... (a finite bonus >= 0, 1..16 word ids > 0)\n";
+          return 1;
+        }
+        bias_phrases[key].push_back(ph);
+      }
+    }
+    auto bias_list_of = [&](const Utt &u) {
+      std::vector<BiasPhrase> list;
+      for (const char *key : {"*", u.key.c_str()}) {
+        auto it = bias_phrases.find(key);
+        if (it != bias_phrases.end() && (key[0] != '*' || key[1] != 0 || u.key != "*")) list.insert(list.end(), it->second.begin(), it->second.end());
+      }
+      return list;
+    };
     if (live_prune && partial_nbest == 0) { std::cerr << "--live-lattice-prune goes with --chunk=N --partial-nbest=K\n"; return 1; }
     LatticeFasterDecoderConfig opt;
     opt.ReadConfigFile(pos[0]);
@@ -648,7 +711,7 @@ int main(int argc, char **argv) {
     }
     if (!lattice_file.empty()) remove(lattice_file.c_str());  // Lattice::Write(file) appends
     if (!nbest_lattice_file.empty()) remove(nbest_lattice_file.c_str());
-    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post || rescale || seq_stats;
+    const bool want_lattice = !lattice_file.empty() || !lattice_text.empty() || nbest > 0 || partial_nbest > 0 || !align_file.empty() || !nearest_file.empty() || !phrase_file.empty() || frame_post || rescale || bias || seq_stats;
     // "HEAD#j word begin end" per word of an aligned sequence, or "HEAD notfound"
     // (--word-confidence: a fourth column conf; --word-alternatives: " none=.. alts=word:post,...")
     auto time_lines = [&](const std::string &head, const std::vector<int> &words, const TimedSeq &a) {
@@ -846,6 +909,21 @@ int main(int argc, char **argv) {
         snprintf(buf, sizeof(buf), " gs=%.9g as=%.9g wip=%.9g found=%d cost=%.17g tot=%.9g lm=%.9g :", rescale_set[q].graph_scale,
                  rescale_set[q].acoustic_scale, rescale_set[q].word_penalty, a.found ? 1 : 0, a.scaled_cost, (double)a.tot, (double)a.lm);
         out << u.key << " rescale " << (q + 1) << buf;
+        for (size_t j = 0; j < a.words.size(); ++j) out << ' ' << a.words[j] << '(' << a.frames[j].first << ',' << a.frames[j].second << ')';
+        out << '\n';
+      }
+    };
+    // --bias: an utterance's lines, one per setting
+    auto emit_bias = [&](const Utt &u, const std::vector<BiasedWords> &bw) {
+      for (size_t q = 0; q < bias_set.size() && q < bw.size(); ++q) {
+        const BiasedWords &a = bw[q];
+        char buf[320];
+        snprintf(buf, sizeof(buf), " gs=%.9g as=%.9g wip=%.9g bs=%.9g found=%d cost=%.17g bonus=%.17g tot=%.9g lm=%.9g hits=", bias_set[q].graph_scale,
+                 bias_set[q].acoustic_scale, bias_set[q].word_penalty, bias_set[q].boost_scale, a.found ? 1 : 0, a.biased_cost, a.bonus, (double)a.tot,
+                 (double)a.lm);
+        out << u.key << " bias " << (q + 1) << buf;
+        for (size_t k = 0; k < a.hits.size(); ++k) out << (k ? "," : "") << a.hits[k].first << '@' << a.hits[k].second;
+        out << " :";
         for (size_t j = 0; j < a.words.size(); ++j) out << ' ' << a.words[j] << '(' << a.frames[j].first << ',' << a.frames[j].second << ')';
         out << '\n';
       }
@@ -1274,6 +1352,14 @@ int main(int argc, char **argv) {
           decode.RescaledWords(rescale_set, &rw);
           emit_rescale(u, rw);
         }
+        if (bias) {
+          const std::vector<BiasPhrase> list = bias_list_of(u);
+          BiasLists bl;
+          if (!list.empty() && !bl.Set(std::vector<std::vector<BiasPhrase> >(1, list), devices[0])) throw std::runtime_error("--bias: the phrases of " + u.key + " make no list");
+          std::vector<BiasedWords> bw;
+          decode.BiasedWords(bl, list.empty() ? -1 : 0, bias_set, &bw);
+          emit_bias(u, bw);
+        }
         if (force_align) {
           AlignGraphs ag;
           if (!ag.Read(std::vector<std::string>(1, force_file(u)), devices[0])) throw std::runtime_error("--force-align: cannot load " + force_file(u));
@@ -1302,6 +1388,7 @@ int main(int argc, char **argv) {
         std::vector<std::vector<NearestPath> > nearest;               // --nearest-words
         std::vector<FramePosteriors> frame_post;                      // --frame-post
         std::vector<std::vector<RescaledWords> > rescaled;            // --rescale
+        std::vector<std::vector<BiasedWords> > biased;                // --bias
         std::vector<SequenceStats> seq_stats;                         // --seq-stats
         std::vector<ForcedAlignment> forced;                          // --force-align
         std::vector<GraphPosteriors> graph_post;                      // --graph-post
@@ -1448,6 +1535,19 @@ int main(int argc, char **argv) {
             }
             if (frame_post) decode.FramePosteriors(ch, true, fp_gs, fp_as, fp_map, fp_min, &o.frame_post);   // every channel in one call
             if (rescale) decode.RescaledWords(ch, rescale_set, true, &o.rescaled);                           // every channel and setting in one call
+            if (bias) {                                                                                      // every channel and setting in one call
+              std::vector<std::vector<BiasPhrase> > lists;
+              std::vector<int> list_of(n, -1);
+              for (int i = 0; i < n; ++i) {
+                const std::vector<BiasPhrase> list = bias_list_of(utts[b0 + i]);
+                if (list.empty()) continue;
+                list_of[i] = (int)lists.size();
+                lists.push_back(list);
+              }
+              BiasLists bl;
+              if (!lists.empty() && !bl.Set(lists, devices[(size_t)di])) throw std::runtime_error("--bias: the phrases of " + bias_file + " make no lists");
+              decode.BiasedWords(ch, bl, list_of, bias_set, true, &o.biased);
+            }
             if (seq_stats) {                                                                                 // every channel in one call
               std::vector<std::vector<int> > refs(n);
               for (int i = 0; i < n; ++i) refs[i] = seq_ref_of(utts[b0 + i]);
@@ -1500,6 +1600,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < n && !o.nearest.empty(); ++i) emit_nearest(utts[b0 + i], o.nearest[i]);
         for (int i = 0; i < n && !o.frame_post.empty(); ++i) emit_frame_post(utts[b0 + i], o.frame_post[i]);
         for (int i = 0; i < n && !o.rescaled.empty(); ++i) emit_rescale(utts[b0 + i], o.rescaled[i]);
+        for (int i = 0; i < n && !o.biased.empty(); ++i) emit_bias(utts[b0 + i], o.biased[i]);
         for (int i = 0; i < n && !o.seq_stats.empty(); ++i) emit_seq_stats(utts[b0 + i], o.seq_stats[i]);
         for (int i = 0; i < n && !o.forced.empty(); ++i) emit_forced(utts[b0 + i], o.forced[i]);
         for (int i = 0; i < n && !o.graph_post.empty(); ++i) emit_graph_post(utts[b0 + i], o.graph_post[i]);

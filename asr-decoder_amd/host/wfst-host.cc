@@ -29,6 +29,9 @@
 #pragma weak wfst_decoder_word_alternatives
 #pragma weak wfst_decoder_frame_posteriors
 #pragma weak wfst_decoder_rescaled_words
+#pragma weak wfst_bias_lists_create
+#pragma weak wfst_bias_lists_free
+#pragma weak wfst_decoder_biased_words
 #pragma weak wfst_decoder_sequence_stats
 #pragma weak wfst_decoder_force_align
 #pragma weak wfst_align_graphs_load
@@ -2512,6 +2515,101 @@ void GpuLatticeDecoder::RescaledWords(const std::vector<RescaleSetting> &setting
     if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
   });
   if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("RescaledWords: " + msg);
+  if (out) out->swap(o[0]);
+}
+
+// ---- phrase boosting (wfst_bias_lists_*, wfst_decoder_biased_words) ---------------------------------------------------------------------
+BiasLists::~BiasLists() {
+  if (_b && wfst_bias_lists_free) wfst_bias_lists_free(_b);
+}
+
+bool BiasLists::Set(const std::vector<std::vector<BiasPhrase> > &lists, int device) {
+  if (!wfst_bias_lists_create) throw std::runtime_error("BiasLists: this build's device library has no wfst_bias_lists_create");
+  if (_b) { wfst_bias_lists_free(_b); _b = nullptr; _n = 0; }
+  std::vector<int32_t> n_phrases, len, words;
+  std::vector<double> bonus;
+  for (const std::vector<BiasPhrase> &list : lists) {
+    n_phrases.push_back((int32_t)list.size());
+    for (const BiasPhrase &p : list) {
+      len.push_back((int32_t)p.words.size());
+      words.insert(words.end(), p.words.begin(), p.words.end());
+      bonus.push_back(p.bonus);
+    }
+  }
+  if (wfst_bias_lists_create((int32_t)lists.size(), n_phrases.data(), len.data(), words.data(), bonus.data(), device, &_b) != WFST_OK) {
+    Warn(std::string("BiasLists: ") + wfst_last_error());
+    _b = nullptr;
+    return false;
+  }
+  _n = (int)lists.size();
+  return true;
+}
+
+// One C-ABI call for `ch`: (*out)[i][q] for settings[q], (*status)[i] the channel's own code.  Returns the call's own code.  A path
+// with more words or hits than the first call made room for is asked for again, once, with the room needed.
+static int BiasedWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const BiasLists &lists, const std::vector<int> &list_of,
+                           const std::vector<BiasSetting> &settings, bool use_final_probs, long long max_cells,
+                           std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status) {
+  if (!wfst_decoder_biased_words) throw std::runtime_error("BiasedWords: this build's device library has no wfst_decoder_biased_words");
+  const size_t cnt = ch.size(), ns = settings.size(), np = cnt * ns;
+  if (!list_of.empty() && list_of.size() != cnt) throw std::runtime_error("BiasedWords: one list per listed channel");
+  std::vector<int32_t> lo(list_of.begin(), list_of.end());
+  std::vector<double> set;
+  for (const BiasSetting &s : settings) { set.push_back(s.graph_scale); set.push_back(s.acoustic_scale); set.push_back(s.word_penalty); set.push_back(s.boost_scale); }
+  size_t cap = 256, hcap = 64;
+  std::vector<int32_t> st(cnt), found(np), na(np), nh(np), nk(np), hyp, b, e, hp, hw;
+  std::vector<double> cost(np), bonus(np);
+  std::vector<float> t(np), l(np);
+  for (int pass = 0;; ++pass) {
+    hyp.assign(np * cap, 0); b.assign(np * cap, 0); e.assign(np * cap, 0); hp.assign(np * hcap, 0); hw.assign(np * hcap, 0);
+    const int rc = wfst_decoder_biased_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, lists.Handle(), lo.empty() ? nullptr : lo.data(),
+                                             (int32_t)ns, set.data(), (int32_t)cap, (int32_t)hcap, max_cells, st.data(), found.data(), na.data(),
+                                             nh.data(), nk.data(), hyp.data(), b.data(), e.data(), hp.data(), hw.data(), cost.data(), bonus.data(),
+                                             t.data(), l.data());
+    if (rc != WFST_OK) return rc;
+    const size_t most = np ? (size_t)*std::max_element(nh.begin(), nh.end()) : 0;
+    const size_t most_k = np ? (size_t)*std::max_element(nk.begin(), nk.end()) : 0;
+    if ((most <= cap && most_k <= hcap) || pass) break;
+    cap = std::max(cap, most);
+    hcap = std::max(hcap, most_k);
+  }
+  out->assign(cnt, std::vector<struct BiasedWords>(ns));
+  for (size_t i = 0; i < cnt; ++i)
+    for (size_t q = 0; q < ns; ++q) {
+      struct BiasedWords &a = (*out)[i][q];
+      const size_t p = i * ns + q;
+      a.found = found[p] != 0;
+      if (!a.found) continue;
+      a.n_arcs = na[p]; a.biased_cost = cost[p]; a.bonus = bonus[p]; a.tot = t[p]; a.lm = l[p];
+      for (size_t j = 0; j < std::min((size_t)nh[p], cap); ++j) {
+        a.words.push_back(hyp[p * cap + j]);
+        a.frames.push_back(std::make_pair(b[p * cap + j], e[p * cap + j]));
+      }
+      for (size_t j = 0; j < std::min((size_t)nk[p], hcap); ++j) a.hits.push_back(std::make_pair(hp[p * hcap + j], hw[p * hcap + j]));
+    }
+  status->assign(st.begin(), st.end());
+  return WFST_OK;
+}
+
+void GpuBatchDecoder::BiasedWords(const std::vector<int> &channels, const BiasLists &lists, const std::vector<int> &list_of,
+                                  const std::vector<BiasSetting> &settings, bool use_final_probs,
+                                  std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status, long long max_cells) {
+  BatchWordQuery("BiasedWords", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return BiasedWordsCall(_dec, ch, lists, list_of, settings, use_final_probs, max_cells, o, st);
+  });
+}
+
+void GpuLatticeDecoder::BiasedWords(const BiasLists &lists, int list, const std::vector<BiasSetting> &settings, std::vector<struct BiasedWords> *out,
+                                    bool use_final_probs) {
+  std::vector<std::vector<struct BiasedWords> > o;
+  std::vector<int> st;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = BiasedWordsCall(_dec, std::vector<int32_t>(1, _chan), lists, std::vector<int>(1, list), settings, use_final_probs, 0, &o, &st);
+    if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("BiasedWords: " + msg);
   if (out) out->swap(o[0]);
 }
 

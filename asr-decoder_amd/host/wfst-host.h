@@ -575,6 +575,43 @@ struct RescaledWords {
   std::vector<std::pair<int, int> > frames;
 };
 
+// A phrase of a bias list: 1..16 word ids and the bonus every occurrence of it in a path's words earns (finite, >= 0).
+struct BiasPhrase {
+  std::vector<int> words;
+  double bonus = 0.0;
+};
+// A set of bias lists resident on one device (wfst_bias_lists), for BiasedWords.
+class BiasLists {
+ public:
+  BiasLists() : _b(nullptr), _n(0) {}
+  ~BiasLists();
+  bool Set(const std::vector<std::vector<BiasPhrase> > &lists, int device = 0);  // false (with a message on stderr) on failure
+  int Size() const { return _n; }
+  const wfst_bias_lists *Handle() const { return _b; }
+
+ private:
+  BiasLists(const BiasLists &);
+  BiasLists &operator=(const BiasLists &);
+  wfst_bias_lists *_b;
+  int _n;
+};
+// A setting of BiasedWords: RescaleSetting's three and the scale of the phrases' bonuses.
+struct BiasSetting {
+  double graph_scale = 1.0, acoustic_scale = 1.0, word_penalty = 0.0, boost_scale = 1.0;
+};
+// The best path of a channel's raw lattice under a BiasSetting and the channel's bias list (wfst_decoder_biased_words): words /
+// frames[j] as RescaledWords has them; biased_cost = its cost, the bonuses taken off, and bonus = their sum, float64, bit for bit
+// reproducible; tot / lm UNSCALED; hits[k] = (phrase's index in the list, index in words of the occurrence's last word), by word,
+// the longest phrase first.  found = false (everything else empty / zero): the channel has no lattice, or no final state is reached.
+struct BiasedWords {
+  bool found = false;
+  int n_arcs = 0;
+  double biased_cost = 0.0, bonus = 0.0;
+  float tot = 0.0f, lm = 0.0f;
+  std::vector<int> words;
+  std::vector<std::pair<int, int> > frames, hits;
+};
+
 class GpuLatticeDecoder : public DecoderItf {
  public:
   GpuLatticeDecoder(Fst *graph, const LatticeFasterDecoderConfig &config, const wfst_limits *limits = nullptr);
@@ -707,6 +744,11 @@ class GpuLatticeDecoder : public DecoderItf {
   // runs in the batcher thread, like AlignWords.
   void RescaledWords(const std::vector<RescaleSetting> &settings, std::vector<struct RescaledWords> *out, bool use_final_probs = true,
                      bool alignment = false);
+  // Phrase boosting: the channel's best path again under each of `settings` (at most 16) with list `list` of `lists` (-1: none) -- on
+  // its RAW lattice, mid-utterance or after FinalizeDecoding, without decoding again (wfst_decoder_biased_words): (*out)[q] for
+  // settings[q].  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
+  void BiasedWords(const BiasLists &lists, int list, const std::vector<BiasSetting> &settings, std::vector<struct BiasedWords> *out,
+                   bool use_final_probs = true);
   // Pruned live lattices (see GpuChannelPool::SetLiveLatticePrune) for this object's device decoder: the private one, or -- over a
   // pool, and so under ShareDevice -- the shared decoder of every object on it (set it before the other threads decode).
   void SetLiveLatticePrune(bool on);
@@ -859,6 +901,13 @@ class GpuBatchDecoder {
   void RescaledWords(const std::vector<int> &channels, const std::vector<RescaleSetting> &settings, bool use_final_probs,
                      std::vector<std::vector<struct RescaledWords> > *out, std::vector<int> *status = nullptr, bool alignment = false,
                      long long max_cells = 0);
+  // BiasedWords (see GpuLatticeDecoder) of many channels (none listed: all), live and finalized mixed, one launch per stage:
+  // list_of[i] = the list of listed channel i (-1: none; empty: none has one), the settings (at most 16) are shared, (*out)[i][q] is
+  // the answer of listed channel i under settings[q]; (*status)[i]: WFST_OK or the channel's own error code (without `status` it
+  // throws).  max_cells: see wfst_decoder_biased_words.
+  void BiasedWords(const std::vector<int> &channels, const BiasLists &lists, const std::vector<int> &list_of,
+                   const std::vector<BiasSetting> &settings, bool use_final_probs, std::vector<std::vector<struct BiasedWords> > *out,
+                   std::vector<int> *status = nullptr, long long max_cells = 0);
   void SetLiveLatticePrune(bool on);   // pruned live lattices for every channel (see GpuChannelPool::SetLiveLatticePrune)
   wfst_decoder *Handle() { return _dec; }
 

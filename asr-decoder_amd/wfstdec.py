@@ -53,6 +53,7 @@ SYMBOLS = [
     "wfst_decoder_rescaled_words", "wfst_decoder_sequence_stats",
     "wfst_align_graphs_create", "wfst_align_graphs_load", "wfst_align_graphs_info", "wfst_align_graphs_free", "wfst_decoder_force_align",
     "wfst_decoder_force_align_workspace", "wfst_decoder_graph_posteriors", "wfst_decoder_graph_posteriors_workspace",
+    "wfst_bias_compile", "wfst_bias_lists_create", "wfst_bias_lists_info", "wfst_bias_lists_free", "wfst_decoder_biased_words",
 ]
 
 
@@ -390,6 +391,65 @@ class AlignGraphs:
     def free(self):
         if self.h:
             lib().wfst_align_graphs_free(self.h)
+            self.h = None
+
+
+def _f64(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _flat_phrases(lists):
+    """[[(words, bonus), ...], ...] as the arrays wfst_bias_lists_create takes: n_phrases per list, then the phrases' lengths,
+    words and bonuses, one list after the other"""
+    lists = [[(list(ws), float(b)) for ws, b in ph] for ph in lists]
+    n_ph = np.ascontiguousarray([len(ph) for ph in lists], dtype=np.int32)
+    ln = np.ascontiguousarray([len(ws) for ph in lists for ws, _ in ph], dtype=np.int32)
+    words = np.ascontiguousarray([int(w) for ph in lists for ws, _ in ph for w in ws], dtype=np.int32)
+    bonus = np.ascontiguousarray([b for ph in lists for _, b in ph], dtype=np.float64)
+    return n_ph, ln, words, bonus
+
+
+def bias_compile(phrases, cap_nodes=256):
+    """The phrase automaton of ONE bias list [(words, bonus), ...] (wfst_bias_compile; host only, no device): dict of n_nodes and the
+    nodes' parent (-1: the root), word (0: the root), fail, phrase (index in the list or -1) and beta (float64), nodes in
+    breadth-first order."""
+    _, ln, words, bonus = _flat_phrases([phrases])
+    cap = int(cap_nodes)
+    n = C.c_int32()
+    v = [np.zeros(max(cap, 1), np.int32) for _ in range(4)]
+    beta = np.zeros(max(cap, 1), np.float64)
+    _check(lib().wfst_bias_compile(len(ln), _i32(ln), _i32(words), _f64(bonus), cap, C.byref(n), *([_i32(x) for x in v] + [_f64(beta)])))
+    k = n.value
+    return dict(n_nodes=k, parent=v[0][:k].copy(), word=v[1][:k].copy(), fail=v[2][:k].copy(), phrase=v[3][:k].copy(), beta=beta[:k].copy())
+
+
+class BiasLists:
+    """A set of bias lists resident in HBM, for BatchDecoder.biased_words (wfst_bias_lists)."""
+
+    def __init__(self, handle, n_lists):
+        self.h = handle
+        self.n_lists = int(n_lists)
+
+    @staticmethod
+    def from_phrases(lists, device=0):
+        """lists: [[(words, bonus), ...], ...] -- per list its phrases, each 1..16 word ids (> 0) and a bonus >= 0."""
+        lists = list(lists)
+        n_ph, ln, words, bonus = _flat_phrases(lists)
+        h = C.c_void_p()
+        _check(lib().wfst_bias_lists_create(len(lists), _i32(n_ph), _i32(ln), _i32(words), _f64(bonus), int(device), C.byref(h)))
+        return BiasLists(h, len(lists))
+
+    def info(self):
+        k = self.n_lists
+        n, tp, tn, b = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        v = [np.zeros(k, np.int32) for _ in range(3)]
+        _check(lib().wfst_bias_lists_info(self.h, C.byref(n), C.byref(tp), C.byref(tn), *([_i32(x) for x in v] + [C.byref(b)])))
+        return dict(n_lists=n.value, total_phrases=tp.value, total_nodes=tn.value, n_phrases=v[0], n_nodes=v[1], n_words=v[2],
+                    device_bytes=b.value)
+
+    def free(self):
+        if self.h:
+            lib().wfst_bias_lists_free(self.h)
             self.h = None
 
 
@@ -1267,6 +1327,53 @@ class BatchDecoder:
                 if want_tids:
                     d.update(n_tids=int(nt[i, q]), tids=tids[i, q, :min(int(nt[i, q]), tcap)].copy())
                 row.append(d)
+            out.append(row)
+        return out
+
+    def biased_words(self, lists, list_of=None, settings=((1, 1, 0, 1),), channels=None, use_final_probs=True, cap_words=256, cap_hits=64,
+                     max_cells=0):
+        """Phrase boosting: the best path of the raw lattice again under scales, a word penalty and a bonus for every occurrence of a
+        phrase of the channel's bias list, for a LIST of channels (None: all), live and finalized ones mixed
+        (wfst_decoder_biased_words).  lists = a BiasLists set (None: no channel has a list), list_of[i] = the list of listed channel
+        i (None: list i where the set has one, else none; -1: none), settings = up to 16 quadruples (graph_scale, acoustic_scale,
+        word_penalty, boost_scale) shared by the listed channels.  Per channel a list with one dict per setting: found, n_arcs, n_hyp,
+        hyp_words, begin / end (int32 arrays per word, frames, end exclusive), biased_cost and bonus (float64), tot, lm (float32: the
+        path's own UNSCALED scores), n_hits, hit_phrase / hit_word (int32 arrays: the phrase's index in the list, the index in
+        hyp_words of the occurrence's last word) and status -- WFST_OK or the CHANNEL's own error code.  Bit for bit reproducible.
+        A path with more words or hits than cap_words / cap_hits hold: the call is made once more, with the room needed."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        if list_of is None:
+            k = lists.n_lists if lists is not None else 0
+            list_of = [i if i < k else -1 for i in range(cnt)]
+        lo = np.ascontiguousarray([int(x) for x in list_of], dtype=np.int32)
+        if lo.shape[0] != cnt:
+            raise ValueError("list_of must have one entry per listed channel")
+        st = np.ascontiguousarray(settings, dtype=np.float64).reshape(-1, 4)
+        ns = int(st.shape[0])
+        cap, hcap = int(cap_words), int(cap_hits)
+        for attempt in range(2):
+            status, found, na, begin, end, tot, lm = self._word_results(cnt, max(ns, 1), max(cap, 1))
+            pair = lambda t: np.zeros((cnt, max(ns, 1)), t)
+            nh, nk, cost, bonus = pair(np.int32), pair(np.int32), pair(np.float64), pair(np.float64)
+            hyp = np.zeros((cnt, max(ns, 1), max(cap, 1)), np.int32)
+            hp, hw = np.zeros((cnt, max(ns, 1), max(hcap, 1)), np.int32), np.zeros((cnt, max(ns, 1), max(hcap, 1)), np.int32)
+            _check(lib().wfst_decoder_biased_words(self.h, _i32(ch), cnt, int(bool(use_final_probs)), lists.h if lists is not None else None,
+                                                   _i32(lo), ns, _f64(st), cap, hcap, C.c_int64(int(max_cells)), _i32(status), _i32(found),
+                                                   _i32(na), _i32(nh), _i32(nk), _i32(hyp), _i32(begin), _i32(end), _i32(hp), _i32(hw),
+                                                   _f64(cost), _f64(bonus), _f32(tot), _f32(lm)))
+            if attempt or not (np.any(nh > cap) or np.any(nk > hcap)):
+                break
+            cap, hcap = max(cap, int(nh.max())), max(hcap, int(nk.max()))   # (a path needs more room: once more, with it)
+        out = []
+        for i in range(cnt):
+            row = []
+            for q in range(ns):
+                m, k = min(int(nh[i, q]), cap), min(int(nk[i, q]), hcap)
+                row.append(dict(found=bool(found[i, q]), n_arcs=int(na[i, q]), n_hyp=int(nh[i, q]), hyp_words=hyp[i, q, :m].copy(),
+                                begin=begin[i, q, :m].copy(), end=end[i, q, :m].copy(), biased_cost=float(cost[i, q]),
+                                bonus=float(bonus[i, q]), tot=np.float32(tot[i, q]), lm=np.float32(lm[i, q]), n_hits=int(nk[i, q]),
+                                hit_phrase=hp[i, q, :k].copy(), hit_word=hw[i, q, :k].copy(), status=int(status[i])))
             out.append(row)
         return out
 

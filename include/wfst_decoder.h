@@ -1045,6 +1045,92 @@ int wfst_decoder_rescaled_words(wfst_decoder *d, const int32_t *channels, int32_
                                 int32_t *tids /* [n][n_set][cap_tids], or NULL */,
                                 double *scaled_cost /* [n][n_set] */, float *tot_score, float *lm_score /* [n][n_set] */);
 
+/* ---- phrase boosting: biased best paths of the raw lattice, a list of phrases per channel -----------------------------------------------
+ * Contextual biasing: a caller brings a short list of phrases per stream -- contact names, product names, a meeting's attendees --
+ * and wants the answer to prefer them.  This call picks the best path of a channel's RAW lattice again as
+ * wfst_decoder_rescaled_words does, under a graph scale, an acoustic scale and a word penalty, and with a bonus for every occurrence
+ * of a listed phrase in the path's word sequence: the product of that call's sweep and a phrase automaton (bias_kernel behind
+ * align_index_kernel, one workgroup per (channel, setting)).  It finds only what the lattice holds: a phrase that lattice_beam
+ * pruned away is not brought back, however large its bonus -- the accepted shape of lattice-rescoring biasing.  Keep lattice_beam
+ * wide enough for the bonuses in use.
+ *
+ * A bias list is P >= 0 phrases; phrase p is 1..WFST_BIAS_MAX_WORDS word ids (> 0) with a bonus b_p, a float64 that is finite and
+ * >= 0; no two phrases of one list are equal.  The phrases of a list form a trie of J nodes including the root, J <=
+ * WFST_BIAS_MAX_NODES.  The nodes are numbered in breadth-first order, root 0, ordered by (depth, parent's number, word id)
+ * ascending; the numbering is part of the definition because the tie rule uses it.  str(j) is the word string that leads from the
+ * root to node j.
+ * The automaton: fail(j) is the node of the longest proper suffix of str(j) that is a node (the root for depth 1); delta(i, w) is
+ * the node of the longest suffix of str(i) . w that is a node, the root if none is; own(j) = b_p where str(j) is phrase p, else 0.0;
+ * beta(0) = 0.0 and beta(j) = own(j) + beta(fail(j)), computed in node order in float64 (a list whose beta is not finite is
+ * refused).  So every occurrence of every phrase as a contiguous run of the path's word sequence earns its bonus: overlapping and
+ * nested occurrences each count, and nothing is retracted.
+ *
+ * settings[q] = (graph_scale gs, acoustic_scale as, word_penalty wip, boost_scale bs), n_set = 1..16 of them shared by the listed
+ * channels; gs, as and bs are finite and >= 0, wip is finite.  The lattice R, "no arc", c_q(a) and the + 0.0 are exactly
+ * wfst_decoder_rescaled_words'.  Along a path the node track is j_0 = 0, then j_k = delta(j_{k-1}, olabel(a_k)) on a word arc
+ * (olabel != 0), else j_{k-1}.  An arc costs
+ *   d = c_q(a) - r,   r = bs * beta(j_k) on a word arc and 0.0 otherwise,
+ * the product and the difference each rounded on its own, under the same contraction-off pragma: no fused multiply-add.
+ * The cells: v[0][0] = +0.0; v[t][j] = the minimum over the in-arcs a: s -> t and the source nodes i whose step over a gives j of
+ * (v[s][i] + d) + 0.0; a sum that is not finite is no transition.  Float addition is monotone for costs of either sign and R is a
+ * DAG (every arc goes to a higher state id), so v[t][j] is the minimum over the paths of the sequential float64 sum, whatever the
+ * order of the arc index: the result is bit for bit reproducible.  Totals may be negative.
+ * The end: the pair (final state e, node j) with the least v, then the least graph state, then the least node; found = 0 only if
+ * no final state is reached.  The traceback runs backwards by exact equality, (v[s][i] + d) + 0.0 == v[t][j]; among several
+ * qualifying (arc, source node) the least wfst_decoder_align_words arc tuple wins, then the least source node.  On biglm lattices
+ * two tokens of a frame may share a graph state: a tie that survives the rule is unspecified there.
+ *
+ * Per listed channel i and setting q: found[i][q]; n_arcs; n_hyp and hyp_words[i][q][..]; begin_frame / end_frame by
+ * wfst_decoder_rescaled_words' definitions (the list of wfst_decoder_set_silence_phones included); biased_cost = v[e][j]; bonus =
+ * the float64 sequential sum of r in hop order; tot_score and lm_score UNSCALED, LatticeToVector's, unchanged by the bias; n_hits
+ * with hit_phrase[i][q][..] (the phrase's index in the channel's list) and hit_word[i][q][..] (the index in hyp_words of the
+ * occurrence's last word), ordered by hit_word ascending, then along the chain j, fail(j), ..., so that the longest phrase comes
+ * first.  list_of[i] maps listed channel i to a list of the set, -1 (or list_of NULL) means no list: J = 1, only the root.  With
+ * J = 1, or with bs = 0, biased_cost is bit for bit wfst_decoder_rescaled_words' scaled_cost at (gs, as, wip), and the whole answer
+ * equals it wherever no decision was a tie.
+ *
+ * A failure of ONE channel goes into status[i] and the call still returns WFST_OK: a device error of that channel's utterance, a
+ * table of lattice states x J cells beyond max_cells (WFST_E_CAPACITY, found[i][..] = 0; 0 = 65 536 states x 256), or a path with
+ * n_hyp > cap_words or, where hit_phrase or hit_word is given, n_hits > cap_hits (WFST_E_CAPACITY: the counts are the room needed,
+ * the first entries are written, and everything else of the channel's answers stands).  The call takes 8 bytes per cell; the
+ * workspace is the decoder's, shared with wfst_decoder_align_words and grown on demand; lists of channels whose cells pass 256 MiB
+ * together are taken in rounds.  The call itself fails, before any device work, with WFST_E_ARG (a NULL decoder or channel list,
+ * n_set outside 1..16, NULL settings, a scale that is negative or not finite, a penalty that is not finite, cap_words <= 0,
+ * cap_hits < 0, max_cells < 0, a bad or duplicate channel list, a list_of outside the set or a list where lists is NULL, lists of
+ * another device) or WFST_E_STATE (a decoder without lattice_links, a listed channel never initialised).  Any output pointer may be NULL.
+ * The decoder's state is only read: decoding goes on bit for bit as without the call.  Synchronous, as wfst_decoder_align_words is.
+ *
+ * wfst_bias_compile is host only: from one list's phrases (phrase_words: the phrases' words one after the other) it returns the
+ * nodes' parent (-1: the root), word (0: the root), fail, phrase (index or -1) and beta, so that the automaton can be looked at
+ * without a device; n_nodes is set even where it exceeds cap_nodes or WFST_BIAS_MAX_NODES (WFST_E_CAPACITY both).
+ * wfst_bias_lists_create validates on the host before any device is touched (phrase_len / phrase_bonus: the lists' phrases one
+ * list after the other): a word id <= 0, a length outside 1..16, a bonus that is negative or not finite or a duplicate phrase is
+ * WFST_E_ARG and the message names list and phrase; more than 256 nodes is WFST_E_CAPACITY; no device is WFST_E_DEVICE.
+ * Not computed here: biasing the first-pass search; lists beyond 256 nodes or a sparse table; n-best lists under a bias;
+ * transition-id output; class or subword biasing. */
+#define WFST_BIAS_MAX_NODES 256
+#define WFST_BIAS_MAX_WORDS 16
+#define WFST_BIAS_MAX_SETTINGS 16
+typedef struct wfst_bias_lists wfst_bias_lists;
+int wfst_bias_compile(int32_t n_phrases, const int32_t *phrase_len /* [n_phrases] */, const int32_t *phrase_words,
+                      const double *phrase_bonus /* [n_phrases] */, int32_t cap_nodes, int32_t *n_nodes,
+                      int32_t *parent, int32_t *word, int32_t *fail, int32_t *phrase, double *beta /* [cap_nodes] each, or NULL */);
+int wfst_bias_lists_create(int32_t n_lists, const int32_t *n_phrases /* [n_lists] */, const int32_t *phrase_len,
+                           const int32_t *phrase_words, const double *phrase_bonus, int device, wfst_bias_lists **out);
+int wfst_bias_lists_info(const wfst_bias_lists *b, int32_t *n_lists, int64_t *total_phrases, int64_t *total_nodes,
+                         int32_t *n_phrases, int32_t *n_nodes, int32_t *n_words /* [n_lists] each */, int64_t *device_bytes);
+void wfst_bias_lists_free(wfst_bias_lists *b);
+int wfst_decoder_biased_words(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                              const wfst_bias_lists *lists, const int32_t *list_of /* [n], -1: no list; NULL: none has one */,
+                              int32_t n_set /* 1..16, shared by the listed channels */,
+                              const double *settings /* [n_set][4]: graph_scale, acoustic_scale, word_penalty, boost_scale */,
+                              int32_t cap_words, int32_t cap_hits, int64_t max_cells /* cells of one table; 0 = default */,
+                              int32_t *status /* [n] */, int32_t *found, int32_t *n_arcs, int32_t *n_hyp,
+                              int32_t *n_hits /* [n][n_set] */,
+                              int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame /* [n][n_set][cap_words] */,
+                              int32_t *hit_phrase, int32_t *hit_word /* [n][n_set][cap_hits] */,
+                              double *biased_cost, double *bonus /* [n][n_set] */, float *tot_score, float *lm_score /* [n][n_set] */);
+
 /* ---- forced alignment: exact Viterbi of a channel's scores against the utterance's own graph -----------------------------------------
  * Everything above reads the lattice the search left behind; a transcript that is not in the lattice is not found there.  This call
  * aligns a channel's SCORES against a small graph the caller brings per utterance -- a compiled training graph, a transcript
