@@ -20,11 +20,12 @@ SRCS = [os.path.join(HERE, "csrc", "wfst_kernels.hip"), os.path.join(HERE, "csrc
         os.path.join(HERE, "csrc", "wfst_framepost.hip"), os.path.join(HERE, "csrc", "wfst_capi_framepost.cc"),
         os.path.join(HERE, "csrc", "wfst_rescale.hip"), os.path.join(HERE, "csrc", "wfst_capi_rescale.cc"),
         os.path.join(HERE, "csrc", "wfst_bias.hip"), os.path.join(HERE, "csrc", "wfst_capi_bias.cc"),
+        os.path.join(HERE, "csrc", "wfst_bias_sparse.hip"), os.path.join(HERE, "csrc", "wfst_capi_bias_sparse.cc"),
         os.path.join(HERE, "csrc", "wfst_seqstat.hip"), os.path.join(HERE, "csrc", "wfst_capi_seqstat.cc"),
         os.path.join(HERE, "csrc", "wfst_forced.hip"), os.path.join(HERE, "csrc", "wfst_capi_forced.cc"),
         os.path.join(HERE, "csrc", "wfst_graphpost.hip"), os.path.join(HERE, "csrc", "wfst_capi_graphpost.cc"),
         os.path.join(HERE, "csrc", "wfst_openfst.cc")]
-HDRS = [os.path.join(HERE, "csrc", "wfst_device.h"), os.path.join(HERE, "csrc", "wfst_determinize.h"), os.path.join(HERE, "csrc", "wfst_determinize_wave.h"), os.path.join(HERE, "csrc", "wfst_openfst.h"), os.path.join(HERE, "csrc", "wfst_hip_own.h"), os.path.join(HERE, "csrc", "wfst_capi_words.h"), os.path.join(HERE, "csrc", "wfst_capi_ingest.h"), os.path.join(HERE, "csrc", "wfst_ingest.h"), os.path.join(HERE, "csrc", "wfst_capi_nbwords.h"), os.path.join(HERE, "csrc", "wfst_capi_liveprune.h"), os.path.join(HERE, "csrc", "wfst_capi_align.h"), os.path.join(HERE, "csrc", "wfst_align_index.h"), os.path.join(HERE, "csrc", "wfst_capi_nearest.h"), os.path.join(HERE, "csrc", "wfst_capi_posterior.h"), os.path.join(HERE, "csrc", "wfst_lattice_sweep.h"), os.path.join(HERE, "csrc", "wfst_capi_seqpost.h"), os.path.join(HERE, "csrc", "wfst_capi_altern.h"), os.path.join(HERE, "csrc", "wfst_capi_framepost.h"), os.path.join(HERE, "csrc", "wfst_capi_rescale.h"), os.path.join(HERE, "csrc", "wfst_capi_bias.h"),os.path.join(HERE, "csrc", "wfst_capi_seqstat.h"), os.path.join(HERE, "csrc", "wfst_capi_forced.h"), os.path.join(HERE, "csrc", "wfst_capi_graphpost.h"),
+HDRS = [os.path.join(HERE, "csrc", "wfst_device.h"), os.path.join(HERE, "csrc", "wfst_determinize.h"), os.path.join(HERE, "csrc", "wfst_determinize_wave.h"), os.path.join(HERE, "csrc", "wfst_openfst.h"), os.path.join(HERE, "csrc", "wfst_hip_own.h"), os.path.join(HERE, "csrc", "wfst_capi_words.h"), os.path.join(HERE, "csrc", "wfst_capi_ingest.h"), os.path.join(HERE, "csrc", "wfst_ingest.h"), os.path.join(HERE, "csrc", "wfst_capi_nbwords.h"), os.path.join(HERE, "csrc", "wfst_capi_liveprune.h"), os.path.join(HERE, "csrc", "wfst_capi_align.h"), os.path.join(HERE, "csrc", "wfst_align_index.h"), os.path.join(HERE, "csrc", "wfst_capi_nearest.h"), os.path.join(HERE, "csrc", "wfst_capi_posterior.h"), os.path.join(HERE, "csrc", "wfst_lattice_sweep.h"), os.path.join(HERE, "csrc", "wfst_capi_seqpost.h"), os.path.join(HERE, "csrc", "wfst_capi_altern.h"), os.path.join(HERE, "csrc", "wfst_capi_framepost.h"), os.path.join(HERE, "csrc", "wfst_capi_rescale.h"), os.path.join(HERE, "csrc", "wfst_capi_bias.h"), os.path.join(HERE, "csrc", "wfst_capi_bias_sparse.h"), os.path.join(HERE, "csrc", "wfst_capi_seqstat.h"), os.path.join(HERE, "csrc", "wfst_capi_forced.h"), os.path.join(HERE, "csrc", "wfst_capi_graphpost.h"),
         os.path.join(HERE, "..", "include", "wfst_decoder.h")]
 LIB = os.path.join(HERE, "lib", "libwfstdec.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

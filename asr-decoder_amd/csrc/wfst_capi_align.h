@@ -44,6 +44,10 @@ struct AlignState {
   DevBuf<int64_t> sstat_in;
   // wfst_decoder_biased_words (wfst_capi_bias.h): the bias list of every slot of a round
   DevBuf<int32_t> bias_list;
+  // wfst_decoder_biased_words_sparse (wfst_capi_bias_sparse.h): the slots' reach regions (sets, edges, stage), their places and
+  // sizes, their result words
+  DevBuf<int32_t> reach, reach_head;
+  DevBuf<int64_t> reach_reg;
 };
 
 // what the entry point sees of a decoder (sil_bits: the silence bitmap over transition-ids 1..sil_ntid, nullptr: none)

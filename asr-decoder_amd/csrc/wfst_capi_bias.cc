@@ -13,8 +13,8 @@ using namespace wfst;
 
 namespace wfst {
 
-int bias_compile(const std::string &who, int32_t n_phrases, const int32_t *phrase_len, const int32_t *phrase_words, const double *phrase_bonus,
-                 BiasAutomaton *out, int32_t *n_nodes) {
+int bias_trie(const std::string &who, int32_t n_phrases, const int32_t *phrase_len, const int32_t *phrase_words, const double *phrase_bonus,
+              int32_t max_nodes, const char *holder, BiasAutomaton *out, int32_t *n_nodes) {
   if (n_nodes) *n_nodes = 0;
   if (n_phrases < 0 || (n_phrases > 0 && (!phrase_len || !phrase_words || !phrase_bonus))) return capi_fail(WFST_E_ARG, who + "n_phrases < 0 or NULL arrays");
   // ---- the phrases, and their trie in the order they came ------------------------------------------------------------------------
@@ -47,8 +47,8 @@ int bias_compile(const std::string &who, int32_t n_phrases, const int32_t *phras
   }
   const int32_t J = (int32_t)tmp.size();
   if (n_nodes) *n_nodes = J;
-  if (J > kBiasMaxNodes)
-    return capi_fail(WFST_E_CAPACITY, who + "its phrases take " + std::to_string(J) + " nodes, a list holds " + std::to_string(kBiasMaxNodes));
+  if (J > max_nodes)
+    return capi_fail(WFST_E_CAPACITY, who + "its phrases take " + std::to_string(J) + " nodes, a " + holder + " holds " + std::to_string(max_nodes));
   // ---- breadth first: by depth, then the parent's number, then the word ---------------------------------------------------------------
   std::vector<int32_t> num((size_t)J, 0), order(1, 0);
   for (int32_t depth = 1; depth <= kBiasMaxWords; ++depth) {
@@ -74,6 +74,9 @@ int bias_compile(const std::string &who, int32_t n_phrases, const int32_t *phras
     own[(size_t)j] = own_tmp[(size_t)order[(size_t)j]];
     if (j) child[{M.parent[(size_t)j], T.word}] = j;
   }
+  // (breadth first by (depth, parent's number, word): a node's children are consecutive numbers, their words ascending)
+  M.first_child.assign((size_t)J, 0); M.n_child.assign((size_t)J, 0);
+  for (int32_t j = J - 1; j >= 1; --j) { M.first_child[(size_t)M.parent[(size_t)j]] = j; ++M.n_child[(size_t)M.parent[(size_t)j]]; }
   // ---- fail, delta, beta: a node's failure link is shallower than the node, so it is numbered, and finished, before it -------------------
   auto delta = [&](int32_t i, int32_t w) {
     for (;;) {
@@ -91,6 +94,24 @@ int bias_compile(const std::string &who, int32_t n_phrases, const int32_t *phras
   }
   std::set<int32_t> ws(M.word.begin() + 1, M.word.end());
   M.words.assign(ws.begin(), ws.end());
+  return WFST_OK;
+}
+
+int bias_compile(const std::string &who, int32_t n_phrases, const int32_t *phrase_len, const int32_t *phrase_words, const double *phrase_bonus,
+                 BiasAutomaton *out, int32_t *n_nodes) {
+  const int rc = bias_trie(who, n_phrases, phrase_len, phrase_words, phrase_bonus, kBiasMaxNodes, "list", out, n_nodes);
+  if (rc != WFST_OK) return rc;
+  BiasAutomaton &M = *out;
+  const int32_t J = M.nodes();
+  // ---- delta as a byte table, and per node the nodes it is reached from over its own word ------------------------------------------------
+  auto delta = [&](int32_t i, int32_t w) {
+    for (;;) {
+      for (int32_t c = M.first_child[(size_t)i]; c < M.first_child[(size_t)i] + M.n_child[(size_t)i]; ++c)
+        if (M.word[(size_t)c] == w) return c;
+      if (i == 0) return (int32_t)0;
+      i = M.fail[(size_t)i];
+    }
+  };
   const size_t W = M.words.size();
   M.table.assign((size_t)J * W, 0);
   for (int32_t i = 0; i < J; ++i)
@@ -101,6 +122,19 @@ int bias_compile(const std::string &who, int32_t n_phrases, const int32_t *phras
     for (int32_t i = 0; i < J; ++i)
       if (M.table[(size_t)i * W + k] == j) M.pred.push_back(i);
     M.pred_off[(size_t)j + 1] = (int32_t)M.pred.size();
+  }
+  return WFST_OK;
+}
+
+int bias_check_settings(int32_t n_set, const double *settings) {
+  if (n_set < 1 || n_set > kBiasMaxSettings) return capi_fail(WFST_E_ARG, "1 <= n_set <= 16 settings");
+  if (!settings) return capi_fail(WFST_E_ARG, "NULL settings");
+  for (int32_t q = 0; q < n_set; ++q) {
+    const double gs = settings[4 * q], as = settings[4 * q + 1], wip = settings[4 * q + 2], bs = settings[4 * q + 3];
+    if (!std::isfinite(gs) || !std::isfinite(as) || gs < 0.0 || as < 0.0)
+      return capi_fail(WFST_E_ARG, "graph_scale / acoustic_scale must be finite and >= 0");
+    if (!std::isfinite(wip)) return capi_fail(WFST_E_ARG, "word_penalty must be finite");
+    if (!std::isfinite(bs) || bs < 0.0) return capi_fail(WFST_E_ARG, "boost_scale must be finite and >= 0");
   }
   return WFST_OK;
 }
@@ -116,28 +150,22 @@ int upload(DevBuf<T> &buf, const std::vector<T> &v) {
 }
 
 struct BiasQuery : WordQuery {
-  size_t np, cap, hcap;   // pairs of the whole call; the caller's rows of words and of hits
+  BiasOutputs O;
   BiasSet set;
   const wfst_bias_lists *lists;
   const int32_t *list_of;   // the caller's [n]
   std::vector<int32_t> h_list;   // a round's upload, alive until the driver has synchronised
-  int32_t *found, *n_arcs, *n_hyp, *n_hits, *hyp_words, *begin_frame, *end_frame, *hit_phrase, *hit_word;
-  double *biased_cost, *bonus;
-  float *tot_score, *lm_score;
-  BiasQuery(size_t np_, int32_t cap_words, int32_t cap_hits) : np(np_), cap((size_t)cap_words), hcap((size_t)cap_hits) {
+  BiasQuery(size_t np, int32_t cap_words, int32_t cap_hits) {
+    O.np = np; O.cap = (size_t)cap_words; O.hcap = (size_t)cap_hits;
     name = "bias"; item = "setting"; abbr = "set";
     default_cells = kBiasDefaultCells; round_cells = kBiasRoundCells;
     cell_words = 2;
-    pair_ints = (size_t)bias_out_ints((int64_t)cap, (int64_t)hcap);
+    pair_ints = (size_t)bias_out_ints((int64_t)O.cap, (int64_t)O.hcap);
     invariant = "a traced path that does not reproduce its cell";
     table_cols = "nodes";
   }
   std::string workspace_note(const WordRound &) const override { return " of 8 bytes"; }
-  void clear() override {
-    align_zero(found, np); align_zero(n_arcs, np); align_zero(n_hyp, np); align_zero(n_hits, np); align_zero(hyp_words, np * cap);
-    align_zero(begin_frame, np * cap); align_zero(end_frame, np * cap); align_zero(hit_phrase, np * hcap); align_zero(hit_word, np * hcap);
-    align_zero(biased_cost, np); align_zero(bonus, np); align_zero(tot_score, np); align_zero(lm_score, np);
-  }
+  void clear() override { O.clear(); }
   int launch(WordRound &R) override {
     const AlignView &V = *R.V;
     AlignState &S = *V.as;
@@ -161,8 +189,8 @@ struct BiasQuery : WordQuery {
     Q.path = S.path.p;
     Q.path_cap = R.A.ns_cap;
     Q.n_set = R.n_seqs;
-    Q.cap_words = (int32_t)cap;
-    Q.cap_hits = (int32_t)hcap;
+    Q.cap_words = (int32_t)O.cap;
+    Q.cap_hits = (int32_t)O.hcap;
     Q.sil_bits = V.sil_bits;
     Q.n_tid = V.sil_ntid;
     Q.out = S.out.p;
@@ -174,32 +202,10 @@ struct BiasQuery : WordQuery {
   }
   int unpack(const WordRound &R, size_t j, size_t o, int32_t channel) override {
     const size_t ns = (size_t)R.n_seqs;
-    const bool want_hits = hit_phrase || hit_word;
     int code = WFST_OK;
     for (size_t q = 0; q < ns; ++q) {
       const int32_t *r = R.landed + (j * ns + q) * pair_ints;
-      if (!r[0]) continue;
-      const size_t p = o * ns + q;
-      const size_t nh = std::min((size_t)r[5], cap), nk = std::min((size_t)r[6], hcap);
-      if (found) found[p] = 1;
-      if (n_arcs) n_arcs[p] = r[1];
-      if (tot_score) memcpy(&tot_score[p], &r[2], 4);
-      if (lm_score) memcpy(&lm_score[p], &r[3], 4);
-      if (n_hyp) n_hyp[p] = r[5];
-      if (n_hits) n_hits[p] = r[6];
-      if (biased_cost) memcpy(&biased_cost[p], &r[8], 8);
-      if (bonus) memcpy(&bonus[p], &r[10], 8);
-      if (hyp_words) memcpy(hyp_words + p * cap, r + kBiasHead, nh * 4);
-      if (begin_frame) memcpy(begin_frame + p * cap, r + kBiasHead + cap, nh * 4);
-      if (end_frame) memcpy(end_frame + p * cap, r + kBiasHead + 2 * cap, nh * 4);
-      if (hit_phrase) memcpy(hit_phrase + p * hcap, r + kBiasHead + 3 * cap, nk * 4);
-      if (hit_word) memcpy(hit_word + p * hcap, r + kBiasHead + 3 * cap + hcap, nk * 4);
-      // the path has more words or hits than the caller made room for: everything else of the answer stands, the counts are the
-      // room it takes
-      if (((size_t)r[5] > cap || (want_hits && (size_t)r[6] > hcap)) && code == WFST_OK)
-        code = capi_fail(WFST_E_CAPACITY, "channel " + std::to_string(channel) + ": bias: a path of " + std::to_string(r[5]) + " words and " +
-                                              std::to_string(r[6]) + " hits, cap_words is " + std::to_string(cap) + " and cap_hits " +
-                                              std::to_string(hcap));
+      if (r[0]) code = O.take(r, o * ns + q, channel, code);
     }
     return code;
   }
@@ -306,15 +312,8 @@ int wfst_decoder_biased_words(wfst_decoder *d, const int32_t *channels, int32_t 
                               int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame, int32_t *hit_phrase, int32_t *hit_word,
                               double *biased_cost, double *bonus, float *tot_score, float *lm_score) {
   if (!d || !channels) return capi_fail(WFST_E_ARG, "NULL decoder / channel list");
-  if (n_set < 1 || n_set > kBiasMaxSettings) return capi_fail(WFST_E_ARG, "1 <= n_set <= 16 settings");
-  if (!settings) return capi_fail(WFST_E_ARG, "NULL settings");
-  for (int32_t q = 0; q < n_set; ++q) {
-    const double gs = settings[4 * q], as = settings[4 * q + 1], wip = settings[4 * q + 2], bs = settings[4 * q + 3];
-    if (!std::isfinite(gs) || !std::isfinite(as) || gs < 0.0 || as < 0.0)
-      return capi_fail(WFST_E_ARG, "graph_scale / acoustic_scale must be finite and >= 0");
-    if (!std::isfinite(wip)) return capi_fail(WFST_E_ARG, "word_penalty must be finite");
-    if (!std::isfinite(bs) || bs < 0.0) return capi_fail(WFST_E_ARG, "boost_scale must be finite and >= 0");
-  }
+  const int bad = bias_check_settings(n_set, settings);
+  if (bad != WFST_OK) return bad;
   if (cap_words <= 0) return capi_fail(WFST_E_ARG, "cap_words <= 0");
   if (cap_hits < 0) return capi_fail(WFST_E_ARG, "cap_hits < 0");
   if (max_cells < 0) return capi_fail(WFST_E_ARG, "max_cells < 0");
@@ -337,9 +336,9 @@ int wfst_decoder_biased_words(wfst_decoder *d, const int32_t *channels, int32_t 
   q.set = BiasSet{};
   std::copy(settings, settings + 4 * ns, q.set.v);
   q.lists = lists; q.list_of = list_of;
-  q.found = found; q.n_arcs = n_arcs; q.n_hyp = n_hyp; q.n_hits = n_hits; q.hyp_words = hyp_words; q.begin_frame = begin_frame;
-  q.end_frame = end_frame; q.hit_phrase = hit_phrase; q.hit_word = hit_word; q.biased_cost = biased_cost; q.bonus = bonus;
-  q.tot_score = tot_score; q.lm_score = lm_score;
+  q.O.found = found; q.O.n_arcs = n_arcs; q.O.n_hyp = n_hyp; q.O.n_hits = n_hits; q.O.hyp_words = hyp_words; q.O.begin_frame = begin_frame;
+  q.O.end_frame = end_frame; q.O.hit_phrase = hit_phrase; q.O.hit_word = hit_word; q.O.biased_cost = biased_cost; q.O.bonus = bonus;
+  q.O.tot_score = tot_score; q.O.lm_score = lm_score;
   // per (channel, setting) one sequence as long as the channel's list has nodes beyond the root: a table of states x nodes cells
   const std::vector<int32_t> ones(N * ns * (size_t)most, 1);
   return word_query_run(q, d, channels, n, use_final_probs, n_set, most, ones.data(), len.data(), max_cells, status);

@@ -751,6 +751,59 @@ struct BiasDev {
 constexpr int64_t bias_out_ints(int64_t cap_words, int64_t cap_hits) { return kBiasHead + 3 * cap_words + 2 * cap_hits; }
 void launch_bias(const AlignDev &A, const BiasDev &Q, const BiasSet &S, const int32_t *chan_list_dev, int cnt, hipStream_t s);
 
+// ---- phrase boosting for large lists: sparse cells over reachable nodes (wfst_bias_sparse.hip) ------------------------------------------
+// bias_kernel's sweep restricted to the cells (lattice state t, node j) with j in R(t), the nodes a path into t can be in.
+// bias_reach_kernel, one workgroup per slot, builds R and the product graph's edges once per call; bias_sparse_kernel, one workgroup
+// per (slot, setting), sweeps the cells and never evaluates the automaton's delta except to check its own traced path.  A book of a
+// wfst_bias_books set, all offsets into the set's concatenated arrays (no byte table, no predecessor lists):
+//   hdr[l][kBookHdr]     {nodes J, distinct words W, offset of its ints, of its beta, phrases, 0, 0, 0}
+//   ints[]               per book: word[J], fail[J], phrase[J], first_child[J], n_child[J], words[W].  Breadth-first numbering makes a
+//                        node's children consecutive numbers in ascending word order: goto(i, w) is a binary search of
+//                        word[first_child[i] .. first_child[i] + n_child[i])
+// A slot's region of BiasReachDev::ints, at reg[4 slot] ints, cell_cap = reg[4 slot + 1], edge_cap = reg[4 slot + 2] (0: skip the slot):
+//   roff[ns_cap + 1]     the cells of state t are roff[t] .. roff[t + 1], in (state, node) order
+//   ncnt[ns_cap]         a round's new set sizes
+//   eoff[na_cap + 1]     the edges of in-arc record a are eoff[a] .. eoff[a + 1]: one per cell of the arc's source state (none for
+//                        an arc that is no arc)
+//   rnode[cell_cap], rstate[cell_cap]   a cell's node and state
+//   edge[edge_cap]       the local index in R(destination) of the cell the transition reaches
+//   stage[edge_cap + ns_cap]   a frame's sorted sets before they are packed
+//   head[slot][kReachHead]     {status (0, kAln* or kReach*), cells, edges, the largest |R(t)|, 0, 0, 0, 0}
+constexpr int32_t kBookHdr = 8;
+constexpr int32_t kReachHead = 8;
+constexpr int32_t kBiasBookMaxNodes = 65536;   // = WFST_BIAS_BOOK_MAX_NODES
+constexpr int32_t kReachOverCells = 6, kReachOverEdges = 7, kReachSkipped = 8;   // beside kAln*: a region is too small; not run
+struct BiasBooksDev {
+  const int32_t *hdr, *ints;
+  const double *beta;
+};
+struct BiasReachDev {
+  BiasBooksDev B;
+  const int32_t *book_of;     // [cnt], -1: no book (J = 1)
+  int32_t *ints;
+  const int64_t *reg;         // [cnt][4]
+  int32_t *head;              // [cnt][kReachHead]
+};
+inline int64_t bias_reach_ints(int64_t ns_cap, int64_t na_cap, int64_t cell_cap, int64_t edge_cap) {
+  return (ns_cap + 1) + ns_cap + (na_cap + 1) + 2 * cell_cap + 2 * edge_cap + ns_cap;
+}
+struct BiasSparseDev {
+  BiasReachDev R;
+  const int32_t *slot_of;     // [cnt of the round]: the slot of the index and of the regions
+  const int4 *lat_toks;
+  int64_t lat_tok_cap;
+  const int64_t *cell_off;    // [cnt of the round][n_set], in cells
+  double *cells;
+  int32_t *path;              // [pair][2 path_cap]: the in-arc records of the traced path, last arc first, then the nodes they reach
+  int32_t path_cap;
+  int32_t n_set, cap_words, cap_hits;
+  const uint32_t *sil_bits;
+  int32_t n_tid;
+  int32_t *out;               // [pair][bias_out_ints]: bias_kernel's layout
+};
+void launch_bias_reach(const AlignDev &A, const BiasReachDev &Q, int cnt, hipStream_t s);
+void launch_bias_sparse(const AlignDev &A, const BiasSparseDev &Q, const BiasSet &S, const int32_t *chan_list_dev, int cnt, hipStream_t s);
+
 // ---- forced alignment against per-utterance graphs (wfst_forced.hip) -----------------------------------------------------------
 // Exact float32 Viterbi of a listed channel's scores against one small graph of a wfst_align_graphs set (include/wfst_decoder.h,
 // wfst_decoder_force_align).  forced_align_kernel runs one workgroup per list entry.  A graph of the set, all offsets into the set's

@@ -105,6 +105,9 @@
 //                  "KEY bias q gs=.. as=.. wip=.. bs=.. found=0|1 cost=.. bonus=.. tot=.. lm=.. hits=phrase@word,... : word(begin,end) ..."
 //                  -- cost and bonus float64 at 17 digits, phrase the phrase's index in the utterance's list, word the index of the
 //                  occurrence's last word.  The other output is what it is without the flag.
+//   --bias-sparse  with --bias=FILE: the lines come from BiasedWordsSparse (wfst_decoder_biased_words_sparse: the cells a path can
+//                  reach, lists of up to 65 536 nodes) whatever the lists' sizes -- the same lines, byte for byte.  Without the flag
+//                  that call is taken only where a list of FILE has more than 256 nodes, which BiasedWords refuses.
 //   --nearest-words=FILE  batch shape and --single-stream: FILE has --align-words' format, its lines being references (transcripts
 //                  that need not be in the lattice); after the utterance's lines, per reference the lattice path nearest it
 //                  (NearestWords: wfst_decoder_nearest_words) as "KEY nearest q err=E cor=C sub=S ins=I del=D arcs=N tot=.. lm=.."
@@ -295,7 +298,7 @@ int main(int argc, char **argv) {
     bool rescale_bad = false;
     std::string bias_file;                     // --bias
     std::vector<BiasSetting> bias_set;         // --bias-settings
-    bool bias_given = false, bias_set_given = false, bias_bad = false;
+    bool bias_given = false, bias_set_given = false, bias_bad = false, bias_sparse = false;
     bool word_conf = false, sent_post = false;
     int word_alts = 0;   // --word-alternatives[=K]: K, 0 = off
     double conf_gs = 1.0, conf_as = 1.0;
@@ -430,6 +433,7 @@ int main(int argc, char **argv) {
         }
       }
       else if (a.compare(0, 7, "--bias=") == 0) { bias_file = a.substr(7); bias_given = true; }
+      else if (a == "--bias-sparse") bias_sparse = true;
       else if (a.compare(0, 16, "--bias-settings=") == 0) {
         // GS,AS,WIP,BS[:GS,AS,WIP,BS...]: every number whole, the scales finite and >= 0, the penalty finite
         bias_set_given = true;
@@ -477,7 +481,7 @@ int main(int argc, char **argv) {
       else pos.push_back(a);
     }
     if (pos.size() < 3) {
-      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--bias=FILE [--bias-settings=GS,AS,WIP,BS[:GS,AS,WIP,BS...]]] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--graph-post=DIR [--graph-post-class=tid|pdf|phone] [--graph-post-scales=GS,AS] [--graph-post-out=FILE]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
+      std::cerr << "usage: wfst-decode [--tid2pdf=FILE] [--batch=N] [--single-stream [--chunk=N [--partial-words] [--partial-nbest=K [--live-lattice-prune]]]] [--word-times [--silence-phones=a:b:c]] [--nbest-word-times] [--align-words=FILE] [--word-confidence[=GS,AS]] [--sentence-posterior] [--phrase-posterior=FILE] [--word-alternatives[=K]] [--nearest-words=FILE] [--frame-post=FILE [--frame-post-class=tid|pdf|phone] [--frame-post-scales=GS,AS] [--frame-post-min=X]] [--rescale=GS,AS,WIP[:GS,AS,WIP...]] [--bias=FILE [--bias-settings=GS,AS,WIP,BS[:GS,AS,WIP,BS...]]] [--bias-sparse] [--force-align=DIR [--force-align-class=tid|pdf|phone]] [--graph-post=DIR [--graph-post-class=tid|pdf|phone] [--graph-post-scales=GS,AS] [--graph-post-out=FILE]] [--seq-stats=FILE --seq-ref=FILE [--seq-criterion=smbr|mmi] [--seq-class=tid|pdf|phone] [--seq-scales=GS,AS] [--seq-silence=a:b:c] [--seq-drop-frames]] [--inflight=K] [--devices=a,b,...] [--nbest=N] [--lattice-out=FILE] [--determinize] "
                    "[--lattice-text=FILE] [--lattice-links=N] [--lm-old=FILE --lm-new=FILE] [--second-lm-old=FILE --second-lm-new=FILE] [--nbest-lattice-out=FILE] "
                    "[--tid2phone=FILE --endpoint.silence-phones=a:b:c [--endpoint.*=..] [--print-endpoints]] "
                    "[--device-chunks --chunk=N [--acoustic-scale=S] [--log-priors=FILE] [--score-dtype=f32|f16|bf16]] CONFIG GRAPH LOGLIKES [WORDS_OUT]\n";
@@ -519,6 +523,7 @@ int main(int argc, char **argv) {
     const bool rescale = !rescale_set.empty();
     if (rescale && n_threads > 0) { std::cerr << "--rescale goes with the batch shape or --single-stream\n"; return 1; }
     if (bias_set_given && !bias_given) { std::cerr << "--bias-settings goes with --bias=FILE\n"; return 1; }
+    if (bias_sparse && !bias_given) { std::cerr << "--bias-sparse goes with --bias=FILE\n"; return 1; }
     if (bias_given && bias_file.empty()) { std::cerr << "--bias=FILE: the file of the phrases, lines KEY bonus w1 w2 ...\n"; return 1; }
     if (bias_bad) { std::cerr << "--bias-settings=GS,AS,WIP,BS[:GS,AS,WIP,BS...]: per setting two finite scales >= 0, a finite word penalty and a finite boost scale >= 0\n"; return 1; }
     if (bias_set.size() > 16) { std::cerr << "--bias-settings: more than 16 settings\n"; return 1; }
@@ -579,6 +584,18 @@ int main(int argc, char **argv) {
         }
         bias_phrases[key].push_back(ph);
       }
+    }
+    // a list of more than 256 nodes is a book: the whole run then goes through BiasedWordsSparse (the node count is host work)
+    for (auto it = bias_phrases.begin(); it != bias_phrases.end() && !bias_sparse; ++it) {
+      std::vector<BiasPhrase> list;
+      if (it->first != "*" && bias_phrases.count("*")) list = bias_phrases["*"];
+      list.insert(list.end(), it->second.begin(), it->second.end());
+      std::vector<int32_t> len, words;
+      std::vector<double> bonus;
+      for (const BiasPhrase &ph : list) { len.push_back((int32_t)ph.words.size()); words.insert(words.end(), ph.words.begin(), ph.words.end()); bonus.push_back(ph.bonus); }
+      int32_t nodes = 0;
+      (void)wfst_bias_book_compile((int32_t)len.size(), len.data(), words.data(), bonus.data(), WFST_BIAS_BOOK_MAX_NODES, &nodes, nullptr, nullptr, nullptr, nullptr, nullptr);
+      bias_sparse = nodes > WFST_BIAS_MAX_NODES;
     }
     auto bias_list_of = [&](const Utt &u) {
       std::vector<BiasPhrase> list;
@@ -1355,9 +1372,12 @@ int main(int argc, char **argv) {
         if (bias) {
           const std::vector<BiasPhrase> list = bias_list_of(u);
           BiasLists bl;
-          if (!list.empty() && !bl.Set(std::vector<std::vector<BiasPhrase> >(1, list), devices[0])) throw std::runtime_error("--bias: the phrases of " + u.key + " make no list");
+          BiasBooks bk;
+          const std::vector<std::vector<BiasPhrase> > one(1, list);
+          if (!list.empty() && !(bias_sparse ? bk.Set(one, devices[0]) : bl.Set(one, devices[0]))) throw std::runtime_error("--bias: the phrases of " + u.key + " make no list");
           std::vector<BiasedWords> bw;
-          decode.BiasedWords(bl, list.empty() ? -1 : 0, bias_set, &bw);
+          if (bias_sparse) decode.BiasedWordsSparse(bk, list.empty() ? -1 : 0, bias_set, &bw);
+          else decode.BiasedWords(bl, list.empty() ? -1 : 0, bias_set, &bw);
           emit_bias(u, bw);
         }
         if (force_align) {
@@ -1545,8 +1565,11 @@ int main(int argc, char **argv) {
                 lists.push_back(list);
               }
               BiasLists bl;
-              if (!lists.empty() && !bl.Set(lists, devices[(size_t)di])) throw std::runtime_error("--bias: the phrases of " + bias_file + " make no lists");
-              decode.BiasedWords(ch, bl, list_of, bias_set, true, &o.biased);
+              BiasBooks bk;
+              if (!lists.empty() && !(bias_sparse ? bk.Set(lists, devices[(size_t)di]) : bl.Set(lists, devices[(size_t)di])))
+                throw std::runtime_error("--bias: the phrases of " + bias_file + " make no lists");
+              if (bias_sparse) decode.BiasedWordsSparse(ch, bk, list_of, bias_set, true, &o.biased);
+              else decode.BiasedWords(ch, bl, list_of, bias_set, true, &o.biased);
             }
             if (seq_stats) {                                                                                 // every channel in one call
               std::vector<std::vector<int> > refs(n);

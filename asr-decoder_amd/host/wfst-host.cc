@@ -32,6 +32,9 @@
 #pragma weak wfst_bias_lists_create
 #pragma weak wfst_bias_lists_free
 #pragma weak wfst_decoder_biased_words
+#pragma weak wfst_bias_books_create
+#pragma weak wfst_bias_books_free
+#pragma weak wfst_decoder_biased_words_sparse
 #pragma weak wfst_decoder_sequence_stats
 #pragma weak wfst_decoder_force_align
 #pragma weak wfst_align_graphs_load
@@ -2545,14 +2548,44 @@ bool BiasLists::Set(const std::vector<std::vector<BiasPhrase> > &lists, int devi
   return true;
 }
 
-// One C-ABI call for `ch`: (*out)[i][q] for settings[q], (*status)[i] the channel's own code.  Returns the call's own code.  A path
-// with more words or hits than the first call made room for is asked for again, once, with the room needed.
-static int BiasedWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const BiasLists &lists, const std::vector<int> &list_of,
-                           const std::vector<BiasSetting> &settings, bool use_final_probs, long long max_cells,
-                           std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status) {
-  if (!wfst_decoder_biased_words) throw std::runtime_error("BiasedWords: this build's device library has no wfst_decoder_biased_words");
+BiasBooks::~BiasBooks() {
+  if (_b && wfst_bias_books_free) wfst_bias_books_free(_b);
+}
+
+bool BiasBooks::Set(const std::vector<std::vector<BiasPhrase> > &books, int device) {
+  if (!wfst_bias_books_create) throw std::runtime_error("BiasBooks: this build's device library has no wfst_bias_books_create");
+  if (_b) { wfst_bias_books_free(_b); _b = nullptr; _n = 0; }
+  std::vector<int32_t> n_phrases, len, words;
+  std::vector<double> bonus;
+  for (const std::vector<BiasPhrase> &book : books) {
+    n_phrases.push_back((int32_t)book.size());
+    for (const BiasPhrase &p : book) {
+      len.push_back((int32_t)p.words.size());
+      words.insert(words.end(), p.words.begin(), p.words.end());
+      bonus.push_back(p.bonus);
+    }
+  }
+  if (wfst_bias_books_create((int32_t)books.size(), n_phrases.data(), len.data(), words.data(), bonus.data(), device, &_b) != WFST_OK) {
+    Warn(std::string("BiasBooks: ") + wfst_last_error());
+    _b = nullptr;
+    return false;
+  }
+  _n = (int)books.size();
+  return true;
+}
+
+// One C-ABI call for `ch` -- wfst_decoder_biased_words with `lists`, or wfst_decoder_biased_words_sparse with `books` where that is
+// given: (*out)[i][q] for settings[q], (*status)[i] the channel's own code.  Returns the call's own code.  A path with more words or
+// hits than the first call made room for is asked for again, once, with the room needed.
+static int BiasedWordsCore(wfst_decoder *dec, const std::vector<int32_t> &ch, const wfst_bias_lists *lists, const wfst_bias_books *books, bool sparse,
+                           const std::vector<int> &list_of, const std::vector<BiasSetting> &settings, bool use_final_probs, long long max_cells,
+                           long long round_cells, std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status) {
+  if (!sparse && !wfst_decoder_biased_words) throw std::runtime_error("BiasedWords: this build's device library has no wfst_decoder_biased_words");
+  if (sparse && !wfst_decoder_biased_words_sparse)
+    throw std::runtime_error("BiasedWordsSparse: this build's device library has no wfst_decoder_biased_words_sparse");
   const size_t cnt = ch.size(), ns = settings.size(), np = cnt * ns;
   if (!list_of.empty() && list_of.size() != cnt) throw std::runtime_error("BiasedWords: one list per listed channel");
+  std::vector<int64_t> cells(cnt, 0);
   std::vector<int32_t> lo(list_of.begin(), list_of.end());
   std::vector<double> set;
   for (const BiasSetting &s : settings) { set.push_back(s.graph_scale); set.push_back(s.acoustic_scale); set.push_back(s.word_penalty); set.push_back(s.boost_scale); }
@@ -2562,10 +2595,15 @@ static int BiasedWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, co
   std::vector<float> t(np), l(np);
   for (int pass = 0;; ++pass) {
     hyp.assign(np * cap, 0); b.assign(np * cap, 0); e.assign(np * cap, 0); hp.assign(np * hcap, 0); hw.assign(np * hcap, 0);
-    const int rc = wfst_decoder_biased_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, lists.Handle(), lo.empty() ? nullptr : lo.data(),
-                                             (int32_t)ns, set.data(), (int32_t)cap, (int32_t)hcap, max_cells, st.data(), found.data(), na.data(),
-                                             nh.data(), nk.data(), hyp.data(), b.data(), e.data(), hp.data(), hw.data(), cost.data(), bonus.data(),
-                                             t.data(), l.data());
+    const int rc = sparse
+        ? wfst_decoder_biased_words_sparse(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, books, lo.empty() ? nullptr : lo.data(), (int32_t)ns,
+                                           set.data(), (int32_t)cap, (int32_t)hcap, max_cells, round_cells, st.data(), cells.data(), found.data(),
+                                           na.data(), nh.data(), nk.data(), hyp.data(), b.data(), e.data(), hp.data(), hw.data(), cost.data(),
+                                           bonus.data(), t.data(), l.data())
+        : wfst_decoder_biased_words(dec, ch.data(), (int32_t)cnt, use_final_probs ? 1 : 0, lists, lo.empty() ? nullptr : lo.data(),
+                                    (int32_t)ns, set.data(), (int32_t)cap, (int32_t)hcap, max_cells, st.data(), found.data(), na.data(),
+                                    nh.data(), nk.data(), hyp.data(), b.data(), e.data(), hp.data(), hw.data(), cost.data(), bonus.data(),
+                                    t.data(), l.data());
     if (rc != WFST_OK) return rc;
     const size_t most = np ? (size_t)*std::max_element(nh.begin(), nh.end()) : 0;
     const size_t most_k = np ? (size_t)*std::max_element(nk.begin(), nk.end()) : 0;
@@ -2579,6 +2617,7 @@ static int BiasedWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, co
       struct BiasedWords &a = (*out)[i][q];
       const size_t p = i * ns + q;
       a.found = found[p] != 0;
+      a.n_cells = (long long)cells[i];
       if (!a.found) continue;
       a.n_arcs = na[p]; a.biased_cost = cost[p]; a.bonus = bonus[p]; a.tot = t[p]; a.lm = l[p];
       for (size_t j = 0; j < std::min((size_t)nh[p], cap); ++j) {
@@ -2589,6 +2628,17 @@ static int BiasedWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, co
     }
   status->assign(st.begin(), st.end());
   return WFST_OK;
+}
+
+static int BiasedWordsCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const BiasLists &lists, const std::vector<int> &list_of,
+                           const std::vector<BiasSetting> &settings, bool use_final_probs, long long max_cells,
+                           std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status) {
+  return BiasedWordsCore(dec, ch, lists.Handle(), nullptr, false, list_of, settings, use_final_probs, max_cells, 0, out, status);
+}
+static int BiasedWordsSparseCall(wfst_decoder *dec, const std::vector<int32_t> &ch, const BiasBooks &books, const std::vector<int> &book_of,
+                                 const std::vector<BiasSetting> &settings, bool use_final_probs, long long max_cells, long long round_cells,
+                                 std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status) {
+  return BiasedWordsCore(dec, ch, nullptr, books.Handle(), true, book_of, settings, use_final_probs, max_cells, round_cells, out, status);
 }
 
 void GpuBatchDecoder::BiasedWords(const std::vector<int> &channels, const BiasLists &lists, const std::vector<int> &list_of,
@@ -2610,6 +2660,29 @@ void GpuLatticeDecoder::BiasedWords(const BiasLists &lists, int list, const std:
     if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
   });
   if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("BiasedWords: " + msg);
+  if (out) out->swap(o[0]);
+}
+
+void GpuBatchDecoder::BiasedWordsSparse(const std::vector<int> &channels, const BiasBooks &books, const std::vector<int> &book_of,
+                                        const std::vector<BiasSetting> &settings, bool use_final_probs,
+                                        std::vector<std::vector<struct BiasedWords> > *out, std::vector<int> *status, long long max_cells,
+                                        long long round_cells) {
+  BatchWordQuery("BiasedWordsSparse", channels, _n, out, status, [&](const auto &ch, auto *o, auto *st) {
+    return BiasedWordsSparseCall(_dec, ch, books, book_of, settings, use_final_probs, max_cells, round_cells, o, st);
+  });
+}
+
+void GpuLatticeDecoder::BiasedWordsSparse(const BiasBooks &books, int book, const std::vector<BiasSetting> &settings,
+                                          std::vector<struct BiasedWords> *out, bool use_final_probs) {
+  std::vector<std::vector<struct BiasedWords> > o;
+  std::vector<int> st;
+  int rc = WFST_OK;
+  std::string msg;
+  OnDevice([&] {
+    rc = BiasedWordsSparseCall(_dec, std::vector<int32_t>(1, _chan), books, std::vector<int>(1, book), settings, use_final_probs, 0, 0, &o, &st);
+    if (rc != WFST_OK || st[0] != WFST_OK) msg = wfst_last_error();
+  });
+  if (rc != WFST_OK || st[0] != WFST_OK) throw std::runtime_error("BiasedWordsSparse: " + msg);
   if (out) out->swap(o[0]);
 }
 

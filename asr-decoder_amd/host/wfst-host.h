@@ -595,6 +595,21 @@ class BiasLists {
   wfst_bias_lists *_b;
   int _n;
 };
+// A set of books -- bias lists of up to 65 536 nodes -- resident on one device (wfst_bias_books), for BiasedWordsSparse.
+class BiasBooks {
+ public:
+  BiasBooks() : _b(nullptr), _n(0) {}
+  ~BiasBooks();
+  bool Set(const std::vector<std::vector<BiasPhrase> > &books, int device = 0);  // false (with a message on stderr) on failure
+  int Size() const { return _n; }
+  const wfst_bias_books *Handle() const { return _b; }
+
+ private:
+  BiasBooks(const BiasBooks &);
+  BiasBooks &operator=(const BiasBooks &);
+  wfst_bias_books *_b;
+  int _n;
+};
 // A setting of BiasedWords: RescaleSetting's three and the scale of the phrases' bonuses.
 struct BiasSetting {
   double graph_scale = 1.0, acoustic_scale = 1.0, word_penalty = 0.0, boost_scale = 1.0;
@@ -603,9 +618,11 @@ struct BiasSetting {
 // frames[j] as RescaledWords has them; biased_cost = its cost, the bonuses taken off, and bonus = their sum, float64, bit for bit
 // reproducible; tot / lm UNSCALED; hits[k] = (phrase's index in the list, index in words of the occurrence's last word), by word,
 // the longest phrase first.  found = false (everything else empty / zero): the channel has no lattice, or no final state is reached.
+// n_cells: BiasedWordsSparse's count of the channel's reachable (state, node) pairs (0 from BiasedWords, -1 beyond max_cells).
 struct BiasedWords {
   bool found = false;
   int n_arcs = 0;
+  long long n_cells = 0;
   double biased_cost = 0.0, bonus = 0.0;
   float tot = 0.0f, lm = 0.0f;
   std::vector<int> words;
@@ -749,6 +766,10 @@ class GpuLatticeDecoder : public DecoderItf {
   // settings[q].  The channel's own failure throws.  Over a pool the call runs in the batcher thread, like AlignWords.
   void BiasedWords(const BiasLists &lists, int list, const std::vector<BiasSetting> &settings, std::vector<struct BiasedWords> *out,
                    bool use_final_probs = true);
+  // The same answers for a book, a bias list of up to 65 536 nodes, from the cells a path can reach
+  // (wfst_decoder_biased_words_sparse); for a list of at most 256 nodes every byte is BiasedWords'.
+  void BiasedWordsSparse(const BiasBooks &books, int book, const std::vector<BiasSetting> &settings, std::vector<struct BiasedWords> *out,
+                         bool use_final_probs = true);
   // Pruned live lattices (see GpuChannelPool::SetLiveLatticePrune) for this object's device decoder: the private one, or -- over a
   // pool, and so under ShareDevice -- the shared decoder of every object on it (set it before the other threads decode).
   void SetLiveLatticePrune(bool on);
@@ -908,6 +929,11 @@ class GpuBatchDecoder {
   void BiasedWords(const std::vector<int> &channels, const BiasLists &lists, const std::vector<int> &list_of,
                    const std::vector<BiasSetting> &settings, bool use_final_probs, std::vector<std::vector<struct BiasedWords> > *out,
                    std::vector<int> *status = nullptr, long long max_cells = 0);
+  // BiasedWordsSparse (see GpuLatticeDecoder) of many channels: BiasedWords' arguments with books; max_cells bounds ONE channel's
+  // reachable cells, round_cells the cost cells of one round (see wfst_decoder_biased_words_sparse; 0: the defaults).
+  void BiasedWordsSparse(const std::vector<int> &channels, const BiasBooks &books, const std::vector<int> &book_of,
+                         const std::vector<BiasSetting> &settings, bool use_final_probs, std::vector<std::vector<struct BiasedWords> > *out,
+                         std::vector<int> *status = nullptr, long long max_cells = 0, long long round_cells = 0);
   void SetLiveLatticePrune(bool on);   // pruned live lattices for every channel (see GpuChannelPool::SetLiveLatticePrune)
   wfst_decoder *Handle() { return _dec; }
 

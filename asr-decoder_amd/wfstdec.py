@@ -54,6 +54,7 @@ SYMBOLS = [
     "wfst_align_graphs_create", "wfst_align_graphs_load", "wfst_align_graphs_info", "wfst_align_graphs_free", "wfst_decoder_force_align",
     "wfst_decoder_force_align_workspace", "wfst_decoder_graph_posteriors", "wfst_decoder_graph_posteriors_workspace",
     "wfst_bias_compile", "wfst_bias_lists_create", "wfst_bias_lists_info", "wfst_bias_lists_free", "wfst_decoder_biased_words",
+    "wfst_bias_book_compile", "wfst_bias_books_create", "wfst_bias_books_info", "wfst_bias_books_free", "wfst_decoder_biased_words_sparse",
 ]
 
 
@@ -450,6 +451,48 @@ class BiasLists:
     def free(self):
         if self.h:
             lib().wfst_bias_lists_free(self.h)
+            self.h = None
+
+
+def bias_book_compile(phrases, cap_nodes=65536):
+    """bias_compile for a BOOK, a bias list of up to 65 536 nodes (wfst_bias_book_compile; host only, no device)."""
+    _, ln, words, bonus = _flat_phrases([phrases])
+    cap = int(cap_nodes)
+    n = C.c_int32()
+    v = [np.zeros(max(cap, 1), np.int32) for _ in range(4)]
+    beta = np.zeros(max(cap, 1), np.float64)
+    _check(lib().wfst_bias_book_compile(len(ln), _i32(ln), _i32(words), _f64(bonus), cap, C.byref(n), *([_i32(x) for x in v] + [_f64(beta)])))
+    k = n.value
+    return dict(n_nodes=k, parent=v[0][:k].copy(), word=v[1][:k].copy(), fail=v[2][:k].copy(), phrase=v[3][:k].copy(), beta=beta[:k].copy())
+
+
+class BiasBooks:
+    """A set of books -- bias lists of up to 65 536 nodes -- resident in HBM, for BatchDecoder.biased_words_sparse (wfst_bias_books)."""
+
+    def __init__(self, handle, n_books):
+        self.h = handle
+        self.n_books = int(n_books)
+
+    @staticmethod
+    def from_phrases(books, device=0):
+        """books: [[(words, bonus), ...], ...] -- per book its phrases, each 1..16 word ids (> 0) and a bonus >= 0."""
+        books = list(books)
+        n_ph, ln, words, bonus = _flat_phrases(books)
+        h = C.c_void_p()
+        _check(lib().wfst_bias_books_create(len(books), _i32(n_ph), _i32(ln), _i32(words), _f64(bonus), int(device), C.byref(h)))
+        return BiasBooks(h, len(books))
+
+    def info(self):
+        k = self.n_books
+        n, tp, tn, b = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        v = [np.zeros(k, np.int32) for _ in range(3)]
+        _check(lib().wfst_bias_books_info(self.h, C.byref(n), C.byref(tp), C.byref(tn), *([_i32(x) for x in v] + [C.byref(b)])))
+        return dict(n_books=n.value, total_phrases=tp.value, total_nodes=tn.value, n_phrases=v[0], n_nodes=v[1], n_words=v[2],
+                    device_bytes=b.value)
+
+    def free(self):
+        if self.h:
+            lib().wfst_bias_books_free(self.h)
             self.h = None
 
 
@@ -1340,7 +1383,10 @@ class BatchDecoder:
         hyp_words, begin / end (int32 arrays per word, frames, end exclusive), biased_cost and bonus (float64), tot, lm (float32: the
         path's own UNSCALED scores), n_hits, hit_phrase / hit_word (int32 arrays: the phrase's index in the list, the index in
         hyp_words of the occurrence's last word) and status -- WFST_OK or the CHANNEL's own error code.  Bit for bit reproducible.
-        A path with more words or hits than cap_words / cap_hits hold: the call is made once more, with the room needed."""
+        A path with more words or hits than cap_words / cap_hits hold: the call is made once more, with the room needed.
+        lists may also be a BiasBooks set: the call is then biased_words_sparse's."""
+        if isinstance(lists, BiasBooks):
+            return self.biased_words_sparse(lists, list_of, settings, channels, use_final_probs, cap_words, cap_hits, max_cells)
         ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
         cnt = int(ch.shape[0])
         if list_of is None:
@@ -1374,6 +1420,50 @@ class BatchDecoder:
                                 begin=begin[i, q, :m].copy(), end=end[i, q, :m].copy(), biased_cost=float(cost[i, q]),
                                 bonus=float(bonus[i, q]), tot=np.float32(tot[i, q]), lm=np.float32(lm[i, q]), n_hits=int(nk[i, q]),
                                 hit_phrase=hp[i, q, :k].copy(), hit_word=hw[i, q, :k].copy(), status=int(status[i])))
+            out.append(row)
+        return out
+
+    def biased_words_sparse(self, books, book_of=None, settings=((1, 1, 0, 1),), channels=None, use_final_probs=True, cap_words=256,
+                            cap_hits=64, max_cells=0, round_cells=0):
+        """biased_words for books, bias lists of up to 65 536 nodes (wfst_decoder_biased_words_sparse): the same answers from the
+        cells a path can reach.  books = a BiasBooks set (None: no channel has a book), book_of as biased_words' list_of.  Every dict
+        of biased_words, and n_cells beside them: the channel's reachable (state, node) pairs, -1 where they pass max_cells (which
+        bounds ONE channel's n_cells here; 0: 4 Mi).  round_cells: the cost cells of one round of the sweep (0: 32 Mi)."""
+        ch = np.ascontiguousarray(list(range(self.n)) if channels is None else [int(c) for c in channels], dtype=np.int32)
+        cnt = int(ch.shape[0])
+        if book_of is None:
+            k = books.n_books if books is not None else 0
+            book_of = [i if i < k else -1 for i in range(cnt)]
+        lo = np.ascontiguousarray([int(x) for x in book_of], dtype=np.int32)
+        if lo.shape[0] != cnt:
+            raise ValueError("book_of must have one entry per listed channel")
+        st = np.ascontiguousarray(settings, dtype=np.float64).reshape(-1, 4)
+        ns = int(st.shape[0])
+        cap, hcap = int(cap_words), int(cap_hits)
+        for attempt in range(2):
+            status, found, na, begin, end, tot, lm = self._word_results(cnt, max(ns, 1), max(cap, 1))
+            pair = lambda t: np.zeros((cnt, max(ns, 1)), t)
+            nh, nk, cost, bonus = pair(np.int32), pair(np.int32), pair(np.float64), pair(np.float64)
+            nc = np.zeros(max(cnt, 1), np.int64)
+            hyp = np.zeros((cnt, max(ns, 1), max(cap, 1)), np.int32)
+            hp, hw = np.zeros((cnt, max(ns, 1), max(hcap, 1)), np.int32), np.zeros((cnt, max(ns, 1), max(hcap, 1)), np.int32)
+            _check(lib().wfst_decoder_biased_words_sparse(self.h, _i32(ch), cnt, int(bool(use_final_probs)), books.h if books is not None else None,
+                                                          _i32(lo), ns, _f64(st), cap, hcap, C.c_int64(int(max_cells)), C.c_int64(int(round_cells)),
+                                                          _i32(status), nc.ctypes.data_as(C.POINTER(C.c_int64)), _i32(found), _i32(na), _i32(nh),
+                                                          _i32(nk), _i32(hyp), _i32(begin), _i32(end), _i32(hp), _i32(hw), _f64(cost), _f64(bonus),
+                                                          _f32(tot), _f32(lm)))
+            if attempt or not (np.any(nh > cap) or np.any(nk > hcap)):
+                break
+            cap, hcap = max(cap, int(nh.max())), max(hcap, int(nk.max()))   # (a path needs more room: once more, with it)
+        out = []
+        for i in range(cnt):
+            row = []
+            for q in range(ns):
+                m, k = min(int(nh[i, q]), cap), min(int(nk[i, q]), hcap)
+                row.append(dict(found=bool(found[i, q]), n_arcs=int(na[i, q]), n_hyp=int(nh[i, q]), hyp_words=hyp[i, q, :m].copy(),
+                                begin=begin[i, q, :m].copy(), end=end[i, q, :m].copy(), biased_cost=float(cost[i, q]),
+                                bonus=float(bonus[i, q]), tot=np.float32(tot[i, q]), lm=np.float32(lm[i, q]), n_hits=int(nk[i, q]),
+                                hit_phrase=hp[i, q, :k].copy(), hit_word=hw[i, q, :k].copy(), status=int(status[i]), n_cells=int(nc[i])))
             out.append(row)
         return out
 

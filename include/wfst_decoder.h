@@ -1131,6 +1131,74 @@ int wfst_decoder_biased_words(wfst_decoder *d, const int32_t *channels, int32_t 
                               int32_t *hit_phrase, int32_t *hit_word /* [n][n_set][cap_hits] */,
                               double *biased_cost, double *bonus /* [n][n_set] */, float *tot_score, float *lm_score /* [n][n_set] */);
 
+/* ---- phrase boosting for large lists: sparse cells over reachable nodes ------------------------------------------------------------------
+ * wfst_decoder_biased_words keeps a cell for every (lattice state, node) pair and so serves lists of at most 256 nodes.  The lists
+ * the feature exists for -- a phone's contacts, a product catalogue -- run to thousands of phrases.  Along one path the automaton is
+ * in exactly one node and most lattice words are in no phrase, so almost all of those cells are +inf.  This call keeps only the
+ * cells a path can reach; its cost follows the lattice, not the list.
+ *
+ * A BOOK is a bias list without the 256-node cap: P >= 0 phrases of 1..WFST_BIAS_MAX_WORDS word ids > 0, each with a bonus that is
+ * finite and >= 0, no two phrases equal; its trie has J <= WFST_BIAS_BOOK_MAX_NODES = 65 536 nodes.  The numbering, fail, delta, own
+ * and beta are exactly wfst_decoder_biased_words': breadth first, root 0, by (depth, parent's number, word id).  The settings,
+ * c_q(a), d = c_q(a) - r, the + 0.0, the end rule, the traceback's tie rule (the wfst_decoder_align_words arc tuple, then the least
+ * source node) and every output are that call's, word for word.  So for a list of <= 256 nodes this call's answer equals that
+ * call's in every byte.
+ *
+ * New in the definition is the reachable set, which does not depend on the settings:
+ *   R(0) = {0};
+ *   for every in-arc a: s -> t that is an arc (its float32 graph + acoustic sum is finite), R(t) contains R(s) if olabel(a) == 0,
+ *   and {delta(i, olabel(a)) : i in R(s)} otherwise;
+ *   R is the least fixed point of these rules (the lattice is a DAG, so R is well defined).
+ * By induction over the DAG, v[t][j] finite implies j in R(t): the table restricted to {(t, j) : j in R(t)}, with the same
+ * recurrence, holds the same bits as the dense one.  A cell inside R may still be +inf (a float64 sum that overflows).
+ * n_cells[i] = the sum over t of |R(t)|, an exact integer, is a per-channel output.
+ *
+ * bias_reach_kernel (one workgroup per channel, once per call, shared by the settings) builds R and the product graph's edges over
+ * align_index_kernel's index; bias_sparse_kernel (one workgroup per (channel, setting)) sweeps the cells, picks the end, walks back
+ * and reads the path forwards, recomputing the node track from the automaton itself: a hop that differs from the traced cell is
+ * reported as an internal error (WFST_E_DEVICE), never answered.  On the device a book is its nodes' word, fail, phrase, first
+ * child and child count, beta and the distinct words; goto(i, w) is a binary search among i's children (consecutive numbers in
+ * ascending word order), delta(i, w) tries goto along i, fail(i), ... down to the root.
+ *
+ * max_cells bounds ONE channel's n_cells (0 = 4 Mi cells; at most 2^30); a channel beyond it gets status[i] = WFST_E_CAPACITY, zeroed
+ * answers and n_cells[i] = -1, the others' answers stand.  The same holds for a channel whose product graph has more than
+ * min(16 x max_cells, 2^30) edges.  The sets live in per-channel regions that start at max(1024, 4 x states) cells and
+ * max(4096, 8 x arcs) edges; a region that overflows is made four times as large and the reach stage runs again, at most
+ * log4(max_cells / first size) + 1 times for each of the two.  round_cells is the number of cost cells (8 bytes each) of the
+ * (channel, setting) pairs taken together in one round of the sweep (0 = 32 Mi cells = 256 MiB); a channel whose own settings need
+ * more runs in a round of its own.  The answers do not depend on max_cells, round_cells or the growth.
+ * Every other failure, argument error and state error is wfst_decoder_biased_words', and round_cells < 0 is WFST_E_ARG.  Any output
+ * pointer may be NULL.  The decoder's state is only read.  Synchronous.
+ *
+ * wfst_bias_book_compile is wfst_bias_compile under the book's cap: host only, n_nodes is set even on WFST_E_CAPACITY.
+ * wfst_bias_books_create validates on the host before any device is touched; its argument errors are wfst_bias_lists_create's, with
+ * "bias book K phrase P" in the message; more than 65 536 nodes is WFST_E_CAPACITY.
+ * Measured on one MI355X (profiles/bias_sparse_probe.json: 64 live channels at frame 150 of the headline lattice configuration, four
+ * settings): 5.1 .. 6.6 ms per call from 2 to 65 536 nodes beside the dense call's 3.1 / 3.9 / 6.9 / 78 ms at 2 / 16 / 64 / 256 nodes,
+ * n_cells / states 1.004 at the median.  Not measured: an idle card, a service end to end, sets of hundreds of nodes per state.
+ * Not computed here: biasing the first-pass search; n-best lists under a bias; transition-id output; class or subword biasing. */
+#define WFST_BIAS_BOOK_MAX_NODES 65536
+typedef struct wfst_bias_books wfst_bias_books;
+int wfst_bias_book_compile(int32_t n_phrases, const int32_t *phrase_len /* [n_phrases] */, const int32_t *phrase_words,
+                           const double *phrase_bonus /* [n_phrases] */, int32_t cap_nodes, int32_t *n_nodes,
+                           int32_t *parent, int32_t *word, int32_t *fail, int32_t *phrase, double *beta /* [cap_nodes] each, or NULL */);
+int wfst_bias_books_create(int32_t n_books, const int32_t *n_phrases /* [n_books] */, const int32_t *phrase_len,
+                           const int32_t *phrase_words, const double *phrase_bonus, int device, wfst_bias_books **out);
+int wfst_bias_books_info(const wfst_bias_books *b, int32_t *n_books, int64_t *total_phrases, int64_t *total_nodes,
+                         int32_t *n_phrases, int32_t *n_nodes, int32_t *n_words /* [n_books] each */, int64_t *device_bytes);
+void wfst_bias_books_free(wfst_bias_books *b);
+int wfst_decoder_biased_words_sparse(wfst_decoder *d, const int32_t *channels, int32_t n, int32_t use_final_probs,
+                                     const wfst_bias_books *books, const int32_t *book_of /* [n], -1: no book; NULL: none has one */,
+                                     int32_t n_set /* 1..16, shared by the listed channels */,
+                                     const double *settings /* [n_set][4]: graph_scale, acoustic_scale, word_penalty, boost_scale */,
+                                     int32_t cap_words, int32_t cap_hits, int64_t max_cells /* reachable cells of one channel; 0 = default */,
+                                     int64_t round_cells /* cost cells of one round; 0 = default */,
+                                     int32_t *status /* [n] */, int64_t *n_cells /* [n] */, int32_t *found, int32_t *n_arcs, int32_t *n_hyp,
+                                     int32_t *n_hits /* [n][n_set] */,
+                                     int32_t *hyp_words, int32_t *begin_frame, int32_t *end_frame /* [n][n_set][cap_words] */,
+                                     int32_t *hit_phrase, int32_t *hit_word /* [n][n_set][cap_hits] */,
+                                     double *biased_cost, double *bonus /* [n][n_set] */, float *tot_score, float *lm_score /* [n][n_set] */);
+
 /* ---- forced alignment: exact Viterbi of a channel's scores against the utterance's own graph -----------------------------------------
  * Everything above reads the lattice the search left behind; a transcript that is not in the lattice is not found there.  This call
  * aligns a channel's SCORES against a small graph the caller brings per utterance -- a compiled training graph, a transcript
